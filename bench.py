@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Benchmark of the MD inner loop (force pass + leapfrog/OU integrator) on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W [--replicas R] [--workload NAME]
+    python bench.py --gpus N --steps K --warmup W [--replicas R] [--workload NAME] [--dump-outputs DIR] [--full]
 
 A "step" is one force evaluation + one leapfrog stage of EVERY replica resident on the GPU (the reference's
 "MD step", /root/reference/src/main.cpp:677-682; one integration cycle = 3 steps,
@@ -19,6 +19,11 @@ multi-GPU configurations, whose total work is fixed (strong scaling):
                      (upside_hip_comm_*: one fp32 per replica all-gathered, verdicts on the device, straddling pairs moved
                      by ncclSend/ncclRecv -- no host staging)
   ens512_syn150      configs[4]: 512 independent 150-residue proteins, 512 / N per GPU, no communication
+
+A plain run sets the workload up, warms up, times the K steps, writes the outputs of the timed engine if --dump-outputs is
+given, and prints the result.  --full adds what the headline figure does not need, each outside the timed region: the oracle
+check of the timed engine (`parity_check`), the per-kernel HIP-event leg and rooflines (`roofline`), the one-replica latency
+leg, the 8-GPU projection of the strong-scaling workloads and the CPU baseline (`cpu_baseline`, N = 1).
 
 Rank 0 prints ONE JSON line.
 """
@@ -54,6 +59,7 @@ def bind(lib):
     c.upside_hip_construct.argtypes = [ct.c_int, ct.c_char_p, ct.c_int, ct.c_bool]
     c.upside_hip_set_pos.argtypes = [ct.c_void_p, ct.c_void_p]
     c.upside_hip_get_pos.argtypes = [ct.c_void_p, ct.c_void_p]
+    c.upside_hip_get_mom.argtypes = [ct.c_void_p, ct.c_void_p]
     c.upside_hip_init_md.argtypes = [ct.c_void_p, ct.c_void_p, ct.c_uint32, ct.c_float, ct.c_float, ct.c_int]
     c.upside_hip_run_md.argtypes = [ct.c_void_p, ct.c_int]
     c.upside_hip_run_steps.argtypes = [ct.c_void_p, ct.c_int]
@@ -226,6 +232,27 @@ def parity_check(pkg, c, eng, fixture, R, n_atom, n_check=4):
                      'oracle/upside_oracle.c; also vs a fresh one-system engine' % len(pick))
 
 
+DUMP_BYTES = 64e6      # --dump-outputs: at most this much in all, over every rank
+
+
+def dump_outputs(c, eng, R, n_atom, out_dir, rank, world):
+    """--dump-outputs: what a caller of the timed path reads back after its last step -- positions and momenta of the engine's
+    replicas (upside_hip_get_pos / _get_mom), float32 (n, n_atom, 3), as pos.npy and mom.npy (pos_rank<r>.npy ... when N > 1).
+    When all replicas would exceed DUMP_BYTES a fixed sample of them is written, drawn from a seeded stream that depends only on
+    the replica count: replica_index.npy (float64) names the replicas of every row."""
+    pos = np.empty((R, n_atom, 3), dtype='f4'); mom = np.empty((R, n_atom, 3), dtype='f4')
+    check(c, c.upside_hip_get_pos(eng, pos.ctypes.data), 'get_pos')
+    check(c, c.upside_hip_get_mom(eng, mom.ctypes.data), 'get_mom')
+    per_replica = pos[0].nbytes + mom[0].nbytes + 8
+    keep = min(R, int((DUMP_BYTES / world - 3 * 4096) // per_replica))
+    idx = np.arange(R) if keep == R else np.sort(np.random.RandomState(4099 + R).choice(R, keep, replace=False))
+    suffix = '' if world == 1 else '_rank%d' % rank
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, 'pos%s.npy' % suffix), np.ascontiguousarray(pos[idx]))
+    np.save(os.path.join(out_dir, 'mom%s.npy' % suffix), np.ascontiguousarray(mom[idx]))
+    np.save(os.path.join(out_dir, 'replica_index%s.npy' % suffix), idx.astype('f8'))
+
+
 def self_launch(n_gpus):
     """`python bench.py --gpus N` without a launcher: start the N ranks as a CHILD torch.distributed.run (one process per GPU,
     rendezvous on 127.0.0.1), relay their output -- rank 0 prints the one JSON line -- and the exit code.  A child, not an exec:
@@ -280,11 +307,18 @@ def main():
     ap.add_argument('--replicas', type=int, default=int(os.environ.get('UPSIDE_BENCH_REPLICAS', '4096')),
                     help='independent replicas resident per GPU')
     ap.add_argument('--workload', default='syn300_10A')
-    ap.add_argument('--no-cpu-baseline', action='store_true')
+    ap.add_argument('--dump-outputs', metavar='DIR',
+                    help='after the timed steps, write the positions and momenta of the timed engine as DIR/<name>.npy (see dump_outputs)')
+    ap.add_argument('--full', action='store_true',
+                    help='after the timed steps, also run the oracle parity check, the per-kernel roofline leg, the one-replica latency leg, '
+                         'the 8-GPU projection and the CPU baseline (each can be left out again with the --no-* options below)')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='with --full: skip the CPU baseline (ignored without --full)')
     ap.add_argument('--no-parity-check', action='store_true',
-                    help='skip the oracle check of the timed engine (profiling passes: keeps its one-system launches out of the averages)')
+                    help='with --full: skip the oracle check of the timed engine (profiling passes: keeps its one-system launches out of the averages; '
+                         'ignored without --full)')
     ap.add_argument('--no-single-system', action='store_true',
-                    help='skip the one-replica latency leg (PMC passes: keeps its small launches out of the per-kernel averages)')
+                    help='with --full: skip the one-replica latency leg (PMC passes: keeps its small launches out of the per-kernel averages; '
+                         'ignored without --full)')
     args = ap.parse_args()
 
     pkg = load_package()
@@ -403,10 +437,12 @@ def main():
     exchange_steps_saved, exchange_steps = exchange_steps, 0      # the profiling legs below run plain MD
 
     _trace('timed region done: %d steps' % steps_done)
+    if args.dump_outputs:
+        dump_outputs(c, eng, R, n_atom, args.dump_outputs, rank, world)
     # ---- parity of what was just timed (outside the timed region): forces of THIS engine -- this batch size, hence these code paths --
     # at the positions its replicas have reached, against the oracle and against a fresh one-system engine
     parity = None
-    if not args.no_parity_check:      # EVERY rank checks its own engine (no rank idles in a barrier while rank 0 runs the oracle); rank 0 reports the worst
+    if args.full and not args.no_parity_check:      # EVERY rank checks its own engine (no rank idles in a barrier while rank 0 runs the oracle); rank 0 reports the worst
         parity = parity_check(pkg, c, eng, fixture, R, n_atom)
         if dist is not None:
             every = [None] * world
@@ -417,7 +453,7 @@ def main():
         _trace('parity check: %r' % (parity,))
     # ---- roofline of the dominant kernel: HIP-event timing on the engine's stream, outside the timed region
     roofline = None
-    if rank == 0:
+    if rank == 0 and args.full:
         check(c, c.upside_hip_profile_reset(eng, 1), 'profile_reset')
         run_steps(30)
         buf = ct.create_string_buffer(1 << 16)
@@ -544,7 +580,7 @@ def main():
     _trace('roofline leg done')
     # single-system latency of the same workload (one replica on the GPU), outside the timed region
     single = None
-    if rank == 0 and not args.no_single_system:
+    if rank == 0 and args.full and not args.no_single_system:
         eng1 = c.upside_hip_construct(n_atom, fixture.encode(), 1, True)
         if eng1:
             p1 = np.ascontiguousarray(pos0[None].astype('f4')); t1 = np.full(1, TEMPERATURE, dtype='f4')
@@ -559,7 +595,7 @@ def main():
     # the strong-scaling workloads: what eight GPUs would deliver if each ran its eighth of the systems at the rate ONE GPU reaches
     # with that many (measured here, plain MD) -- so that the first run on an 8-GPU node surprises nobody
     projected = None
-    if rank == 0 and total_systems and world == 1 and total_systems % 8 == 0:
+    if rank == 0 and args.full and total_systems and world == 1 and total_systems % 8 == 0:
         r8 = total_systems // 8
         eng8 = c.upside_hip_construct(n_atom, fixture.encode(), r8, True)
         if eng8:
@@ -600,7 +636,7 @@ def main():
             res['parity_check'] = parity
         if projected is not None:      # (outside `config`: nothing downstream should take it for a scaling measurement)
             res['not_measured_projection_8gpu'] = projected
-        if not args.no_cpu_baseline and world == 1:   # the CPU leg is timed at N=1 only (rank 0 has the host to itself)
+        if args.full and not args.no_cpu_baseline and world == 1:   # the CPU leg is timed at N=1 only (rank 0 has the host to itself)
             res['cpu_baseline'] = cpu_baseline(fixture, variant, one_core=(R == 1), n_atom=int(n_atom))
         # (flushed at once: tearing down the RCCL communicator below has been seen to end the process without running Python's
         #  exit-time flush of a buffered stdout)

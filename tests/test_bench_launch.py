@@ -115,3 +115,52 @@ def test_counter_calibration_is_what_the_traffic_table_applies():
         bp = entry.get('bp:rotamer')
         if bp:
             assert abs(bp['bytes_per_launch'] - (rf * bp['fetch_bytes_counted'] + bp['write_bytes'])) < 1e-3 * bp['bytes_per_launch']
+
+
+def test_dump_outputs_writes_a_fixed_sample_within_64_mb(tmp_path, monkeypatch):
+    """--dump-outputs at the default size (4096 replicas of the 900-atom benchmark protein: 88 MB of positions and momenta) writes
+    a seeded sample of whole replicas within 64 MB in all -- the same sample every run, every row the replica replica_index.npy
+    names -- and splits that budget between ranks; a batch that fits is written whole."""
+    import ctypes as ct
+    import importlib.util
+    import numpy as np
+    spec = importlib.util.spec_from_file_location('bench_mod', BENCH)
+    b = importlib.util.module_from_spec(spec)
+    monkeypatch.setattr(sys, 'argv', ['bench.py'])
+    spec.loader.exec_module(b)
+
+    class FakeEngine:      # replica r: every position coordinate r, every momentum r + 0.5
+        def __init__(self, R, n_atom):
+            self.shape = (R, n_atom, 3)
+
+        def _fill(self, ptr, offset):
+            a = np.ctypeslib.as_array(ct.cast(ptr, ct.POINTER(ct.c_float)), shape=self.shape)
+            a[...] = (np.arange(self.shape[0], dtype='f4') + offset)[:, None, None]
+            return 0
+
+        def upside_hip_get_pos(self, eng, ptr):
+            return self._fill(ptr, 0.)
+
+        def upside_hip_get_mom(self, eng, ptr):
+            return self._fill(ptr, 0.5)
+
+    def dump(R, n_atom, rank, world, name):
+        d = tmp_path / name
+        b.dump_outputs(FakeEngine(R, n_atom), None, R, n_atom, str(d), rank, world)
+        sfx = '' if world == 1 else '_rank%d' % rank
+        out = {nm: np.load(str(d / ('%s%s.npy' % (nm, sfx)))) for nm in ('pos', 'mom', 'replica_index')}
+        return out, sum(f.stat().st_size for f in d.iterdir())
+
+    a, size = dump(4096, 900, 0, 1, 'a')
+    again, _ = dump(4096, 900, 0, 1, 'b')
+    idx = a['replica_index']
+    assert size <= 64e6 and 2048 < len(idx) < 4096 and a['replica_index'].dtype == np.float64
+    assert a['pos'].dtype == a['mom'].dtype == np.float32 and a['pos'].shape == a['mom'].shape == (len(idx), 900, 3)
+    assert np.all(np.diff(idx) > 0) and idx[0] >= 0 and idx[-1] < 4096
+    assert np.array_equal(a['pos'][:, 0, 0], idx) and np.array_equal(a['mom'][:, -1, 2], idx + 0.5)
+    for nm in a:
+        assert np.array_equal(a[nm], again[nm]), nm
+    r1, size1 = dump(4096, 900, 1, 2, 'rank1')
+    assert size1 <= 32e6 and np.array_equal(r1['pos'][:, 0, 0], r1['replica_index'])
+    small, _ = dump(8, 900, 0, 1, 'small')
+    assert small['replica_index'].tolist() == list(range(8)) and small['pos'].shape == (8, 900, 3)

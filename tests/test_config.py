@@ -140,20 +140,37 @@ def test_break_chains_on_a_fixture(tmp_path):
     orc.close()
 
 
-@pytest.mark.skipif(not os.path.isdir('/root/reference/parameters'), reason='needs the reference parameter directory (build container)')
+def _force_field():
+    """the force-field parameters write_config reads, stored under tests/golden/parameters: the reference's parameters/ff_1
+    side-chain and environment libraries and hydrogen-bond energy, and parameters/common/rama_reference.pkl as a (72, 72) .npy"""
+    d = os.path.join(P.GOLDEN_DIR, 'parameters')
+    with open(os.path.join(d, 'ff_1', 'hbond')) as f:
+        hbond_energy = float(f.read())
+    return dict(sidechain_lib=os.path.join(d, 'ff_1', 'sidechain.h5'), environment_lib=os.path.join(d, 'ff_1', 'environment.h5'),
+                rama_ref=np.load(os.path.join(d, 'rama_reference.npy')), hbond_energy=hbond_energy)
+
+
+def test_rama_reference_loader(tmp_path):
+    """config.load_rama_reference reads the reference's pickled (72, 72) Ramachandran reference state: a protocol-2 pickle of the
+    stored map comes back as the same float64 array"""
+    import pickle
+    want = np.load(os.path.join(P.GOLDEN_DIR, 'parameters', 'rama_reference.npy'))
+    f = str(tmp_path / 'rama_reference.pkl')
+    with open(f, 'wb') as h:
+        pickle.dump(want, h, protocol=2)
+    got = cfg.load_rama_reference(f)
+    assert got.dtype == np.float64 and got.shape == (72, 72) and np.array_equal(got, want)
+
+
 def test_two_chain_configuration_from_scratch(tmp_path):
     """write_config(chain_first_residue=...) + break_chains(): the path of py/upside_config.py --chain-break-from-file followed
     by py/ugly_hack_break_chain.py --chain-break-from-file.  The junction residues have no hydrogen-bond sites (:1445-1449), the
     chain break is recorded, and the unmodified reference library and the C restatement agree on the resulting potential."""
-    PARAM = '/root/reference/parameters'
     fasta = cfg.fasta_from_one_letter(cfg.PROTEIN_G[:24])
     pos = cfg.helix_chain(24)
     pos[36:] += np.array([0., 9., 0.])                                           # second chain (residues 12..23) moved beside the first
     f = str(tmp_path / 'dimer.up')
-    cfg.write_config(f, fasta, pos, sidechain_lib=os.path.join(PARAM, 'ff_1', 'sidechain.h5'),
-                     environment_lib=os.path.join(PARAM, 'ff_1', 'environment.h5'),
-                     rama_ref=cfg.load_rama_reference(os.path.join(PARAM, 'common', 'rama_reference.pkl')),
-                     hbond_energy=float(open(os.path.join(PARAM, 'ff_1', 'hbond')).read()), chain_first_residue=[12])
+    cfg.write_config(f, fasta, pos, chain_first_residue=[12], **_force_field())
     with P.pkg.h5lite.open_file(f) as t:      # (no group handle outlives the block: the file is reopened for writing below)
         don = t.group('input/potential/infer_H_O').group('donors').read('residue', 'i4')
         acc = t.group('input/potential/infer_H_O').group('acceptors').read('residue', 'i4')
@@ -275,11 +292,9 @@ def test_fixed_rotamer_states():
         cfg.fixed_rotamer_states(fasta, [('1', 'VAL', 'A', '2', '60', '60')], order, tab)
 
 
-@pytest.mark.skipif(not os.path.isdir('/root/reference/parameters'), reason='needs the reference parameter directory (build container)')
 def test_configuration_with_rama_library_fixed_rotamers_and_loose_criteria(tmp_path):
     """write_config with --rama-library / --rama-sheet-mixing-energy / --secstr-bias, --fix-rotamer and --loose-hbond-criteria:
     the unmodified reference library loads the file and agrees with the C restatement; the options leave their marks in it"""
-    PARAM = '/root/reference/parameters'
     libf = str(tmp_path / 'rama_lib.h5')
     with P.pkg.h5lite.open_file(libf, 'w') as h:       # a library over the 20 residue types + ALL + CPR, 72 x 72 like the README's
         rs = np.random.RandomState(5)
@@ -296,9 +311,7 @@ def test_configuration_with_rama_library_fixed_rotamers_and_loose_criteria(tmp_p
     fasta = list(cfg.fasta_from_one_letter(cfg.PROTEIN_G[:20])); fasta[7] = 'CPR' if fasta[7] == 'PRO' else fasta[7]
     pos = cfg.helix_chain(20)
     fixrows = [(str(i), fasta[i] if fasta[i] != 'CPR' else 'PRO', 'A', str(i + 1), '-65', '170') for i in (2, 5, 11)]
-    common = dict(sidechain_lib=os.path.join(PARAM, 'ff_1', 'sidechain.h5'), environment_lib=os.path.join(PARAM, 'ff_1', 'environment.h5'),
-                  rama_ref=cfg.load_rama_reference(os.path.join(PARAM, 'common', 'rama_reference.pkl')),
-                  hbond_energy=float(open(os.path.join(PARAM, 'ff_1', 'hbond')).read()))
+    common = _force_field()
     f0, f1 = str(tmp_path / 'plain.up'), str(tmp_path / 'options.up')
     i0 = cfg.write_config(f0, fasta, pos, **common)
     i1 = cfg.write_config(f1, fasta, pos, rama_library=libf, rama_sheet_mixing_energy=1.0, secstr_bias=[(3, 'helix', -1.0)], fix_rotamer=fixrows,

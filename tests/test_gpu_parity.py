@@ -1007,12 +1007,12 @@ def test_upside_main_pivot_moves_match_reference(hip, tmp_path):
 
 
 def test_bench_contract(tmp_path):
-    """bench.py prints ONE JSON line with the fields the driver reads (metric, value, steps exactly as asked,
+    """bench.py --full prints ONE JSON line with the fields the driver reads (metric, value, steps exactly as asked,
     roofline of the dominant kernel with live HIP-event timing, cpu_baseline object at N=1)."""
     import json
     import subprocess
     out = subprocess.run([sys.executable, os.path.join(P.ROOT, 'bench.py'), '--gpus', '1', '--steps', '7', '--warmup', '4',
-                          '--replicas', '3', '--workload', 'syn150_10A'], check=True, stdout=subprocess.PIPE,
+                          '--replicas', '3', '--workload', 'syn150_10A', '--full'], check=True, stdout=subprocess.PIPE,
                          stderr=subprocess.PIPE, timeout=900, env=dict(os.environ, UPSIDE_BENCH_CPU_BUDGET_S='1')).stdout.decode()
     lines = [ln for ln in out.strip().split('\n') if ln.strip()]
     assert len(lines) == 1
@@ -1045,6 +1045,35 @@ def test_bench_contract(tmp_path):
     assert ig['valu']['bound'] == 'valu' and 0.3 < ig['valu']['hbm_frac_at_fp32_peak'] < 1.0, ig
 
 
+def test_bench_plain_run_dumps_reproducible_outputs(tmp_path):
+    """a plain bench.py run (no --full) prints the headline line only -- no parity, roofline or CPU legs -- and --dump-outputs
+    writes the positions and momenta of the timed engine after its last step; two runs with the same arguments write the
+    same arrays (seeded inputs, a bit-reproducible engine), so that two builds can be compared output for output."""
+    import json
+    import subprocess
+    dumps = []
+    for k in range(2):
+        d_out = tmp_path / ('run%d' % k)
+        out = subprocess.run([sys.executable, os.path.join(P.ROOT, 'bench.py'), '--gpus', '1', '--steps', '5', '--warmup', '2',
+                              '--replicas', '3', '--workload', 'syn150_10A', '--dump-outputs', str(d_out)], check=True,
+                             stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=600).stdout.decode()
+        lines = [ln for ln in out.strip().split('\n') if ln.strip()]
+        assert len(lines) == 1
+        d = json.loads(lines[0])
+        assert d['steps'] == 5 and d['warmup'] == 2 and d['unit'] == 'system-steps/s' and d['dtype'] == 'f32'
+        assert abs(d['value'] - 3 * 5 / (d['ms_per_step'] * 5e-3)) < 1e-6 * d['value']
+        assert d['roofline'] is None and 'parity_check' not in d and 'cpu_baseline' not in d
+        assert d['config']['single_system_steps_per_s'] is None
+        dumps.append({nm: np.load(str(d_out / (nm + '.npy'))) for nm in ('pos', 'mom', 'replica_index')})
+    n_atom = P.pkg.config.read_pos(P.fixture('syn150_10A')).shape[0]
+    a, b = dumps
+    assert a['pos'].shape == a['mom'].shape == (3, n_atom, 3) and a['pos'].dtype == a['mom'].dtype == np.float32
+    assert a['replica_index'].tolist() == [0., 1., 2.]
+    assert np.isfinite(a['pos']).all() and np.isfinite(a['mom']).all() and np.abs(a['mom']).max() > 0.
+    for nm in a:
+        assert np.array_equal(a[nm], b[nm]), nm
+
+
 def test_bench_self_launch_two_ranks_on_one_gpu(tmp_path):
     """`python bench.py --gpus 2 --workload remd64_proteinG56` with NO launcher in the environment: bench.py starts its two ranks
     itself (child torch.distributed.run), each builds its half of the 64-temperature ladder and they exchange through
@@ -1058,7 +1087,7 @@ def test_bench_self_launch_two_ranks_on_one_gpu(tmp_path):
     for k in ('RANK', 'LOCAL_RANK', 'WORLD_SIZE', 'MASTER_ADDR', 'MASTER_PORT'):
         env.pop(k, None)
     r = subprocess.run([sys.executable, os.path.join(P.ROOT, 'bench.py'), '--gpus', '2', '--steps', '1200', '--warmup', '30',
-                        '--workload', 'remd64_proteinG56', '--no-cpu-baseline'], stdout=subprocess.PIPE, stderr=subprocess.PIPE,
+                        '--workload', 'remd64_proteinG56', '--full', '--no-cpu-baseline'], stdout=subprocess.PIPE, stderr=subprocess.PIPE,
                        timeout=900, env=env)
     assert r.returncode == 0, r.stderr.decode()[-3000:]
     lines = [ln for ln in r.stdout.decode().split('\n') if ln.strip().startswith('{')]

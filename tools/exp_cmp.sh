@@ -13,7 +13,7 @@ for f in $L/exp/*.so; do
   for c in $CASES; do
     w=${c%%:*}; r=${c##*:}
     if [ "$r" -ge 1024 ]; then st="--steps 30 --warmup 10"; else st="--steps 600 --warmup 60"; fi
-    v=$(python bench.py --workload $w --replicas $r $st --no-cpu-baseline --no-single-system 2>/dev/null | python -c "
+    v=$(python bench.py --workload $w --replicas $r $st --full --no-cpu-baseline --no-single-system 2>/dev/null | python -c "
 import sys,json
 try:
     d=json.loads([l for l in sys.stdin.read().splitlines() if l.startswith('{')][-1])

@@ -8,7 +8,7 @@ for round in $(seq $ROUNDS); do
 for f in $L/exp/*.so; do
   t=$(basename $f .so); [ "$t" = "_keep" ] && continue
   cp $f $L/libupside_hip.so
-  python bench.py --workload $W --replicas $R --steps 30 --warmup 10 --no-cpu-baseline --no-single-system --no-parity-check 2>/dev/null | python -c "
+  python bench.py --workload $W --replicas $R --steps 30 --warmup 10 --full --no-cpu-baseline --no-single-system --no-parity-check 2>/dev/null | python -c "
 import sys,json
 try:
     d=json.loads([l for l in sys.stdin.read().splitlines() if l.startswith('{')][-1])

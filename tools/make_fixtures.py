@@ -11,6 +11,7 @@ usage: python tools/make_fixtures.py [name ...]
        python tools/make_fixtures.py --add-param-derivs [name ...]   (adds param_deriv/<node> to existing golden files)
        python tools/make_fixtures.py --restraints                    (proteinG56_restraints: every optional node)
        python tools/make_fixtures.py --edge-cases                    (edge_*: degenerate sequences)
+       python tools/make_fixtures.py --parameters                    (tests/golden/parameters: what write_config reads)
 """
 import os
 import subprocess
@@ -312,7 +313,34 @@ def make(name):
         os.path.getsize(os.path.join(GOLD, name + '.golden.npz')) / 1e6))
 
 
+# the force-field data config.write_config reads (tests/test_config.py writes configurations from scratch with it).  The side-chain
+# library is rebuilt from the datasets write_config uses: the reference's file also carries the source of the script that fitted
+# it (attributes `program_text`), which is not data.  The environment library holds data only and is copied as it is.
+SIDECHAIN_DATASETS = ['restype_order', 'bead_order', 'rotamer_center_fixed', 'rotamer_prob', 'rotamer_start_stop_bead',
+                      'restype_and_chi_and_state', 'pair_interaction', 'coverage_interaction', 'hydrophobe_placement',
+                      'hydrophobe_interaction']
+
+
+def make_parameters():
+    import shutil
+    out = os.path.join(GOLD, 'parameters')
+    os.makedirs(os.path.join(out, 'ff_1'), exist_ok=True)
+    dst = os.path.join(out, 'ff_1', 'sidechain.h5')
+    if os.path.exists(dst):
+        os.remove(dst)
+    with pkg.h5lite.open_file(os.path.join(PARAM, 'ff_1', 'sidechain.h5')) as src, pkg.h5lite.open_file(dst, 'w') as d:
+        for nm in SIDECHAIN_DATASETS:
+            d.write(nm, src.read(nm))
+    shutil.copyfile(os.path.join(PARAM, 'ff_1', 'environment.h5'), os.path.join(out, 'ff_1', 'environment.h5'))
+    with open(os.path.join(out, 'ff_1', 'hbond'), 'w') as f:
+        f.write(repr(HBOND) + '\n')
+    np.save(os.path.join(out, 'rama_reference.npy'), cfg.load_rama_reference(os.path.join(PARAM, 'common', 'rama_reference.pkl')))
+
+
 if __name__ == '__main__':
+    if sys.argv[1:2] == ['--parameters']:
+        make_parameters()
+        sys.exit(0)
     if sys.argv[1:2] == ['--edge-cases']:
         make_edge_cases()
         sys.exit(0)

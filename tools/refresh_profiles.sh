@@ -13,10 +13,10 @@ mkdir -p "$OUT"
 want() { [ "$MODE" = all ] || [ "$MODE" = "$1" ]; }
 
 if want pmc; then
-[ -s "$OUT/bench_R4096.json" ] || python3 bench.py --steps 100 --warmup 30 --no-cpu-baseline 2>"$OUT/bench_R4096.err" | grep '^{' | tail -1 > "$OUT/bench_R4096.json"
+[ -s "$OUT/bench_R4096.json" ] || python3 bench.py --steps 100 --warmup 30 --full --no-cpu-baseline 2>"$OUT/bench_R4096.err" | grep '^{' | tail -1 > "$OUT/bench_R4096.json"
 # (the one-replica latency leg is left out of the profiled command: its launches of the same kernels would dilute the
 #  per-launch averages of the counters)
-CMD="python3 bench.py --steps 60 --warmup 15 --no-cpu-baseline --no-single-system --no-parity-check"
+CMD="python3 bench.py --steps 60 --warmup 15 --full --no-cpu-baseline --no-single-system --no-parity-check"
 for t in trace fetch write sq; do rm -rf "$OUT/$t"; done
 rocprofv3 --kernel-trace --stats -d "$OUT/trace" -o trace -- $CMD > "$OUT/trace.log" 2>&1
 rocprofv3 --kernel-trace --pmc FETCH_SIZE -d "$OUT/fetch" -o fetch -- $CMD > "$OUT/fetch.log" 2>&1
@@ -40,7 +40,7 @@ fi
 if want bench; then
 for R in 1 8 64 256 1024 4096; do
   st=100; [ $R -le 64 ] && st=300
-  python3 bench.py --replicas $R --steps $st --warmup 30 2>"$OUT/bench_R$R.err" | grep '^{' | tail -1 > "$OUT/bench_R$R.json"
+  python3 bench.py --replicas $R --steps $st --warmup 30 --full 2>"$OUT/bench_R$R.err" | grep '^{' | tail -1 > "$OUT/bench_R$R.json"
 done
 fi
 
@@ -54,10 +54,10 @@ done; done > "$OUT/other_configs.txt"
 # BASELINE configs[3] and [4] on one GPU (the multi-GPU lines need a node the builder cannot launch on)
 # BASELINE configs[1]: ONE protein G, with the reference timed on one host core in the same line; and the batch of 8
 for R in 1 8; do
-  python3 bench.py --workload proteinG56_7A --replicas $R --steps 400 --warmup 50 2>/dev/null | grep '^{' | tail -1 > "$OUT/bench_proteinG56_7A_R$R.json"
+  python3 bench.py --workload proteinG56_7A --replicas $R --steps 400 --warmup 50 --full 2>/dev/null | grep '^{' | tail -1 > "$OUT/bench_proteinG56_7A_R$R.json"
 done
 for w in remd64_proteinG56 ens512_syn150; do
-  python3 bench.py --workload $w --steps 1665 --warmup 111 --no-cpu-baseline 2>/dev/null | grep '^{' | tail -1 > "$OUT/bench_$w.json"
+  python3 bench.py --workload $w --steps 1665 --warmup 111 --full --no-cpu-baseline 2>/dev/null | grep '^{' | tail -1 > "$OUT/bench_$w.json"
 done
 fi
 ls -la "$OUT"
