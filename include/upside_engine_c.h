@@ -180,6 +180,21 @@ int upside_hip_rotamer_iterations(DerivEngine* engine, int* iters);
 /* last error text of this thread ("" if none) */
 /* get_param_deriv (engine_c_library.h:20) for any system of the batch */
 int upside_hip_get_param_deriv(DerivEngine* engine, const char* node_name, int system, int n_param, float* deriv);
+/* Parameter derivatives of every system of the batch, for training (e.g. contrastive divergence: <dE/dtheta> over native
+ * structures minus the same over simulated frames).  Semantics of get_param_deriv(system): the derivative at the state of the
+ * LAST FORCE PASS, not at the current positions -- after set_pos or MD steps, call upside_hip_compute(engine, NULL, NULL) first.
+ * n_param = the size of the node's get_param_deriv (= get_param() size; 0 for a node without a derivative, e.g. protein_hbond,
+ * for which the calls do nothing and return 0).  Deterministic: a system's derivative is bit-identical run to run and whatever else
+ * shares its batch.  Errors (unknown node, wrong n_param, NULL output) return 1 with upside_hip_last_error set.
+ *   _get_param_deriv_all: deriv is host (n_system, n_param), row s = upside_hip_get_param_deriv(system s).
+ *   _param_deriv_accumulate: enqueues sum[node] += sum over s (ascending) of weights[s] * dE_s/dtheta, in double; weights is host
+ *     (n_system), NULL = all 1, negative allowed (one accumulator can hold "native minus simulated"); frames[node] += 1.  Returns
+ *     without synchronising the engine's stream.
+ *   _param_deriv_read: sum (n_param doubles) and the number of accumulate calls since the last reset (n_frame, never NULL);
+ *     reset != 0 clears both after reading. */
+int upside_hip_get_param_deriv_all(DerivEngine* engine, const char* node_name, int n_param, float* deriv);
+int upside_hip_param_deriv_accumulate(DerivEngine* engine, const char* node_name, const float* weights);
+int upside_hip_param_deriv_read(DerivEngine* engine, const char* node_name, int n_param, double* sum, long long* n_frame, int reset);
 const char* upside_hip_last_error(void);
 
 /* Per-kernel timing hooks used by bench.py.  With profiling enabled every interaction-graph / BP kernel

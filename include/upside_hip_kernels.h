@@ -363,6 +363,26 @@ int upk_nonlinear_coupling_param_deriv(const upk_launch_t* L, upk_coord_t input,
 /* sum over the elements of output component `comp` (hbond.cpp:436-448: n_hbond) */
 int upk_column_sum(const upk_launch_t* L, upk_coord_t c, int comp, int system, float* out);
 
+/* ---- parameter derivatives of ALL systems in one launch (upside_hip_get_param_deriv_all) ---------------------------
+ * The same quantities as the one-system launchers above, written whole (no zeroing needed) into table [n_system][n_param]
+ * (n_param = the node's get_param() size).  Deterministic: every entry is summed exactly in 64-bit fixed point in LDS and
+ * stored once, so a system's table is bit-identical run to run and whatever else shares its batch.  Off the MD path. */
+int upk_igraph_param_deriv_all(const upk_launch_t* L, const upk_igraph_t* G, int sens_mode, const float* sens1, const float* sens2,
+                               long sens_sys_stride, int sens_stride, float* table);
+int upk_rotamer_param_deriv_all(const upk_launch_t* L, const upk_rotamer_t* R, float* table);
+int upk_placement_param_deriv_all(const upk_launch_t* L, const upk_placement_t* P, upk_coord_t aff, upk_coord_t out, int n_param, float* table);
+int upk_nonlinear_coupling_param_deriv_all(const upk_launch_t* L, upk_coord_t input, const int* types, int n_coeff, int n_param,
+                                           float offset, float inv_dx, float* table);
+/* n_param = 2 + n_coeff */
+int upk_uniform_transform_param_deriv_all(const upk_launch_t* L, upk_coord_t in, const float* coeff, int n_coeff, float offset, float inv_dx,
+                                          float* table);
+int upk_linear_coupling_param_deriv_all(const upk_launch_t* L, upk_coord_t in, const int* types, int n_param, upk_coord_t inact,
+                                        int has_inact, int inact_dim, float* table);
+/* table [n_system][1] */
+int upk_column_sum_all(const upk_launch_t* L, upk_coord_t c, int comp, float* table);
+/* acc[p] += sum over s (ascending) of weight[s] * d[s][p], in double; weight NULL = all 1 */
+int upk_param_deriv_reduce(const upk_launch_t* L, const float* d, int n_param, const float* weight, double* acc);
+
 /* measured VALU issue ceilings of the device for the pair kernels' launch shape (one 1024-lane workgroup per CU): wave-level
  * fp32 FMA instructions per second, rates[0] for a dependent scalar chain, rates[1] with four independent chains per lane */
 int upk_calibrate_valu(double* rates);

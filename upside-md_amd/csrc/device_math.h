@@ -226,4 +226,18 @@ __device__ __forceinline__ void boxmuller(float& a, float& b, uint32_t u0, uint3
     a = sinf(ang) * r; b = cosf(ang) * r;
 }
 
+// fixed-point image of a float (|v| < 2^31): v * 2^32 as a 64-bit two's-complement integer, exact down to 2^-31.  Integer adds commute, so
+// sums accumulated through LDS atomics in any order are the EXACT sum of the contributions (and bit-reproducible); LDS integer
+// atomics run at full rate on gfx950, float ones at 3 cycles per lane (tools/ubench/lds_atomics.hip)
+__device__ __forceinline__ unsigned long long to_fixed32(float v) {
+    const float h = rintf(v);                                     // nearest integer; v - h is exact (|v| < 0.5: h = 0; else h within a factor 2 of v)
+    const int hi = (int)h, half = (int)((v - h) * 2147483648.f);  // |v - h| <= 0.5: the product is exact, |half| <= 2^30 (resolution 2^-31)
+    return ((unsigned long long)(unsigned)(hi + (half >> 31)) << 32) | (unsigned)(half << 1);   // hi * 2^32 + sign-extended 2 * half: 8 instructions
+}
+__device__ __forceinline__ float from_fixed32(unsigned long long a) { return (float)((double)(long long)a * 2.3283064365386963e-10); }
+__device__ __forceinline__ void lds_add_fixed(unsigned long long* p, float v) {
+    __hip_atomic_fetch_add(p, to_fixed32(v), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+}
+
+
 }  // namespace up

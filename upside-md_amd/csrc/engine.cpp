@@ -717,6 +717,49 @@ static void warn_removed_switches() {
 }
 void DerivEngine::sync() { ctx.flush(); hip_check(hipStreamSynchronize(ctx.stream), "hipStreamSynchronize"); }
 
+// ---- parameter derivatives of every system (upside_hip_get_param_deriv_all / _param_deriv_accumulate / _read) ----------------
+DerivEngine::ParamDeriv& DerivEngine::param_deriv_state(int node) {
+    DerivComputation* c = nodes.at(node).computation.get();
+    if (!c) throw string("impossible pointer value");
+    auto* b = dynamic_cast<BatchedParamDeriv*>(c);
+    const size_t n = b ? b->param_deriv_size() : c->get_param_deriv(0).size();
+    ParamDeriv& st = param_derivs[node];
+    if (n != st.n_param) { st.n_param = n; st.table.alloc(0); st.sum.alloc(0); st.n_frame = 0; }   // (set_param may change the size)
+    return st;
+}
+const float* DerivEngine::param_deriv_all(int node) {
+    ParamDeriv& st = param_deriv_state(node);
+    if (!st.n_param) return nullptr;
+    const int S = ctx.n_system;
+    if (!st.table.n) st.table.alloc((size_t)S * st.n_param);
+    DerivComputation* c = nodes[node].computation.get();
+    if (auto* b = dynamic_cast<BatchedParamDeriv*>(c)) { b->param_deriv_all(st.table.p); return st.table.p; }
+    vector<float> h((size_t)S * st.n_param);   // a node without the batched form: one system at a time
+    for (int s = 0; s < S; ++s) {
+        auto v = c->get_param_deriv(s);
+        if (v.size() != st.n_param) throw string("get_param_deriv returned a different size for system ") + to_string(s);
+        copy(v.begin(), v.end(), h.begin() + (size_t)s * st.n_param);
+    }
+    hip_check(hipMemcpyAsync(st.table.p, h.data(), h.size() * sizeof(float), hipMemcpyHostToDevice, ctx.stream), "H2D param_deriv");
+    sync();
+    return st.table.p;
+}
+void DerivEngine::param_deriv_accumulate(int node, const float* weights) {
+    const float* d = param_deriv_all(node);
+    ParamDeriv& st = param_derivs[node];
+    if (d) {
+        if (!st.sum.n) st.sum.alloc(st.n_param);
+        const float* w = nullptr;
+        if (weights) {
+            if (!st.weight.n) st.weight.alloc(ctx.n_system);
+            hip_check(hipMemcpyAsync(st.weight.p, weights, ctx.n_system * sizeof(float), hipMemcpyHostToDevice, ctx.stream), "H2D weights");
+            w = st.weight.p;
+        }
+        upk_check(upk_param_deriv_reduce(&ctx.L, d, (int)st.n_param, w, st.sum.p), "param_deriv_reduce");
+    }
+    ++st.n_frame;
+}
+
 void DerivEngine::check_device_errors() {
     sync();
     auto f = ctx.error_flag.download();

@@ -20,6 +20,18 @@ struct Pos : public CoordNode {   // deriv_engine.h:122-141
     void propagate_deriv() override {}
 };
 
+// Parameter derivatives of every system of the batch at once (upside_hip_get_param_deriv_all / _param_deriv_accumulate).
+// Engine-internal: the built-in nodes that override get_param_deriv implement it; the engine finds it by dynamic_cast, and
+// falls back to get_param_deriv(s) system by system for any other node (plug-ins are compiled against the class layout of
+// include/upside_hip_plugin.h, which this does not touch).
+struct BatchedParamDeriv {
+    virtual ~BatchedParamDeriv() {}
+    virtual size_t param_deriv_size() const = 0;   // = get_param_deriv(s).size(); 0 = no derivative
+    // enqueue, on the engine stream, the derivative of every system into dev [n_system][param_deriv_size()] (written whole),
+    // from the state of the last force pass; deterministic: a system's row does not depend on the rest of the batch
+    virtual void param_deriv_all(float* dev) = 0;
+};
+
 struct DerivEngine {   // deriv_engine.h:145-237
     struct Node {
         std::string name;
@@ -96,6 +108,18 @@ struct DerivEngine {   // deriv_engine.h:145-237
     void mc_step(uint64_t round);                      // every loaded sampler in the reference's order (pivot, jump): two
                                                        // energy evaluations + proposal + Metropolis each, every system
     void* comm = nullptr; void (*comm_free)(void*) = nullptr;   // replica exchange across GPUs (comm_rccl.cpp), owned by the engine
+    // per-node state of the batched parameter derivatives, allocated on first use
+    struct ParamDeriv {
+        size_t n_param = 0;
+        DevBuf<float> table;       // [S][n_param], the last param_deriv_all
+        DevBuf<double> sum;        // [n_param], sum over accumulate calls of sum_s weight[s] * table[s]
+        DevBuf<float> weight;      // [S], the weights of the last accumulate
+        long long n_frame = 0;     // accumulate calls since the last reset
+    };
+    std::map<int, ParamDeriv> param_derivs;
+    ParamDeriv& param_deriv_state(int node);          // n_param known, nothing allocated yet
+    const float* param_deriv_all(int node);            // enqueue every system's derivative; the device table [S][n_param]
+    void param_deriv_accumulate(int node, const float* weights);   // enqueue sum += weights . table; no synchronisation
     void check_device_errors();                // throws if a capacity overflow was flagged
     void sync();
 };

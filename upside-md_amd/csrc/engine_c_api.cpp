@@ -150,6 +150,48 @@ extern "C" int get_param_deriv(int n_param, float* deriv, DerivEngine* e, const 
 extern "C" int upside_hip_get_param_deriv(DerivEngine* e, const char* node_name, int system, int n_param, float* deriv) {
     API_TRY
     return param_deriv_of(n_param, deriv, e, node_name, system); API_CATCH(1) }
+// every system at once, deterministic (DerivEngine::param_deriv_all); n_param = the size of get_param_deriv, 0 for a node without one
+static DerivEngine::ParamDeriv& param_deriv_request(DerivEngine* e, const char* node_name, int n_param, const void* out) {
+    if (!node_name) throw string("node name is NULL");
+    const int node = e->get_idx(string(node_name), false);
+    if (node < 0) throw string("name not found: ") + node_name;
+    auto& st = e->param_deriv_state(node);
+    if (st.n_param != size_t(n_param)) throw string("Wrong number of parameters, expected ") + to_string(st.n_param) + " but got " + to_string(n_param);
+    if (n_param && !out) throw string("output array is NULL");
+    return st;
+}
+extern "C" int upside_hip_get_param_deriv_all(DerivEngine* e, const char* node_name, int n_param, float* deriv) {
+    API_TRY
+    auto& st = param_deriv_request(e, node_name, n_param, deriv);
+    if (!st.n_param) return 0;
+    const float* d = e->param_deriv_all(e->get_idx(node_name));
+    hip_check(hipMemcpyAsync(deriv, d, (size_t)e->ctx.n_system * st.n_param * sizeof(float), hipMemcpyDeviceToHost, e->ctx.stream), "D2H param_deriv");
+    e->sync();
+    return 0;
+    API_CATCH(1)
+}
+extern "C" int upside_hip_param_deriv_accumulate(DerivEngine* e, const char* node_name, const float* weights) {
+    API_TRY
+    if (!node_name) throw string("node name is NULL");
+    e->param_deriv_accumulate(e->get_idx(string(node_name)), weights);
+    return 0;
+    API_CATCH(1)
+}
+extern "C" int upside_hip_param_deriv_read(DerivEngine* e, const char* node_name, int n_param, double* sum, long long* n_frame, int reset) {
+    API_TRY
+    auto& st = param_deriv_request(e, node_name, n_param, sum);
+    if (!n_frame) throw string("n_frame is NULL");
+    if (st.n_param) {
+        if (st.sum.n) hip_check(hipMemcpyAsync(sum, st.sum.p, st.n_param * sizeof(double), hipMemcpyDeviceToHost, e->ctx.stream), "D2H param_deriv sum");
+        e->sync();
+        if (!st.sum.n) fill(sum, sum + st.n_param, 0.);
+        if (reset && st.sum.n) hip_check(hipMemsetAsync(st.sum.p, 0, st.n_param * sizeof(double), e->ctx.stream), "memset");
+    }
+    *n_frame = st.n_frame;
+    if (reset) st.n_frame = 0;
+    return 0;
+    API_CATCH(1)
+}
 
 extern "C" int get_output_dims(int* n_elem, int* elem_width, DerivEngine* e, const char* node_name) {
     API_TRY

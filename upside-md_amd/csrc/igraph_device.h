@@ -14,7 +14,7 @@
 //     64 pairs).  Rows of a batch have (nearly) the same length, so the groups run in lock step and the batch bookkeeping is
 //     uniform code, amortised over the batch's trips;
 //   * forward passes are gathers with a fixed summation order; backward passes visit a pair ONCE and hand the partner
-//     element's share to 64-bit fixed-point integer LDS atomics (to_fixed32 below), whose sums do not depend on the order of
+//     element's share to 64-bit fixed-point integer LDS atomics (to_fixed32, device_math.h), whose sums do not depend on the order of
 //     arrival -- no floating-point atomic decides a result, so trajectories are reproducible bit for bit.  (LDS float
 //     atomics run at 3 cycles per LANE on gfx950 -- tools/ubench/lds_atomics.hip: 192 cycles per wave instruction against
 //     <= 20 for integer ones -- which is what sank the float version of the one-visit pass that was tried first.)
@@ -146,10 +146,10 @@ __device__ __forceinline__ float quadspline_pair(const QuadShape& Q, P p, const 
 
 // Parameter derivative of one quadspline pair (bead_interaction.h:86-130): the value is linear in the spline
 // coefficients, so d(value)/d(coefficient) is the basis weight of that coefficient (spline.h:318-336, 375-392) times
-// the other factors of  wide + a1*a2*narrow.  `scale` (pair sensitivity) * those weights is added to the parameter
-// row `out` of the pair's type combination.  Not on the MD path: plain global atomics.
-template <typename P>
-__device__ __forceinline__ void quadspline_param_accum(const QuadShape& Q, P p, const float* x1, const float* x2, float scale, float* out) {
+// the other factors of  wide + a1*a2*narrow.  add(k, scale * weight) receives the 16 terms of the pair, k = offset in the
+// parameter row of the pair's type combination.
+template <typename P, typename Add>
+__device__ __forceinline__ void quadspline_param_visit(const QuadShape& Q, P p, const float* x1, const float* x2, float scale, Add add) {
     const f3 displace = mk3(x2[0] - x1[0], x2[1] - x1[1], x2[2] - x1[2]);
     const f3 rvec1 = mk3(x1[3], x1[4], x1[5]), rvec2 = mk3(x2[3], x2[4], x2[5]);
     const float dist2 = mag2(displace), inv_dist = rsqrtf(dist2);
@@ -172,11 +172,16 @@ __device__ __forceinline__ void quadspline_param_accum(const QuadShape& Q, P p, 
     }
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
-        atomicAdd(out + 2 * Q.ka + rbin + i, scale * br[i]);
-        atomicAdd(out + 2 * Q.ka + Q.k + rbin + i, scale * (a1 * a2 * br[i]));
-        atomicAdd(out + bin1 - 1 + i, scale * (a2 * narrow * b1[i]));
-        atomicAdd(out + Q.ka + bin2 - 1 + i, scale * (a1 * narrow * b2[i]));
+        add(2 * Q.ka + rbin + i, scale * br[i]);
+        add(2 * Q.ka + Q.k + rbin + i, scale * (a1 * a2 * br[i]));
+        add(bin1 - 1 + i, scale * (a2 * narrow * b1[i]));
+        add(Q.ka + bin2 - 1 + i, scale * (a1 * narrow * b2[i]));
     }
+}
+// the same into the parameter row `out` with plain global atomics (get_param_deriv of one system; not on the MD path)
+template <typename P>
+__device__ __forceinline__ void quadspline_param_accum(const QuadShape& Q, P p, const float* x1, const float* x2, float scale, float* out) {
+    quadspline_param_visit(Q, p, x1, x2, scale, [&](int k, float v) { atomicAdd(out + k, v); });
 }
 
 // environment.cpp:27-60.  d1: CB frame (6), d2: weighted side-chain bead (x, y, z, probability)
@@ -285,19 +290,7 @@ __device__ __forceinline__ void stage_table(float* lds, const float* __restrict_
 // is_compatible, bead_interaction.h:209-218, checked when the node is built) is kept as its upper triangle only (the host
 // packs it, upk_rotamer_t::param_tri): half the LDS
 __device__ __forceinline__ int tri_row(int lo, int hi, int nt) { return lo * nt - ((lo * (lo - 1)) >> 1) + (hi - lo); }   // lo <= hi
-// fixed-point image of a float (|v| < 2^31): v * 2^32 as a 64-bit two's-complement integer, exact down to 2^-31.  Integer adds commute, so
-// sums accumulated through LDS atomics in any order are the EXACT sum of the contributions (and bit-reproducible); LDS integer
-// atomics run at full rate on gfx950, float ones at 3 cycles per lane (tools/ubench/lds_atomics.hip)
-__device__ __forceinline__ unsigned long long to_fixed32(float v) {
-    const float h = rintf(v);                                     // nearest integer; v - h is exact (|v| < 0.5: h = 0; else h within a factor 2 of v)
-    const int hi = (int)h, half = (int)((v - h) * 2147483648.f);  // |v - h| <= 0.5: the product is exact, |half| <= 2^30 (resolution 2^-31)
-    return ((unsigned long long)(unsigned)(hi + (half >> 31)) << 32) | (unsigned)(half << 1);   // hi * 2^32 + sign-extended 2 * half: 8 instructions
-}
-__device__ __forceinline__ float from_fixed32(unsigned long long a) { return (float)((double)(long long)a * 2.3283064365386963e-10); }
-__device__ __forceinline__ void lds_add_fixed(unsigned long long* p, float v) {
-    __hip_atomic_fetch_add(p, to_fixed32(v), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-}
-
+// (to_fixed32 / lds_add_fixed: device_math.h)
 __device__ __forceinline__ void load_row8(float* x, const float* p) {   // one 32-byte packed element
     const float4 lo = *(const float4*)p, hi = *(const float4*)(p + 4);
     x[0] = lo.x; x[1] = lo.y; x[2] = lo.z; x[3] = lo.w; x[4] = hi.x; x[5] = hi.y; x[6] = hi.z; x[7] = hi.w;

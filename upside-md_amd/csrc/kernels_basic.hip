@@ -1344,22 +1344,28 @@ extern "C" int upk_swap_system_pairs(const upk_launch_t* L, upk_coord_t pos, int
 
 // placement_fixed_*: sum over the elements of a layer of the sensitivity rotated into the reference frame
 // (placement.cpp:144-148 called from :296, read back by :156-160)
-__global__ void k_placement_param_deriv(upk_placement_t P, upk_coord_t aff, upk_coord_t out, int s, float* __restrict__ table) {
-    const int ne = blockIdx.x * blockDim.x + threadIdx.x;
-    if (ne >= P.n_elem) return;
+// The terms of one element go to add(index in the table, value): global float atomics for one system (below), the
+// fixed-point LDS table of elem_param_deriv_all for every system at once.
+template <typename Add>
+__device__ __forceinline__ void placement_param_terms(const upk_placement_t& P, upk_coord_t aff, upk_coord_t out, int s, int ne, Add add) {
     const float* a = C_OUT(aff, s) + (size_t)P.affine_residue[ne] * aff.stride;
     float U[9]; quat_to_rot(U, a[3], a[4], a[5], a[6]);
     const float* sn = C_SENS(out, s) + (size_t)ne * out.stride;
-    float* t = table + (size_t)P.layer[ne] * P.n_pos_dim;
+    const int t = P.layer[ne] * P.n_pos_dim;
     int off = 0;
     for (int k = 0; k < P.n_sig; ++k) {
-        if (P.sig[k] == 0) { atomicAdd(t + off, sn[off]); off += 1; }
+        if (P.sig[k] == 0) { add(t + off, sn[off]); off += 1; }
         else {
             const f3 rs = apply_inverse_rotation(U, ld3(sn + off));
-            atomicAdd(t + off, rs.x); atomicAdd(t + off + 1, rs.y); atomicAdd(t + off + 2, rs.z);
+            add(t + off, rs.x); add(t + off + 1, rs.y); add(t + off + 2, rs.z);
             off += 3;
         }
     }
+}
+__global__ void k_placement_param_deriv(upk_placement_t P, upk_coord_t aff, upk_coord_t out, int s, float* __restrict__ table) {
+    const int ne = blockIdx.x * blockDim.x + threadIdx.x;
+    if (ne >= P.n_elem) return;
+    placement_param_terms(P, aff, out, s, ne, [&](int k, float v) { atomicAdd(table + k, v); });
 }
 extern "C" int upk_placement_param_deriv(const upk_launch_t* L, const upk_placement_t* P, upk_coord_t aff, upk_coord_t out, int system,
                                          float* table) {
@@ -1370,10 +1376,9 @@ extern "C" int upk_placement_param_deriv(const upk_launch_t* L, const upk_placem
 }
 
 // nonlinear_coupling: basis weights of the 4 coefficients under each element's coordinate (environment.cpp:375-389)
-__global__ void k_nonlinear_coupling_param_deriv(upk_coord_t input, const int* __restrict__ types, int n_coeff, float offset, float inv_dx,
-                                                 int s, float* __restrict__ table) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= input.n_elem) return;
+template <typename Add>
+__device__ __forceinline__ void nonlinear_coupling_param_terms(upk_coord_t input, const int* __restrict__ types, int n_coeff, float offset,
+                                                               float inv_dx, int s, int i, Add add) {
     const float x = (C_OUT(input, s)[(size_t)i * input.stride] - offset) * inv_dx;
     int bin; float w[4];
     if (x <= 1.f) { bin = 0; w[0] = 1.f / 6.f; w[1] = 2.f / 3.f; w[2] = 1.f / 6.f; w[3] = 0.f; }                       // spline.h:375-392
@@ -1387,7 +1392,13 @@ __global__ void k_nonlinear_coupling_param_deriv(upk_coord_t input, const int* _
         uniform_deBoor(w[2], der, 0.f, 0.f, 1.f, 0.f, excess);
         uniform_deBoor(w[3], der, 0.f, 0.f, 0.f, 1.f, excess);
     }
-    for (int k = 0; k < 4; ++k) atomicAdd(table + (size_t)types[i] * n_coeff + bin + k, w[k]);
+    for (int k = 0; k < 4; ++k) add(types[i] * n_coeff + bin + k, w[k]);
+}
+__global__ void k_nonlinear_coupling_param_deriv(upk_coord_t input, const int* __restrict__ types, int n_coeff, float offset, float inv_dx,
+                                                 int s, float* __restrict__ table) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= input.n_elem) return;
+    nonlinear_coupling_param_terms(input, types, n_coeff, offset, inv_dx, s, i, [&](int k, float v) { atomicAdd(table + k, v); });
 }
 extern "C" int upk_nonlinear_coupling_param_deriv(const upk_launch_t* L, upk_coord_t input, const int* types, int n_coeff, float offset,
                                                   float inv_dx, int system, float* table) {
@@ -1551,10 +1562,9 @@ extern "C" int upk_uniform_transform_bwd(const upk_launch_t* L, upk_coord_t in, 
     return launch_status();
 }
 // d(potential)/d(offset, inv_dx, coefficients) of uniform_transform (environment.cpp:205-221), one system
-__global__ void k_uniform_transform_param_deriv(upk_coord_t in, const float* __restrict__ coeff, int n_coeff, float offset, float inv_dx,
-                                                int s, float* __restrict__ table) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= in.n_elem) return;
+template <typename Add>
+__device__ __forceinline__ void uniform_transform_param_terms(upk_coord_t in, const float* __restrict__ coeff, int n_coeff, float offset,
+                                                              float inv_dx, int s, int i, Add add) {
     const float x0 = C_OUT(in, s)[(size_t)i * in.stride] - offset, x = x0 * inv_dx;
     float v, dv;
     clamped_deBoor_vd_scalar(v, dv, coeff, x, n_coeff);
@@ -1567,8 +1577,14 @@ __global__ void k_uniform_transform_param_deriv(upk_coord_t in, const float* __r
         uniform_deBoor(w[0], der, 1.f, 0.f, 0.f, 0.f, excess); uniform_deBoor(w[1], der, 0.f, 1.f, 0.f, 0.f, excess);
         uniform_deBoor(w[2], der, 0.f, 0.f, 1.f, 0.f, excess); uniform_deBoor(w[3], der, 0.f, 0.f, 0.f, 1.f, excess);
     }
-    atomicAdd(table, dv); atomicAdd(table + 1, dv * x0);
-    for (int k = 0; k < 4; ++k) atomicAdd(table + 2 + bin + k, w[k]);
+    add(0, dv); add(1, dv * x0);
+    for (int k = 0; k < 4; ++k) add(2 + bin + k, w[k]);
+}
+__global__ void k_uniform_transform_param_deriv(upk_coord_t in, const float* __restrict__ coeff, int n_coeff, float offset, float inv_dx,
+                                                int s, float* __restrict__ table) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= in.n_elem) return;
+    uniform_transform_param_terms(in, coeff, n_coeff, offset, inv_dx, s, i, [&](int k, float v) { atomicAdd(table + k, v); });
 }
 extern "C" int upk_uniform_transform_param_deriv(const upk_launch_t* L, upk_coord_t in, const float* coeff, int n_coeff, float offset,
                                                  float inv_dx, int system, float* table) {
@@ -1599,18 +1615,125 @@ extern "C" int upk_linear_coupling(const upk_launch_t* L, upk_coord_t in, const 
     return launch_status();
 }
 // environment.cpp:301-312 (note: act = 1 - inactivation there, not its square)
+template <typename Add>
+__device__ __forceinline__ void linear_coupling_param_terms(upk_coord_t in, const int* __restrict__ types, upk_coord_t inact, int has_inact,
+                                                            int inact_dim, int s, int i, Add add) {
+    const float act = has_inact ? 1.f - C_OUT(inact, s)[(size_t)i * inact.stride + inact_dim] : 1.f;
+    add(types[i], C_OUT(in, s)[(size_t)i * in.stride] * act);
+}
 __global__ void k_linear_coupling_param_deriv(upk_coord_t in, const int* __restrict__ types, upk_coord_t inact, int has_inact, int inact_dim,
                                               int s, float* __restrict__ table) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= in.n_elem) return;
-    const float act = has_inact ? 1.f - C_OUT(inact, s)[(size_t)i * inact.stride + inact_dim] : 1.f;
-    atomicAdd(table + types[i], C_OUT(in, s)[(size_t)i * in.stride] * act);
+    linear_coupling_param_terms(in, types, inact, has_inact, inact_dim, s, i, [&](int k, float v) { atomicAdd(table + k, v); });
 }
 extern "C" int upk_linear_coupling_param_deriv(const upk_launch_t* L, upk_coord_t in, const int* types, upk_coord_t inact, int has_inact,
                                                int inact_dim, int system, float* table) {
     UPK_FLUSH(L);
     if (system < 0 || system >= L->n_system) return 9101;
     hipLaunchKernelGGL(k_linear_coupling_param_deriv, grid1(in.n_elem, 1), dim3(UPK_BLOCK), 0, ST(L), in, types, inact, has_inact, inact_dim, system, table);
+    return launch_status();
+}
+
+// ------------------------------------------------------------------------------------------------
+// Parameter derivatives of the per-element nodes for ALL systems in one launch (upside_hip_get_param_deriv_all /
+// upside_hip_param_deriv_accumulate), into a [n_system][n_param] table that every launch writes whole.
+// One 256-lane workgroup per (slice of PD_ELEM_SLICE table entries, system) adds the terms of its system's elements to a
+// 64-bit fixed-point image of its slice in LDS (to_fixed32: integer adds are exact and commute, so an entry depends neither on
+// the order of arrival nor on the other systems of the batch -- no float atomic decides a value), then stores the slice as
+// fp32 with plain coalesced stores.  Overflow: an entry is exact while |sum| < 2^31; the terms are sensitivities, spline basis
+// weights (<= 1) and node outputs of one system's few hundred elements, orders of magnitude below.  Resolution 2^-32 per term.
+#define PD_ELEM_SLICE 4096     // 32 KiB of LDS: five workgroups per CU
+template <typename Terms>
+__device__ __forceinline__ void elem_param_deriv_all(int n_elem, int n_param, float* __restrict__ table, Terms terms) {
+    __shared__ unsigned long long acc[PD_ELEM_SLICE];
+    const int s = blockIdx.y, lo = blockIdx.x * PD_ELEM_SLICE;
+    const int n = n_param - lo < PD_ELEM_SLICE ? n_param - lo : PD_ELEM_SLICE;
+    for (int t = threadIdx.x; t < n; t += blockDim.x) acc[t] = 0ull;
+    __syncthreads();
+    auto add = [&](int k, float v) { const unsigned q = (unsigned)(k - lo); if (q < (unsigned)n) lds_add_fixed(acc + q, v); };
+    for (int i = threadIdx.x; i < n_elem; i += blockDim.x) terms(s, i, add);
+    __syncthreads();
+    float* out = table + (size_t)s * n_param + lo;
+    for (int t = threadIdx.x; t < n; t += blockDim.x) out[t] = from_fixed32(acc[t]);
+}
+static inline dim3 pd_elem_grid(int n_param, int S) { return dim3((unsigned)((n_param + PD_ELEM_SLICE - 1) / PD_ELEM_SLICE), (unsigned)S); }
+
+__global__ void __launch_bounds__(UPK_BLOCK) k_placement_param_deriv_all(upk_placement_t P, upk_coord_t aff, upk_coord_t out, int n_param,
+                                                                         float* __restrict__ table) {
+    elem_param_deriv_all(P.n_elem, n_param, table, [&](int s, int i, auto add) { placement_param_terms(P, aff, out, s, i, add); });
+}
+extern "C" int upk_placement_param_deriv_all(const upk_launch_t* L, const upk_placement_t* P, upk_coord_t aff, upk_coord_t out, int n_param,
+                                             float* table) {
+    UPK_FLUSH(L);
+    if (n_param <= 0) return 0;
+    hipLaunchKernelGGL(k_placement_param_deriv_all, pd_elem_grid(n_param, L->n_system), dim3(UPK_BLOCK), 0, ST(L), *P, aff, out, n_param, table);
+    return launch_status();
+}
+__global__ void __launch_bounds__(UPK_BLOCK) k_nonlinear_coupling_param_deriv_all(upk_coord_t input, const int* __restrict__ types, int n_coeff,
+                                                                                  int n_param, float offset, float inv_dx, float* __restrict__ table) {
+    elem_param_deriv_all(input.n_elem, n_param, table,
+                         [&](int s, int i, auto add) { nonlinear_coupling_param_terms(input, types, n_coeff, offset, inv_dx, s, i, add); });
+}
+extern "C" int upk_nonlinear_coupling_param_deriv_all(const upk_launch_t* L, upk_coord_t input, const int* types, int n_coeff, int n_param,
+                                                      float offset, float inv_dx, float* table) {
+    UPK_FLUSH(L);
+    if (n_param <= 0) return 0;
+    hipLaunchKernelGGL(k_nonlinear_coupling_param_deriv_all, pd_elem_grid(n_param, L->n_system), dim3(UPK_BLOCK), 0, ST(L), input, types, n_coeff,
+                       n_param, offset, inv_dx, table);
+    return launch_status();
+}
+__global__ void __launch_bounds__(UPK_BLOCK) k_uniform_transform_param_deriv_all(upk_coord_t in, const float* __restrict__ coeff, int n_coeff,
+                                                                                 float offset, float inv_dx, float* __restrict__ table) {
+    elem_param_deriv_all(in.n_elem, 2 + n_coeff, table,
+                         [&](int s, int i, auto add) { uniform_transform_param_terms(in, coeff, n_coeff, offset, inv_dx, s, i, add); });
+}
+extern "C" int upk_uniform_transform_param_deriv_all(const upk_launch_t* L, upk_coord_t in, const float* coeff, int n_coeff, float offset,
+                                                     float inv_dx, float* table) {
+    UPK_FLUSH(L);
+    hipLaunchKernelGGL(k_uniform_transform_param_deriv_all, pd_elem_grid(2 + n_coeff, L->n_system), dim3(UPK_BLOCK), 0, ST(L), in, coeff, n_coeff,
+                       offset, inv_dx, table);
+    return launch_status();
+}
+__global__ void __launch_bounds__(UPK_BLOCK) k_linear_coupling_param_deriv_all(upk_coord_t in, const int* __restrict__ types, int n_param,
+                                                                               upk_coord_t inact, int has_inact, int inact_dim,
+                                                                               float* __restrict__ table) {
+    elem_param_deriv_all(in.n_elem, n_param, table,
+                         [&](int s, int i, auto add) { linear_coupling_param_terms(in, types, inact, has_inact, inact_dim, s, i, add); });
+}
+extern "C" int upk_linear_coupling_param_deriv_all(const upk_launch_t* L, upk_coord_t in, const int* types, int n_param, upk_coord_t inact,
+                                                   int has_inact, int inact_dim, float* table) {
+    UPK_FLUSH(L);
+    if (n_param <= 0) return 0;
+    hipLaunchKernelGGL(k_linear_coupling_param_deriv_all, pd_elem_grid(n_param, L->n_system), dim3(UPK_BLOCK), 0, ST(L), in, types, n_param, inact,
+                       has_inact, inact_dim, table);
+    return launch_status();
+}
+__global__ void __launch_bounds__(UPK_BLOCK) k_column_sum_all(upk_coord_t c, int comp, float* __restrict__ table) {
+    elem_param_deriv_all(c.n_elem, 1, table, [&](int s, int i, auto add) { add(0, C_OUT(c, s)[(size_t)i * c.stride + comp]); });
+}
+extern "C" int upk_column_sum_all(const upk_launch_t* L, upk_coord_t c, int comp, float* table) {
+    UPK_FLUSH(L);
+    hipLaunchKernelGGL(k_column_sum_all, dim3(1, L->n_system), dim3(UPK_BLOCK), 0, ST(L), c, comp, table);
+    return launch_status();
+}
+
+// acc[p] += sum_s weight[s] * d[s][p] in double, s ascending, one lane per parameter (upside_hip_param_deriv_accumulate):
+// the same order whatever the launch shape, so the accumulator is bit-reproducible.  weight == nullptr: all 1.
+__global__ void __launch_bounds__(64) k_param_deriv_reduce(const float* __restrict__ d, int S, int n_param, const float* __restrict__ weight,
+                                                           double* __restrict__ acc) {
+    const int p = blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= n_param) return;
+    const float* col = d + p;
+    double a = acc[p];
+#pragma unroll 16
+    for (int s = 0; s < S; ++s) a += (double)(weight ? weight[s] : 1.f) * (double)col[(size_t)s * n_param];
+    acc[p] = a;
+}
+extern "C" int upk_param_deriv_reduce(const upk_launch_t* L, const float* d, int n_param, const float* weight, double* acc) {
+    UPK_FLUSH(L);
+    if (n_param <= 0) return 0;
+    hipLaunchKernelGGL(k_param_deriv_reduce, dim3((unsigned)((n_param + 63) / 64)), dim3(64), 0, ST(L), d, L->n_system, n_param, weight, acc);
     return launch_status();
 }
 

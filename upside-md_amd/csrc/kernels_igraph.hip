@@ -724,6 +724,32 @@ extern "C" int upk_igraph_inrange(const upk_launch_t* L, const upk_igraph_t* G, 
 // Parameter derivative of one system's pair potential (interaction_graph.h:404-416, 497-503, 537-543): every
 // in-range pair adds  pair_sensitivity * d(pair value)/d(interaction_param[type1][type2][:])  to `table`
 // ([n_type1][n_type2][n_param], zeroed by the caller).  sens_mode as in k_igraph_grad.  Off the MD path.
+// The terms of one in-range pair (parameter row p, sensitivity ps) go to add(offset in the row, value).
+template <typename Add>
+__device__ __forceinline__ void igraph_pair_param_terms(const upk_igraph_t& G, const QuadShape& Q, const float* p, const float* xr,
+                                                        const float* xo, float ps, Add add) {
+    if (G.itype == UPK_IT_HBOND_COVERAGE) {                      // hbond.cpp:278-283
+        const float one_m = 1.f - xr[6];
+        quadspline_param_visit(Q, p, xr, xo, ps * (one_m * one_m), add);
+    } else if (G.itype == UPK_IT_RADIAL || G.itype == UPK_IT_HBOND_SC_RADIAL) {   // sidechain_radial.cpp:63-77
+        const float dist = sqrtf(sqr(xr[0] - xo[0]) + sqr(xr[1] - xo[1]) + sqr(xr[2] - xo[2]));
+        const float x = p[0] * dist;
+        float v, dv;
+        clamped_deBoor_vd_scalar(v, dv, p + 1, x, 16);
+        add(0, ps * dv * dist);
+        int bin; float w[4];
+        if (x <= 1.f) { bin = 0; w[0] = 1.f / 6.f; w[1] = 2.f / 3.f; w[2] = 1.f / 6.f; w[3] = 0.f; }
+        else if (x >= 14.f) { bin = 12; w[0] = 0.f; w[1] = 1.f / 6.f; w[2] = 2.f / 3.f; w[3] = 1.f / 6.f; }
+        else { const int xb = (int)x; bin = xb - 1; float db[4]; bspline_basis(x - (float)xb, w, db); }
+        for (int k = 0; k < 4; ++k) add(1 + bin + k, ps * w[k]);
+    }   // environment.cpp:62-65: "not implemented" = zeros; protein_hbond has no get_param_deriv in the reference
+}
+__device__ __forceinline__ float igraph_pair_sens(int sens_mode, const float* S1, const float* S2, int sens_stride, int row, int j) {
+    float ps = sens_mode == 0 ? 1.f : 0.f;
+    if (sens_mode == 1 || sens_mode == 3) ps += S1[(size_t)row * sens_stride];
+    if (sens_mode == 2 || sens_mode == 3) ps += S2[(size_t)j * sens_stride];
+    return ps;
+}
 __global__ void k_igraph_param_deriv(upk_igraph_t G, int s, int sens_mode, const float* __restrict__ sens1, const float* __restrict__ sens2,
                                      long sens_sys_stride, int sens_stride, float* __restrict__ table) {
     const int lane = threadIdx.x & 63;
@@ -742,28 +768,11 @@ __global__ void k_igraph_param_deriv(upk_igraph_t G, int s, int sens_mode, const
             float xo[8];
             load_elem(xo, G.node2, s, G.loc2[j], G.dim2);
             if (!(dist2_exact(xr[0], xr[1], xr[2], xo[0], xo[1], xo[2]) < cut2)) continue;
-            float ps = sens_mode == 0 ? 1.f : 0.f;
-            if (sens_mode == 1 || sens_mode == 3) ps += S1[(size_t)row * sens_stride];
-            if (sens_mode == 2 || sens_mode == 3) ps += S2[(size_t)j * sens_stride];
+            if (G.symmetric && j <= row) continue;                       // each pair once (i1 < i2)
+            const float ps = igraph_pair_sens(sens_mode, S1, S2, sens_stride, row, j);
             const size_t prow = (size_t)(t1 * G.n_type2 + G.type2[j]) * G.n_param;
             float* out = table + prow;
-            if (G.itype == UPK_IT_HBOND_COVERAGE) {                      // hbond.cpp:278-283
-                const float one_m = 1.f - xr[6];
-                quadspline_param_accum(Q, G.param + prow, xr, xo, ps * (one_m * one_m), out);
-            } else if (G.itype == UPK_IT_RADIAL || G.itype == UPK_IT_HBOND_SC_RADIAL) {   // sidechain_radial.cpp:63-77
-                if (G.symmetric && j <= row) continue;                                  // each pair once (i1 < i2)
-                const float* p = G.param + prow;
-                const float dist = sqrtf(sqr(xr[0] - xo[0]) + sqr(xr[1] - xo[1]) + sqr(xr[2] - xo[2]));
-                const float x = p[0] * dist;
-                float v, dv;
-                clamped_deBoor_vd_scalar(v, dv, p + 1, x, 16);
-                atomicAdd(out, ps * dv * dist);
-                int bin; float w[4];
-                if (x <= 1.f) { bin = 0; w[0] = 1.f / 6.f; w[1] = 2.f / 3.f; w[2] = 1.f / 6.f; w[3] = 0.f; }
-                else if (x >= 14.f) { bin = 12; w[0] = 0.f; w[1] = 1.f / 6.f; w[2] = 2.f / 3.f; w[3] = 1.f / 6.f; }
-                else { const int xb = (int)x; bin = xb - 1; float db[4]; bspline_basis(x - (float)xb, w, db); }
-                for (int k = 0; k < 4; ++k) atomicAdd(out + 1 + bin + k, ps * w[k]);
-            }   // environment.cpp:62-65: "not implemented" = zeros; protein_hbond has no get_param_deriv in the reference
+            igraph_pair_param_terms(G, Q, G.param + prow, xr, xo, ps, [&](int q, float v) { atomicAdd(out + q, v); });
         }
     }
 }
@@ -774,5 +783,75 @@ extern "C" int upk_igraph_param_deriv(const upk_launch_t* L, const upk_igraph_t*
     if (G->itype == UPK_IT_ROTAMER) return 9102;   // upk_rotamer_param_deriv owns the pair sensitivities of that graph
     hipLaunchKernelGGL(k_igraph_param_deriv, dim3(rows_grid(G->n1)), dim3(IG_BLOCK), 0, ST(L), *G, system,
                        sens_mode, sens1, sens2, sens_sys_stride, sens_stride, table);
+    return launch_status();
+}
+
+// Parameter derivatives of ALL systems in one launch (upside_hip_get_param_deriv_all), into [n_system][n_type1][n_type2][n_param],
+// every entry written.  grid: x = slice of the table's type-pair rows (pd_table_slices), y = system; one workgroup adds the terms
+// of the pairs of its system whose row lies in its slice to a 64-bit fixed-point image of the slice in LDS (to_fixed32: integer
+// adds are exact and commute, so an entry depends neither on the order of arrival nor on the other systems of the batch -- no
+// float atomic decides a value) and stores it as fp32 with plain coalesced stores.  Pairs of other slices are skipped before
+// their spline evaluation.  Overflow: an entry is exact while |sum| < 2^31; it sums, over the in-range pairs of one type pair of
+// one system, sensitivity (a coverage's or a bead's, O(1)) x basis weight (<= 1) x spline values (O(10)), far below.
+__global__ void __launch_bounds__(IG_BLOCK) k_igraph_param_deriv_all(upk_igraph_t G, int rows_per_slice, int sens_mode, const float* __restrict__ sens1,
+                                                                     const float* __restrict__ sens2, long sens_sys_stride, int sens_stride,
+                                                                     float* __restrict__ table) {
+    extern __shared__ unsigned long long pd_acc[];
+    const int s = blockIdx.y, lane = threadIdx.x & 63;
+    const int n_rows = G.n_type1 * G.n_type2;
+    const int r_lo = blockIdx.x * rows_per_slice, r_hi = min(r_lo + rows_per_slice, n_rows);
+    const int n_acc = (r_hi - r_lo) * G.n_param;
+    for (int t = threadIdx.x; t < n_acc; t += blockDim.x) pd_acc[t] = 0ull;
+    __syncthreads();
+    const float cut2 = G.cutoff * G.cutoff;
+    const float* S1 = sens1 ? sens1 + (size_t)s * sens_sys_stride : nullptr;
+    const float* S2 = sens2 ? sens2 + (size_t)s * sens_sys_stride : nullptr;
+    const QuadShape Q = quad_shape(G);
+    for (int row = threadIdx.x >> 6; row < G.n1; row += blockDim.x >> 6) {
+        const size_t row_at = ((size_t)s * G.n1 + row) * G.cap1;
+        const int cnt = G.cnt1[(size_t)s * G.n1 + row];
+        float xr[8];
+        load_elem(xr, G.node1, s, G.loc1[row], G.dim1);
+        const int t1 = G.type1[row];
+        for (int k = lane; k < cnt; k += 64) {
+            const int j = list_word_at(G.nbr1, row_at + k, G.word16);
+            const int trow = t1 * G.n_type2 + G.type2[j];
+            if (trow < r_lo || trow >= r_hi) continue;
+            float xo[8];
+            load_elem(xo, G.node2, s, G.loc2[j], G.dim2);
+            if (!(dist2_exact(xr[0], xr[1], xr[2], xo[0], xo[1], xo[2]) < cut2)) continue;
+            if (G.symmetric && j <= row) continue;
+            const float ps = igraph_pair_sens(sens_mode, S1, S2, sens_stride, row, j);
+            unsigned long long* a = pd_acc + (size_t)(trow - r_lo) * G.n_param;
+            igraph_pair_param_terms(G, Q, G.param + (size_t)trow * G.n_param, xr, xo, ps,
+                                    [&](int q, float v) { if ((unsigned)q < (unsigned)G.n_param) lds_add_fixed(a + q, v); });
+        }
+    }
+    __syncthreads();
+    float* out = table + ((size_t)s * n_rows + r_lo) * G.n_param;
+    for (int t = threadIdx.x; t < n_acc; t += blockDim.x) out[t] = from_fixed32(pd_acc[t]);
+}
+// rows of n_param entries per workgroup so that a slice's fixed-point image fits the LDS (the pair passes' 158 KiB); 0: one row
+// alone does not fit
+static int pd_table_slices(int n_rows, int n_param, int& n_slice) {
+    const size_t row_bytes = (size_t)(n_param > 0 ? n_param : 1) * sizeof(unsigned long long);
+    const int fit = (int)((size_t)158 * 1024 / row_bytes);
+    if (fit < 1 || n_rows < 1) { n_slice = 0; return 0; }
+    n_slice = (n_rows + fit - 1) / fit;
+    return (n_rows + n_slice - 1) / n_slice;      // balanced slices
+}
+extern "C" int upk_igraph_param_deriv_all(const upk_launch_t* L, const upk_igraph_t* G, int sens_mode, const float* sens1, const float* sens2,
+                                          long sens_sys_stride, int sens_stride, float* table) {
+    UPK_FLUSH(L);
+    if (G->itype == UPK_IT_ROTAMER) return 9102;
+    const size_t n = (size_t)L->n_system * G->n_type1 * G->n_type2 * G->n_param;
+    if (G->itype != UPK_IT_HBOND_COVERAGE && G->itype != UPK_IT_RADIAL && G->itype != UPK_IT_HBOND_SC_RADIAL) {   // zeros, as above
+        if (n) { const hipError_t e = hipMemsetAsync(table, 0, n * sizeof(float), ST(L)); if (e != hipSuccess) return (int)e; }
+        return 0;
+    }
+    int n_slice; const int rows = pd_table_slices(G->n_type1 * G->n_type2, G->n_param, n_slice);
+    if (!n_slice) return n ? 9103 : 0;
+    hipLaunchKernelGGL(k_igraph_param_deriv_all, dim3(n_slice, L->n_system), dim3(IG_BLOCK), (size_t)rows * G->n_param * sizeof(unsigned long long),
+                       ST(L), *G, rows, sens_mode, sens1, sens2, sens_sys_stride, sens_stride, table);
     return launch_status();
 }

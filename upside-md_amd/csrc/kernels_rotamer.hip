@@ -806,6 +806,77 @@ extern "C" int upk_rotamer_param_deriv(const upk_launch_t* L, const upk_rotamer_
     return launch_status();
 }
 
+// The same for ALL systems in one launch (upside_hip_get_param_deriv_all), into [n_system][n_type][n_type][n_param], every entry
+// written: the pairs, pair sensitivities and row_first type ordering of k_rotamer_param_deriv.  grid: x = slice of the table's
+// type-pair rows, y = system.  A 1024-lane workgroup walks every row of its system (one wavefront per row, lanes over the
+// partners), skips the pairs whose type-pair row lies outside its slice before their spline evaluation, and adds the 16 terms of
+// the others to a 64-bit fixed-point image of the slice in LDS (lds_add_fixed: one ds_add_u64 per term, exact and commutative, so
+// an entry depends neither on the order of arrival nor on the other systems of the batch -- no float atomic decides a value);
+// then it stores the slice as fp32 with plain coalesced stores.  The 10 A table (20 x 20 x 40 x 8 B = 125 KiB) is one slice,
+// the 7 A one (20 x 20 x 62 x 8 B = 194 KiB) two.
+// Overflow: an entry is exact while |sum| < 2^31.  A term is pair sensitivity (a probability, <= 1) x basis weight (<= 1) x at
+// most a product of two angular spline values and a radial one (O(10) for the shipped tables); an entry sums the pairs of one
+// type pair of one system (< 10^5): below 10^7.  Resolution 2^-32 per term.
+__global__ void __launch_bounds__(1024) k_rotamer_param_deriv_all(upk_rotamer_t R, int rows_per_slice, float* __restrict__ table) {
+    extern __shared__ unsigned long long pd_acc[];
+    const upk_igraph_t& G = R.G;
+    const int s = blockIdx.y, lane = threadIdx.x & 63;
+    const int n_rows = G.n_type1 * G.n_type2;
+    const int r_lo = blockIdx.x * rows_per_slice, r_hi = min(r_lo + rows_per_slice, n_rows);
+    const int n_acc = (r_hi - r_lo) * G.n_param;
+    for (int t = threadIdx.x; t < n_acc; t += blockDim.x) pd_acc[t] = 0ull;
+    __syncthreads();
+    const float cut2 = G.cutoff * G.cutoff;
+    const float* base = G.node1.out + (size_t)s * G.node1.n_elem * G.node1.stride;
+    const float* marg = R.marg + (size_t)s * R.slot_cap * 36;
+    const float* nbm = R.nb_cur + (size_t)s * R.n_node * 6;
+    const QuadShape Q = quad_shape(G);
+    for (int row = threadIdx.x >> 6; row < G.n1; row += blockDim.x >> 6) {
+        const int* nbr = G.nbr1 + ((size_t)s * G.n1 + row) * G.cap1;
+        const int cnt = G.cnt1[(size_t)s * G.n1 + row];
+        float xr[6];
+#pragma unroll
+        for (int c = 0; c < 6; ++c) xr[c] = base[(size_t)G.loc1[row] * G.node1.stride + c];
+        const int mr = R.bead_meta[row], a = R.bead_node[row];
+        const int ra = (mr >> 8) & 0xF, na = (mr >> 12) & 0xF;
+        for (int k = lane; k < cnt; k += 64) {
+            const int w = nbr[k];
+            const int j = w & ((1 << UPK_ROT_J_BITS) - 1), sl = (int)((unsigned)w >> UPK_ROT_J_BITS);
+            const int mo = R.bead_meta[j];
+            const bool row_first = !R.bead_orig || R.bead_orig[row] < R.bead_orig[j];
+            const int trow = row_first ? (mr & 0xFF) * G.n_type2 + (mo & 0xFF) : (mo & 0xFF) * G.n_type2 + (mr & 0xFF);
+            if (trow < r_lo || trow >= r_hi) continue;
+            float xo[6];
+#pragma unroll
+            for (int c = 0; c < 6; ++c) xo[c] = base[(size_t)G.loc1[j] * G.node1.stride + c];
+            if (!(dist2_exact(xr[0], xr[1], xr[2], xo[0], xo[1], xo[2]) < cut2)) continue;
+            const int b = R.bead_node[j];
+            const int rb = (mo >> 8) & 0xF, nb = (mo >> 12) & 0xF;
+            float ps;
+            if (na == 1 && nb == 1) ps = 1.f;
+            else if (na == 1) ps = nbm[b * 6 + rb];
+            else if (nb == 1) ps = nbm[a * 6 + ra];
+            else ps = sl == UPK_ROT_SLOT_NONE ? 0.f : marg[PIDX6(R.slot_cap, sl, a < b ? ra : rb, a < b ? rb : ra)];
+            unsigned long long* acc = pd_acc + (size_t)(trow - r_lo) * G.n_param;
+            const float* p = G.param + (size_t)trow * G.n_param;
+            auto add = [&](int q, float v) { if ((unsigned)q < (unsigned)G.n_param) lds_add_fixed(acc + q, v); };   // (a NaN coordinate's bin)
+            if (row_first) quadspline_param_visit(Q, p, xr, xo, ps, add);
+            else quadspline_param_visit(Q, p, xo, xr, ps, add);
+        }
+    }
+    __syncthreads();
+    float* out = table + ((size_t)s * n_rows + r_lo) * G.n_param;
+    for (int t = threadIdx.x; t < n_acc; t += blockDim.x) out[t] = from_fixed32(pd_acc[t]);
+}
+extern "C" int upk_rotamer_param_deriv_all(const upk_launch_t* L, const upk_rotamer_t* R, float* table) {
+    UPK_FLUSH(L);
+    int n_slice; const int rows = pd_table_slices(R->G.n_type1 * R->G.n_type2, R->G.n_param, n_slice);
+    if (!n_slice) return 9103;
+    hipLaunchKernelGGL(k_rotamer_param_deriv_all, dim3(n_slice, L->n_system), dim3(1024), (size_t)rows * R->G.n_param * sizeof(unsigned long long),
+                       ST(L), *R, rows, table);
+    return launch_status();
+}
+
 // ------------------------------------------------------------------------------------------------
 // belief propagation: one persistent workgroup per system (rotamer.cpp:1005-1061)
 __device__ __forceinline__ float block_max(float v, float* scratch) {

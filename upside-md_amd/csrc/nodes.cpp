@@ -212,7 +212,7 @@ static vector<float> param_deriv_table(DeviceCtx* ctx, size_t n, F launch) {
 
 // ---------------------------------------------------------------------------------------------------
 // placement: placement.cpp:233-325.  signature: 0 scalar, 1 vector, 2 point
-struct PlacementNode : public CoordNode {
+struct PlacementNode : public CoordNode, BatchedParamDeriv {
     CoordNode& alignment; CoordNode* rama;
     upk_placement_t P;
     DevBuf<int> affine_residue, layer, rama_residue; DevBuf<float> fixed_data, spline_coeff, rama_deriv;
@@ -284,6 +284,10 @@ struct PlacementNode : public CoordNode {
         if (rama) return vector<float>();
         return param_deriv_table(ctx, host_fixed.size(), [&](float* t) {
             upk_check(upk_placement_param_deriv(&ctx->L, &P, alignment.coord(), coord(), system, t), "placement_param_deriv"); });
+    }
+    size_t param_deriv_size() const override { return rama ? 0 : host_fixed.size(); }
+    void param_deriv_all(float* dev) override {
+        upk_check(upk_placement_param_deriv_all(&ctx->L, &P, alignment.coord(), coord(), (int)host_fixed.size(), dev), "placement_param_deriv_all");
     }
     void set_param(const vector<float>& p) override {
         if (rama) return;
@@ -762,7 +766,7 @@ struct ProteinHBond : public CoordNode {
 RegisterNodeType<Builtin<ProteinHBond>, 1> hbond_node("protein_hbond");
 
 // hbond_coverage: hbond.cpp:371-414
-struct HBondCoverage : public CoordNode {
+struct HBondCoverage : public CoordNode, BatchedParamDeriv {
     IGraphHost ig;
     HBondCoverage(DeviceCtx* c, hid_t_compat grp, CoordNode& infer_, CoordNode& sidechains_)
         : CoordNode(c, (int)dset_size(1, H(grp), "index2")[0], 1), ig(c, H(grp), UPK_IT_HBOND_COVERAGE, &infer_, &sidechains_) {
@@ -804,6 +808,11 @@ struct HBondCoverage : public CoordNode {
         return param_deriv_table(ctx, ig.param.size(), [&](float* t) {
             upk_check(upk_igraph_param_deriv(&ctx->L, &ig.G, system, 2, nullptr, sens.p, sys_stride(), stride, t), "hbond_coverage param_deriv"); });
     }
+    size_t param_deriv_size() const override { return ig.param.size(); }
+    void param_deriv_all(float* dev) override {
+        ig.ensure_all_sides();
+        upk_check(upk_igraph_param_deriv_all(&ctx->L, &ig.G, 2, nullptr, sens.p, sys_stride(), stride, dev), "hbond_coverage param_deriv_all");
+    }
     vector<float> get_value_by_name(const char* log_name) override {
         if (!strcmp(log_name, "count_edges_by_type")) return ig.count_edges_by_type(0);
         throw string("Value ") + log_name + string(" not implemented");
@@ -812,7 +821,7 @@ struct HBondCoverage : public CoordNode {
 RegisterNodeType<Builtin<HBondCoverage>, 2> coverage_node("hbond_coverage");
 
 // environment_coverage: environment.cpp:71-109
-struct EnvironmentCoverage : public CoordNode {
+struct EnvironmentCoverage : public CoordNode, BatchedParamDeriv {
     IGraphHost ig;
     EnvironmentCoverage(DeviceCtx* c, hid_t_compat grp, CoordNode& cb_pos_, CoordNode& weighted_sidechains_)
         : CoordNode(c, (int)dset_size(1, H(grp), "index1")[0], 1), ig(c, H(grp), UPK_IT_ENVIRONMENT, &cb_pos_, &weighted_sidechains_) {
@@ -835,11 +844,15 @@ struct EnvironmentCoverage : public CoordNode {
         return param_deriv_table(ctx, ig.param.size(), [&](float* t) {
             upk_check(upk_igraph_param_deriv(&ctx->L, &ig.G, system, 1, sens.p, nullptr, sys_stride(), stride, t), "environment_coverage param_deriv"); });
     }
+    size_t param_deriv_size() const override { return ig.param.size(); }
+    void param_deriv_all(float* dev) override {   // all zeros (no pair is visited)
+        upk_check(upk_igraph_param_deriv_all(&ctx->L, &ig.G, 1, sens.p, nullptr, sys_stride(), stride, dev), "environment_coverage param_deriv_all");
+    }
 };
 RegisterNodeType<Builtin<EnvironmentCoverage>, 2> environment_coverage_node("environment_coverage");
 
 // hbond_energy: hbond.cpp:417-456
-struct HBondEnergy : public HBondCounter {
+struct HBondEnergy : public HBondCounter, BatchedParamDeriv {
     CoordNode& protein_hbond; float E_protein;
     HBondEnergy(DeviceCtx* c, hid_t_compat grp, CoordNode& ph) : HBondCounter(c), protein_hbond(ph), E_protein(attr<float>(H(grp), ".", "protein_hbond_energy")) {
         check_elem_width(ph, 7);
@@ -854,6 +867,8 @@ struct HBondEnergy : public HBondCounter {
     vector<float> get_param_deriv(int system) override {   // hbond.cpp:447-448: n_hbond of the last evaluation
         return param_deriv_table(ctx, 1, [&](float* t) { upk_check(upk_column_sum(&ctx->L, protein_hbond.coord(), 6, system, t), "hbond_energy param_deriv"); });
     }
+    size_t param_deriv_size() const override { return 1; }
+    void param_deriv_all(float* dev) override { upk_check(upk_column_sum_all(&ctx->L, protein_hbond.coord(), 6, dev), "hbond_energy param_deriv_all"); }
     void set_param(const vector<float>& p) override {
         if (p.size() != 1u) throw string("expected 1 param to hbond_energy but got " + to_string(p.size()));
         E_protein = p[0];
@@ -880,7 +895,7 @@ struct WeightedPos : public CoordNode {
 RegisterNodeType<Builtin<WeightedPos>, 2> weighted_pos_node("weighted_pos");
 
 // nonlinear_coupling: environment.cpp:324-397
-struct NonlinearCoupling : public PotentialNode {
+struct NonlinearCoupling : public PotentialNode, BatchedParamDeriv {
     CoordNode& input; int n_restype, n_coeff; float spline_offset, spline_inv_dx;
     vector<float> coeff; DevBuf<float> d_coeff; DevBuf<int> types;
     NonlinearCoupling(DeviceCtx* c, hid_t_compat grp, CoordNode& input_) : PotentialNode(c), input(input_) {
@@ -910,6 +925,11 @@ struct NonlinearCoupling : public PotentialNode {
     vector<float> get_param_deriv(int system) override {   // environment.cpp:375-389
         return param_deriv_table(ctx, coeff.size(), [&](float* t) {
             upk_check(upk_nonlinear_coupling_param_deriv(&ctx->L, input.coord(), types.p, n_coeff, spline_offset, spline_inv_dx, system, t), "nonlinear_coupling param_deriv"); });
+    }
+    size_t param_deriv_size() const override { return coeff.size(); }
+    void param_deriv_all(float* dev) override {
+        upk_check(upk_nonlinear_coupling_param_deriv_all(&ctx->L, input.coord(), types.p, n_coeff, (int)coeff.size(), spline_offset, spline_inv_dx, dev),
+                  "nonlinear_coupling param_deriv_all");
     }
     void set_param(const vector<float>& p) override {
         if (p.size() != coeff.size()) throw string("attempting to change size of coeff vector on set_param");
@@ -1023,7 +1043,7 @@ RegisterNodeType<Builtin<ContactEnergy>, 1> contact_node("contact");
 // radial (symmetric, sidechain_radial.cpp:81-104) and hbond_sc_radial (two nodes, :107-136): the sum over in-range pairs of
 // a clamped spline of their distance; every pair has sensitivity 1.  Old-style potentials without shipped parameters:
 // they run on the generic per-row kernels (`k_igraph_rowsum` / `k_igraph_grad`), not on the LDS-staged ones.
-struct RadialPairs : public PotentialNode {
+struct RadialPairs : public PotentialNode, BatchedParamDeriv {
     IGraphHost ig;
     RadialPairs(DeviceCtx* c, hid_t_compat grp, CoordNode& a, CoordNode* b)
         : PotentialNode(c), ig(c, H(grp), b ? UPK_IT_HBOND_SC_RADIAL : UPK_IT_RADIAL, &a, b) { alloc_terms(ig.G.n1); }
@@ -1044,6 +1064,10 @@ struct RadialPairs : public PotentialNode {
         if (ig.G.symmetric) return vector<float>();
         return param_deriv_table(ctx, ig.param.size(), [&](float* t) {
             upk_check(upk_igraph_param_deriv(&ctx->L, &ig.G, system, 0, nullptr, nullptr, 0, 0, t), "hbond_sc_radial param_deriv"); });
+    }
+    size_t param_deriv_size() const override { return ig.G.symmetric ? 0 : ig.param.size(); }
+    void param_deriv_all(float* dev) override {
+        upk_check(upk_igraph_param_deriv_all(&ctx->L, &ig.G, 0, nullptr, nullptr, 0, 0, dev), "hbond_sc_radial param_deriv_all");
     }
 };
 struct SidechainRadialPairs : RadialPairs { SidechainRadialPairs(DeviceCtx* c, hid_t_compat g, CoordNode& a) : RadialPairs(c, g, a, nullptr) {} };
@@ -1083,7 +1107,7 @@ struct Slice : public CoordNode {
 RegisterNodeType<Builtin<Slice>, 1> slice_node("slice");
 
 // uniform_transform: environment.cpp:158-235
-struct UniformTransform : public CoordNode {
+struct UniformTransform : public CoordNode, BatchedParamDeriv {
     CoordNode& input; int n_coeff; float spline_offset, spline_inv_dx;
     vector<float> coeff; DevBuf<float> d_coeff, jac;
     UniformTransform(DeviceCtx* c, hid_t_compat grp, CoordNode& input_) : CoordNode(c, input_.n_elem, 1), input(input_) {
@@ -1101,6 +1125,11 @@ struct UniformTransform : public CoordNode {
         return param_deriv_table(ctx, 2 + n_coeff, [&](float* t) {
             upk_check(upk_uniform_transform_param_deriv(&ctx->L, input.coord(), d_coeff.p, n_coeff, spline_offset, spline_inv_dx, system, t), "uniform_transform param_deriv"); });
     }
+    size_t param_deriv_size() const override { return 2 + n_coeff; }
+    void param_deriv_all(float* dev) override {
+        upk_check(upk_uniform_transform_param_deriv_all(&ctx->L, input.coord(), d_coeff.p, n_coeff, spline_offset, spline_inv_dx, dev),
+                  "uniform_transform param_deriv_all");
+    }
     void set_param(const vector<float>& p) override {              // environment.cpp:223-233
         if (p.size() < size_t(2 + 4)) throw string("too small of size for spline");
         n_coeff = (int)p.size() - 2; spline_offset = p[0]; spline_inv_dx = p[1];
@@ -1110,7 +1139,7 @@ struct UniformTransform : public CoordNode {
 RegisterNodeType<Builtin<UniformTransform>, 1> uniform_transform_node("uniform_transform");
 
 // linear_coupling_uniform / linear_coupling_with_inactivation: environment.cpp:237-321
-struct LinearCoupling : public PotentialNode {
+struct LinearCoupling : public PotentialNode, BatchedParamDeriv {
     CoordNode& input; CoordNode* inactivation; int inactivation_dim = 0;
     vector<float> couplings; DevBuf<float> d_couplings; DevBuf<int> types;
     LinearCoupling(DeviceCtx* c, hid_t_compat grp, CoordNode& input_, CoordNode* inact_) : PotentialNode(c), input(input_), inactivation(inact_) {
@@ -1144,6 +1173,11 @@ struct LinearCoupling : public PotentialNode {
     vector<float> get_param_deriv(int system) override {           // environment.cpp:301-312
         return param_deriv_table(ctx, couplings.size(), [&](float* t) {
             upk_check(upk_linear_coupling_param_deriv(&ctx->L, input.coord(), types.p, inact_coord(), inactivation != nullptr, inactivation_dim, system, t), "linear_coupling param_deriv"); });
+    }
+    size_t param_deriv_size() const override { return couplings.size(); }
+    void param_deriv_all(float* dev) override {
+        upk_check(upk_linear_coupling_param_deriv_all(&ctx->L, input.coord(), types.p, (int)couplings.size(), inact_coord(), inactivation != nullptr,
+                                                      inactivation_dim, dev), "linear_coupling param_deriv_all");
     }
     void set_param(const vector<float>& p) override {
         if (p.size() != couplings.size()) throw string("attempting to change size of couplings vector on set_param");
@@ -1205,7 +1239,7 @@ RegisterNodeType<Builtin<MembranePotential>, 3> membrane_potential_node("membran
 
 // ---------------------------------------------------------------------------------------------------
 // rotamer: rotamer.cpp:581-1082
-struct RotamerSidechain : public PotentialNode {
+struct RotamerSidechain : public PotentialNode, BatchedParamDeriv {
     vector<CoordNode*> prob_nodes;
     IGraphHost ig;
     upk_rotamer_t R;
@@ -1442,6 +1476,8 @@ struct RotamerSidechain : public PotentialNode {
     vector<float> get_param_deriv(int system) override {   // rotamer.cpp:1064-1066
         return param_deriv_table(ctx, ig.param.size(), [&](float* t) { upk_check(upk_rotamer_param_deriv(&ctx->L, &R, system, t), "rotamer param_deriv"); });
     }
+    size_t param_deriv_size() const override { return ig.param.size(); }
+    void param_deriv_all(float* dev) override { upk_check(upk_rotamer_param_deriv_all(&ctx->L, &R, dev), "rotamer param_deriv_all"); }
 
     template <typename T> static vector<T> head(const DevBuf<T>& b, size_t n) { return sys_slice(b, 0, n); }
     // Pair energies of one system for the current structure (diagnostics / logging): the solve clears its accumulators,

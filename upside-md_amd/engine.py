@@ -248,6 +248,9 @@ class Ensemble(object):
         c.upside_hip_comm_init.argtypes = [vp, i32, i32, ct.c_char_p, vp]
         c.upside_hip_comm_replica_swap.argtypes = [vp, i32, vp, u32, u64, i32, vp]
         c.upside_hip_comm_free.argtypes = [vp]
+        c.upside_hip_get_param_deriv_all.argtypes = [vp, ct.c_char_p, i32, vp]
+        c.upside_hip_param_deriv_accumulate.argtypes = [vp, ct.c_char_p, vp]
+        c.upside_hip_param_deriv_read.argtypes = [vp, ct.c_char_p, i32, vp, vp, i32]
         c.upside_hip_last_error.restype = ct.c_char_p
         c._ensemble_bound = True
 
@@ -313,6 +316,34 @@ class Ensemble(object):
 
     def run_rounds(self, n_round):
         self._check(self.calc.upside_hip_run_md(self.engine, int(n_round)), 'run_md')
+
+    # -- parameter derivatives of every system (training: e.g. contrastive divergence) ----------------------------------
+    # All three see the state of the LAST force pass (as get_param_deriv does): after set_pos or MD steps, call energies()
+    # (or upside_hip_compute) first.  `shape` is the node's get_param() shape; () for a node without a derivative.
+    def param_deriv(self, node_name, shape):
+        """d(potential)/d(get_param of node_name) of every system: array (n_system,) + shape, deterministic"""
+        shape = tuple(shape)
+        out = np.zeros((self.n_system,) + shape, 'f4')
+        self._check(self.calc.upside_hip_get_param_deriv_all(self.engine, _b(node_name), int(np.prod(shape, dtype=np.int64)) if shape else 0,
+                                                             out.ctypes.data), 'get_param_deriv_all')
+        return out
+
+    def param_deriv_accumulate(self, node_name, weights=None):
+        """enqueue sum[node] += sum_s weights[s] * param_deriv[s] on the device (weights: (n_system,), None = all 1, signed)"""
+        w = None
+        if weights is not None:
+            w = np.ascontiguousarray(np.broadcast_to(np.asarray(weights, 'f4'), (self.n_system,)))
+        self._check(self.calc.upside_hip_param_deriv_accumulate(self.engine, _b(node_name), None if w is None else w.ctypes.data),
+                    'param_deriv_accumulate')
+
+    def param_deriv_read(self, node_name, shape, reset=True):
+        """(sum, n_frame): the accumulated float64 sum with the given shape and the number of accumulate calls since the last reset"""
+        shape = tuple(shape)
+        out = np.zeros(shape, 'f8')
+        n = np.zeros(1, 'i8')
+        self._check(self.calc.upside_hip_param_deriv_read(self.engine, _b(node_name), int(np.prod(shape, dtype=np.int64)) if shape else 0,
+                                                          out.ctypes.data, n.ctypes.data, int(bool(reset))), 'param_deriv_read')
+        return out, int(n[0])
 
     # -- replica exchange across the engines of a job, inside the library (comm_rccl.cpp) -------------
     COMM_ID_BYTES = 128
