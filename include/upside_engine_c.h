@@ -195,6 +195,30 @@ int upside_hip_get_param_deriv(DerivEngine* engine, const char* node_name, int s
 int upside_hip_get_param_deriv_all(DerivEngine* engine, const char* node_name, int n_param, float* deriv);
 int upside_hip_param_deriv_accumulate(DerivEngine* engine, const char* node_name, const float* weights);
 int upside_hip_param_deriv_read(DerivEngine* engine, const char* node_name, int n_param, double* sum, long long* n_frame, int reset);
+
+/* Hamiltonian ladders in one engine: systems whose potentials share their structure (node set, arguments, index datasets,
+ * shapes) and differ only in the values of the per-system table (dist/angle/dihedral_spring equil_dist and spring_const,
+ * cavity_radial, atom_pos_spring, tension, AFM, z_flat_bottom, contact values, the protein_hbond_energy attribute of
+ * hbond_energy).
+ *   _construct_files: one system per file, in order (a file may repeat).  NULL, with upside_hip_last_error naming the first
+ *     file, node and dataset that differs in a way one engine cannot hold, otherwise.  Systems whose values agree share
+ *     their arrays: n copies of one file compute what upside_hip_construct(file, n) computes, bit for bit.
+ *   _group_configurations: the grouping upside_main uses (HDF5 only, no device): group_of[i] = group of files[i], groups
+ *     numbered by first appearance; returns the number of groups, -1 on failure.  Files that are identical or differ only
+ *     in the table's values share a group; UPSIDE_HIP_HAMILTONIAN_BATCH=0 groups by the whole /input/potential instead.
+ *   _set_param_system / _get_param_system: set_param / get_param of one system (nodes with parameters: hbond_energy).
+ *     set_param keeps its meaning (every system); get_param returns system 0's values.
+ *   _hamiltonian_swap: one swap set (main.cpp:251-273) on the engine's stream: energy pass, the pairs trade coordinates,
+ *     energy pass, Metropolis verdicts of upside_replica_decide_lboltz (each system's own temperature), refused pairs trade
+ *     back.  draw0 >= 0: first draw of the set (0 for the first set of an attempt); draw0 < 0: continue from the draw the
+ *     previous set of this engine left on the device.  accepted (n_pair + 1: verdicts, then the next draw) may be NULL: the
+ *     call then returns without synchronising. */
+DerivEngine* upside_hip_construct_files(int n_atom, int n_file, const char* const* files, bool quiet);
+int upside_hip_group_configurations(int n_file, const char* const* files, int* group_of);
+int upside_hip_set_param_system(DerivEngine* engine, const char* node_name, int system, int n_param, const float* param);
+int upside_hip_get_param_system(DerivEngine* engine, const char* node_name, int system, int n_param, float* param);
+int upside_hip_hamiltonian_swap(DerivEngine* engine, int n_pair, const int* pairs, uint32_t base_seed, uint64_t round, int draw0,
+                                int* accepted);
 const char* upside_hip_last_error(void);
 
 /* Per-kernel timing hooks used by bench.py.  With profiling enabled every interaction-graph / BP kernel

@@ -111,6 +111,12 @@ int upk_spring(const upk_launch_t* L, int kind, upk_coord_t pos, const int* id, 
                float* contrib, long contrib_stride, float* pot_terms);
 int upk_cavity_radial(const upk_launch_t* L, upk_coord_t pos, const int* id, const float* radius, const float* k, int n,
                       float* contrib, long contrib_stride, float* pot_terms);
+/* the same with per-system parameter rows: system s reads equil / k / radius at base + s * par_stride (0 = one shared row;
+ * the entry points above pass 0) */
+int upk_spring_strided(const upk_launch_t* L, int kind, upk_coord_t pos, const int* id, const float* equil, const float* k, long par_stride,
+                       int n, float* contrib, long contrib_stride, float* pot_terms);
+int upk_cavity_radial_strided(const upk_launch_t* L, upk_coord_t pos, const int* id, const float* radius, const float* k, long par_stride,
+                              int n, float* contrib, long contrib_stride, float* pot_terms);
 
 /* ---- placement (src/placement.cpp:264-307) ------------------------------------------------------- */
 typedef struct {
@@ -139,6 +145,8 @@ int upk_nonlinear_coupling(const upk_launch_t* L, upk_coord_t input, const int* 
                            float offset, float inv_dx, float* pot_terms);
 /* hbond_energy (src/hbond.cpp:430-444) */
 int upk_hbond_energy(const upk_launch_t* L, upk_coord_t protein_hbond, float E_protein, float* pot_terms);
+/* the same with one energy scale per system: E_protein is a device array [S] */
+int upk_hbond_energy_sys(const upk_launch_t* L, upk_coord_t protein_hbond, const float* E_protein, float* pot_terms);
 /* backbone_pairs (src/backbone_steric.cpp:81-145): gather form over residue pairs; aff_contrib [res][6]; pot_terms [S][n_res]
  * (each pair counted once).  cache (may be NULL: every residue scans all others each step, what the reference does): per-row lists
  * of the residues within dist_cutoff + skin of the row's REFERENCE centre, rebuilt by the kernel when the two largest centre
@@ -399,6 +407,11 @@ int upk_point_potential(const upk_launch_t* L, int kind, upk_coord_t pos, const 
 /* contact (sidechain_radial.cpp:139-205): id (n,2); par [n][4] = energy, dist, 1/width, cutoff; contrib (n,2,3) */
 int upk_contact(const upk_launch_t* L, upk_coord_t bead, const int* id, const float* par, int n, float* contrib, long contrib_stride,
                 float* pot_terms);
+/* per-system parameter rows: system s reads par + s * par_stride (0 = shared; the entry points above pass 0) */
+int upk_point_potential_strided(const upk_launch_t* L, int kind, upk_coord_t pos, const int* id, const float* par, long par_stride, int n,
+                                float time, float* contrib, long contrib_stride, float* pot_terms);
+int upk_contact_strided(const upk_launch_t* L, upk_coord_t bead, const int* id, const float* par, long par_stride, int n, float* contrib,
+                        long contrib_stride, float* pot_terms);
 /* constant (bonds.cpp:550-587), slice (bonds.cpp:589-621) */
 int upk_broadcast_rows(const upk_launch_t* L, const float* value, upk_coord_t out);
 int upk_slice_fwd(const upk_launch_t* L, upk_coord_t in, const int* id, upk_coord_t out);
@@ -448,6 +461,12 @@ int upk_replica_decide(const upk_launch_t* L, float* energy_all, const float* be
 int upk_replica_apply(const upk_launch_t* L, upk_coord_t pos, int n_pair, const int* plan, const int* accepted, const float* staging);
 /* swap the coordinates of n_pair disjoint (s1, s2) pairs of systems; pairs is a device array */
 int upk_swap_system_pairs(const upk_launch_t* L, upk_coord_t pos, int n_pair, const int* pairs);
+/* Hamiltonian swap set: Metropolis verdicts from the energies before (e_old) and after (e_new) the pairs traded coordinates, beta [S];
+ * draw0 >= 0: first draw of the set, < 0: continue from *draw_io; accepted [n_pair + 1] (last = next draw), *draw_io = next draw */
+int upk_hamiltonian_decide(const upk_launch_t* L, const float* e_old, const float* e_new, const float* beta, int n_pair, const int* pairs,
+                           uint32_t seed, uint64_t round, int draw0, int* draw_io, int* accepted);
+/* swap back the pairs whose accepted[p] is 0 */
+int upk_swap_refused_pairs(const upk_launch_t* L, upk_coord_t pos, int n_pair, const int* pairs, const int* accepted);
 
 #ifdef __cplusplus
 }

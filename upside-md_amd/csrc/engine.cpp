@@ -807,7 +807,8 @@ static void load_plugins_from_env() {
     }
 }
 
-DerivEngine* initialize_engine_from_hdf5(int n_atom, int n_system, hid_t_compat potential_group_, bool quiet) {
+DerivEngine* initialize_engine_from_hdf5(int n_atom, int n_system, hid_t_compat potential_group_, bool quiet,
+                                         const std::function<void(DerivEngine&)>& before_finalize) {
     (void)quiet;
     load_plugins_from_env();
     hid_t potential_group = (hid_t)potential_group_;
@@ -853,6 +854,53 @@ DerivEngine* initialize_engine_from_hdf5(int n_atom, int n_system, hid_t_compat 
             throw "while adding '" + nm + "', " + e;
         }
     }
+    if (before_finalize) before_finalize(*engine);
     engine->finalize();
     return engine.release();
+}
+
+// One Hamiltonian swap set on the engine's stream (main.cpp:251-273 for systems of one engine whose parameter values differ):
+// energy pass, the pairs trade coordinates, energy pass, Metropolis verdicts on the device, refused pairs trade back.  Nothing
+// synchronises unless the caller wants the verdicts.
+void DerivEngine::hamiltonian_swap(int n_pair, const int* pairs, uint32_t base_seed, uint64_t round, int draw0, int* accepted) {
+    const int S = ctx.n_system;
+    if ((int)temperature.size() != S || (int)noise_scale.n != S) throw string("a Hamiltonian swap needs the systems' temperatures: call upside_hip_init_md first");
+    if (n_pair < 0 || (n_pair && !pairs)) throw string("invalid swap pairs");
+    vector<int> key(pairs, pairs + 2 * (size_t)n_pair);
+    vector<char> used(S, 0);
+    for (int x : key) {
+        if (x < 0 || x >= S) throw string("invalid system");
+        if (used[x]) throw string("Overlapping indices in swap set.");
+        used[x] = 1;
+    }
+    HSwap& H = hswap;
+    if (!H.e_old.n) {
+        H.e_old.alloc(S); H.e_new.alloc(S); H.draw.alloc(1);
+        vector<const float*> ptrs;      // node order: the sum of fetch_potentials
+        for (auto& n : nodes) if (n.computation->potential_term) ptrs.push_back(static_cast<PotentialNode*>(n.computation.get())->potential_dev.p);
+        H.n_node_pot = (int)ptrs.size(); H.node_pot.upload(ptrs);
+    }
+    vector<float> beta(S);
+    for (int s = 0; s < S; ++s) beta[s] = 1.f / temperature[s];
+    if (beta != H.beta_host) { sync(); H.beta.upload(beta); H.beta_host = beta; }
+    if (n_pair == 0) {
+        if (accepted) { sync(); accepted[0] = draw0 >= 0 ? draw0 : H.draw.download()[0]; }
+        return;
+    }
+    auto& dp = H.pairs[key];
+    if (!dp) { sync(); dp.reset(new DevBuf<int>()); dp->upload(key); }
+    if ((int)H.accepted.n < n_pair + 1) { sync(); H.accepted.alloc(n_pair + 1); }
+    compute(PotentialAndDerivMode);
+    upk_check(upk_sum_potentials(&ctx.L, H.node_pot.p, H.n_node_pot, H.e_old.p), "sum_potentials");
+    upk_check(upk_swap_system_pairs(&ctx.L, pos->coord(), n_pair, dp->p), "swap_system_pairs");
+    compute(PotentialAndDerivMode);
+    upk_check(upk_sum_potentials(&ctx.L, H.node_pot.p, H.n_node_pot, H.e_new.p), "sum_potentials");
+    upk_check(upk_hamiltonian_decide(&ctx.L, H.e_old.p, H.e_new.p, H.beta.p, n_pair, dp->p, base_seed, round, draw0, H.draw.p, H.accepted.p), "hamiltonian_decide");
+    upk_check(upk_swap_refused_pairs(&ctx.L, pos->coord(), n_pair, dp->p, H.accepted.p), "swap_refused_pairs");
+    swap_energy.clear();
+    if (accepted) {
+        check_device_errors();
+        hip_check(hipMemcpyAsync(accepted, H.accepted.p, (size_t)(n_pair + 1) * sizeof(int), hipMemcpyDeviceToHost, ctx.stream), "D2H accepted");
+        sync();
+    }
 }

@@ -32,6 +32,25 @@ struct BatchedParamDeriv {
     virtual void param_deriv_all(float* dev) = 0;
 };
 
+// Hamiltonian ladders in one engine (upside_hip_construct_files): nodes whose parameter VALUES may differ per system while the
+// structure (node set, arguments, index datasets, shapes) is shared.  The table lists, per registry prefix, the datasets of the
+// node's group (and attributes of the group itself) that may differ; everything else of the node must be byte-identical to
+// system 0's file (checked by the engine before load_system_values is called).  Engine-internal, like BatchedParamDeriv.
+struct PerSystemValueSpec { std::string type; std::vector<std::string> datasets, attributes; };
+const std::vector<PerSystemValueSpec>& per_system_value_table();
+const PerSystemValueSpec* per_system_value_spec(const std::string& node_name);   // by the registry's prefix rule; NULL = not in the table
+struct PerSystemValues {
+    virtual ~PerSystemValues() {}
+    // read system s's values from its own file's group of this node (system 0's are the node's construction values)
+    virtual void load_system_values(int system, hid_t_compat group) = 0;
+    // after every system is loaded, before the first force pass: a node whose systems all agree keeps its single array (stride 0)
+    virtual void finish_system_values() = 0;
+    virtual bool values_differ() const = 0;
+    // per-system set_param / get_param (nodes with parameters only)
+    virtual void set_param_system(int, const std::vector<float>&) { throw std::string("this node has no per-system parameters"); }
+    virtual std::vector<float> get_param_system(int) const { throw std::string("this node has no per-system parameters"); }
+};
+
 struct DerivEngine {   // deriv_engine.h:145-237
     struct Node {
         std::string name;
@@ -120,9 +139,18 @@ struct DerivEngine {   // deriv_engine.h:145-237
     ParamDeriv& param_deriv_state(int node);          // n_param known, nothing allocated yet
     const float* param_deriv_all(int node);            // enqueue every system's derivative; the device table [S][n_param]
     void param_deriv_accumulate(int node, const float* weights);   // enqueue sum += weights . table; no synchronisation
+    // device Hamiltonian swap sets (upside_hip_hamiltonian_swap): buffers allocated on first use, pairs uploaded once per distinct set
+    struct HSwap {
+        DevBuf<float> e_old, e_new, beta; std::vector<float> beta_host;
+        DevBuf<int> draw, accepted;
+        DevBuf<const float*> node_pot; int n_node_pot = 0;
+        std::map<std::vector<int>, std::unique_ptr<DevBuf<int>>> pairs;
+    } hswap;
+    void hamiltonian_swap(int n_pair, const int* pairs, uint32_t base_seed, uint64_t round, int draw0, int* accepted);
     void check_device_errors();                // throws if a capacity overflow was flagged
     void sync();
 };
 
-DerivEngine* initialize_engine_from_hdf5(int n_atom, int n_system, hid_t_compat potential_group, bool quiet = false);
+DerivEngine* initialize_engine_from_hdf5(int n_atom, int n_system, hid_t_compat potential_group, bool quiet = false,
+                                         const std::function<void(DerivEngine&)>& before_finalize = nullptr);
 

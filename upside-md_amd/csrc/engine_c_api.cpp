@@ -51,6 +51,133 @@ extern "C" DerivEngine* upside_hip_construct(int n_atom, const char* potential_f
     return initialize_engine_from_hdf5(n_atom, n_system, (hid_t_compat)(hid_t)potential_group, quiet);
     API_CATCH(nullptr)
 }
+// ---- Hamiltonian ladders: one engine, parameter values per system ------------------------------------------
+namespace {
+bool hamiltonian_batch_enabled() { const char* v = getenv("UPSIDE_HIP_HAMILTONIAN_BATCH"); return !(v && !strcmp(v, "0")); }
+bool listed(const vector<string>& v, const string& x) { return find(v.begin(), v.end(), x) != v.end(); }
+// the value bytes the table lets differ, for objects named below /input/potential ("node", "node/dataset")
+h5u::DigestSkip potential_value_skip() {
+    return [](const string& obj, const string& attr) {
+        const size_t slash = obj.find('/');
+        const auto* sp = per_system_value_spec(obj.substr(0, slash));
+        if (!sp) return false;
+        if (attr.empty()) return slash != string::npos && obj.find('/', slash + 1) == string::npos && listed(sp->datasets, obj.substr(slash + 1));
+        return slash == string::npos && listed(sp->attributes, attr);
+    };
+}
+// the same for objects named below one node's group (".", "dataset")
+h5u::DigestSkip node_value_skip(const PerSystemValueSpec* sp) {
+    return [sp](const string& obj, const string& attr) {
+        if (!sp) return false;
+        if (attr.empty()) return obj != "." && listed(sp->datasets, obj);
+        return obj == "." && listed(sp->attributes, attr);
+    };
+}
+hid_t open_config(const string& p) {
+    hid_t f = H5Fopen(p.c_str(), H5F_ACC_RDONLY, H5P_DEFAULT);
+    if (f < 0) throw string("unable to open ") + p;
+    return f;
+}
+struct ConfigFile {
+    h5u::Handle file;
+    explicit ConfigFile(const string& p) : file(open_config(p), H5Fclose) {}
+};
+}  // namespace
+
+extern "C" int upside_hip_group_configurations(int n_file, const char* const* files, int* group_of) {
+    API_TRY
+    if (n_file < 0 || (n_file && (!files || !group_of))) throw string("invalid file list");
+    H5Eset_auto2(H5E_DEFAULT, NULL, NULL);
+    const bool batch = hamiltonian_batch_enabled();
+    const h5u::DigestSkip skip = potential_value_skip();
+    vector<unsigned long long> keys;
+    for (int i = 0; i < n_file; ++i) {
+        ConfigFile cf(files[i]);
+        auto pg = h5u::open_group(cf.file, "/input/potential");
+        const unsigned long long k = h5u::group_digest(pg, batch ? &skip : nullptr);
+        size_t g = 0;
+        while (g < keys.size() && keys[g] != k) ++g;
+        if (g == keys.size()) keys.push_back(k);
+        group_of[i] = (int)g;
+    }
+    return (int)keys.size();
+    API_CATCH(-1)
+}
+
+extern "C" DerivEngine* upside_hip_construct_files(int n_atom, int n_file, const char* const* files, bool quiet) {
+    API_TRY
+    if (n_file < 1 || !files) throw string("n_file must be positive");
+    H5Eset_auto2(H5E_DEFAULT, NULL, NULL);
+    vector<unique_ptr<ConfigFile>> cf;
+    vector<h5u::Handle> pg;
+    for (int i = 0; i < n_file; ++i) { cf.emplace_back(new ConfigFile(files[i])); pg.push_back(h5u::open_group(cf.back()->file, "/input/potential")); }
+    // what each system loads on top of system 0's engine: (system, node) of every node group that is not byte-identical
+    vector<pair<int, string>> to_load;
+    const auto names0 = h5u::node_names_in_group(pg[0]);
+    const unsigned long long full0 = h5u::group_digest(pg[0]);
+    for (int i = 1; i < n_file; ++i) {
+        if (h5u::group_digest(pg[i]) == full0) continue;
+        const auto names = h5u::node_names_in_group(pg[i]);
+        for (auto& nm : names) if (!listed(names0, nm)) throw string(files[i]) + ": node " + nm + " is not in " + files[0] + " (one engine holds one node set)";
+        for (auto& nm : names0) if (!listed(names, nm)) throw string(files[i]) + ": node " + nm + " of " + files[0] + " is missing (one engine holds one node set)";
+        for (auto& nm : names0) {
+            auto g0 = h5u::open_group(pg[0], nm), g1 = h5u::open_group(pg[i], nm);
+            if (h5u::group_digest(g0) == h5u::group_digest(g1)) continue;
+            const PerSystemValueSpec* sp = per_system_value_spec(nm);
+            const h5u::DigestSkip skip = node_value_skip(sp);
+            const auto d0 = h5u::object_digests(g0, &skip), d1 = h5u::object_digests(g1, &skip);
+            if (d0 != d1) {
+                string what;
+                for (auto& kv : d0) { auto it = d1.find(kv.first); if (it == d1.end() || it->second != kv.second) { what = kv.first; break; } }
+                if (what.empty()) for (auto& kv : d1) if (!d0.count(kv.first)) { what = kv.first; break; }
+                throw string(files[i]) + ": node " + nm + ", " + (what == "." ? string("the node's attributes") : "dataset " + what) + " differs from " + files[0] +
+                      (sp ? string(" (only the values of the per-system table may differ)") : string(" (this node type's values cannot differ per system)"));
+            }
+            to_load.emplace_back(i, nm);
+        }
+    }
+    return initialize_engine_from_hdf5(n_atom, n_file, (hid_t_compat)(hid_t)pg[0], quiet, [&](DerivEngine& e) {
+        for (auto& sl : to_load) {
+            auto* pv = dynamic_cast<PerSystemValues*>(e.get(sl.second).computation.get());
+            if (!pv) throw string(files[sl.first]) + ": node " + sl.second + " cannot hold per-system values";
+            auto g = h5u::open_group(pg[sl.first], sl.second);
+            try { pv->load_system_values(sl.first, (hid_t_compat)(hid_t)g); }
+            catch (const string& err) { throw string(files[sl.first]) + ": node " + sl.second + ": " + err; }
+        }
+        for (auto& n : e.nodes) if (auto* pv = dynamic_cast<PerSystemValues*>(n.computation.get())) pv->finish_system_values();
+    });
+    API_CATCH(nullptr)
+}
+static PerSystemValues& per_system_node(DerivEngine* e, const char* node_name, int system) {
+    if (!e || !node_name) throw string("engine or node name is NULL");
+    if (system < 0 || system >= e->ctx.n_system) throw string("system index out of range");
+    auto* pv = dynamic_cast<PerSystemValues*>(e->get(string(node_name)).computation.get());
+    if (!pv) throw string("node ") + node_name + " has no per-system values";
+    return *pv;
+}
+extern "C" int upside_hip_set_param_system(DerivEngine* e, const char* node_name, int system, int n_param, const float* param) {
+    API_TRY
+    per_system_node(e, node_name, system).set_param_system(system, vector<float>(param, param + n_param));
+    e->swap_energy.clear();
+    return 0;
+    API_CATCH(1)
+}
+extern "C" int upside_hip_get_param_system(DerivEngine* e, const char* node_name, int system, int n_param, float* param) {
+    API_TRY
+    auto v = per_system_node(e, node_name, system).get_param_system(system);
+    if (v.size() != size_t(n_param)) throw string("Wrong number of parameters, expected ") + to_string(v.size()) + " but got " + to_string(n_param);
+    copy(begin(v), end(v), param);
+    return 0;
+    API_CATCH(1)
+}
+extern "C" int upside_hip_hamiltonian_swap(DerivEngine* e, int n_pair, const int* pairs, uint32_t base_seed, uint64_t round, int draw0, int* accepted) {
+    API_TRY
+    if (!e) throw string("engine is NULL");
+    e->hamiltonian_swap(n_pair, pairs, base_seed, round, draw0, accepted);
+    return 0;
+    API_CATCH(1)
+}
+
 extern "C" DerivEngine* construct_deriv_engine(int n_atom, const char* potential_file, bool quiet) {
     return upside_hip_construct(n_atom, potential_file, 1, quiet);
 }

@@ -5,6 +5,8 @@
 #pragma once
 #include <hdf5.h>
 #include <algorithm>
+#include <functional>
+#include <map>
 #include <string>
 #include <vector>
 
@@ -125,8 +127,13 @@ inline std::vector<std::string> node_names_in_group(hid_t loc) {   // h5_support
 
 // 64-bit FNV-1a digest of everything below a group: object paths, attribute names and raw bytes, dataset shapes and raw
 // bytes (in the file's own types).  Two configuration files hold the same potential iff their /input/potential digests agree.
+// skip(object, attribute): true = the value bytes of that dataset (attribute "") or attribute are left out of the digest (its name,
+// type and shape still count): the digest of a structure whose values may differ (upside_hip_group_configurations).
+using DigestSkip = std::function<bool(const std::string& object, const std::string& attribute)>;
 struct DigestCtx {
     unsigned long long h = 1469598103934665603ull; hid_t root = -1; std::string error;
+    const DigestSkip* skip = nullptr; std::string object;
+    std::map<std::string, unsigned long long>* per_object = nullptr;      // (set: one digest per object instead of one in all)
     void bytes(const void* p, size_t n) { const unsigned char* b = (const unsigned char*)p; for (size_t i = 0; i < n; ++i) { h ^= b[i]; h *= 1099511628211ull; } }
     void text(const std::string& s) { bytes(s.data(), s.size()); const unsigned char z = 0; bytes(&z, 1); }
 };
@@ -145,14 +152,16 @@ inline herr_t digest_attribute(hid_t obj, const char* name, const H5A_info_t*, v
         if (!strs.empty()) H5Dvlen_reclaim(mt, sp, H5P_DEFAULT, strs.data());
         return 0;
     }
+    if (c.skip && (*c.skip)(c.object, name)) { c.bytes(&n, sizeof(n)); c.text("<value>"); return 0; }
     std::vector<unsigned char> buf((size_t)(n > 0 ? n : 0) * H5Tget_size(ty));
     if (!buf.empty() && H5Aread(a, ty, buf.data()) < 0) { c.error = std::string("unable to read attribute ") + name; return -1; }
     c.bytes(buf.data(), buf.size());
     return 0;
 }
-inline herr_t digest_object(hid_t, const char* name, const H5O_info_t* info, void* data) {
+inline herr_t digest_object_body(hid_t, const char* name, const H5O_info_t* info, void* data) {
     DigestCtx& c = *static_cast<DigestCtx*>(data);
     c.text(name);
+    c.object = name;
     Handle obj(H5Oopen(c.root, name, H5P_DEFAULT), H5Oclose);
     if (obj < 0) { c.error = std::string("unable to open ") + name; return -1; }
     hsize_t idx = 0;
@@ -170,16 +179,31 @@ inline herr_t digest_object(hid_t, const char* name, const H5O_info_t* info, voi
             c.text("<variable-length>");
             return 0;
         }
+        if (c.skip && (*c.skip)(c.object, "")) { c.text(std::to_string(H5Tget_class(ty)) + ":" + std::to_string(H5Tget_size(ty))); c.text("<value>"); return 0; }
         std::vector<unsigned char> buf((size_t)(n > 0 ? n : 0) * H5Tget_size(ty));
         if (!buf.empty() && H5Dread(obj, ty, H5S_ALL, H5S_ALL, H5P_DEFAULT, buf.data()) < 0) { c.error = std::string("unable to read ") + name; return -1; }
         c.bytes(buf.data(), buf.size());
     }
     return 0;
 }
-inline unsigned long long group_digest(hid_t group) {
-    DigestCtx c; c.root = group;
+inline herr_t digest_object(hid_t loc, const char* name, const H5O_info_t* info, void* data) {
+    DigestCtx& c = *static_cast<DigestCtx*>(data);
+    if (c.per_object) c.h = 1469598103934665603ull;
+    const herr_t r = digest_object_body(loc, name, info, data);
+    if (c.per_object) (*c.per_object)[name] = c.h;
+    return r;
+}
+inline unsigned long long group_digest(hid_t group, const DigestSkip* skip = nullptr) {
+    DigestCtx c; c.root = group; c.skip = skip;
     if (H5Ovisit(group, H5_INDEX_NAME, H5_ITER_INC, digest_object, &c) < 0) throw std::string("while hashing a group: ") + c.error;
     return c.h;
+}
+// one digest per object below the group ("." = the group itself and its attributes)
+inline std::map<std::string, unsigned long long> object_digests(hid_t group, const DigestSkip* skip = nullptr) {
+    std::map<std::string, unsigned long long> m;
+    DigestCtx c; c.root = group; c.skip = skip; c.per_object = &m;
+    if (H5Ovisit(group, H5_INDEX_NAME, H5_ITER_INC, digest_object, &c) < 0) throw std::string("while hashing a group: ") + c.error;
+    return m;
 }
 
 }  // namespace h5u

@@ -591,11 +591,13 @@ extern "C" int upk_infer_bwd(const upk_launch_t* L, upk_coord_t infer, const flo
 
 // ------------------------------------------------------------------------------------------------
 // bonded springs (bonds.cpp:297-318, 457-487, 519-545)
-struct SpringArgs { int kind; upk_coord_t pos; const int* id; const float* equil; const float* kk; int n; float* contrib; long contrib_stride; float* pot_terms; };
+// par_stride: floats between the equil / kk rows of consecutive systems (0: one row shared by every system)
+struct SpringArgs { int kind; upk_coord_t pos; const int* id; const float* equil; const float* kk; int n; float* contrib; long contrib_stride; float* pot_terms; long par_stride; };
 __device__ __forceinline__ void b_spring(const int nt, const int s, int kind, upk_coord_t pos, const int* __restrict__ id, const float* __restrict__ equil,
                                          const float* __restrict__ kk, int n, float* __restrict__ contrib, long contrib_stride,
-                                         float* __restrict__ pot_terms) {
+                                         float* __restrict__ pot_terms, long par_stride) {
     if (nt >= n) return;
+    equil += (size_t)s * par_stride; kk += (size_t)s * par_stride;
     const float* x = C_OUT(pos, s);
     float* o = contrib + (size_t)s * contrib_stride + (size_t)nt * kind * 3;
     float pot;
@@ -631,17 +633,23 @@ __device__ __forceinline__ void b_spring(const int nt, const int s, int kind, up
     }
     if (pot_terms) pot_terms[(size_t)s * n + nt] = pot;
 }
-extern "C" int upk_spring(const upk_launch_t* L, int kind, upk_coord_t pos, const int* id, const float* equil, const float* k, int n,
-                          float* contrib, long contrib_stride, float* pot_terms) {
+extern "C" int upk_spring_strided(const upk_launch_t* L, int kind, upk_coord_t pos, const int* id, const float* equil, const float* k, long par_stride,
+                                  int n, float* contrib, long contrib_stride, float* pot_terms) {
     FARGS(SpringArgs, a); a.kind = kind; a.pos = cz(pos); a.id = id; a.equil = equil; a.kk = k; a.n = n; a.contrib = contrib; a.contrib_stride = contrib_stride; a.pot_terms = pot_terms;
+    a.par_stride = par_stride;
     return fuse_submit(L, FOP_SPRING, a, n, {r_out(pos, false), r_slice(contrib, (size_t)n * kind * 12, (size_t)contrib_stride * 4, true), r_buf(pot_terms, pot_terms ? (size_t)n * 4 : 0, true)});
 }
+extern "C" int upk_spring(const upk_launch_t* L, int kind, upk_coord_t pos, const int* id, const float* equil, const float* k, int n,
+                          float* contrib, long contrib_stride, float* pot_terms) {
+    return upk_spring_strided(L, kind, pos, id, equil, k, 0, n, contrib, contrib_stride, pot_terms);
+}
 
-__global__ void k_cavity(upk_coord_t pos, const int* __restrict__ id, const float* __restrict__ radius, const float* __restrict__ kk,
+__global__ void k_cavity(upk_coord_t pos, const int* __restrict__ id, const float* __restrict__ radius, const float* __restrict__ kk, long par_stride,
                          int n, float* __restrict__ contrib, long contrib_stride, float* __restrict__ pot_terms) {   // bonds.cpp:350-372
     const int nt = blockIdx.x * blockDim.x + threadIdx.x;
     if (nt >= n) return;
     const int s = blockIdx.y;
+    radius += (size_t)s * par_stride; kk += (size_t)s * par_stride;
     const f3 x = ld3(C_OUT(pos, s) + (size_t)id[nt] * pos.stride);
     const float r2 = mag2(x);
     float pot = 0.f; f3 d = mk3(0.f, 0.f, 0.f);
@@ -654,11 +662,15 @@ __global__ void k_cavity(upk_coord_t pos, const int* __restrict__ id, const floa
     o[0] = d.x; o[1] = d.y; o[2] = d.z;
     if (pot_terms) pot_terms[(size_t)s * n + nt] = pot;
 }
+extern "C" int upk_cavity_radial_strided(const upk_launch_t* L, upk_coord_t pos, const int* id, const float* radius, const float* k, long par_stride,
+                                         int n, float* contrib, long contrib_stride, float* pot_terms) {
+    UPK_FLUSH(L);
+    hipLaunchKernelGGL(k_cavity, grid1(n, L->n_system), dim3(UPK_BLOCK), 0, ST(L), pos, id, radius, k, par_stride, n, contrib, contrib_stride, pot_terms);
+    return launch_status();
+}
 extern "C" int upk_cavity_radial(const upk_launch_t* L, upk_coord_t pos, const int* id, const float* radius, const float* k, int n,
                                  float* contrib, long contrib_stride, float* pot_terms) {
-    UPK_FLUSH(L);
-    hipLaunchKernelGGL(k_cavity, grid1(n, L->n_system), dim3(UPK_BLOCK), 0, ST(L), pos, id, radius, k, n, contrib, contrib_stride, pot_terms);
-    return launch_status();
+    return upk_cavity_radial_strided(L, pos, id, radius, k, 0, n, contrib, contrib_stride, pot_terms);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -815,11 +827,18 @@ extern "C" int upk_nonlinear_coupling(const upk_launch_t* L, upk_coord_t input, 
 }
 
 // hbond_energy (hbond.cpp:430-444)
-struct HBondEnergyArgs { upk_coord_t ph; float Ep; float* pot_terms; };
-__device__ __forceinline__ void b_hbond_energy(const int nv, const int s, upk_coord_t ph, float Ep, float* __restrict__ pot_terms) {
+// Ep_sys (may be NULL: Ep for every system): [S], one energy scale per system, read from the device so that a captured graph sees changes
+struct HBondEnergyArgs { upk_coord_t ph; float Ep; float* pot_terms; const float* Ep_sys; };
+__device__ __forceinline__ void b_hbond_energy(const int nv, const int s, upk_coord_t ph, float Ep, float* __restrict__ pot_terms, const float* __restrict__ Ep_sys) {
     if (nv >= ph.n_elem) return;
+    if (Ep_sys) Ep = Ep_sys[s];
     C_SENS(ph, s)[(size_t)nv * ph.stride + 6] += Ep;
     if (pot_terms) pot_terms[(size_t)s * ph.n_elem + nv] = C_OUT(ph, s)[(size_t)nv * ph.stride + 6] * Ep;
+}
+extern "C" int upk_hbond_energy_sys(const upk_launch_t* L, upk_coord_t protein_hbond, const float* E_protein, float* pot_terms) {
+    FARGS(HBondEnergyArgs, a); a.ph = cz(protein_hbond); a.Ep_sys = E_protein; a.pot_terms = pot_terms;
+    return fuse_submit(L, FOP_HBOND_ENERGY, a, protein_hbond.n_elem, {r_out(protein_hbond, false), r_sens(protein_hbond, true), r_buf(pot_terms, pot_terms ? (size_t)protein_hbond.n_elem * 4 : 0, true),
+                                                                     r_slice(E_protein, 4, 4, false)});
 }
 extern "C" int upk_hbond_energy(const upk_launch_t* L, upk_coord_t protein_hbond, float E_protein, float* pot_terms) {
     FARGS(HBondEnergyArgs, a); a.ph = cz(protein_hbond); a.Ep = E_protein; a.pot_terms = pot_terms;
@@ -1338,6 +1357,55 @@ extern "C" int upk_swap_system_pairs(const upk_launch_t* L, upk_coord_t pos, int
     return launch_status();
 }
 
+// Hamiltonian swap set (main.cpp:251-273) after its two energy passes: e_old = energies before the pairs traded coordinates, e_new =
+// after.  lboltz_diff = (-b1 E1' - b2 E2') - (-b1 E1 - b2 E2) in the fp32 order of the host procedure; the Metropolis draw of
+// upside_replica_decide_lboltz on the round's counter-based stream.  draw0 >= 0 starts the set at that draw, draw0 < 0 continues
+// from *draw_io (the previous set of the attempt).  accepted[n_pair] = the draw after the set.  One thread: n_pair is small.
+__global__ void k_hamiltonian_decide(const float* __restrict__ e_old, const float* __restrict__ e_new, const float* __restrict__ beta, int n_pair,
+                                     const int* __restrict__ pairs, uint32_t seed, uint64_t round, int draw0, int* __restrict__ draw_io,
+                                     int* __restrict__ accepted) {
+    if (threadIdx.x != 0 || blockIdx.x != 0) return;
+    int draw = draw0 >= 0 ? draw0 : *draw_io;
+    for (int p = 0; p < n_pair; ++p) {
+        const int s1 = pairs[p * 2], s2 = pairs[p * 2 + 1];
+        const float old_lb = -beta[s1] * e_old[s1] + -beta[s2] * e_old[s2];
+        const float new_lb = -beta[s1] * e_new[s1] + -beta[s2] * e_new[s2];
+        const float lb = new_lb - old_lb;
+        int ok = 1;
+        if (lb < 0.f) {
+            const uint32_t key[4] = {seed, 1u /* REPLICA_EXCHANGE_RANDOM_STREAM */, 0u, 0u};
+            uint32_t X[4] = {(uint32_t)(round & 0xffffffffu), (uint32_t)(round >> 32), 0u, (uint32_t)draw};
+            threefry4x32_20(X, key);
+            ++draw;
+            if (expf(lb) < u01f(X[0])) ok = 0;
+        }
+        accepted[p] = ok;
+    }
+    accepted[n_pair] = draw;
+    *draw_io = draw;
+}
+extern "C" int upk_hamiltonian_decide(const upk_launch_t* L, const float* e_old, const float* e_new, const float* beta, int n_pair, const int* pairs,
+                                      uint32_t seed, uint64_t round, int draw0, int* draw_io, int* accepted) {
+    UPK_FLUSH(L);
+    hipLaunchKernelGGL(k_hamiltonian_decide, dim3(1), dim3(64), 0, ST(L), e_old, e_new, beta, n_pair, pairs, seed, round, draw0, draw_io, accepted);
+    return launch_status();
+}
+// trade back the coordinates of the pairs whose verdict was a refusal
+__global__ void k_swap_refused_pairs(upk_coord_t pos, const int* __restrict__ pairs, const int* __restrict__ accepted) {
+    const int p = blockIdx.y;
+    if (accepted[p]) return;
+    float* a = C_OUT(pos, pairs[p * 2]); float* b = C_OUT(pos, pairs[p * 2 + 1]);
+    const int n = pos.n_elem * pos.stride;
+    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) { const float t = a[i]; a[i] = b[i]; b[i] = t; }
+}
+extern "C" int upk_swap_refused_pairs(const upk_launch_t* L, upk_coord_t pos, int n_pair, const int* pairs, const int* accepted) {
+    UPK_FLUSH(L);
+    if (n_pair <= 0) return 0;
+    const int n = pos.n_elem * pos.stride;
+    hipLaunchKernelGGL(k_swap_refused_pairs, dim3((unsigned)((n + UPK_BLOCK - 1) / UPK_BLOCK), (unsigned)n_pair), dim3(UPK_BLOCK), 0, ST(L), pos, pairs, accepted);
+    return launch_status();
+}
+
 // ------------------------------------------------------------------------------------------------
 // Parameter derivatives of the per-element nodes, for ONE system, into a zeroed table (the reference's
 // get_param_deriv under PARAM_DERIV).  Off the MD path: global atomics.
@@ -1430,13 +1498,13 @@ extern "C" int upk_column_sum(const upk_launch_t* L, upk_coord_t c, int comp, in
 //   kind 1 tension         (bonds.cpp:73-88)  par = tension_coeff[3]
 //   kind 2 AFM             (bonds.cpp:147-166) par = k, starting_tip_pos[3], pulling_vel[3];  time = time_estimate
 //   kind 3 z_flat_bottom   (bonds.cpp:406-425) par = z0, radius, k
-__global__ void k_point_potential(int kind, upk_coord_t pos, const int* __restrict__ id, const float* __restrict__ par, int n, float time,
+__global__ void k_point_potential(int kind, upk_coord_t pos, const int* __restrict__ id, const float* __restrict__ par, long par_stride, int n, float time,
                                   float* __restrict__ contrib, long contrib_stride, float* __restrict__ pot_terms) {
     const int nt = blockIdx.x * blockDim.x + threadIdx.x;
     if (nt >= n) return;
     const int s = blockIdx.y;
     const f3 x = ld3(C_OUT(pos, s) + (size_t)id[nt] * pos.stride);
-    const float* p = par + (size_t)nt * 8;
+    const float* p = par + (size_t)s * par_stride + (size_t)nt * 8;
     float pot = 0.f; f3 d = mk3(0.f, 0.f, 0.f);
     if (kind == 0) {
         const f3 disp = x - mk3(p[0], p[1], p[2]);
@@ -1461,23 +1529,27 @@ __global__ void k_point_potential(int kind, upk_coord_t pos, const int* __restri
     o[0] = d.x; o[1] = d.y; o[2] = d.z;
     if (pot_terms) pot_terms[(size_t)s * n + nt] = pot;
 }
-extern "C" int upk_point_potential(const upk_launch_t* L, int kind, upk_coord_t pos, const int* id, const float* par, int n, float time,
-                                   float* contrib, long contrib_stride, float* pot_terms) {
+extern "C" int upk_point_potential_strided(const upk_launch_t* L, int kind, upk_coord_t pos, const int* id, const float* par, long par_stride, int n,
+                                           float time, float* contrib, long contrib_stride, float* pot_terms) {
     UPK_FLUSH(L);
-    hipLaunchKernelGGL(k_point_potential, grid1(n, L->n_system), dim3(UPK_BLOCK), 0, ST(L), kind, pos, id, par, n, time, contrib,
+    hipLaunchKernelGGL(k_point_potential, grid1(n, L->n_system), dim3(UPK_BLOCK), 0, ST(L), kind, pos, id, par, par_stride, n, time, contrib,
                        contrib_stride, pot_terms);
     return launch_status();
 }
+extern "C" int upk_point_potential(const upk_launch_t* L, int kind, upk_coord_t pos, const int* id, const float* par, int n, float time,
+                                   float* contrib, long contrib_stride, float* pot_terms) {
+    return upk_point_potential_strided(L, kind, pos, id, par, 0, n, time, contrib, contrib_stride, pot_terms);
+}
 
 // contact (sidechain_radial.cpp:187-204): par is [n][4] = energy, dist, scale (1/width), cutoff
-__global__ void k_contact(upk_coord_t bead, const int* __restrict__ id, const float* __restrict__ par, int n, float* __restrict__ contrib,
+__global__ void k_contact(upk_coord_t bead, const int* __restrict__ id, const float* __restrict__ par, long par_stride, int n, float* __restrict__ contrib,
                           long contrib_stride, float* __restrict__ pot_terms) {
     const int nc = blockIdx.x * blockDim.x + threadIdx.x;
     if (nc >= n) return;
     const int s = blockIdx.y;
     const float* x = C_OUT(bead, s);
     const f3 disp = ld3(x + (size_t)id[nc * 2] * bead.stride) - ld3(x + (size_t)id[nc * 2 + 1] * bead.stride);
-    const float* p = par + (size_t)nc * 4;
+    const float* p = par + (size_t)s * par_stride + (size_t)nc * 4;
     const float dist = sqrtf(mag2(disp));
     float pot = 0.f; f3 d = mk3(0.f, 0.f, 0.f);
     if (!(dist >= p[3])) {
@@ -1490,11 +1562,15 @@ __global__ void k_contact(upk_coord_t bead, const int* __restrict__ id, const fl
     o[0] = d.x; o[1] = d.y; o[2] = d.z; o[3] = -d.x; o[4] = -d.y; o[5] = -d.z;
     if (pot_terms) pot_terms[(size_t)s * n + nc] = pot;
 }
+extern "C" int upk_contact_strided(const upk_launch_t* L, upk_coord_t bead, const int* id, const float* par, long par_stride, int n, float* contrib,
+                                   long contrib_stride, float* pot_terms) {
+    UPK_FLUSH(L);
+    hipLaunchKernelGGL(k_contact, grid1(n, L->n_system), dim3(UPK_BLOCK), 0, ST(L), bead, id, par, par_stride, n, contrib, contrib_stride, pot_terms);
+    return launch_status();
+}
 extern "C" int upk_contact(const upk_launch_t* L, upk_coord_t bead, const int* id, const float* par, int n, float* contrib,
                            long contrib_stride, float* pot_terms) {
-    UPK_FLUSH(L);
-    hipLaunchKernelGGL(k_contact, grid1(n, L->n_system), dim3(UPK_BLOCK), 0, ST(L), bead, id, par, n, contrib, contrib_stride, pot_terms);
-    return launch_status();
+    return upk_contact_strided(L, bead, id, par, 0, n, contrib, contrib_stride, pot_terms);
 }
 
 // constant (bonds.cpp:550-587): the same values in every system;  slice (bonds.cpp:589-621)
@@ -1816,7 +1892,7 @@ __device__ __forceinline__ void run_fused_op(const FusedOp& op, const int s, flo
         case FOP_INFER_BWD: { const auto& a = fop_args<InferBwdArgs>(op);
             FOP_LOOP(i, n) b_infer_bwd(i, s, a.infer, a.bond_length, a.dfd, a.n_virtual, a.contrib, a.contrib_stride); } break;
         case FOP_SPRING: { const auto& a = fop_args<SpringArgs>(op);
-            FOP_LOOP(i, n) b_spring(i, s, a.kind, a.pos, a.id, a.equil, a.kk, a.n, a.contrib, a.contrib_stride, a.pot_terms); } break;
+            FOP_LOOP(i, n) b_spring(i, s, a.kind, a.pos, a.id, a.equil, a.kk, a.n, a.contrib, a.contrib_stride, a.pot_terms, a.par_stride); } break;
         case FOP_PLACEMENT_FWD: { const auto& a = fop_args<PlacementFwdArgs>(op);
             FOP_LOOP(i, n) b_placement_fwd(i, s, a.P, a.aff, a.rama, a.out, a.rama_deriv); } break;
         case FOP_PLACEMENT_BWD: { const auto& a = fop_args<PlacementBwdArgs>(op);
@@ -1830,7 +1906,7 @@ __device__ __forceinline__ void run_fused_op(const FusedOp& op, const int s, flo
         case FOP_NONLINEAR_COUPLING: { const auto& a = fop_args<NonlinearCouplingArgs>(op);
             FOP_LOOP(i, n) b_nonlinear_coupling(i, s, a.input, a.types, a.coeff, a.n_coeff, a.offset, a.inv_dx, a.pot_terms); } break;
         case FOP_HBOND_ENERGY: { const auto& a = fop_args<HBondEnergyArgs>(op);
-            FOP_LOOP(i, n) b_hbond_energy(i, s, a.ph, a.Ep, a.pot_terms); } break;
+            FOP_LOOP(i, n) b_hbond_energy(i, s, a.ph, a.Ep, a.pot_terms, a.Ep_sys); } break;
         case FOP_PROTEIN_HBOND_FINISH: { const auto& a = fop_args<ProteinHBondFinishArgs>(op);
             FOP_LOOP(i, n) b_protein_hbond_finish(i, s, a.infer, a.out); } break;
         case FOP_PROTEIN_HBOND_BWD_PRE: { const auto& a = fop_args<ProteinHBondBwdPreArgs>(op);

@@ -255,15 +255,22 @@ int upside_main_impl(int argc, const char* const* argv, int verbose) {
 
     if (anneal_duration == -1.) anneal_duration = duration;      // main.cpp:434
     const vector<float> initial_temps = temps;
-    // One engine per DISTINCT potential (the reference builds one engine per file, main.cpp:450-571, which is what Hamiltonian
-    // replica exchange and mixed runs use): the files are grouped by a digest of /input/potential -- node names, arguments,
-    // attributes and dataset bytes alike -- and every group becomes one batched engine.  Only /input/pos (and the output)
-    // differ inside a group.  The common case is one group.
+    // One engine per group of files (the reference builds one engine per file, main.cpp:450-571, which is what Hamiltonian
+    // replica exchange and mixed runs use): files whose /input/potential agree in everything but the values of the per-system
+    // table (upside_hip_group_configurations; a Hamiltonian ladder) share one batched engine, every other difference -- node
+    // set, arguments, index datasets, shapes, other values -- makes another group.  UPSIDE_HIP_HAMILTONIAN_BATCH=0: one group
+    // per distinct /input/potential (node names, arguments, attributes and dataset bytes alike).  The common case is one group.
     H5Eset_auto2(H5E_DEFAULT, NULL, NULL);
     int n_atom = 0;
     unsigned long long potential_digest = 0;
     vector<float> all_pos;
-    vector<unsigned long long> digest_of_group; vector<vector<int>> members; vector<int> group_of(n_system), local_of(n_system);
+    vector<vector<int>> members; vector<int> group_of(n_system), local_of(n_system);
+    vector<unsigned long long> full_digest(n_system, 0ull);
+    {
+        vector<const char*> fp; for (auto& f : files) fp.push_back(f.c_str());
+        if (n_total > 1 && upside_hip_group_configurations(n_system, fp.data(), group_of.data()) < 0) throw string(upside_hip_last_error());
+        if (n_total == 1) group_of[0] = 0;
+    }
     for (int ns = 0; ns < n_system; ++ns) {
         hid_t f = H5Fopen(files[ns].c_str(), H5F_ACC_RDONLY, H5P_DEFAULT);
         if (f < 0) throw string("unable to open ") + files[ns];
@@ -276,21 +283,43 @@ int upside_main_impl(int argc, const char* const* argv, int verbose) {
         if (ns == 0) { n_atom = (int)dims[0]; potential_digest = dg; }
         else if ((int)dims[0] != n_atom)      // (replica exchange trades coordinates between any two systems of the run)
             throw string("the systems of one run must have the same number of atoms: ") + files[ns] + " differs from " + files[0];
-        size_t g = 0;
-        while (g < digest_of_group.size() && digest_of_group[g] != dg) ++g;
-        if (g == digest_of_group.size()) { digest_of_group.push_back(dg); members.emplace_back(); }
-        group_of[ns] = (int)g; local_of[ns] = (int)members[g].size(); members[g].push_back(ns);
+        full_digest[ns] = dg;
+        const size_t g = (size_t)group_of[ns];
+        if (g >= members.size()) members.resize(g + 1);
+        local_of[ns] = (int)members[g].size(); members[g].push_back(ns);
         all_pos.insert(all_pos.end(), p.begin(), p.end());
     }
     const int n_group = (int)members.size();
+    vector<char> ladder(n_group, 0);      // the group's files differ in the values of the per-system table: one engine of several Hamiltonians
+    for (int g = 0; g < n_group; ++g) for (int ns : members[g]) if (full_digest[ns] != full_digest[members[g][0]]) ladder[g] = 1;
+    const bool hamiltonian_ladder = n_group == 1 && ladder[0];
     if (n_group > 1 && use_comm)
         throw string("systems must share one potential when the run is spread over several processes: /input/potential of ") + files[members[1][0]] +
               " differs from that of " + files[0];
+    if (hamiltonian_ladder && use_comm)      // (each rank's engine would be a ladder of its own: exchange across ranks assumes one Hamiltonian)
+        throw string("Hamiltonian replica exchange across processes is not available: the /input/potential values of ") + files[members[0][1]] +
+              " differ from those of " + files[0] + "; run the ladder in one process";
     if (n_group > 1 && mc_interval > 0.) throw string("Monte-Carlo moves are not available in a run that mixes potentials");
+    if (hamiltonian_ladder && mc_interval > 0.) {      // one sampler for the whole engine: its tables must be those of every file
+        for (const char* grp : {"/input/pivot_moves", "/input/jump_moves"}) {
+            unsigned long long d0 = 0ull;
+            for (int ns = 0; ns < n_system; ++ns) {
+                hid_t f = H5Fopen(files[ns].c_str(), H5F_ACC_RDONLY, H5P_DEFAULT);
+                if (f < 0) throw string("unable to open ") + files[ns];
+                h5u::Handle fh(f, H5Fclose);
+                const unsigned long long d = h5u::exists(f, grp) ? h5u::group_digest(h5u::open_group(f, grp)) : 1ull;
+                if (ns == 0) d0 = d;
+                else if (d != d0) throw string("Monte-Carlo moves need the same ") + grp + " in every file of a run: " + files[ns] + " differs from " + files[0];
+            }
+        }
+    }
     vector<DerivEngine*> engines(n_group, nullptr);
     struct Guard { vector<DerivEngine*>& v; ~Guard() { for (auto* x : v) delete x; } } guard{engines};
     for (int g = 0; g < n_group; ++g) {
-        engines[g] = upside_hip_construct(n_atom, files[members[g][0]].c_str(), (int)members[g].size(), !verbose);
+        if (ladder[g]) {
+            vector<const char*> fp; for (int ns : members[g]) fp.push_back(files[ns].c_str());
+            engines[g] = upside_hip_construct_files(n_atom, (int)fp.size(), fp.data(), !verbose);
+        } else engines[g] = upside_hip_construct(n_atom, files[members[g][0]].c_str(), (int)members[g].size(), !verbose);
         if (!engines[g]) throw string("unable to construct the engine: ") + upside_hip_last_error();
     }
     DerivEngine* e = engines[0];      // the only engine of an ordinary run
@@ -417,7 +446,8 @@ int upside_main_impl(int argc, const char* const* argv, int verbose) {
         if (rank == 0) remove(path.c_str());                         // (ncclCommInitRank returns when every rank has joined)
         // every rank keeps its own files under ONE engine and the Metropolis kernel assumes one Hamiltonian for the whole ladder:
         // the ranks' potentials must agree as the files of one rank must.  Checked with the communicator, so that every rank
-        // learns of a mismatch and none is left waiting for a peer that has gone.
+        // learns of a mismatch and none is left waiting for a peer that has gone.  (A run over several processes holds no Hamiltonian
+        // ladder, refused above, so the digest that groups its files is that of the whole /input/potential.)
         int differs = -1;
         if (upside_hip_comm_agree(e, potential_digest, &differs)) throw string(upside_hip_last_error());
         if (differs >= 0) {
@@ -610,6 +640,9 @@ int upside_main_impl(int argc, const char* const* argv, int verbose) {
                     if (upside_replica_decide_lboltz(np, diff.data(), base_seed, rnd, draw, acc.data())) throw string(upside_hip_last_error());
                     draw = acc.back();
                     for (int i = 0; i < np; ++i) if (!acc[i]) coord_swap(sets[k][2 * i], sets[k][2 * i + 1]);      // a rejected swap is reversed
+                } else if (hamiltonian_ladder) {     // one engine, several Hamiltonians: the same procedure on the device (upside_hip_hamiltonian_swap)
+                    if (upside_hip_hamiltonian_swap(e, (int)sets[k].size() / 2, sets[k].data(), base_seed, rnd, draw, acc.data())) throw string(upside_hip_last_error());
+                    draw = acc.back();
                 } else if (use_comm) {     // global indices; energies all-gathered, verdicts on the device, straddling pairs over RCCL
                     if (upside_hip_comm_replica_swap(e, (int)sets[k].size() / 2, sets[k].data(), base_seed, rnd, k == 0, acc.data()))
                         throw string(upside_hip_last_error());

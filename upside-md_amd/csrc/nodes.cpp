@@ -37,13 +37,40 @@ void require_injective(const vector<int>& loc, int n_target, const char* what) {
     }
 }
 
+// Per-system parameter values (PerSystemValues, engine.h): a node keeps the values of every system on the host, row 0 from its
+// own construction; only when some row differs from row 0 does the device array grow to [S][per] (stride per), otherwise it
+// stays the single row it was built with (stride 0: the same memory and arithmetic as an engine of identical systems).
+struct SysRows {
+    size_t per = 0; int S = 1; vector<float> host; bool differs = false;
+    void init(const vector<float>& row0, int n_system) { per = row0.size(); S = n_system; host.resize(per * (size_t)S); for (int s = 0; s < S; ++s) copy(row0.begin(), row0.end(), host.begin() + (size_t)s * per); }
+    void set_row(int s, const vector<float>& row) {
+        if (row.size() != per) throw string("per-system values of the wrong size");
+        copy(row.begin(), row.end(), host.begin() + (size_t)s * per);
+        if (memcmp(row.data(), host.data(), per * sizeof(float))) differs = true;
+    }
+    vector<float> row(int s) const { return vector<float>(host.begin() + (size_t)s * per, host.begin() + (size_t)(s + 1) * per); }
+    long stride() const { return differs ? (long)per : 0L; }
+    void upload_to(DevBuf<float>& d) const { if (differs) d.upload(host); }   // (unchanged single row otherwise)
+};
+
 // ---------------------------------------------------------------------------------------------------
 // bonded springs: bonds.cpp:252-320 (dist_spring), 430-489 (angle_spring), 492-547 (dihedral_spring)
-struct SpringNode : public PotentialNode {
+struct SpringNode : public PotentialNode, PerSystemValues {
     int kind, n_elem;
     CoordNode& pos;
     DevBuf<int> id; DevBuf<float> equil, k;
     int src = -1;
+    SysRows equil_rows, k_rows;      // [S][n_elem] each
+    void load_system_values(int s, hid_t_compat g) override {
+        check_size(H(g), "equil_dist", {(size_t)n_elem}); check_size(H(g), "spring_const", {(size_t)n_elem});
+        equil_rows.set_row(s, read<float>(H(g), "equil_dist", 1)); k_rows.set_row(s, read<float>(H(g), "spring_const", 1));
+    }
+    bool values_differ() const override { return equil_rows.differs || k_rows.differs; }
+    void finish_system_values() override {   // (one stride for both: both become [S][n] when either differs)
+        if (!values_differ()) return;
+        equil_rows.differs = k_rows.differs = true;
+        equil_rows.upload_to(equil); k_rows.upload_to(k);
+    }
     SpringNode(DeviceCtx* c, hid_t_compat grp, CoordNode& pos_, int kind_) : PotentialNode(c), kind(kind_), pos(pos_) {
         vector<hsize_t> dims;
         auto ids = read<int>(H(grp), "id", 2, &dims);
@@ -56,12 +83,13 @@ struct SpringNode : public PotentialNode {
         id.upload(ids);
         equil.upload(read<float>(H(grp), "equil_dist", 1));
         k.upload(read<float>(H(grp), "spring_const", 1));
+        equil_rows.init(equil.download(), c->n_system); k_rows.init(k.download(), c->n_system);
         src = pos.scatter.add_source(n_elem, kind, 3, ids);
         alloc_terms(n_elem);
         fused_forward = fused_backward = true;
     }
     void compute_value(ComputeMode mode) override {
-        upk_check(upk_spring(&ctx->L, kind, pos.coord(), id.p, equil.p, k.p, n_elem, pos.scatter.source_ptr(src), pos.scatter.arena_size,
+        upk_check(upk_spring_strided(&ctx->L, kind, pos.coord(), id.p, equil.p, k.p, equil_rows.stride(), n_elem, pos.scatter.source_ptr(src), pos.scatter.arena_size,
                              mode == PotentialAndDerivMode ? pot_terms.p : nullptr), "spring");
         if (mode == PotentialAndDerivMode) reduce_terms();
     }
@@ -77,19 +105,31 @@ RegisterNodeType<Builtin<AngleSpring>, 1> angle_spring_node("angle_spring");
 RegisterNodeType<Builtin<DihedralSpring>, 1> dihedral_spring_node("dihedral_spring");
 
 // cavity_radial: bonds.cpp:323-374 (used to compact synthetic chains)
-struct CavityRadial : public PotentialNode {
+struct CavityRadial : public PotentialNode, PerSystemValues {
     int n_term; CoordNode& pos;
     DevBuf<int> id; DevBuf<float> radius, k; int src;
+    SysRows radius_rows, k_rows;
+    void load_system_values(int s, hid_t_compat g) override {
+        check_size(H(g), "radius", {(size_t)n_term}); check_size(H(g), "spring_constant", {(size_t)n_term});
+        radius_rows.set_row(s, read<float>(H(g), "radius", 1)); k_rows.set_row(s, read<float>(H(g), "spring_constant", 1));
+    }
+    bool values_differ() const override { return radius_rows.differs || k_rows.differs; }
+    void finish_system_values() override {
+        if (!values_differ()) return;
+        radius_rows.differs = k_rows.differs = true;
+        radius_rows.upload_to(radius); k_rows.upload_to(k);
+    }
     CavityRadial(DeviceCtx* c, hid_t_compat grp, CoordNode& pos_) : PotentialNode(c), pos(pos_) {
         auto ids = read<int>(H(grp), "id", 1);
         n_term = (int)ids.size();
         check_size(H(grp), "radius", {(size_t)n_term}); check_size(H(grp), "spring_constant", {(size_t)n_term});
         id.upload(ids); radius.upload(read<float>(H(grp), "radius", 1)); k.upload(read<float>(H(grp), "spring_constant", 1));
+        radius_rows.init(radius.download(), c->n_system); k_rows.init(k.download(), c->n_system);
         src = pos.scatter.add_source(n_term, 1, 3, ids);
         alloc_terms(n_term);
     }
     void compute_value(ComputeMode mode) override {
-        upk_check(upk_cavity_radial(&ctx->L, pos.coord(), id.p, radius.p, k.p, n_term, pos.scatter.source_ptr(src), pos.scatter.arena_size,
+        upk_check(upk_cavity_radial_strided(&ctx->L, pos.coord(), id.p, radius.p, k.p, radius_rows.stride(), n_term, pos.scatter.source_ptr(src), pos.scatter.arena_size,
                                     mode == PotentialAndDerivMode ? pot_terms.p : nullptr), "cavity_radial");
         if (mode == PotentialAndDerivMode) reduce_terms();
     }
@@ -852,18 +892,37 @@ struct EnvironmentCoverage : public CoordNode, BatchedParamDeriv {
 RegisterNodeType<Builtin<EnvironmentCoverage>, 2> environment_coverage_node("environment_coverage");
 
 // hbond_energy: hbond.cpp:417-456
-struct HBondEnergy : public HBondCounter, BatchedParamDeriv {
+// E_protein is a device array of one value per system (E_dev), written by stream-ordered copies: a captured MD graph reads the
+// values of the moment it is replayed, and set_param needs no new capture.
+struct HBondEnergy : public HBondCounter, BatchedParamDeriv, PerSystemValues {
     CoordNode& protein_hbond; float E_protein;
+    vector<float> E_sys; DevBuf<float> E_dev;      // [S]
     HBondEnergy(DeviceCtx* c, hid_t_compat grp, CoordNode& ph) : HBondCounter(c), protein_hbond(ph), E_protein(attr<float>(H(grp), ".", "protein_hbond_energy")) {
         check_elem_width(ph, 7);
         alloc_terms(ph.n_elem);
         fused_forward = fused_backward = true;
+        E_sys.assign(c->n_system, E_protein); E_dev.upload(E_sys);
     }
     void compute_value(ComputeMode mode) override {
-        upk_check(upk_hbond_energy(&ctx->L, protein_hbond.coord(), E_protein, mode == PotentialAndDerivMode ? pot_terms.p : nullptr), "hbond_energy");
+        upk_check(upk_hbond_energy_sys(&ctx->L, protein_hbond.coord(), E_dev.p, mode == PotentialAndDerivMode ? pot_terms.p : nullptr), "hbond_energy");
         if (mode == PotentialAndDerivMode) reduce_terms();
     }
-    vector<float> get_param() const override { return vector<float>(1, E_protein); }
+    void write_E() {      // the host row may be rewritten only once the previous copy has left it
+        hip_check(hipStreamSynchronize(ctx->stream), "hipStreamSynchronize");
+        E_host_staging = E_sys;
+        hip_check(hipMemcpyAsync(E_dev.p, E_host_staging.data(), E_sys.size() * sizeof(float), hipMemcpyHostToDevice, ctx->stream), "H2D E_protein");
+    }
+    vector<float> E_host_staging;
+    void load_system_values(int s, hid_t_compat g) override { E_sys[s] = attr<float>(H(g), ".", "protein_hbond_energy"); }
+    bool values_differ() const override { for (float x : E_sys) if (memcmp(&x, &E_sys[0], sizeof(float))) return true; return false; }
+    void finish_system_values() override { E_dev.upload(E_sys); }
+    void set_param_system(int s, const vector<float>& p) override {
+        if (p.size() != 1u) throw string("expected 1 param to hbond_energy but got " + to_string(p.size()));
+        E_sys.at(s) = p[0];
+        write_E();
+    }
+    vector<float> get_param_system(int s) const override { return vector<float>(1, E_sys.at(s)); }
+    vector<float> get_param() const override { return vector<float>(1, E_sys[0]); }
     vector<float> get_param_deriv(int system) override {   // hbond.cpp:447-448: n_hbond of the last evaluation
         return param_deriv_table(ctx, 1, [&](float* t) { upk_check(upk_column_sum(&ctx->L, protein_hbond.coord(), 6, system, t), "hbond_energy param_deriv"); });
     }
@@ -872,6 +931,8 @@ struct HBondEnergy : public HBondCounter, BatchedParamDeriv {
     void set_param(const vector<float>& p) override {
         if (p.size() != 1u) throw string("expected 1 param to hbond_energy but got " + to_string(p.size()));
         E_protein = p[0];
+        fill(E_sys.begin(), E_sys.end(), E_protein);      // (every system, as the reference's set_param)
+        write_E();
     }
 };
 RegisterNodeType<Builtin<HBondEnergy>, 1> hbond_energy_node("hbond_energy");
@@ -942,15 +1003,11 @@ RegisterNodeType<Builtin<NonlinearCoupling>, 1> nonlinear_coupling_node("nonline
 // Optional restraint / external-field nodes (not emitted for the README force field)
 
 // atom_pos_spring (bonds.cpp:9-50), tension (:53-90), AFM (:93-168), z_flat_bottom (:377-427): one atom per term
-struct PointPotential : public PotentialNode {
+struct PointPotential : public PotentialNode, PerSystemValues {
     int kind, n_term; CoordNode& pos; DevBuf<int> id; DevBuf<float> par; int src;
-    float time_initial = 0.f, time_step = 0.f; int round_num = 0;     // AFM only
-    PointPotential(DeviceCtx* c, hid_t_compat grp, CoordNode& pos_, int kind_) : PotentialNode(c), kind(kind_), pos(pos_) {
-        check_elem_width_lower_bound(pos, 3);
-        const char* id_name = kind == 0 ? "id" : "atom";
-        auto ids = read<int>(H(grp), id_name, 1);
-        n_term = (int)ids.size();
-        for (int x : ids) if (x < 0 || x >= pos.n_elem) throw string("atom index out of range");
+    float time_initial = 0.f, time_step = 0.f; int round_num = 0;     // AFM only (the tip clock is the engine's: its attributes agree across systems)
+    SysRows par_rows;      // [S][n_term * 8]
+    vector<float> read_par(hid_t_compat grp) {
         vector<float> p((size_t)n_term * 8, 0.f);
         auto col = [&](const char* name, int off) {
             check_size(H(grp), name, {(size_t)n_term});
@@ -964,18 +1021,30 @@ struct PointPotential : public PotentialNode {
         else if (kind == 1) vec3("tension_coeff", 0);
         else if (kind == 2) {
             col("spring_const", 0); vec3("starting_tip_pos", 1); vec3("pulling_vel", 4);
-            time_initial = attr<float>(H(grp), "pulling_vel", "time_initial"); time_step = attr<float>(H(grp), "pulling_vel", "time_step");
         } else { col("z0", 0); col("radius", 1); col("spring_constant", 2); }
-        id.upload(ids); par.upload(p);
+        return p;
+    }
+    PointPotential(DeviceCtx* c, hid_t_compat grp, CoordNode& pos_, int kind_) : PotentialNode(c), kind(kind_), pos(pos_) {
+        check_elem_width_lower_bound(pos, 3);
+        const char* id_name = kind == 0 ? "id" : "atom";
+        auto ids = read<int>(H(grp), id_name, 1);
+        n_term = (int)ids.size();
+        for (int x : ids) if (x < 0 || x >= pos.n_elem) throw string("atom index out of range");
+        auto p = read_par(grp);
+        if (kind == 2) { time_initial = attr<float>(H(grp), "pulling_vel", "time_initial"); time_step = attr<float>(H(grp), "pulling_vel", "time_step"); }
+        id.upload(ids); par.upload(p); par_rows.init(p, c->n_system);
         src = pos.scatter.add_source(n_term, 1, 3, ids);
         alloc_terms(n_term);
     }
+    void load_system_values(int s, hid_t_compat g) override { par_rows.set_row(s, read_par(g)); }
+    bool values_differ() const override { return par_rows.differs; }
+    void finish_system_values() override { par_rows.upload_to(par); }
     bool capturable() const override { return kind != 2; }   // the AFM tip position travels as a kernel argument
     void add_loggers(vector<LogValue>& out) override {   // bonds.cpp:130-145 (AFM only, basic level)
         if (kind != 2) return;
         LogValue tip; tip.name = "tip_pos"; tip.dims = {(size_t)n_term, 3}; tip.level = 0;
-        tip.fill = [this](int, float* b) {
-            auto p = par.download(); const float t = time_initial + time_step * round_num;
+        tip.fill = [this](int sys, float* b) {      // (the system's own row)
+            auto p = par_rows.row(sys); const float t = time_initial + time_step * round_num;
             for (int i = 0; i < n_term; ++i) for (int d = 0; d < 3; ++d) b[i * 3 + d] = p[(size_t)i * 8 + 1 + d] + p[(size_t)i * 8 + 4 + d] * t; };
         out.push_back(tip);
         LogValue te; te.name = "time_estimate"; te.dims = {1}; te.level = 0;
@@ -988,7 +1057,7 @@ struct PointPotential : public PotentialNode {
             if (mode == DerivMode) round_num += 1;
             time = time_initial + time_step * round_num;
         }
-        upk_check(upk_point_potential(&ctx->L, kind, pos.coord(), id.p, par.p, n_term, time, pos.scatter.source_ptr(src), pos.scatter.arena_size,
+        upk_check(upk_point_potential_strided(&ctx->L, kind, pos.coord(), id.p, par.p, par_rows.stride(), n_term, time, pos.scatter.source_ptr(src), pos.scatter.arena_size,
                                       mode == PotentialAndDerivMode ? pot_terms.p : nullptr), "point_potential");
         if (mode == PotentialAndDerivMode) reduce_terms();
     }
@@ -1003,15 +1072,10 @@ RegisterNodeType<Builtin<AFMPotential>, 1> AFM_node("AFM");
 RegisterNodeType<Builtin<ZFlatBottom>, 1> z_flat_bottom_node("z_flat_bottom");
 
 // contact: sidechain_radial.cpp:139-205
-struct ContactEnergy : public PotentialNode {
+struct ContactEnergy : public PotentialNode, PerSystemValues {
     int n_contact; CoordNode& bead_pos; DevBuf<int> id; DevBuf<float> par; int src; vector<int> host_id;
-    ContactEnergy(DeviceCtx* c, hid_t_compat grp, CoordNode& bead_pos_) : PotentialNode(c), bead_pos(bead_pos_) {
-        check_elem_width_lower_bound(bead_pos, 3);
-        vector<hsize_t> dims;
-        auto ids = read<int>(H(grp), "id", 2, &dims);
-        n_contact = (int)dims[0];
-        if ((int)dims[1] != 2) throw string("wrong width for id");
-        for (int x : ids) if (x < 0 || x >= bead_pos.n_elem) throw string("contact index out of range");
+    SysRows par_rows;      // [S][n_contact * 4]: the derived scale and cutoff columns per system too
+    vector<float> read_par(hid_t_compat grp) {
         check_size(H(grp), "energy", {(size_t)n_contact}); check_size(H(grp), "distance", {(size_t)n_contact}); check_size(H(grp), "width", {(size_t)n_contact});
         auto en = read<float>(H(grp), "energy", 1), dist = read<float>(H(grp), "distance", 1), width = read<float>(H(grp), "width", 1);
         vector<float> p((size_t)n_contact * 4);
@@ -1019,7 +1083,20 @@ struct ContactEnergy : public PotentialNode {
             const float scale = 1.f / width[i];
             p[(size_t)i * 4] = en[i]; p[(size_t)i * 4 + 1] = dist[i]; p[(size_t)i * 4 + 2] = scale; p[(size_t)i * 4 + 3] = dist[i] + 1.f / scale;   // :171
         }
-        id.upload(ids); par.upload(p); host_id = ids;
+        return p;
+    }
+    void load_system_values(int s, hid_t_compat g) override { par_rows.set_row(s, read_par(g)); }
+    bool values_differ() const override { return par_rows.differs; }
+    void finish_system_values() override { par_rows.upload_to(par); }
+    ContactEnergy(DeviceCtx* c, hid_t_compat grp, CoordNode& bead_pos_) : PotentialNode(c), bead_pos(bead_pos_) {
+        check_elem_width_lower_bound(bead_pos, 3);
+        vector<hsize_t> dims;
+        auto ids = read<int>(H(grp), "id", 2, &dims);
+        n_contact = (int)dims[0];
+        if ((int)dims[1] != 2) throw string("wrong width for id");
+        for (int x : ids) if (x < 0 || x >= bead_pos.n_elem) throw string("contact index out of range");
+        auto p = read_par(grp);
+        id.upload(ids); par.upload(p); host_id = ids; par_rows.init(p, c->n_system);
         src = bead_pos.scatter.add_source(n_contact, 2, 3, ids);
         alloc_terms(n_contact);
     }
@@ -1033,7 +1110,7 @@ struct ContactEnergy : public PotentialNode {
         out.push_back(l);
     }
     void compute_value(ComputeMode mode) override {
-        upk_check(upk_contact(&ctx->L, bead_pos.coord(), id.p, par.p, n_contact, bead_pos.scatter.source_ptr(src), bead_pos.scatter.arena_size,
+        upk_check(upk_contact_strided(&ctx->L, bead_pos.coord(), id.p, par.p, par_rows.stride(), n_contact, bead_pos.scatter.source_ptr(src), bead_pos.scatter.arena_size,
                               mode == PotentialAndDerivMode ? pot_terms.p : nullptr), "contact");
         if (mode == PotentialAndDerivMode) reduce_terms();
     }
@@ -1750,4 +1827,27 @@ double engine_igraph_bytes(DerivEngine& e) {
         if (ig) b += ig->algorithmic_bytes() / e.ctx.n_system;
     }
     return b;
+}
+
+// the values that may differ per system in one engine (upside_hip_construct_files); the nodes above implement PerSystemValues
+const vector<PerSystemValueSpec>& per_system_value_table() {
+    static const vector<PerSystemValueSpec> t = {
+        {"dist_spring", {"equil_dist", "spring_const"}, {}},
+        {"angle_spring", {"equil_dist", "spring_const"}, {}},
+        {"dihedral_spring", {"equil_dist", "spring_const"}, {}},
+        {"cavity_radial", {"radius", "spring_constant"}, {}},
+        {"atom_pos_spring", {"x0", "spring_const"}, {}},
+        {"tension", {"tension_coeff"}, {}},
+        {"AFM", {"spring_const", "starting_tip_pos", "pulling_vel"}, {}},   // (the attributes of pulling_vel must agree: one tip clock)
+        {"z_flat_bottom", {"z0", "radius", "spring_constant"}, {}},
+        {"contact", {"energy", "distance", "width"}, {}},
+        {"hbond_energy", {}, {"protein_hbond_energy"}},
+    };
+    return t;
+}
+const PerSystemValueSpec* per_system_value_spec(const string& node_name) {
+    string type;
+    for (auto& kv : node_creation_map()) if (is_prefix(kv.first, node_name)) type = kv.first;   // the registry's rule (initialize_engine_from_hdf5)
+    for (auto& sp : per_system_value_table()) if (sp.type == type) return &sp;
+    return nullptr;
 }

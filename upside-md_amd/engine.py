@@ -223,6 +223,29 @@ class Ensemble(object):
         if not self.engine:
             raise RuntimeError('Unable to initialize upside engine: %s' % c.upside_hip_last_error().decode())
 
+    @classmethod
+    def from_files(cls, paths, device=None, quiet=True, library=None):
+        """one system per configuration file, in order (a file may repeat): a Hamiltonian ladder in one engine.  The files
+        share their potential's structure; only the values of the per-system table may differ."""
+        self = cls.__new__(cls)
+        self.lib = library if library is not None else default_library()
+        c = self.calc = self.lib.calc
+        cls._bind(c)
+        paths = [str(p) for p in paths]
+        self.config_file_path = paths[0]
+        self.config_file_paths = paths
+        self.n_system = len(paths)
+        with h5lite.open_file(paths[0]) as t:
+            self.initial_pos = t.read('input/pos', 'f4')[:, :, 0]
+        self.n_atom = self.initial_pos.shape[0]
+        if device is not None:
+            self._check(c.upside_hip_set_device(int(device)), 'set_device')
+        arr = (ct.c_char_p * len(paths))(*[_b(p) for p in paths])
+        self.engine = c.upside_hip_construct_files(self.n_atom, len(paths), arr, bool(quiet))
+        if not self.engine:
+            raise RuntimeError('Unable to initialize upside engine: %s' % c.upside_hip_last_error().decode())
+        return self
+
     @staticmethod
     def _bind(c):
         if getattr(c, '_ensemble_bound', False):
@@ -251,6 +274,12 @@ class Ensemble(object):
         c.upside_hip_get_param_deriv_all.argtypes = [vp, ct.c_char_p, i32, vp]
         c.upside_hip_param_deriv_accumulate.argtypes = [vp, ct.c_char_p, vp]
         c.upside_hip_param_deriv_read.argtypes = [vp, ct.c_char_p, i32, vp, vp, i32]
+        c.upside_hip_construct_files.restype = vp
+        c.upside_hip_construct_files.argtypes = [i32, i32, ct.POINTER(ct.c_char_p), ct.c_bool]
+        c.upside_hip_group_configurations.argtypes = [i32, ct.POINTER(ct.c_char_p), vp]
+        c.upside_hip_set_param_system.argtypes = [vp, ct.c_char_p, i32, i32, vp]
+        c.upside_hip_get_param_system.argtypes = [vp, ct.c_char_p, i32, i32, vp]
+        c.upside_hip_hamiltonian_swap.argtypes = [vp, i32, vp, u32, u64, i32, vp]
         c.upside_hip_last_error.restype = ct.c_char_p
         c._ensemble_bound = True
 
@@ -316,6 +345,36 @@ class Ensemble(object):
 
     def run_rounds(self, n_round):
         self._check(self.calc.upside_hip_run_md(self.engine, int(n_round)), 'run_md')
+
+    # -- parameters (set_param / get_param of the reference; per system for the nodes of the per-system table) -----------------
+    def set_param(self, param, node_name, system=None):
+        """system=None: every system (the reference's set_param); otherwise that system only"""
+        p = np.require(np.asarray(param, 'f4').ravel(), dtype='f4', requirements='C')
+        if system is None:
+            self._check(self.calc.set_param(len(p), p.ctypes.data, self.engine, _b(node_name)), 'set_param')
+        else:
+            self._check(self.calc.upside_hip_set_param_system(self.engine, _b(node_name), int(system), len(p), p.ctypes.data), 'set_param_system')
+
+    def get_param(self, shape, node_name, system=0):
+        shape = tuple(shape)
+        out = np.zeros(shape, 'f4')
+        n = int(np.prod(shape, dtype=np.int64))
+        if system == 0:      # (get_param: system 0's values, any node)
+            self._check(self.calc.get_param(n, out.ctypes.data, self.engine, _b(node_name)), 'get_param')
+        else:
+            self._check(self.calc.upside_hip_get_param_system(self.engine, _b(node_name), int(system), n, out.ctypes.data), 'get_param_system')
+        return out
+
+    def hamiltonian_swap(self, pairs, base_seed, round_num, draw0=0, want_accepted=False):
+        """one Hamiltonian swap set on the device (main.cpp:251-273): energy pass, pairs trade coordinates, energy pass,
+        Metropolis verdicts at each system's own temperature, refused pairs trade back.  draw0 < 0 continues the draw counter
+        of the previous set on the device.  want_accepted: (accepted as bool array, next draw) read back (synchronises);
+        otherwise None and nothing waits."""
+        p = np.ascontiguousarray(np.asarray(pairs, 'i4').reshape(-1, 2))
+        acc = np.zeros(len(p) + 1, 'i4') if want_accepted else None
+        self._check(self.calc.upside_hip_hamiltonian_swap(self.engine, int(len(p)), p.ctypes.data, int(base_seed) & 0xFFFFFFFF, int(round_num),
+                                                          int(draw0), acc.ctypes.data if want_accepted else None), 'hamiltonian_swap')
+        return (acc[:-1].astype(bool), int(acc[-1])) if want_accepted else None
 
     # -- parameter derivatives of every system (training: e.g. contrastive divergence) ----------------------------------
     # All three see the state of the LAST force pass (as get_param_deriv does): after set_pos or MD steps, call energies()
@@ -383,6 +442,19 @@ class Ensemble(object):
             self.close()
         except Exception:
             pass
+
+
+def group_configurations(paths, library=None):
+    """the grouping upside_main uses (HDF5 only, no GPU): group index of every file, numbered by first appearance.  Files that
+    are identical or differ only in the values of the per-system table share a group."""
+    lib = library if library is not None else default_library()
+    Ensemble._bind(lib.calc)
+    paths = [str(p) for p in paths]
+    arr = (ct.c_char_p * len(paths))(*[_b(p) for p in paths])
+    out = np.zeros(len(paths), 'i4')
+    if lib.calc.upside_hip_group_configurations(len(paths), arr, out.ctypes.data) < 0:
+        raise RuntimeError('group_configurations failed: %s' % lib.calc.upside_hip_last_error().decode())
+    return out
 
 
 def replica_decide(pairs, beta, energy, base_seed, round_num, draw0=0, library=None):
