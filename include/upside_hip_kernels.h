@@ -468,6 +468,30 @@ int upk_hamiltonian_decide(const upk_launch_t* L, const float* e_old, const floa
 /* swap back the pairs whose accepted[p] is 0 */
 int upk_swap_refused_pairs(const upk_launch_t* L, upk_coord_t pos, int n_pair, const int* pairs, const int* accepted);
 
+/* ---- learned backbone potential (src/nn.cpp: backbone_featurizer, conv1d, scaled_sum), csrc/kernels_nn.hip ----
+ * backbone_featurizer: out row r = (sin phi, cos phi, sin psi, cos psi, don, acc); phi, psi = columns 0, 1 of rama row rama_idx[r],
+ * don / acc = column 6 of hbond rows hbond_idx[2r] / hbond_idx[2r+1] (0 where the index is -1).  The backward pass ADDS into the
+ * parents' sens with plain read-modify-writes: the indices must be distinct (checked by the node). */
+int upk_backbone_featurizer_fwd(const upk_launch_t* L, upk_coord_t rama, upk_coord_t hbond, const int* rama_idx, const int* hbond_idx, upk_coord_t out);
+int upk_backbone_featurizer_bwd(const upk_launch_t* L, upk_coord_t rama, upk_coord_t hbond, const int* rama_idx, const int* hbond_idx, upk_coord_t self);
+/* conv1d: out[r,co] = act(bias[co] + sum_{w,ci} in[r+w,ci] * weights[w,ci,co]), r < n_in - W + 1.  param = weights [W][C_in][C_out]
+ * followed by bias [C_out] in ONE device array (set_param rewrites it in place).  Every sum runs in one fixed order (w, then the
+ * channel, ascending) whatever the batch or the tiling. */
+enum { UPK_ACT_IDENTITY = 0, UPK_ACT_RELU = 1, UPK_ACT_TANH = 2 };
+typedef struct { const float* param; int W, C_in, C_out, act; } upk_conv1d_t;
+/* 1 when the layer's tiles (a slice of the weights + the rows of a tile and their halo) fit the workgroup's LDS for the forward,
+ * backward and weight-gradient kernels: always for W <= 15 and C_in, C_out <= 64 */
+int upk_conv1d_fits(int W, int C_in, int C_out);
+int upk_conv1d_fwd(const upk_launch_t* L, const upk_conv1d_t* P, upk_coord_t in, upk_coord_t out);
+/* in.sens[j,ci] += sum_{w,co} g[j-w,co] * weights[w,ci,co], g = out.sens * act'(out.out): a gather over the <= W rows that read j */
+int upk_conv1d_bwd(const upk_launch_t* L, const upk_conv1d_t* P, upk_coord_t in, upk_coord_t out);
+/* dW[w,ci,co] = sum_r g[r,co] * in[r+w,ci], db[co] = sum_r g[r,co] (r ascending), in the layout of param: one system into
+ * table [n_param], or every system into table [n_system][n_param] */
+int upk_conv1d_param_deriv(const upk_launch_t* L, const upk_conv1d_t* P, upk_coord_t in, upk_coord_t out, int system, float* table);
+int upk_conv1d_param_deriv_all(const upk_launch_t* L, const upk_conv1d_t* P, upk_coord_t in, upk_coord_t out, float* table);
+/* scaled_sum: in.sens[r] += *scale, pot_terms[s][r] = *scale * in[r] (pot_terms may be NULL); scale is a device value */
+int upk_scaled_sum(const upk_launch_t* L, upk_coord_t in, const float* scale, float* pot_terms);
+
 #ifdef __cplusplus
 }
 #endif

@@ -3,7 +3,8 @@
 of upside_config.py; needs the reference's parameter directory, so it runs where /root/reference is available).
 
     python tools/make_config.py --pdb 1abc.pdb --chains A --out 1abc.up [--param-dir /root/reference/parameters]
-                                [--cutoff 7|10] [--cavity-radius R] [--contacts table] [--z-flat-bottom table] ...
+                                [--cutoff 7|10] [--cavity-radius R] [--contacts table] [--z-flat-bottom table]
+                                [--backbone-network net.npz] ...
 
 The Ramachandran maps come from --rama-library (the README's rama.dat: neighbour-dependent coil / sheet maps, with
 --rama-sheet-mixing-energy, --rama-library-combining-rule, --secstr-bias as in py/upside_config.py) or, without one, are the
@@ -45,6 +46,8 @@ def main():
     ap.add_argument('--fix-rotamer', default='', help='table "residue restype chain resnum chi1 chi2" (degrees): those residues keep one rotamer state')
     ap.add_argument('--hbond-exclude-residues', default='', help='comma-separated residues without backbone H-bond sites (ranges a-b allowed)')
     ap.add_argument('--loose-hbond-criteria', action='store_true', help='permissive H-bond geometry (static structures only)')
+    ap.add_argument('--backbone-network', default='', help='.npz with weights_k [W, C_in, C_out], bias_k [C_out], activation_k (ReLU | Tanh | '
+                    'Identity) for k = 0, 1, ... and scale: appended as backbone_featurizer -> conv1d layers -> scaled_sum')
     a = ap.parse_args()
     pkg = load_package(); cfg = pkg.config
     if not a.pdb:
@@ -79,6 +82,12 @@ def main():
         cfg.add_restraints(a.out, **extra)
     if a.pivot_moves:
         cfg.add_pivot_moves(a.out)
+    if a.backbone_network:
+        net = np.load(a.backbone_network)
+        n_layer = len([k for k in net.files if k.startswith('weights_')])
+        layers = [(net['weights_%d' % k], net['bias_%d' % k], str(np.ravel(net['activation_%d' % k])[0])) for k in range(n_layer)]
+        names = cfg.add_backbone_network(a.out, layers, float(np.ravel(net['scale'])[0]))
+        print('backbone network: %s' % ' -> '.join(names))
     print('%s: %i residues, %i side-chain beads' % (a.out, info['n_res'], info['n_bead']))
 
 

@@ -13,15 +13,35 @@ mkdir -p "$OUT"
 want() { [ "$MODE" = all ] || [ "$MODE" = "$1" ]; }
 
 if want pmc; then
-[ -s "$OUT/bench_R4096.json" ] || python3 bench.py --steps 100 --warmup 30 --full --no-cpu-baseline 2>"$OUT/bench_R4096.err" | grep '^{' | tail -1 > "$OUT/bench_R4096.json"
-# (the one-replica latency leg is left out of the profiled command: its launches of the same kernels would dilute the
-#  per-launch averages of the counters)
-CMD="python3 bench.py --steps 60 --warmup 15 --full --no-cpu-baseline --no-single-system --no-parity-check"
-for t in trace fetch write sq; do rm -rf "$OUT/$t"; done
-rocprofv3 --kernel-trace --stats -d "$OUT/trace" -o trace -- $CMD > "$OUT/trace.log" 2>&1
-rocprofv3 --kernel-trace --pmc FETCH_SIZE -d "$OUT/fetch" -o fetch -- $CMD > "$OUT/fetch.log" 2>&1
-rocprofv3 --kernel-trace --pmc WRITE_SIZE -d "$OUT/write" -o write -- $CMD > "$OUT/write.log" 2>&1
-rocprofv3 --kernel-trace --pmc SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_INST_ANY SQ_ACTIVE_INST_VALU SQ_INSTS_VALU SQ_ACTIVE_INST_LDS SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE -d "$OUT/sq" -o sq -- $CMD > "$OUT/sq.log" 2>&1
+# Every GPU program of this block runs under a time limit of its own and the block stops at the first one that does not end with
+# status 0 (a fault, an abort, a limit): nothing more is started on a device that may have faulted.  The limit of a profiler pass
+# is sized from the duration of the bench run just made (a pass runs fewer steps, under the profiler): 3 x that + 3 minutes;
+# 15 minutes where the bench line was already there.
+pmc_passes() {
+  local limit=900 t0 dur
+  if [ ! -s "$OUT/bench_R4096.json" ]; then
+    t0=$(date +%s)
+    timeout -k 10 900 python3 bench.py --steps 100 --warmup 30 --full --no-cpu-baseline >"$OUT/bench_R4096.out" 2>"$OUT/bench_R4096.err" \
+      || { echo "refresh_profiles: the bench run ended with status $?: stopping" >&2; return 1; }
+    dur=$(( $(date +%s) - t0 ))
+    limit=$(( 3 * dur + 180 ))
+    grep '^{' "$OUT/bench_R4096.out" | tail -1 > "$OUT/bench_R4096.json"
+  fi
+  # (the one-replica latency leg is left out of the profiled command: its launches of the same kernels would dilute the
+  #  per-launch averages of the counters)
+  local CMD="python3 bench.py --steps 60 --warmup 15 --full --no-cpu-baseline --no-single-system --no-parity-check"
+  local t
+  for t in trace fetch write sq; do rm -rf "$OUT/$t"; done
+  timeout -k 10 $limit rocprofv3 --kernel-trace --stats -d "$OUT/trace" -o trace -- $CMD > "$OUT/trace.log" 2>&1 \
+    || { echo "refresh_profiles: the kernel-trace pass ended with status $?: stopping" >&2; return 1; }
+  timeout -k 10 $limit rocprofv3 --kernel-trace --pmc FETCH_SIZE -d "$OUT/fetch" -o fetch -- $CMD > "$OUT/fetch.log" 2>&1 \
+    || { echo "refresh_profiles: the FETCH_SIZE pass ended with status $?: stopping" >&2; return 1; }
+  timeout -k 10 $limit rocprofv3 --kernel-trace --pmc WRITE_SIZE -d "$OUT/write" -o write -- $CMD > "$OUT/write.log" 2>&1 \
+    || { echo "refresh_profiles: the WRITE_SIZE pass ended with status $?: stopping" >&2; return 1; }
+  timeout -k 10 $limit rocprofv3 --kernel-trace --pmc SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_INST_ANY SQ_ACTIVE_INST_VALU SQ_INSTS_VALU SQ_ACTIVE_INST_LDS SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE -d "$OUT/sq" -o sq -- $CMD > "$OUT/sq.log" 2>&1 \
+    || { echo "refresh_profiles: the SQ pass ended with status $?: stopping" >&2; return 1; }
+}
+pmc_passes || exit 1
 for t in trace fetch write sq; do
   db=$(find "$OUT/$t" -name "*.db" | head -1)
   [ -n "$db" ] && python3 tools/rocpd_summary.py "$db" "$OUT/${t}_summary.txt"

@@ -810,6 +810,73 @@ def add_restraints(path, z_flat_bottom=None, tension=None, afm=None, pos_spring=
 
 
 # --- real structures: the main path of py/PDB_to_initial_structure.py without ProDy ---------------------------------
+NETWORK_ACTIVATIONS = ('ReLU', 'Tanh', 'Identity')
+
+
+def add_backbone_network(path, layers, scale, name='backbone_nn'):
+    """append the reference's learned backbone potential (src/nn.cpp) to an existing configuration:
+      backbone_featurizer          arguments rama_coord, protein_hbond; one row of six features per residue
+                                   (sin/cos of phi and psi, donor and acceptor hydrogen-bond counts);
+                                   rama_idx = every residue, hbond_idx[res] = (the protein_hbond row whose id1 is res,
+                                   n_donor + the row whose id2 is res), -1 for a residue without that site
+      conv1d_<name>_<k>            one per entry (weights [W, C_in, C_out], bias [C_out], activation) of `layers`,
+                                   each reading the previous one; activation is 'ReLU', 'Tanh' or 'Identity'
+      scaled_sum_<name>            energy = scale * sum over the rows of the last layer (which has one channel)
+    Every layer shortens the chain by W - 1 rows.  A second network (another `name`) shares the featurizer node.
+    Returns the node names in graph order."""
+    layers = [(np.asarray(w, 'f4'), np.asarray(b, 'f4').reshape(-1), str(a)) for w, b, a in layers]
+    if not layers:
+        raise ValueError('a backbone network needs at least one layer')
+    c_prev, halo = 6, 0
+    for k, (w, b, a) in enumerate(layers):
+        if w.ndim != 3 or w.shape[0] < 1:
+            raise ValueError('layer %d: weights must have shape [W, C_in, C_out]' % k)
+        if w.shape[1] != c_prev:
+            raise ValueError('layer %d: weights have %d input channels but the previous layer has %d' % (k, w.shape[1], c_prev))
+        if b.shape != (w.shape[2],):
+            raise ValueError('layer %d: bias has %d entries for %d output channels' % (k, b.size, w.shape[2]))
+        if a not in NETWORK_ACTIVATIONS:
+            raise ValueError('layer %d: activation %r is not one of %s' % (k, a, ', '.join(NETWORK_ACTIVATIONS)))
+        c_prev = w.shape[2]
+        halo += w.shape[0] - 1
+    if c_prev != 1:
+        raise ValueError('the last layer must have one output channel (scaled_sum adds up a 1-wide node), not %d' % c_prev)
+    with h5lite.open_file(path, 'r+') as f:
+        pot = f.group('input').group('potential')
+        for need in ('rama_coord', 'protein_hbond'):
+            if need not in pot:
+                raise ValueError('%s has no %s node' % (path, need))
+        n_res = pot.group('rama_coord').shape('id')[0]
+        if n_res <= halo:
+            raise ValueError('the chain has %d residues, not more than the %d rows the layers consume' % (n_res, halo))
+        ph = pot.group('protein_hbond')
+        id1, id2 = ph.read('id1', 'i4'), ph.read('id2', 'i4')
+        hbond_idx = np.full((n_res, 2), -1, 'i4')
+        for col, ids, first in ((0, id1, 0), (1, id2, len(id1))):
+            for row, res in enumerate(ids):
+                if not 0 <= res < n_res:
+                    raise ValueError('protein_hbond names residue %d outside the chain' % res)
+                if hbond_idx[res, col] != -1:
+                    raise ValueError('protein_hbond has two sites of one kind on residue %d' % res)
+                hbond_idx[res, col] = first + row
+        names = ['backbone_featurizer']
+        names += ['conv1d_%s_%d' % (name, k) for k in range(len(layers))]
+        names.append('scaled_sum_' + name)
+        for nm in names[1:]:
+            if nm in pot:
+                raise ValueError('%s already has a node %s' % (path, nm))
+        if names[0] not in pot:
+            g = pot.create_group(names[0]); _args(g, ['rama_coord', 'protein_hbond'])
+            g.write('rama_idx', np.arange(n_res, dtype='i4')); g.write('hbond_idx', hbond_idx)
+        for k, (w, b, a) in enumerate(layers):
+            g = pot.create_group(names[1 + k]); _args(g, [names[k]])
+            g.write('weights', w); g.write('bias', b)
+            g.set_attr('activation', [a])
+        g = pot.create_group(names[-1]); _args(g, [names[-2]])
+        g.set_attr('scale', float(scale))
+    return names
+
+
 def _dihedral(x1, x2, x3, x4):
     b1, b2, b3 = x2 - x1, x3 - x2, x4 - x3
     b2b3 = np.cross(b2, b3)

@@ -1708,6 +1708,115 @@ struct RegisterRotamer {
 };
 RegisterRotamer rotamer_node("rotamer");
 
+// ---------------------------------------------------------------------------------------------------
+// Learned backbone potential: nn.cpp:14-107 (backbone_featurizer), :110-205 (conv1d), :208-241 (scaled_sum); kernels_nn.hip.
+// conv1d and scaled_sum also serve their weight gradients (the reference's nodes have no get_param_deriv).
+
+// backbone_featurizer: one row (sin phi, cos phi, sin psi, cos psi, donor count, acceptor count) per entry of rama_idx.
+// The backward pass adds into the parents' sens directly, as weighted_pos does: the indices must be distinct.
+struct BackboneFeaturizer : public CoordNode {
+    CoordNode &rama, &hbond; DevBuf<int> rama_idx, hbond_idx;
+    BackboneFeaturizer(DeviceCtx* c, hid_t_compat grp, CoordNode& rama_, CoordNode& hbond_)
+        : CoordNode(c, (int)dset_size(1, H(grp), "rama_idx")[0], 6), rama(rama_), hbond(hbond_) {
+        check_elem_width_lower_bound(rama, 2);
+        check_elem_width_lower_bound(hbond, 7);
+        check_size(H(grp), "rama_idx", {(size_t)n_elem}); check_size(H(grp), "hbond_idx", {(size_t)n_elem, 2});
+        auto ri = read<int>(H(grp), "rama_idx", 1); auto hi = read<int>(H(grp), "hbond_idx", 2);
+        require_injective(ri, rama.n_elem, "backbone_featurizer rama_idx");
+        vector<int> named;
+        for (int x : hi) {
+            if (x < -1 || x >= hbond.n_elem) throw string("backbone_featurizer hbond_idx: index out of range");
+            if (x >= 0) named.push_back(x);
+        }
+        require_injective(named, hbond.n_elem, "backbone_featurizer hbond_idx");
+        rama_idx.upload(ri); hbond_idx.upload(hi);
+    }
+    void compute_value(ComputeMode) override {
+        upk_check(upk_backbone_featurizer_fwd(&ctx->L, rama.coord(), hbond.coord(), rama_idx.p, hbond_idx.p, coord()), "backbone_featurizer_fwd"); }
+    void propagate_deriv() override {
+        upk_check(upk_backbone_featurizer_bwd(&ctx->L, rama.coord(), hbond.coord(), rama_idx.p, hbond_idx.p, coord()), "backbone_featurizer_bwd"); }
+};
+RegisterNodeType<Builtin<BackboneFeaturizer>, 2> backbone_featurizer_node("backbone_featurizer");
+
+// conv1d along the chain.  get_param() = weights [W][C_in][C_out] in file order, then bias [C_out]; one device array, rewritten in
+// place by set_param (no kernel argument changes: a captured MD graph reads the new weights at its next replay).
+struct Conv1D : public CoordNode, BatchedParamDeriv {
+    CoordNode& input; upk_conv1d_t P; vector<float> param; DevBuf<float> d_param;
+    static int rows_out(hid_t_compat grp, const CoordNode& in) {
+        const int W = (int)dset_size(3, H(grp), "weights")[0];
+        if (W < 1) throw string("conv1d: weights must have at least one row (W >= 1)");
+        if (in.n_elem < W) throw string("conv1d: the argument has ") + to_string(in.n_elem) + " rows, fewer than the kernel width W = " + to_string(W);
+        return in.n_elem - W + 1;
+    }
+    Conv1D(DeviceCtx* c, hid_t_compat grp, CoordNode& input_)
+        : CoordNode(c, rows_out(grp, input_), (int)dset_size(3, H(grp), "weights")[2]), input(input_) {
+        memset(&P, 0, sizeof(P));
+        vector<hsize_t> dims;
+        param = read<float>(H(grp), "weights", 3, &dims);
+        P.W = (int)dims[0]; P.C_in = (int)dims[1]; P.C_out = (int)dims[2];
+        if (P.C_in != input.elem_width)
+            throw string("conv1d: weights have C_in = ") + to_string(P.C_in) + " input channels but the argument has elem_width " + to_string(input.elem_width);
+        if (P.C_out < 1) throw string("conv1d: weights must have at least one output channel");
+        const size_t n_bias = dset_size(1, H(grp), "bias")[0];
+        if (n_bias != (size_t)P.C_out) throw string("conv1d: bias has ") + to_string(n_bias) + " entries, expected C_out = " + to_string(P.C_out);
+        auto bias = read<float>(H(grp), "bias", 1);
+        param.insert(param.end(), bias.begin(), bias.end());
+        auto activation_str = attr_strings(H(grp), ".", "activation");
+        if (activation_str.size() != 1u) throw string("Invalid number of activations");
+        if (activation_str[0] == "ReLU") P.act = UPK_ACT_RELU;
+        else if (activation_str[0] == "Tanh") P.act = UPK_ACT_TANH;
+        else if (activation_str[0] == "Identity") P.act = UPK_ACT_IDENTITY;
+        else throw string("Invalid activation name");
+        if (!upk_conv1d_fits(P.W, P.C_in, P.C_out))
+            throw string("conv1d: a layer with W = ") + to_string(P.W) + ", C_in = " + to_string(P.C_in) + ", C_out = " + to_string(P.C_out) +
+                  " exceeds the device limit (W <= 15 with C_in, C_out <= 64 always fits; beyond that two channels of the weights and a 64-row tile with its halo must fit 60 KB of LDS)";
+        d_param.upload(param); P.param = d_param.p;
+    }
+    void compute_value(ComputeMode) override { upk_check(upk_conv1d_fwd(&ctx->L, &P, input.coord(), coord()), "conv1d_fwd"); }
+    void propagate_deriv() override { upk_check(upk_conv1d_bwd(&ctx->L, &P, input.coord(), coord()), "conv1d_bwd"); }
+    vector<float> get_param() const override { return param; }
+    void set_param(const vector<float>& p) override {
+        if (p.size() != param.size()) throw string("conv1d expects ") + to_string(param.size()) + " parameters (weights, then bias) but got " + to_string(p.size());
+        param = p;
+        hip_check(hipStreamSynchronize(ctx->stream), "hipStreamSynchronize");
+        hip_check(hipMemcpy(d_param.p, p.data(), p.size() * sizeof(float), hipMemcpyHostToDevice), "H2D");
+    }
+    vector<float> get_param_deriv(int system) override {
+        return param_deriv_table(ctx, param.size(), [&](float* t) {
+            upk_check(upk_conv1d_param_deriv(&ctx->L, &P, input.coord(), coord(), system, t), "conv1d param_deriv"); });
+    }
+    size_t param_deriv_size() const override { return param.size(); }
+    void param_deriv_all(float* dev) override { upk_check(upk_conv1d_param_deriv_all(&ctx->L, &P, input.coord(), coord(), dev), "conv1d param_deriv_all"); }
+};
+RegisterNodeType<Builtin<Conv1D>, 1> conv1d_node("conv1d");
+
+// scaled_sum: potential = scale * sum of a 1-wide argument.  scale is a device value (set_param changes no kernel argument).
+struct ScaledSum : public PotentialNode, BatchedParamDeriv {
+    CoordNode& input; float scale; DevBuf<float> d_scale;
+    ScaledSum(DeviceCtx* c, hid_t_compat grp, CoordNode& input_) : PotentialNode(c), input(input_), scale(attr<float>(H(grp), ".", "scale")) {
+        if (input.elem_width != 1) throw string("Sum only works on elem width 1");
+        d_scale.upload(vector<float>(1, scale));
+        alloc_terms(input.n_elem);
+    }
+    void compute_value(ComputeMode mode) override {
+        upk_check(upk_scaled_sum(&ctx->L, input.coord(), d_scale.p, mode == PotentialAndDerivMode ? pot_terms.p : nullptr), "scaled_sum");
+        if (mode == PotentialAndDerivMode) reduce_terms();
+    }
+    vector<float> get_param() const override { return vector<float>(1, scale); }
+    void set_param(const vector<float>& p) override {
+        if (p.size() != 1u) throw string("expected 1 param to scaled_sum but got " + to_string(p.size()));
+        scale = p[0];
+        hip_check(hipStreamSynchronize(ctx->stream), "hipStreamSynchronize");
+        hip_check(hipMemcpy(d_scale.p, &scale, sizeof(float), hipMemcpyHostToDevice), "H2D");
+    }
+    vector<float> get_param_deriv(int system) override {
+        return param_deriv_table(ctx, 1, [&](float* t) { upk_check(upk_column_sum(&ctx->L, input.coord(), 0, system, t), "scaled_sum param_deriv"); });
+    }
+    size_t param_deriv_size() const override { return 1; }
+    void param_deriv_all(float* dev) override { upk_check(upk_column_sum_all(&ctx->L, input.coord(), 0, dev), "scaled_sum param_deriv_all"); }
+};
+RegisterNodeType<Builtin<ScaledSum>, 1> scaled_sum_node("scaled_sum");
+
 }  // namespace
 
 // accessors used by the C-ABI layer (engine_c_api.cpp)
