@@ -221,6 +221,40 @@ int upside_hip_hamiltonian_swap(DerivEngine* engine, int n_pair, const int* pair
                                 int* accepted);
 const char* upside_hip_last_error(void);
 
+/* Collective variables of every system, computed on the device in one launch (csrc/kernels_cv.hip) and recordable during MD with no
+ * host round trip.  kind: 0 rg (radius of gyration of the selection), 1 rmsd (minimum over proper rigid motions to a reference given
+ * for the same selection), 2 contacts (Q = mean over pairs of 1 / (1 + exp(beta (r_ij - lambda r0_ij)))), 3 distance.
+ *   _cv_define: CSR layout -- atoms[atom_start[c] : atom_start[c+1]] is the selection of CV c (two atoms for a distance, interleaved
+ *     pairs for contacts); ref_pos (rows of 3) holds the references of the rmsd CVs back to back in CV order, contact_r0 the r0 of the
+ *     contacts CVs' pairs likewise; contact_beta / contact_lambda have n_cv entries (read for contacts CVs only).  Arrays a definition
+ *     has no use for may be NULL.  Replaces any earlier definition (and stops a recording); n_cv = 0 clears it.  Refused, with
+ *     upside_hip_last_error set and the earlier definition still in force: an unknown kind, an atom out of range, an empty selection,
+ *     an rmsd selection under 3 atoms, an odd contacts list, a distance without exactly 2 atoms, r0 <= 0, more than 64 CVs
+ *     (UPK_CV_MAX) or more than 2^24 entries in one list (UPK_CV_MAX_LIST).
+ *   _cv_load: the same from the group /input/collective_variables of a configuration (datasets kind, atom_start, atoms, ref_pos (n,3),
+ *     contact_r0, contact_beta, contact_lambda and the fixed-length string vector names; config.add_collective_variables writes it).
+ *     Returns the number of CVs, 0 without the group, -1 on error (the convention of upside_hip_load_mc).
+ *   _cv_count: the number of CVs defined.
+ *   _cv_compute: out is host (n_system, n_cv), at the current device positions; no force pass, pair lists untouched.
+ *   _cv_record: from this call on every every_n_round-th completed MD round (three leapfrog stages; counted from the call) appends one
+ *     (n_system, n_cv) sample to a device buffer of `capacity` samples, inside upside_hip_run_md / _run_steps, on the engine's stream,
+ *     without synchronising.  The sample decision lives on the device, so the eager loop and the captured graph give the same
+ *     series.  A full buffer stops storing; further samples are only counted.  every_n_round = 0 stops recording and frees the
+ *     buffer; with recording off the MD loop enqueues nothing for it.  Samples follow the slot (temperature / Hamiltonian) like
+ *     /output: a replica swap trades coordinates and the slot's series continues.  Monte-Carlo steps take no samples.
+ *   _cv_read: samples [first, first + n) into out (n, n_system, n_cv) (n = 0: counts only, out may be NULL); *n_stored samples are held,
+ *     *n_attempted were due since the last reset (either may be NULL); reset != 0 empties the buffer, the round count runs on.
+ * A system's values are bit-identical run to run, whatever the batch size or its place in the batch, recorded or computed. */
+int upside_hip_cv_define(DerivEngine* engine, int n_cv, const int* kind, const int* atom_start /* n_cv+1 */, const int* atoms,
+                         const float* ref_pos, const float* contact_r0, const float* contact_beta /* n_cv */,
+                         const float* contact_lambda /* n_cv */);
+int upside_hip_cv_load(DerivEngine* engine, const char* config_file);
+int upside_hip_cv_count(DerivEngine* engine);
+int upside_hip_cv_compute(DerivEngine* engine, float* out /* host (n_system, n_cv) */);
+int upside_hip_cv_record(DerivEngine* engine, int every_n_round, int capacity);
+int upside_hip_cv_read(DerivEngine* engine, int first, int n, float* out /* (n, n_system, n_cv) */, long long* n_stored,
+                       long long* n_attempted, int reset);
+
 /* Per-kernel timing hooks used by bench.py.  With profiling enabled every interaction-graph / BP kernel
  * launch is bracketed by HIP events on the engine's stream.  upside_hip_profile_dump writes one text line per
  * kernel: "<kind>:<node> <total ms> <launches> <total algorithmic bytes> <total pair evaluations>" (bytes as defined in

@@ -492,6 +492,33 @@ int upk_conv1d_param_deriv_all(const upk_launch_t* L, const upk_conv1d_t* P, upk
 /* scaled_sum: in.sens[r] += *scale, pot_terms[s][r] = *scale * in[r] (pot_terms may be NULL); scale is a device value */
 int upk_scaled_sum(const upk_launch_t* L, upk_coord_t in, const float* scale, float* pot_terms);
 
+/* ---- collective variables of every system (upside_hip_cv_*), csrc/kernels_cv.hip ---------------------------------------------
+ * n_cv CVs, each over its own atom list atoms[atom_start[c] : atom_start[c+1]] (CSR):
+ *   UPK_CV_RG        sqrt of the mean squared distance to the list's centroid
+ *   UPK_CV_RMSD      minimum RMSD over proper rigid motions to ref rows aux_start[c].. (one per list atom, CENTRED by the host, fp64);
+ *                    ref_g[c] = sum of their squared norms
+ *   UPK_CV_CONTACTS  the list is interleaved pairs; mean over pairs of 1 / (1 + exp(beta[c] * (r - lambda[c] * r0))), r0 = r0[aux_start[c] + pair]
+ *   UPK_CV_DISTANCE  |x(atoms[0]) - x(atoms[1])|
+ * One workgroup per system, every sum in fp64 and in one fixed order, no atomics: a system's row is bit-identical run to run and
+ * whatever else shares its batch.  The lists are not staged anywhere, so the only limits are UPK_CV_MAX CVs per definition and
+ * UPK_CV_MAX_LIST entries per list (what the launch checks and the 32-bit indices hold). */
+enum { UPK_CV_RG = 0, UPK_CV_RMSD = 1, UPK_CV_CONTACTS = 2, UPK_CV_DISTANCE = 3 };
+#define UPK_CV_MAX 64
+#define UPK_CV_MAX_LIST (1 << 24)   /* entries of one CV's list */
+typedef struct {
+    int n_cv;
+    const int *kind, *atom_start, *atoms, *aux_start;   /* [n_cv], [n_cv+1], [atom_start[n_cv]], [n_cv] */
+    const double *ref, *ref_g;                          /* [n_ref_atom][3], [n_cv] */
+    const float *r0, *beta, *lambda;                    /* [n_contact_pair], [n_cv], [n_cv] */
+} upk_cv_t;
+/* out [S][n_cv] at the current positions */
+int upk_cv_compute(const upk_launch_t* L, upk_coord_t pos, const upk_cv_t* C, float* out);
+/* One completed MD round: system s advances rounds[s]; on every `every`-th round it takes sample number n_attempt[s]++, stored at
+ * samples[sample][s][0..n_cv) while sample < capacity.  The decision is taken on the device from the system's own counters (equal
+ * entries), so the launch replays unchanged from a captured graph. */
+typedef struct { unsigned long long* rounds; int* n_attempt; int every, capacity; float* samples; } upk_cv_record_t;
+int upk_cv_record(const upk_launch_t* L, upk_coord_t pos, const upk_cv_t* C, const upk_cv_record_t* R);
+
 #ifdef __cplusplus
 }
 #endif

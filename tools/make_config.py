@@ -48,6 +48,9 @@ def main():
     ap.add_argument('--loose-hbond-criteria', action='store_true', help='permissive H-bond geometry (static structures only)')
     ap.add_argument('--backbone-network', default='', help='.npz with weights_k [W, C_in, C_out], bias_k [C_out], activation_k (ReLU | Tanh | '
                     'Identity) for k = 0, 1, ... and scale: appended as backbone_featurizer -> conv1d layers -> scaled_sum')
+    ap.add_argument('--collective-variables', action='store_true', help='also write /input/collective_variables: over the CA atoms, Rg, '
+                    'RMSD and fraction of native contacts Q to the input structure, end-to-end distance (computed on the device; '
+                    'upside_hip adds /output/cv)')
     a = ap.parse_args()
     pkg = load_package(); cfg = pkg.config
     if not a.pdb:
@@ -88,6 +91,9 @@ def main():
         layers = [(net['weights_%d' % k], net['bias_%d' % k], str(np.ravel(net['activation_%d' % k])[0])) for k in range(n_layer)]
         names = cfg.add_backbone_network(a.out, layers, float(np.ravel(net['scale'])[0]))
         print('backbone network: %s' % ' -> '.join(names))
+    if a.collective_variables:
+        p = cfg.add_collective_variables(a.out, cfg.default_collective_variables(cfg.read_pos(a.out)))
+        print('collective variables: %s' % ', '.join(x.decode() for x in p['names']))
     print('%s: %i residues, %i side-chain beads' % (a.out, info['n_res'], info['n_bead']))
 
 

@@ -686,6 +686,133 @@ def add_jump_moves(path, atom_ranges, sigma_trans, sigma_rot):
         g.write('sigma_rot', np.asarray(sigma_rot, 'f4').reshape(-1))
 
 
+CV_KINDS = ('rg', 'rmsd', 'contacts', 'distance')      # the kind codes of upside_hip_cv_define, in order
+CV_MAX = 64                                            # UPK_CV_MAX of include/upside_hip_kernels.h
+
+
+def native_contacts(pos, atoms, cutoff=8.0, min_seq_sep=4):
+    """pairs (m,2) of `atoms` (atom indices into pos (n_atom,3), taken to be in sequence order) closer than `cutoff` in the
+    structure `pos` and at least `min_seq_sep` apart along `atoms`, each pair once (first < second), with their distances r0 (m,):
+    the pair list and r0 of a `contacts` collective variable."""
+    pos = np.asarray(pos, 'f8')
+    atoms = np.asarray(atoms, 'i4').reshape(-1)
+    if pos.ndim != 2 or pos.shape[1] != 3:
+        raise ValueError('native_contacts: pos must be (n_atom, 3)')
+    if len(atoms) and (atoms.min() < 0 or atoms.max() >= len(pos)):
+        raise ValueError('native_contacts: atom out of range')
+    if not cutoff > 0 or min_seq_sep < 1:
+        raise ValueError('native_contacts: cutoff must be positive and min_seq_sep at least 1')
+    x = pos[atoms]
+    d = np.sqrt(((x[:, None] - x[None, :]) ** 2).sum(-1))
+    i, j = np.triu_indices(len(atoms), int(min_seq_sep))
+    keep = d[i, j] < cutoff
+    return np.column_stack((atoms[i[keep]], atoms[j[keep]])).astype('i4'), d[i[keep], j[keep]].astype('f4')
+
+
+def pack_collective_variables(specs, n_atom):
+    """the CSR arrays of upside_hip_cv_define / of /input/collective_variables from a list of dicts:
+         {'name': .., 'kind': 'rg', 'atoms': (n,)}
+         {'kind': 'rmsd', 'atoms': (n,), 'ref': (n,3)}                  reference positions of the SAME atoms, in order
+         {'kind': 'contacts', 'pairs': (m,2), 'r0': (m,) or scalar, 'beta': 5., 'lambda': 1.8}
+         {'kind': 'distance', 'pair': (a,b)}
+    'name' defaults to the kind, numbered when it repeats.  Raises ValueError naming the spec and what is wrong with it."""
+    if len(specs) > CV_MAX:
+        raise ValueError('%d collective variables exceed the limit of %d' % (len(specs), CV_MAX))
+    kind, atom_start, atoms, ref, r0, beta, lam, names = [], [0], [], [], [], [], [], []
+    for c, sp in enumerate(specs):
+        who = 'collective variable %d' % c
+        if not isinstance(sp, dict) or 'kind' not in sp:
+            raise ValueError(who + ": a dict with a 'kind' is expected")
+        k = sp['kind']
+        if k not in CV_KINDS:
+            raise ValueError(who + ': unknown kind %r (one of %s)' % (k, ', '.join(CV_KINDS)))
+        who += ' (%s)' % k
+        allowed = {'rg': ('atoms',), 'rmsd': ('atoms', 'ref'), 'contacts': ('pairs', 'r0', 'beta', 'lambda'), 'distance': ('pair',)}[k]
+        extra = sorted(set(sp) - set(allowed) - set(('kind', 'name')))
+        if extra:
+            raise ValueError(who + ': unexpected key %r' % extra[0])
+        missing = [a for a in allowed if a not in sp and a not in ('beta', 'lambda')]
+        if missing:
+            raise ValueError(who + ': %r is missing' % missing[0])
+        b, l = 0., 0.
+        if k in ('rg', 'rmsd'):
+            a = np.asarray(sp['atoms']).reshape(-1)
+            if k == 'rmsd':
+                rf = np.asarray(sp['ref'], 'f8')
+                if rf.shape != (len(a), 3):
+                    raise ValueError(who + ': ref must be (%d, 3), one row per atom of the selection' % len(a))
+                if len(a) < 3:
+                    raise ValueError(who + ': an rmsd selection needs at least 3 atoms')
+                if not np.isfinite(rf).all():
+                    raise ValueError(who + ': ref is not finite')
+                ref.append(rf)
+        elif k == 'contacts':
+            pr = np.asarray(sp['pairs'])
+            if pr.ndim != 2 or pr.shape[1] != 2:
+                raise ValueError(who + ': pairs must be (m, 2)')
+            a = pr.reshape(-1)
+            r = np.asarray(sp['r0'], 'f8')
+            r = np.full(len(pr), float(r)) if r.ndim == 0 else r.reshape(-1)
+            if len(r) != len(pr):
+                raise ValueError(who + ': r0 must have one entry per pair')
+            if not (np.isfinite(r).all() and (r > 0).all()):
+                raise ValueError(who + ': r0 must be positive')
+            b, l = float(sp.get('beta', 5.)), float(sp.get('lambda', 1.8))
+            if not (np.isfinite(b) and np.isfinite(l)):
+                raise ValueError(who + ': beta and lambda must be finite')
+            r0.append(r)
+        else:
+            a = np.asarray(sp['pair']).reshape(-1)
+            if len(a) != 2:
+                raise ValueError(who + ': pair must hold exactly 2 atoms')
+        if len(a) == 0:
+            raise ValueError(who + ': empty selection')
+        if a.dtype.kind not in 'iu':
+            raise ValueError(who + ': atom indices must be integers')
+        if a.min() < 0 or a.max() >= n_atom:
+            raise ValueError(who + ': atom %d out of range (n_atom %d)' % (int(a.min() if a.min() < 0 else a.max()), n_atom))
+        kind.append(CV_KINDS.index(k)); atoms.append(a.astype('i4')); atom_start.append(atom_start[-1] + len(a))
+        beta.append(b); lam.append(l)
+        names.append(str(sp.get('name', k)))
+    given = list(names)
+    for c, nm in enumerate(given):      # a repeated default name gets its position
+        if given.count(nm) > 1 and 'name' not in specs[c]:
+            names[c] = '%s_%d' % (nm, c)
+    if len(set(names)) != len(names):
+        raise ValueError('collective variables: names must be distinct')
+    cat = lambda v, t, shape: (np.concatenate(v).astype(t) if v else np.zeros(shape, t))
+    return dict(kind=np.asarray(kind, 'i4'), atom_start=np.asarray(atom_start, 'i4'), atoms=cat(atoms, 'i4', (0,)),
+                ref_pos=cat(ref, 'f4', (0, 3)), contact_r0=cat(r0, 'f4', (0,)), contact_beta=np.asarray(beta, 'f4'),
+                contact_lambda=np.asarray(lam, 'f4'), names=np.asarray(names, 'S') if names else np.zeros((0,), 'S1'))
+
+
+def add_collective_variables(path, specs):
+    """write /input/collective_variables (replacing it) into an existing configuration: the observables the engine computes on the
+    device for every system (upside_hip_cv_load; `upside_hip` then adds /output/cv).  specs as in pack_collective_variables."""
+    with h5lite.open_file(path, 'r+') as f:
+        inp = f.group('input')
+        p = pack_collective_variables(specs, inp.shape('pos')[0])
+        if 'collective_variables' in inp:
+            inp.delete('collective_variables')
+        g = inp.create_group('collective_variables')
+        for k in ('kind', 'atom_start', 'atoms', 'ref_pos', 'contact_r0', 'contact_beta', 'contact_lambda', 'names'):
+            g.write(k, p[k])
+    return p
+
+
+def default_collective_variables(pos, contact_cutoff=8.0, min_seq_sep=4, beta=5., lam=1.8):
+    """the standard folding observables over the CA atoms (atom 3 r + 1) against the structure `pos` (n_atom,3): Rg, RMSD and
+    fraction of native contacts Q to it, end-to-end distance (what `make_config.py --collective-variables` writes)"""
+    pos = np.asarray(pos, 'f8')
+    ca = np.arange(1, len(pos), 3, dtype='i4')
+    specs = [{'name': 'rg', 'kind': 'rg', 'atoms': ca}, {'name': 'rmsd', 'kind': 'rmsd', 'atoms': ca, 'ref': pos[ca]}]
+    pairs, r0 = native_contacts(pos, ca, contact_cutoff, min_seq_sep)
+    if len(pairs):
+        specs.append({'name': 'q', 'kind': 'contacts', 'pairs': pairs, 'r0': r0, 'beta': beta, 'lambda': lam})
+    specs.append({'name': 'end_to_end', 'kind': 'distance', 'pair': (int(ca[0]), int(ca[-1]))})
+    return specs
+
+
 def radial_spline_params(rs, n_type1, n_type2, symmetric, inv_dx=1.5, scale=0.3):
     """interaction_param (n_type1, n_type2, 17) obeying the four conditions of sidechain_radial.cpp:23-27: p[0] = 1/dx,
     p[1] == p[3] (flat at the origin), p[-3] == p[-1] and zero value at the cut-off"""

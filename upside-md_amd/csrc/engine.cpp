@@ -572,7 +572,10 @@ void DerivEngine::md_step() {
         n_invocations++;
     }
     integration_stage(stage_num, dt, 0.f);                        // main.cpp:663
-    if (++stage_num == 3) { stage_num = 0; ++round_num; }
+    if (++stage_num == 3) {
+        stage_num = 0; ++round_num;
+        if (cv.R.every > 0) upk_check(upk_cv_record(&ctx.L, pos->coord(), &cv.C, &cv.R), "cv_record");      // a completed round (recording off: no launch)
+    }
     ++steps_done;
 }
 void DerivEngine::invalidate_graph() {
@@ -758,6 +761,106 @@ void DerivEngine::param_deriv_accumulate(int node, const float* weights) {
         upk_check(upk_param_deriv_reduce(&ctx.L, d, (int)st.n_param, w, st.sum.p), "param_deriv_reduce");
     }
     ++st.n_frame;
+}
+
+// ---- collective variables (upside_hip_cv_define / _compute / _record / _read) -----------------------------------------------------
+void DerivEngine::cv_define(int n_cv, const int* kind, const int* atom_start, const int* atoms, const float* ref_pos, const float* contact_r0,
+                            const float* contact_beta, const float* contact_lambda) {
+    static const char* kind_name[] = {"rg", "rmsd", "contacts", "distance"};
+    if (n_cv < 0) throw string("collective variables: n_cv is negative");
+    if (n_cv > UPK_CV_MAX) throw string("collective variables: ") + to_string(n_cv) + " CVs exceed the kernel's limit of " + to_string(UPK_CV_MAX) + " (UPK_CV_MAX)";
+    if (n_cv && (!kind || !atom_start || !atoms)) throw string("collective variables: kind, atom_start and atoms must be given");
+    // everything is checked and built on the host before the first device array is touched: a refusal leaves the old definition in force
+    vector<int> h_kind, h_start, h_atoms, h_aux((size_t)n_cv, 0);
+    vector<double> h_ref, h_ref_g((size_t)n_cv, 0.);
+    vector<float> h_r0, h_beta((size_t)n_cv, 0.f), h_lambda((size_t)n_cv, 0.f);
+    if (n_cv) {
+        h_kind.assign(kind, kind + n_cv); h_start.assign(atom_start, atom_start + n_cv + 1);
+        if (h_start[0] != 0) throw string("collective variables: atom_start[0] must be 0");
+        size_t n_ref = 0, n_pair = 0;
+        for (int c = 0; c < n_cv; ++c) {
+            const string who = "collective variable " + to_string(c);
+            if (h_kind[c] < 0 || h_kind[c] > UPK_CV_DISTANCE) throw who + ": unknown kind " + to_string(h_kind[c]) + " (0 rg, 1 rmsd, 2 contacts, 3 distance)";
+            const string whok = who + " (" + kind_name[h_kind[c]] + ")";
+            const long n = (long)h_start[c + 1] - h_start[c];
+            if (n < 0) throw whok + ": atom_start must not decrease";
+            if (n == 0) throw whok + ": empty selection";
+            if (n > UPK_CV_MAX_LIST) throw whok + ": " + to_string(n) + " list entries exceed the limit of " + to_string(UPK_CV_MAX_LIST) + " (UPK_CV_MAX_LIST)";
+            for (long i = h_start[c]; i < h_start[c + 1]; ++i)
+                if (atoms[i] < 0 || atoms[i] >= pos->n_atom) throw whok + ": atom " + to_string(atoms[i]) + " out of range (n_atom " + to_string(pos->n_atom) + ")";
+            if (h_kind[c] == UPK_CV_RMSD) {
+                if (n < 3) throw whok + ": an rmsd selection needs at least 3 atoms";
+                if (!ref_pos) throw whok + ": ref_pos must be given";
+                h_aux[c] = (int)n_ref; n_ref += (size_t)n;
+            } else if (h_kind[c] == UPK_CV_CONTACTS) {
+                if (n % 2) throw whok + ": a contacts list holds interleaved pairs, its length must be even";
+                if (!contact_r0 || !contact_beta || !contact_lambda) throw whok + ": contact_r0, contact_beta and contact_lambda must be given";
+                for (long i = 0; i < n / 2; ++i) { const float r = contact_r0[n_pair + i]; if (!(r > 0.f) || !std::isfinite(r)) throw whok + ": r0 must be positive and finite"; }
+                if (!std::isfinite(contact_beta[c]) || !std::isfinite(contact_lambda[c])) throw whok + ": beta and lambda must be finite";
+                h_aux[c] = (int)n_pair; n_pair += (size_t)(n / 2);
+                h_beta[c] = contact_beta[c]; h_lambda[c] = contact_lambda[c];
+            } else if (h_kind[c] == UPK_CV_DISTANCE && n != 2) throw whok + ": a distance needs exactly 2 atoms";
+        }
+        h_atoms.assign(atoms, atoms + h_start[n_cv]);
+        h_r0.assign(contact_r0, contact_r0 + (contact_r0 ? n_pair : 0));
+        h_ref.resize(n_ref * 3);
+        for (int c = 0; c < n_cv; ++c) if (h_kind[c] == UPK_CV_RMSD) {      // the reference centred in double, and its squared norm
+            const size_t n = (size_t)(h_start[c + 1] - h_start[c]), o = (size_t)h_aux[c] * 3;
+            double cen[3] = {0., 0., 0.};
+            for (size_t i = 0; i < n; ++i) for (int d = 0; d < 3; ++d) { const double v = ref_pos[o + 3 * i + d]; if (!std::isfinite(v)) throw string("collective variable ") + to_string(c) + " (rmsd): ref_pos is not finite"; cen[d] += v; }
+            for (int d = 0; d < 3; ++d) cen[d] /= (double)n;
+            double g = 0.;
+            for (size_t i = 0; i < n; ++i) for (int d = 0; d < 3; ++d) { const double v = (double)ref_pos[o + 3 * i + d] - cen[d]; h_ref[o + 3 * i + d] = v; g += v * v; }
+            h_ref_g[c] = g;
+        }
+    }
+    sync();
+    invalidate_graph();
+    cv_record(0, 0);                       // samples of another definition have another width
+    cv.names.clear();
+    cv.kind.upload(h_kind); cv.atom_start.upload(h_start); cv.atoms.upload(h_atoms); cv.aux_start.upload(h_aux);
+    cv.ref.upload(h_ref); cv.ref_g.upload(h_ref_g); cv.r0.upload(h_r0); cv.beta.upload(h_beta); cv.lambda.upload(h_lambda);
+    cv.out.alloc((size_t)ctx.n_system * n_cv);
+    cv.C.n_cv = n_cv; cv.C.kind = cv.kind.p; cv.C.atom_start = cv.atom_start.p; cv.C.atoms = cv.atoms.p; cv.C.aux_start = cv.aux_start.p;
+    cv.C.ref = cv.ref.p; cv.C.ref_g = cv.ref_g.p; cv.C.r0 = cv.r0.p; cv.C.beta = cv.beta.p; cv.C.lambda = cv.lambda.p;
+}
+void DerivEngine::cv_compute(float* out_host) {
+    if (!cv.C.n_cv) throw string("no collective variables defined (upside_hip_cv_define / upside_hip_cv_load)");
+    if (!out_host) throw string("upside_hip_cv_compute: out is NULL");
+    upk_check(upk_cv_compute(&ctx.L, pos->coord(), &cv.C, cv.out.p), "cv_compute");
+    hip_check(hipMemcpyAsync(out_host, cv.out.p, cv.out.n * sizeof(float), hipMemcpyDeviceToHost, ctx.stream), "D2H cv");
+    sync();
+}
+void DerivEngine::cv_record(int every_n_round, int capacity) {
+    if (every_n_round < 0) throw string("upside_hip_cv_record: every_n_round is negative");
+    if (every_n_round > 0) {
+        if (!cv.C.n_cv) throw string("no collective variables defined (upside_hip_cv_define / upside_hip_cv_load)");
+        if (capacity < 1) throw string("upside_hip_cv_record: capacity must be positive");
+    }
+    if (!every_n_round && !cv.R.every) return;
+    sync();
+    invalidate_graph();                    // the captured rounds hold (or lack) the record launch and its arguments
+    cv.R = upk_cv_record_t{};
+    if (!every_n_round) { cv.rounds.alloc(0); cv.n_attempt.alloc(0); cv.samples.alloc(0); return; }
+    cv.rounds.alloc(ctx.n_system); cv.n_attempt.alloc(ctx.n_system);       // (zeroed: rounds are counted from this call)
+    cv.samples.alloc((size_t)capacity * ctx.n_system * cv.C.n_cv);
+    cv.R.rounds = cv.rounds.p; cv.R.n_attempt = cv.n_attempt.p; cv.R.samples = cv.samples.p; cv.R.every = every_n_round; cv.R.capacity = capacity;
+}
+void DerivEngine::cv_read(int first, int n, float* out_host, long long* n_stored, long long* n_attempted, int reset) {
+    if (cv.R.every <= 0) throw string("collective variables are not being recorded (upside_hip_cv_record)");
+    sync();
+    int attempted = 0;
+    hip_check(hipMemcpy(&attempted, cv.n_attempt.p, sizeof(int), hipMemcpyDeviceToHost), "D2H cv counters");      // (equal entries)
+    const long long stored = std::min<long long>(attempted, cv.R.capacity);
+    if (n_stored) *n_stored = stored;
+    if (n_attempted) *n_attempted = attempted;
+    if (n > 0) {
+        if (!out_host) throw string("upside_hip_cv_read: out is NULL");
+        if (first < 0 || (long long)first + n > stored) throw string("upside_hip_cv_read: samples [") + to_string(first) + ", " + to_string((long long)first + n) + ") requested, " + to_string(stored) + " stored";
+        const size_t row = (size_t)ctx.n_system * cv.C.n_cv;
+        hip_check(hipMemcpy(out_host, cv.samples.p + (size_t)first * row, (size_t)n * row * sizeof(float), hipMemcpyDeviceToHost), "D2H cv samples");
+    } else if (n < 0) throw string("upside_hip_cv_read: n is negative");
+    if (reset) cv.n_attempt.fill_bytes(0);      // the round counter runs on: the sampling phase is kept
 }
 
 void DerivEngine::check_device_errors() {

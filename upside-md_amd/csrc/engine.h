@@ -147,6 +147,20 @@ struct DerivEngine {   // deriv_engine.h:145-237
         std::map<std::vector<int>, std::unique_ptr<DevBuf<int>>> pairs;
     } hswap;
     void hamiltonian_swap(int n_pair, const int* pairs, uint32_t base_seed, uint64_t round, int draw0, int* accepted);
+    // collective variables of every system (upside_hip_cv_*; kernels_cv.hip).  A definition is replaced whole; recording appends one
+    // (n_system, n_cv) sample per `every` completed rounds from inside md_step, the decision taken on the device (captured graphs replay it)
+    struct CollectiveVariables {
+        upk_cv_t C{}; std::vector<std::string> names;
+        DevBuf<int> kind, atom_start, atoms, aux_start; DevBuf<double> ref, ref_g; DevBuf<float> r0, beta, lambda;
+        DevBuf<float> out;                      // [S][n_cv] of upside_hip_cv_compute
+        upk_cv_record_t R{};                    // R.every > 0: recording
+        DevBuf<unsigned long long> rounds; DevBuf<int> n_attempt; DevBuf<float> samples;
+    } cv;
+    void cv_define(int n_cv, const int* kind, const int* atom_start, const int* atoms, const float* ref_pos, const float* contact_r0,
+                   const float* contact_beta, const float* contact_lambda);      // throws, leaving the previous definition in force
+    void cv_compute(float* out_host);
+    void cv_record(int every_n_round, int capacity);
+    void cv_read(int first, int n, float* out_host, long long* n_stored, long long* n_attempted, int reset);
     void check_device_errors();                // throws if a capacity overflow was flagged
     void sync();
 };

@@ -487,6 +487,70 @@ extern "C" int upside_hip_run_steps(DerivEngine* e, int n_step) {
     return 0;
     API_CATCH(1)
 }
+// ---- collective variables of every system (kernels_cv.hip) ---------------------------------------------------
+extern "C" int upside_hip_cv_define(DerivEngine* e, int n_cv, const int* kind, const int* atom_start, const int* atoms, const float* ref_pos,
+                                    const float* contact_r0, const float* contact_beta, const float* contact_lambda) {
+    API_TRY e->cv_define(n_cv, kind, atom_start, atoms, ref_pos, contact_r0, contact_beta, contact_lambda); return 0; API_CATCH(1)
+}
+namespace {
+vector<string> read_string_dataset(hid_t loc, const string& name) {      // fixed-length strings, one dimension
+    h5u::Handle d(H5Dopen2(loc, name.c_str(), H5P_DEFAULT), H5Dclose);
+    if (d < 0) throw string("dataset '") + name + "' not found";
+    h5u::Handle sp(H5Dget_space(d), H5Sclose), ty(H5Dget_type(d), H5Tclose);
+    if (H5Tget_class(ty) != H5T_STRING || H5Tis_variable_str(ty) > 0) throw string("'") + name + "' must hold fixed-length strings";
+    if (H5Sget_simple_extent_ndims(sp) != 1) throw string("'") + name + "' must have one dimension";
+    hsize_t n = 0; H5Sget_simple_extent_dims(sp, &n, NULL);
+    const size_t w = H5Tget_size(ty);
+    vector<char> buf(n * w + 1, '\0');
+    if (n && H5Dread(d, ty, H5S_ALL, H5S_ALL, H5P_DEFAULT, buf.data()) < 0) throw string("unable to read dataset '") + name + "'";
+    vector<string> out;
+    for (hsize_t i = 0; i < n; ++i) { string t(buf.data() + i * w, w); while (t.size() && (t.back() == '\0' || t.back() == ' ')) t.pop_back(); out.push_back(t); }
+    return out;
+}
+}
+extern "C" int upside_hip_cv_load(DerivEngine* e, const char* config_file) {
+    API_TRY
+    H5Eset_auto2(H5E_DEFAULT, NULL, NULL);
+    hid_t f = H5Fopen(config_file, H5F_ACC_RDONLY, H5P_DEFAULT);
+    if (f < 0) throw string("unable to open ") + config_file;
+    h5u::Handle config(f, H5Fclose);
+    auto input = h5u::open_group(config, "/input");
+    if (!h5u::exists(input, "collective_variables")) return 0;
+    auto g = h5u::open_group(input, "collective_variables");
+    auto kind = h5u::read<int>(g, "kind", 1);
+    const size_t n_cv = kind.size();
+    auto atom_start = h5u::read<int>(g, "atom_start", 1);
+    if (atom_start.size() != n_cv + 1) throw string("/input/collective_variables: atom_start must have n_cv + 1 entries");
+    auto atoms = h5u::read<int>(g, "atoms", 1);
+    if (atom_start.back() != (int)atoms.size() || atom_start[0] != 0) throw string("/input/collective_variables: atom_start does not span atoms");
+    vector<hsize_t> d;
+    auto ref_pos = h5u::read<float>(g, "ref_pos", 2, &d);
+    if (d[0] && d[1] != 3) throw string("/input/collective_variables: ref_pos must be (n, 3)");
+    auto r0 = h5u::read<float>(g, "contact_r0", 1);
+    auto beta = h5u::read<float>(g, "contact_beta", 1), lambda = h5u::read<float>(g, "contact_lambda", 1);
+    if (beta.size() != n_cv || lambda.size() != n_cv) throw string("/input/collective_variables: contact_beta and contact_lambda must have n_cv entries");
+    auto names = read_string_dataset(g, "names");
+    if (names.size() != n_cv) throw string("/input/collective_variables: names must have n_cv entries");
+    // the packed arrays must be as long as the kinds say (upside_hip_cv_define reads them by those counts)
+    size_t n_ref = 0, n_pair = 0;
+    for (size_t c = 0; c < n_cv; ++c) {
+        const long n = (long)atom_start[c + 1] - atom_start[c];
+        if (n < 0) throw string("/input/collective_variables: atom_start must not decrease");
+        if (kind[c] == UPK_CV_RMSD) n_ref += (size_t)n; else if (kind[c] == UPK_CV_CONTACTS) n_pair += (size_t)(n / 2);
+    }
+    if (ref_pos.size() != n_ref * 3) throw string("/input/collective_variables: ref_pos holds ") + to_string(ref_pos.size() / 3) + " rows, the rmsd selections " + to_string(n_ref);
+    if (r0.size() != n_pair) throw string("/input/collective_variables: contact_r0 holds ") + to_string(r0.size()) + " entries, the contacts lists " + to_string(n_pair) + " pairs";
+    e->cv_define((int)n_cv, kind.data(), atom_start.data(), atoms.data(), ref_pos.data(), r0.data(), beta.data(), lambda.data());
+    e->cv.names = names;
+    return (int)n_cv;
+    API_CATCH(-1)
+}
+extern "C" int upside_hip_cv_count(DerivEngine* e) { return e ? e->cv.C.n_cv : 0; }
+extern "C" int upside_hip_cv_compute(DerivEngine* e, float* out) { API_TRY e->cv_compute(out); return 0; API_CATCH(1) }
+extern "C" int upside_hip_cv_record(DerivEngine* e, int every_n_round, int capacity) { API_TRY e->cv_record(every_n_round, capacity); return 0; API_CATCH(1) }
+extern "C" int upside_hip_cv_read(DerivEngine* e, int first, int n, float* out, long long* n_stored, long long* n_attempted, int reset) {
+    API_TRY e->cv_read(first, n, out, n_stored, n_attempted, reset); return 0; API_CATCH(1)
+}
 // ---- Monte-Carlo pivot moves (monte_carlo_sampler.cpp; main.cpp:628-630) ---------------------------------
 extern "C" int upside_hip_load_mc(DerivEngine* e, const char* config_file) {
     API_TRY

@@ -103,6 +103,22 @@ struct OutputLogger {   // one per system / configuration file (H5Logger, state_
         log_jump = with_jump;
         if (log_jump) jump_stats.create(group, "jump_stats", H5T_NATIVE_INT, 4, {2});
     }
+    // collective variables (/input/collective_variables present): cv (frame,1,n_cv) f32 and the attribute `names` on it and on /output
+    EArray cv; bool log_cv = false;
+    void add_cv(const vector<string>& names) {
+        cv.create(group, "cv", H5T_NATIVE_FLOAT, 4, {1, (hsize_t)names.size()});
+        log_cv = true;
+        size_t w = 1; for (auto& n : names) w = max(w, n.size());
+        vector<char> buf(names.size() * w, '\0');
+        for (size_t i = 0; i < names.size(); ++i) memcpy(&buf[i * w], names[i].data(), names[i].size());
+        hid_t st = H5Tcopy(H5T_C_S1); H5Tset_size(st, w);
+        hsize_t n = names.size(); hid_t sp = H5Screate_simple(1, &n, nullptr);
+        for (hid_t obj : {group, cv.dset}) {
+            hid_t at = H5Acreate2(obj, obj == group ? "cv_names" : "names", st, sp, H5P_DEFAULT, H5P_DEFAULT);
+            if (at >= 0) { H5Awrite(at, st, buf.data()); H5Aclose(at); }
+        }
+        H5Sclose(sp); H5Tclose(st);
+    }
     // the nodes' own per-frame quantities (default_logger->add_logger in the reference's node constructors)
     vector<EArray> extra; vector<LogValue> extra_spec;
     void add_node_loggers(const vector<LogValue>& specs) {
@@ -137,12 +153,14 @@ struct OutputLogger {   // one per system / configuration file (H5Logger, state_
         if (log_pivot) pivot_stats.flush();
         if (log_jump) jump_stats.flush();
         for (auto& x : extra) x.flush();
+        if (log_cv) cv.flush();
         if (file >= 0) H5Fflush(file, H5F_SCOPE_LOCAL);
     }
     void close() {
         if (file < 0) return;
         pos.close(); kinetic.close(); potential.close(); time.close(); temperature.close(); replica_index.close(); replica_cumulative_swaps.close(); pivot_stats.close(); jump_stats.close();
         for (auto& x : extra) x.close();
+        cv.close();
         H5Gclose(group); H5Fclose(file); file = group = -1;
     }
     ~OutputLogger() { try { close(); } catch (...) {} }
@@ -515,6 +533,13 @@ int upside_main_impl(int argc, const char* const* argv, int verbose) {
         if (n_sampler < 0) throw string(upside_hip_last_error());
         have_mc = n_sampler > 0;
     }
+    // collective variables: each engine takes the definition of its first file; its systems' files get /output/cv, sampled at the frames
+    // (read before the loggers open the files for writing)
+    vector<int> n_cv_of(n_group, 0);
+    for (int g = 0; g < n_group; ++g) {
+        n_cv_of[g] = upside_hip_cv_load(engines[g], files[members[g][0]].c_str());
+        if (n_cv_of[g] < 0) throw string(upside_hip_last_error());
+    }
     const bool have_pivot = have_mc && upside_hip_mc_loaded(e, 0), have_jump = have_mc && upside_hip_mc_loaded(e, 1);
     vector<int> mc_stats((size_t)n_system * 2, 0), mcj_stats((size_t)n_system * 2, 0);
     // the swap pairs every system takes part in (set order, then pair order: main.cpp:176-192) and their running counts
@@ -540,6 +565,8 @@ int upside_main_impl(int argc, const char* const* argv, int verbose) {
             }
         for (int ns = 0; ns < n_system; ++ns) loggers[ns].add_node_loggers(node_loggers[group_of[ns]]);
     }
+    if (write_output) for (int ns = 0; ns < n_system; ++ns) if (n_cv_of[group_of[ns]]) loggers[ns].add_cv(engines[group_of[ns]]->cv.names);
+    vector<vector<float>> frame_cv(n_group);
     vector<int> replica_index(n_total);     // by GLOBAL slot; every rank keeps the whole table (the verdicts are identical everywhere)
     for (int ns = 0; ns < n_total; ++ns) replica_index[ns] = ns;
     vector<float> frame_pos((size_t)n_system * n_atom * 3), frame_mom((size_t)n_system * n_atom * 3);
@@ -563,6 +590,10 @@ int upside_main_impl(int argc, const char* const* argv, int verbose) {
                 if (upside_hip_get_pos(engines[g], gp.data()) || upside_hip_get_mom(engines[g], gm.data())) throw string(upside_hip_last_error());
                 from_group(g, gp, frame_pos.data(), (size_t)n_atom * 3); from_group(g, gm, frame_mom.data(), (size_t)n_atom * 3);
             }
+            for (int g = 0; g < n_group; ++g) if (n_cv_of[g]) {
+                frame_cv[g].resize(members[g].size() * (size_t)n_cv_of[g]);
+                if (upside_hip_cv_compute(engines[g], frame_cv[g].data())) throw string(upside_hip_last_error());
+            }
             if (have_pivot && upside_hip_mc_stats(e, 0, mc_stats.data(), 1)) throw string(upside_hip_last_error());   // reset per frame
             if (have_jump && upside_hip_mc_stats(e, 1, mcj_stats.data(), 1)) throw string(upside_hip_last_error());
             if (write_output && any_node_logger) {
@@ -576,6 +607,7 @@ int upside_main_impl(int argc, const char* const* argv, int verbose) {
                 for (int i = 0; i < n_atom * 3; ++i) sum_kin += (double)(m[i] * m[i]);
                 vector<int> cum;
                 for (auto& pr : participating[sys_lo + ns]) { cum.push_back(pair_success[pr.set][pr.pair]); cum.push_back(pair_attempt[pr.set][pr.pair]); }
+                if (write_output && loggers[ns].log_cv) loggers[ns].cv.push(&frame_cv[group_of[ns]][(size_t)local_of[ns] * n_cv_of[group_of[ns]]]);
                 if (write_output) loggers[ns].sample(x, (0.5 / n_atom) * sum_kin, (double)energy[ns], (double)(3 * dt * (float)rnd) /* fp32 product as main.cpp:540 */, (double)temps[ns], replica_index[sys_lo + ns], &mc_stats[(size_t)ns * 2], &mcj_stats[(size_t)ns * 2], cum.data());
                 double com[3] = {0, 0, 0}, rg = 0.;
                 for (int i = 0; i < n_atom; ++i) for (int d = 0; d < 3; ++d) com[d] += x[i * 3 + d];

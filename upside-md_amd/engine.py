@@ -281,6 +281,12 @@ class Ensemble(object):
         c.upside_hip_get_param_system.argtypes = [vp, ct.c_char_p, i32, i32, vp]
         c.upside_hip_hamiltonian_swap.argtypes = [vp, i32, vp, u32, u64, i32, vp]
         c.upside_hip_last_error.restype = ct.c_char_p
+        c.upside_hip_cv_define.argtypes = [vp, i32, vp, vp, vp, vp, vp, vp, vp]
+        c.upside_hip_cv_load.argtypes = [vp, ct.c_char_p]
+        c.upside_hip_cv_count.argtypes = [vp]
+        c.upside_hip_cv_compute.argtypes = [vp, vp]
+        c.upside_hip_cv_record.argtypes = [vp, i32, i32]
+        c.upside_hip_cv_read.argtypes = [vp, i32, i32, vp, vp, vp, i32]
         c._ensemble_bound = True
 
     def _check(self, rc, what):
@@ -404,6 +410,59 @@ class Ensemble(object):
                                                           out.ctypes.data, n.ctypes.data, int(bool(reset))), 'param_deriv_read')
         return out, int(n[0])
 
+    # -- collective variables of every system, on the device (kernels_cv.hip) --------------------------------------------
+    def define_cvs(self, specs):
+        """specs: the list of dicts config.add_collective_variables takes, or its packed form (the dict config.pack_collective_variables
+        returns).  Replaces any earlier definition; [] clears it.  A refused definition raises and leaves the earlier one in force."""
+        from . import config
+        p = specs if isinstance(specs, dict) else config.pack_collective_variables(specs, self.n_atom)
+        n_cv = len(p['kind'])
+        arr = dict((k, np.ascontiguousarray(p[k], t)) for k, t in (('kind', 'i4'), ('atom_start', 'i4'), ('atoms', 'i4'), ('ref_pos', 'f4'),
+                                                                     ('contact_r0', 'f4'), ('contact_beta', 'f4'), ('contact_lambda', 'f4')))
+        self._check(self.calc.upside_hip_cv_define(self.engine, n_cv, *[arr[k].ctypes.data for k in
+                    ('kind', 'atom_start', 'atoms', 'ref_pos', 'contact_r0', 'contact_beta', 'contact_lambda')]), 'cv_define')
+        self.cv_names = [x.decode() if isinstance(x, bytes) else str(x) for x in p['names']]
+
+    def load_cvs(self, path=None):
+        """/input/collective_variables of a configuration (default: the engine's own); returns the number of CVs (0: no such group)"""
+        path = self.config_file_path if path is None else str(path)
+        n = self.calc.upside_hip_cv_load(self.engine, _b(path))
+        if n < 0:
+            raise RuntimeError('cv_load failed: %s' % self.calc.upside_hip_last_error().decode())
+        if n:
+            with h5lite.open_file(path) as t:
+                self.cv_names = [x.decode() for x in t.group('input').group('collective_variables').read('names').ravel()]
+        return n
+
+    @property
+    def n_cv(self):
+        return int(self.calc.upside_hip_cv_count(self.engine))
+
+    def cvs(self):
+        """(n_system, n_cv) at the current device positions: one launch, no force pass"""
+        out = np.zeros((self.n_system, self.n_cv), 'f4')
+        self._check(self.calc.upside_hip_cv_compute(self.engine, out.ctypes.data), 'cv_compute')
+        return out
+
+    def record_cvs(self, every, capacity=0):
+        """from now on every `every`-th completed MD round appends one (n_system, n_cv) sample to a device buffer of `capacity`
+        samples, inside run_rounds / run_steps, with no host round trip; every=0 stops and frees the buffer"""
+        self._check(self.calc.upside_hip_cv_record(self.engine, int(every), int(capacity)), 'cv_record')
+
+    def cv_counts(self):
+        """(n_stored, n_attempted) of the recording"""
+        ns, na = np.zeros(1, 'i8'), np.zeros(1, 'i8')
+        self._check(self.calc.upside_hip_cv_read(self.engine, 0, 0, None, ns.ctypes.data, na.ctypes.data, 0), 'cv_read')
+        return int(ns[0]), int(na[0])
+
+    def read_cvs(self, reset=True, with_counts=False):
+        """the stored samples (n_stored, n_system, n_cv); with_counts: also (n_stored, n_attempted) -- more were due than stored when
+        the buffer ran full.  reset empties the buffer (the round count, and with it the sampling phase, runs on)."""
+        ns, na = self.cv_counts()
+        out = np.zeros((ns, self.n_system, self.n_cv), 'f4')
+        self._check(self.calc.upside_hip_cv_read(self.engine, 0, ns, out.ctypes.data, None, None, int(bool(reset))), 'cv_read')
+        return (out, ns, na) if with_counts else out
+
     # -- replica exchange across the engines of a job, inside the library (comm_rccl.cpp) -------------
     COMM_ID_BYTES = 128
 
@@ -442,6 +501,9 @@ class Ensemble(object):
             self.close()
         except Exception:
             pass
+
+
+BatchEngine = Ensemble      # the batched engine under the name the documents use
 
 
 def group_configurations(paths, library=None):
