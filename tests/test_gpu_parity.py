@@ -638,7 +638,6 @@ def test_ideal_chain_alignment_frames(hip):
 ALT_PATHS = [
     {'UPSIDE_HIP_BP_CLUSTER': '1'},          # one-workgroup belief propagation instead of the cluster solve
     {'UPSIDE_HIP_BP_CLUSTER': '3'},          # cluster too small for the pair matrices: on-device fallback flag
-    {'UPSIDE_HIP_BP_SPLIT': '3'},            # split cluster solve: 3 workgroups per system over global-memory matrices
     {'UPSIDE_HIP_BP_CLUSTER': '6', 'UPSIDE_HIP_BP_CLUSTER_TEST_ABORT': '1'},   # a cluster workgroup never arrives: barriers give up, the one-workgroup solve re-solves
     {'UPSIDE_HIP_ASYNC_PREPARE': '0'},       # list upkeep inline on the main stream
     {'UPSIDE_HIP_IG_UNSTAGED': '1'},         # coverage graphs through the kernels for systems too large for LDS
@@ -663,7 +662,6 @@ ALT_PATHS = [
     {'UPSIDE_HIP_BATCH': '0'},               # no merged launches: every upkeep kernel and pair pass as a launch of its own, upkeep on side streams
     {'UPSIDE_HIP_BATCH': '1'},               # merged launches whatever the batch size
     {'UPSIDE_HIP_FUSE_BARRIERS': '1'},       # a workgroup barrier in front of every fused op (no dependency analysis)
-    {'UPSIDE_HIP_SCHEDULE': 'bfs'},          # the reference's level-by-level order of the sweep instead of the grouped one
     {'UPSIDE_HIP_FUSE_THREADS': '1024'},     # fused launches with 1024-lane workgroups (the instance that spills the alignment ops)
     {'UPSIDE_HIP_FUSE_THREADS': '128'},      # ... and with two wavefronts per system
     {'UPSIDE_HIP_NODE_PROB_IN_SOLVE': '0'},  # node probabilities by a kernel of their own (large batches) instead of in the solve's prologue
@@ -717,6 +715,34 @@ def test_large_batch_solver_on_every_fixture():
                               '-k', 'force_pass or degenerate or named_values or truncated or golden'], env=env,
                              stdout=subprocess.PIPE, stderr=subprocess.STDOUT, timeout=1200).stdout.decode()
         assert ' passed' in out and 'failed' not in out and 'error' not in out.lower(), (extra, out[-3000:])
+
+
+def test_removed_switches_are_named_and_change_nothing():
+    """UPSIDE_HIP_BP_SPLIT and UPSIDE_HIP_SCHEDULE selected code that is gone: an engine built with them set says so on stderr, once each,
+    and computes the very bytes of a run without them (an A/B script that still sets them learns it compares a build with itself)"""
+    import subprocess
+    code = ("import sys; sys.path.insert(0, %r); sys.path.insert(0, %r)\n"
+            "import parity_util as P\n"
+            "g = P.golden('trpcage20_7A')\n"
+            "up = P.pkg.Upside(P.fixture('trpcage20_7A'))\n"
+            "import numpy as np\n"
+            "e = np.float32(up.energy(g['pos'])); d = np.ascontiguousarray(up.deriv(g['pos']), 'f4')\n"
+            "up.close()\n"
+            "print('RESULT', e.tobytes().hex(), d.tobytes().hex())\n") % (P.ROOT, os.path.dirname(os.path.abspath(__file__)))
+
+    def run(extra):
+        r = subprocess.run([sys.executable, '-c', code], env=dict(os.environ, **extra), stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=300)
+        assert r.returncode == 0, r.stderr.decode()[-2000:]
+        result = [ln for ln in r.stdout.decode().splitlines() if ln.startswith('RESULT ')]
+        assert len(result) == 1 and len(result[0].split()) == 3 and len(result[0].split()[2]) > 8 * 3 * 20
+        return result[0], r.stderr.decode()
+
+    plain, plain_err = run({})
+    assert 'no longer read by this build' not in plain_err, plain_err[-2000:]
+    with_switches, err = run({'UPSIDE_HIP_BP_SPLIT': '3', 'UPSIDE_HIP_SCHEDULE': 'bfs'})
+    for v in ('UPSIDE_HIP_BP_SPLIT', 'UPSIDE_HIP_SCHEDULE'):
+        assert '%s is set but no longer read by this build' % v in err, err[-2000:]
+    assert with_switches == plain
 
 
 def test_side_chain_node_limit_is_refused_with_a_message():

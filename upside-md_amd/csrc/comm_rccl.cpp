@@ -44,9 +44,8 @@ Rccl& rccl() {
     // UPSIDE_HIP_COMM_LIB names another library with the same nine entry points (tests: tests/plugin/libshmccl.so runs
     // two ranks on one GPU, which RCCL cannot).  A TEST seam: honoured only together with UPSIDE_HIP_TESTING=1, so that a stray
     // variable in a production environment cannot make the library load arbitrary code in RCCL's place.
-    const char* over = getenv("UPSIDE_HIP_COMM_LIB");
-    const char* testing = getenv("UPSIDE_HIP_TESTING");
-    if (over && !(testing && atoi(testing) == 1)) {
+    const char* over = env_str("UPSIDE_HIP_COMM_LIB");
+    if (over && env_int("UPSIDE_HIP_TESTING", 0) != 1) {
         static bool warned = false;
         if (!warned) { warned = true; fprintf(stderr, "upside_hip: UPSIDE_HIP_COMM_LIB is ignored without UPSIDE_HIP_TESTING=1 (using RCCL)\n"); }
         over = nullptr;

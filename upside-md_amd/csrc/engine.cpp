@@ -236,8 +236,7 @@ DerivEngine::DerivEngine(int n_atom, int n_system) {
     //   128: 407 / 357, 256: 571 / 612;  150 residues: 32: 56.5 / 51.1, 48: 79.1 / 74.0, 64: 81.5 / 85.8;  300 residues: 24: 31.7 / 31.2,
     //   32: 35.6 / 35.0 (54.1 / 52.5 at the 7 A list), 64: 56.3 / 62.1
     // -- up to 16 systems always, else while atoms x systems <= 24 000 and systems <= 160.
-    { const char* e = getenv("UPSIDE_HIP_BATCH");
-      const bool on = e ? atoi(e) != 0 : (n_system <= 16 || ((long)n_system * n_atom <= 24000 && n_system <= 160));
+    { const bool on = env_int("UPSIDE_HIP_BATCH", (n_system <= 16 || ((long)n_system * n_atom <= 24000 && n_system <= 160)) ? 1 : 0) != 0;
       ctx.L.batch = on ? upk_batch_create() : nullptr; }
     ctx.error_flag.alloc(1);
     potential.assign(n_system, 0.f);
@@ -290,11 +289,8 @@ void DerivEngine::finalize() {
     // Order of the sweep.  Any order that runs a node after its parents (forward) / after its children (backward) computes the
     // same graph; the reference walks it level by level.  Here steps that only enqueue fused per-element ops are drawn together:
     // forward, every such step whose parents are done, then ONE other step, and so on; then the same backward.  The per-element
-    // work of a force pass then reaches the device in a handful of launches instead of one per level.  UPSIDE_HIP_SCHEDULE=bfs
-    // keeps the reference's level order (tests).
-    const char* sched_env = getenv("UPSIDE_HIP_SCHEDULE");
-    const bool grouped = !(sched_env && !strcmp(sched_env, "bfs"));
-    if (grouped) {
+    // work of a force pass then reaches the device in a handful of launches instead of one per level.
+    {
         const size_t N = nodes.size();
         std::vector<char> done(N, 0);
         n_batch_group = 0;
@@ -346,24 +342,6 @@ void DerivEngine::finalize() {
             }
         };
         sweep(false); sweep(true);
-    } else
-    for (int lvl = 0, not_finished = 1;; ++lvl, not_finished = 0) {
-        for (size_t i = 0; i < nodes.size(); ++i) {
-            auto& n = nodes[i];
-            if (n.germ_exec_level == -1) {
-                not_finished = 1;
-                bool all_parents = all_of(begin(n.parents), end(n.parents), [&](size_t ip) {
-                    int l = nodes[ip].germ_exec_level; return l != -1 && l != lvl; });
-                if (all_parents) { schedule.push_back(Step{(int)i, false}); n.germ_exec_level = lvl; }
-            }
-            if (n.deriv_exec_level == -1 && n.germ_exec_level != -1) {
-                not_finished = 1;
-                bool all_children = all_of(begin(n.children), end(n.children), [&](size_t ip) {
-                    int l = nodes[ip].deriv_exec_level; return l != -1 && l != lvl; });
-                if (all_children) { schedule.push_back(Step{(int)i, true}); n.deriv_exec_level = lvl; }
-            }
-        }
-        if (!not_finished) break;
     }
     // one launch clears every sensitivity buffer at the start of a force pass
     {
@@ -379,7 +357,7 @@ void DerivEngine::finalize() {
     }
     // hoist prepare() of the nodes that have one to just after the forward step of the last parent it reads, on a
     // side stream
-    if (ctx.L.batch && grouped) {
+    if (ctx.L.batch) {
         // Merged launches: the list upkeep of ALL graphs as one group, placed behind the last forward step any of it reads (the
         // graphs' lists do not depend on each other: check / rebuild / refine of the five graphs run side by side in a handful of
         // launches, kernels_batch.h).  On the main stream: the per-element steps it could overlap with are one fused launch now.
@@ -409,8 +387,7 @@ void DerivEngine::finalize() {
         print_schedule();
         return;
     }
-    const char* env = getenv("UPSIDE_HIP_ASYNC_PREPARE");
-    if (env && atoi(env) == 0) { print_schedule(); return; }
+    if (env_int("UPSIDE_HIP_ASYNC_PREPARE", 1) == 0) { print_schedule(); return; }
     // nodes a prepare() reads: the ones it names (any node of the graph, e.g. a grandparent whose output a parent copies
     // through), else all its parents
     std::vector<std::vector<size_t>> deps_of(nodes.size());
@@ -436,7 +413,7 @@ void DerivEngine::finalize() {
         schedule.swap(first);
     }
     // One upkeep stream per node: the rebuilds of different graphs run side by side.  (A single shared upkeep stream was an option until
-    // round 6 -- UPSIDE_HIP_UPKEEP_STREAMS=1 -- and lost at every batch size since the per-element nodes became a dozen fused launches:
+    // round 6, behind a switch of its own, and lost at every batch size since the per-element nodes became a dozen fused launches:
     // 128 systems 86.6 vs 98.3 k, 256: 124.4 vs 138.8 k, 1024: 168.9 vs 177.0 k, 4096: 182.8 vs 188.7 k system-steps/s.)
     std::vector<Step> hoisted;
     std::vector<int> n_dep_left(nodes.size(), -1);
@@ -468,7 +445,7 @@ void DerivEngine::finalize() {
     print_schedule();
 }
 void DerivEngine::print_schedule() {
-    if (!getenv("UPSIDE_HIP_PRINT_SCHEDULE")) return;
+    if (!env_set("UPSIDE_HIP_PRINT_SCHEDULE")) return;
     for (auto& st : schedule) {
         auto& n = nodes[st.node];
         fprintf(stderr, "%-8s L%-2d batch %-2d %s%-44s parents:", st.prepare ? "prepare" : (st.backward ? "backward" : "forward"),
@@ -586,7 +563,7 @@ void DerivEngine::invalidate_graph() {
 bool DerivEngine::capture_md_graph() {
     invalidate_graph();
     const int sn = stage_num; const uint64_t rn = round_num, ni = n_invocations, sd = steps_done, nc = n_compute;
-    static const bool debug = getenv("UPSIDE_HIP_GRAPH_DEBUG") != nullptr;
+    static const bool debug = env_set("UPSIDE_HIP_GRAPH_DEBUG");
     ctx.flush();
     hipError_t err = hipStreamBeginCapture(ctx.stream, hipStreamCaptureModeGlobal);
     if (err != hipSuccess) { if (debug) fprintf(stderr, "graph: begin capture failed: %s\n", hipGetErrorString(err)); (void)hipGetLastError(); return false; }
@@ -610,8 +587,8 @@ void DerivEngine::run_steps(int n_step) {
     // UPSIDE_HIP_GRAPH: six MD steps replayed from a captured hipGraph.  Default: wherever launches are merged, where a step is a chain of ~17
     // dependent launches and a graph node boundary is cheaper than an eager one (one / eight 56-residue systems: 193 / 223 against
     // 201 / 233 us per step; one 300-residue system 465 against 474; 64 x 150 residues 716 against 689: off there)
-    static const int graph_env = [] { const char* e = getenv("UPSIDE_HIP_GRAPH"); return e ? atoi(e) : -1; }();
-    static const bool sync_diag = getenv("UPSIDE_HIP_FUSE_TRACE") != nullptr;      // (the trace reads its clocks back after every flush: a capturing stream cannot be synchronised)
+    static const int graph_env = env_int("UPSIDE_HIP_GRAPH", -1);
+    static const bool sync_diag = env_set("UPSIDE_HIP_FUSE_TRACE");      // (the trace reads its clocks back after every flush: a capturing stream cannot be synchronised)
     const int use_graph = sync_diag ? 0 : (graph_env >= 0 ? graph_env : (ctx.L.batch ? 1 : 0));        // (with the merged launches: one stream; a multi-stream capture replays slower than it launches)
     int left = n_step;
     while (left > 0) {
@@ -715,8 +692,9 @@ static void warn_removed_switches() {
     done = true;
     for (const char* v : {"UPSIDE_HIP_BP_RESIDENT", "UPSIDE_HIP_BP_THREADS", "UPSIDE_HIP_BP_LDS_CAP_KB", "UPSIDE_HIP_FUSE_W8", "UPSIDE_HIP_BATCH_KINDS",
                           "UPSIDE_HIP_HB_THREADS", "UPSIDE_HIP_PLR_ROWS_SMALL", "UPSIDE_HIP_SLOT_WGS", "UPSIDE_HIP_ORDER_EVERY", "UPSIDE_HIP_CLEAR_SLOTS",
-                          "UPSIDE_HIP_BP_CLUSTER_MIN_C", "UPSIDE_HIP_MAX_SYSTEMS", "UPSIDE_HIP_PAIR2_ENERGY", "UPSIDE_HIP_UPKEEP_STREAMS"})
-        if (getenv(v)) fprintf(stderr, "upside_hip: %s is set but no longer read by this build (removed experiment switch, see INTEGRATION.md section 6)\n", v);
+                          "UPSIDE_HIP_BP_CLUSTER_MIN_C", "UPSIDE_HIP_MAX_SYSTEMS", "UPSIDE_HIP_PAIR2_ENERGY", "UPSIDE_HIP_UPKEEP_STREAMS",
+                          "UPSIDE_HIP_BP_SPLIT", "UPSIDE_HIP_SCHEDULE"})
+        if (env_set(v)) fprintf(stderr, "upside_hip: %s is set but no longer read by this build (removed experiment switch, see INTEGRATION.md section 6)\n", v);
 }
 void DerivEngine::sync() { ctx.flush(); hip_check(hipStreamSynchronize(ctx.stream), "hipStreamSynchronize"); }
 
@@ -900,7 +878,7 @@ static void load_plugins_from_env() {
     static bool done = false;
     if (done) return;
     done = true;
-    const char* e = getenv("UPSIDE_HIP_PLUGINS");
+    const char* e = env_str("UPSIDE_HIP_PLUGINS");
     if (!e) return;
     string all(e);
     for (size_t b = 0; b <= all.size();) {

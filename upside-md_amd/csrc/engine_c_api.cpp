@@ -53,7 +53,7 @@ extern "C" DerivEngine* upside_hip_construct(int n_atom, const char* potential_f
 }
 // ---- Hamiltonian ladders: one engine, parameter values per system ------------------------------------------
 namespace {
-bool hamiltonian_batch_enabled() { const char* v = getenv("UPSIDE_HIP_HAMILTONIAN_BATCH"); return !(v && !strcmp(v, "0")); }
+bool hamiltonian_batch_enabled() { const char* v = env_str("UPSIDE_HIP_HAMILTONIAN_BATCH"); return !(v && !strcmp(v, "0")); }
 bool listed(const vector<string>& v, const string& x) { return find(v.begin(), v.end(), x) != v.end(); }
 // the value bytes the table lets differ, for objects named below /input/potential ("node", "node/dataset")
 h5u::DigestSkip potential_value_skip() {

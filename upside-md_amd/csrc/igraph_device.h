@@ -23,7 +23,7 @@
 #include "../../include/upside_hip_kernels.h"
 #include <hip/amd_detail/amd_hip_unsafe_atomics.h>
 
-#include <cstdlib>
+#include "env_switch.h"
 
 // block coordinates of a kernel body: those of its own launch, or its range of a merged launch (kernels_batch.h)
 struct BX { int bx, gx, by, gy; };
@@ -415,17 +415,18 @@ __device__ __forceinline__ void group_batch_loop(Op& op, int n_rows, const unsig
 // launch geometry of an LDS-staged pair pass: workgroups per system and lanes per workgroup.  A large batch runs one
 // 1024-lane workgroup (16 wavefronts = 128 rows in flight) per system; small batches spread a system over several smaller
 // workgroups (each stages the system again, so only as many as it takes to give every CU work).
-static inline void pair_geometry(int n_system, int n_rows, int& wgs_per_system, int& threads) {
-    static int target = 0;
-    if (!target) { const char* e = getenv("UPSIDE_HIP_IG_WGS"); target = e ? atoi(e) : 256; if (target < 1) target = 256; }
+// lanes_per_row, rows_per_full_wg: PG_LANES and 128 for the 8-row batches of pair_walk, P2_LANES and 256 for the 16-row batches of pair2_walk.
+static inline void pair_geometry(int n_system, int n_rows, int lanes_per_row, int rows_per_full_wg, int& wgs_per_system, int& threads) {
+    static const int wgs_env = env_int("UPSIDE_HIP_IG_WGS", 256);
+    const int target = wgs_env < 1 ? 256 : wgs_env;
     int bps = (target + n_system - 1) / n_system;
-    // every workgroup stages the whole system (table, elements, row order): at least one batch of 8 rows per wavefront of a
-    // 1024-lane workgroup, i.e. 128 rows each -- a single system is served by ~10 fat workgroups, not by 40 thin ones
-    const int max_bps = (n_rows + 127) / 128;
+    // every workgroup stages the whole system (table, elements, row order): at least one batch of rows per wavefront of a
+    // 1024-lane workgroup, i.e. 128 (256) rows each -- a single system is served by ~10 fat workgroups, not by 40 thin ones
+    const int max_bps = (n_rows + rows_per_full_wg - 1) / rows_per_full_wg;
     if (bps > max_bps) bps = max_bps;
     if (bps < 1) bps = 1;
     const int rows_per_wg = (n_rows + bps - 1) / bps;
-    int t = ((rows_per_wg * PG_LANES + 63) / 64) * 64;           // one batch per wavefront
+    int t = ((rows_per_wg * lanes_per_row + 63) / 64) * 64;      // one batch per wavefront
     threads = t < 256 ? 256 : (t > 1024 ? 1024 : t);
     wgs_per_system = bps;
 }

@@ -4,6 +4,7 @@
 // gathers deterministically (upk_gather_contrib) -- no float atomics anywhere in the force pass.
 #include "device_math.h"
 #include "../../include/upside_hip_kernels.h"
+#include "env_switch.h"
 #include <cstdio>
 #include <cstring>
 #include <cstdlib>
@@ -1965,8 +1966,8 @@ unsigned long long fuse_hash(const FusedOp& op) {
 // workgroup size of a fused launch: enough lanes for the per-element loops of a system (a few hundred to a few thousand items) in a
 // small batch, several systems resident per CU in a large one
 int fuse_threads(int n_system) {
-    static int forced = -1;
-    if (forced < 0) { const char* e = getenv("UPSIDE_HIP_FUSE_THREADS"); forced = e ? atoi(e) : 0; if (forced % 64 || forced > 1024) forced = 0; }
+    static const int forced_env = env_int("UPSIDE_HIP_FUSE_THREADS", 0);
+    const int forced = (forced_env % 64 || forced_env > 1024) ? 0 : forced_env;
     if (forced) return forced;
     // (256-lane workgroups fill a CU eight at a time: worth it once there are systems for all of them -- 512 lanes against 256, k
     //  system-steps/s: 300 residues x 256 149 / 142, x 1024 178 / 175, x 2048 equal, x 4096 186 / 187; 56 residues x 256 664 / 613,
@@ -1995,11 +1996,10 @@ static_assert(sizeof(FusedOp) == 16 + FUSE_PAYLOAD && sizeof(FusedOp) % 8 == 0, 
 extern "C" void* upk_fuse_create(int n_system) {
     FuseQueue* q = new FuseQueue;
     q->n_system = n_system; q->threads = fuse_threads(n_system);
-    const char* e = getenv("UPSIDE_HIP_FUSE");
-    q->enabled = !(e && !atoi(e));
+    q->enabled = env_int("UPSIDE_HIP_FUSE", 1) != 0;
     q->pending.n = 0;
-    { const char* b = getenv("UPSIDE_HIP_FUSE_BARRIERS"); q->elide = !(b && atoi(b)); }
-    if (getenv("UPSIDE_HIP_FUSE_TRACE")) (void)hipMalloc((void**)&q->trace_dev, sizeof(long long) * (FUSE_MAX_PENDING + 1));
+    q->elide = env_int("UPSIDE_HIP_FUSE_BARRIERS", 0) == 0;
+    if (env_set("UPSIDE_HIP_FUSE_TRACE")) (void)hipMalloc((void**)&q->trace_dev, sizeof(long long) * (FUSE_MAX_PENDING + 1));
     if (hipMalloc((void**)&q->table_dev, (size_t)q->cap * sizeof(FusedOp)) != hipSuccess) { delete q; return nullptr; }
     q->table.reserve(256);
     return q;
@@ -2017,7 +2017,7 @@ extern "C" void upk_fuse_destroy(void* fuse) {
         fprintf(stderr, "fused ops per force pass: %.1f us\n", tot);
         (void)hipFree(q->trace_dev);
     }
-    if (getenv("UPSIDE_HIP_FUSE_STATS")) fprintf(stderr, "fused ops: %ld launches, %ld ops, %zu distinct ops registered\n", q->n_launch, q->n_ops_run, q->table.size());
+    if (env_set("UPSIDE_HIP_FUSE_STATS")) fprintf(stderr, "fused ops: %ld launches, %ld ops, %zu distinct ops registered\n", q->n_launch, q->n_ops_run, q->table.size());
     if (q->table_dev) (void)hipFree(q->table_dev);
     delete q;
 }
@@ -2028,7 +2028,7 @@ extern "C" int upk_fuse_flush(const upk_launch_t* L) {
     if (!q || !q->pending.n) return 0;
     if (L->batch) { const int r_ = upk_batch_run(L); if (r_) return r_; }      // items of an open merged launch precede the ops queued behind them
     size_t lds = (size_t)q->pending_lds; if (lds < 64) lds = 64;      // (c_reduce_sum's partial sums)
-    static const bool debug = getenv("UPSIDE_HIP_FUSE_DEBUG") != nullptr;
+    static const bool debug = env_set("UPSIDE_HIP_FUSE_DEBUG");
     if (debug) { fprintf(stderr, "fused launch (%s):", q->pending_heavy ? "heavy" : "light"); for (int k = 0; k < q->pending.n; ++k) fprintf(stderr, " %d%s", q->table[q->pending.id[k]].kind, (q->table[q->pending.id[k]].flags & 1) ? "" : "|"); fprintf(stderr, "\n"); }
     { const int T = q->pending_heavy && q->threads > 512 ? 512 : q->threads; for (int k = 0; k < q->pending.n; ++k) q->pending.rot[k] %= T; }   // (the heavy instance runs 512 lanes)
     fuse_launch<true>(q->pending_heavy, q->threads, q->n_system, lds, ST(L), (const FusedOp*)q->table_dev, q->pending, q->trace_dev);
@@ -2037,7 +2037,7 @@ extern "C" int upk_fuse_flush(const upk_launch_t* L) {
         if (hipStreamSynchronize(ST(L)) == hipSuccess && hipMemcpy(t, q->trace_dev, sizeof(long long) * (q->pending.n + 1), hipMemcpyDeviceToHost) == hipSuccess)
         {
             for (int k = 0; k < q->pending.n; ++k) { const int kind = q->table[q->pending.id[k]].kind; q->trace_us[kind] += (t[k + 1] - t[k]) * 0.01; q->trace_n[kind] += 1; }
-            static const int level = atoi(getenv("UPSIDE_HIP_FUSE_TRACE"));
+            static const int level = env_int("UPSIDE_HIP_FUSE_TRACE", 0);
             if (level >= 2 && q->n_launch >= 1000 && q->n_launch < 1012) {      // (a dozen launches of a warmed-up run: "kind@us since the list's start", | = barrier in front)
                 fprintf(stderr, "fused list %ld (%s):", q->n_launch, q->pending_heavy ? "heavy" : "light");
                 for (int k = 0; k < q->pending.n; ++k) fprintf(stderr, " %s%d@%.1f", (q->table[q->pending.id[k]].flags & 1) ? "" : "| ", q->table[q->pending.id[k]].kind, (t[k] - t[0]) * 0.01);

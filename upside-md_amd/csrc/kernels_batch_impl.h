@@ -55,7 +55,7 @@ __global__ void __launch_bounds__(1024) PG_KERNEL_ATTR k_batch(BatchArgs A) {
 extern "C" void* upk_batch_create() { return new BatchState; }
 extern "C" void upk_batch_destroy(void* b) {
     BatchState* s = (BatchState*)b;
-    if (s && getenv("UPSIDE_HIP_FUSE_STATS")) fprintf(stderr, "merged launches: %ld launches for %ld kernels\n", s->n_merged, s->n_items);
+    if (s && env_set("UPSIDE_HIP_FUSE_STATS")) fprintf(stderr, "merged launches: %ld launches for %ld kernels\n", s->n_merged, s->n_items);
     delete s;
 }
 extern "C" int upk_batch_begin(const upk_launch_t* L) {

@@ -325,8 +325,7 @@ extern "C" int upk_pairlist_build_sides(const upk_launch_t* L, const upk_igraph_
     const int n_max = G->n1 > G->n2 ? G->n1 : G->n2;
     const size_t lds = (size_t)((n_max + 63) & ~63) * 16;
     const dim3 grid(blocks1 + blocks2, UPK_FLAG_GRID(L->n_system));
-    static int force_unstaged = -1;   // UPSIDE_HIP_PLB_UNSTAGED=1 exercises the path of systems whose elements do not fit LDS
-    if (force_unstaged < 0) { const char* e = getenv("UPSIDE_HIP_PLB_UNSTAGED"); force_unstaged = (e && atoi(e)) ? 1 : 0; }
+    static const bool force_unstaged = env_int("UPSIDE_HIP_PLB_UNSTAGED", 0) != 0;   // =1 exercises the path of systems whose elements do not fit LDS
     const bool staged = lds <= 150 * 1024 && !force_unstaged;
     if (staged) {       // merged launch (kernels_batch.h)
         const int bk = G->itype == UPK_IT_ROTAMER ? BK_BUILD_ROT : G->itype == UPK_IT_HBOND_COVERAGE ? BK_BUILD_COV : G->itype == UPK_IT_ENVIRONMENT ? BK_BUILD_ENV

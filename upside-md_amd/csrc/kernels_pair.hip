@@ -498,11 +498,6 @@ __global__ void __launch_bounds__(1024) PG_KERNEL_ATTR k_cov_backward2(upk_igrap
     extern __shared__ __attribute__((aligned(16))) float lds_dyn_[];
     d_cov_backward2<RS, POLY>(G, A, BX_REAL, lds_dyn_);
 }
-static bool pair2_enabled() {          // UPSIDE_HIP_PAIR2=0: the scalar passes (one partner per lane) -- A/B and tests
-    static int v = -1;
-    if (v < 0) { const char* e = getenv("UPSIDE_HIP_PAIR2"); v = (e && !atoi(e)) ? 0 : 1; }
-    return v != 0;
-}
 
 // global accumulators (several workgroups per system) -> the other side's sens; cleared for the next evaluation
 __device__ __forceinline__ void d_pair_backward_finish(const upk_igraph_t& G, int other_side, double unit, const BX B, float* lds_unused) {   // unit: value of one accumulator count
@@ -527,8 +522,7 @@ static bool pair_lds_bytes(const upk_igraph_t* G, bool poly, int& tab_floats, si
     if (poly && !(G->itype == UPK_IT_HBOND_COVERAGE && G->param_poly)) return false;
     const int n_max = G->n1 > G->n2 ? G->n1 : G->n2;
     bytes = ((size_t)((tab_floats + 3) & ~3) + (size_t)(G->n1 + G->n2) * 8 + PG_WALK_LDS_WORDS(n_max) + 4) * sizeof(float);
-    static int force_unstaged = -1;   // UPSIDE_HIP_IG_UNSTAGED=1 exercises the path taken by systems too large for LDS staging
-    if (force_unstaged < 0) { const char* e = getenv("UPSIDE_HIP_IG_UNSTAGED"); force_unstaged = (e && atoi(e)) ? 1 : 0; }
+    static const bool force_unstaged = env_int("UPSIDE_HIP_IG_UNSTAGED", 0) != 0;   // =1 exercises the path taken by systems too large for LDS staging
     return bytes <= 158 * 1024 && !force_unstaged && n_max < 65536 && G->cap1 < 65536 && G->cap2 < 65536;
 }
 
@@ -546,8 +540,7 @@ static void rows_launch_sides(const upk_launch_t* L, const upk_igraph_t* G, int 
 }
 // the polynomial table when it fits LDS next to the elements (and extra bytes), else the spline coefficients, else nothing fits
 static int pair_table_choice(const upk_igraph_t* G, size_t extra, int& tab_floats, size_t& lds) {
-    static int no_poly = -1;      // UPSIDE_HIP_IG_POLY=0: always the spline-coefficient table (A/B and the large-table path)
-    if (no_poly < 0) { const char* e = getenv("UPSIDE_HIP_IG_POLY"); no_poly = (e && !atoi(e)) ? 1 : 0; }
+    static const bool no_poly = env_int("UPSIDE_HIP_IG_POLY", 1) == 0;   // =0: always the spline-coefficient table (A/B and the large-table path)
     if (!no_poly && pair_lds_bytes(G, true, tab_floats, lds) && lds + extra <= 158 * 1024) return 2;
     if (pair_lds_bytes(G, false, tab_floats, lds) && lds + extra <= 158 * 1024) return 1;
     return 0;
@@ -590,7 +583,7 @@ extern "C" int upk_igraph_rows(const upk_launch_t* L, const upk_igraph_t* G, int
     const int n_rows = side == 1 ? G->n1 : (side == 2 ? G->n2 : (G->n1 > G->n2 ? G->n1 : G->n2));
     int bps, threads;
     if (G->itype == UPK_IT_HBOND_COVERAGE && mode == 0 && side != 3 && pair2_enabled() && lds + 64 <= 158 * 1024) {   // packed pass
-        pair2_geometry(L->n_system, n_rows, bps, threads);
+        pair_geometry(L->n_system, n_rows, P2_LANES, 256, bps, threads);
         if (side == 2 && batch_add(L, table == 2 ? BK_COV_ROWS2_POLY : BK_COV_ROWS2, bps, L->n_system, lds + 64, G, sizeof(*G), &A, sizeof(A))) return 0;
         UPK_FLUSH(L);
         const dim3 grid2(bps, L->n_system), block2(threads);
@@ -598,7 +591,7 @@ extern "C" int upk_igraph_rows(const upk_launch_t* L, const upk_igraph_t* G, int
         else { if (table == 2) hipLaunchKernelGGL((k_cov_rows2<2, true>), grid2, block2, lds + 64, ST(L), *G, A); else hipLaunchKernelGGL((k_cov_rows2<2, false>), grid2, block2, lds + 64, ST(L), *G, A); }
         return launch_status();
     }
-    pair_geometry(L->n_system, n_rows, bps, threads);
+    pair_geometry(L->n_system, n_rows, PG_LANES, 128, bps, threads);
     // (a few hundred rows of two or three pairs: the pass is the latency of staging the system, which several small workgroups
     //  per CU overlap: 1024 lanes 0.29 + 0.23 ms, 512: 0.25 + 0.18, 256: 0.23 + 0.17, 128: 0.29 + 0.20; the environment graph, 300 rows of ~40 pairs, is best left at 1024)
     if (G->itype == UPK_IT_PROTEIN_HBOND && bps == 1) {
@@ -660,7 +653,7 @@ extern "C" int upk_igraph_backward(const upk_launch_t* L, const upk_igraph_t* G,
         const int table2 = pair_table_choice(G, acc_bytes + extra, tf, lds2);
         if (table2) {
             A.tab_floats = tf; lds2 += acc_bytes + extra;
-            pair2_geometry(L->n_system, n_rows, bps, threads);
+            pair_geometry(L->n_system, n_rows, P2_LANES, 256, bps, threads);
             if (!G->gacc) bps = 1;
             if (row_side == 2 && batch_add(L, table2 == 2 ? BK_COV_BWD2_POLY : BK_COV_BWD2, bps, L->n_system, lds2, G, sizeof(*G), &A, sizeof(A))) {
                 if (bps > 1 && !batch_add(L, BK_BWD_FINISH, (n_other * 8 + 1023) / 1024, L->n_system, 0, G, sizeof(*G), nullptr, 0, 3 - row_side, 0, 1.0 / (double)(1 << P2_FIX_BITS)))
@@ -675,7 +668,7 @@ extern "C" int upk_igraph_backward(const upk_launch_t* L, const upk_igraph_t* G,
             return launch_status();
         }
     }
-    pair_geometry(L->n_system, n_rows, bps, threads);
+    pair_geometry(L->n_system, n_rows, PG_LANES, 128, bps, threads);
     if (!G->gacc) bps = 1;
     if (G->itype == UPK_IT_ENVIRONMENT && row_side == 1 && batch_add(L, BK_ENV_BWD, bps, L->n_system, lds, G, sizeof(*G), &A, sizeof(A))) {
         if (bps > 1 && !batch_add(L, BK_BWD_FINISH, (n_other * 8 + 1023) / 1024, L->n_system, 0, G, sizeof(*G), nullptr, 0, 3 - row_side, 0, 1.0 / 4294967296.0))

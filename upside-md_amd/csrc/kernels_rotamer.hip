@@ -265,8 +265,8 @@ extern "C" int upk_rotamer_build_slots(const upk_launch_t* L, const upk_rotamer_
     // a small system's slot stamping (upk_rotamer_nbr_slots) rides behind the numbering in the same workgroup: one launch less on the upkeep chain
     if (R->G.n1 <= 512 && batch_add(L, BK_SLOTS_BOTH, 1, L->n_system < wgs ? L->n_system : wgs, lds, R, sizeof(*R))) { batch_of(L)->skip_nbr_slots = true; return 0; }
     // workgroups per system (see the kernel): several while the device has CUs to spare, one when systems fill it
-    static int split = -1;    // UPSIDE_HIP_SLOT_SPLIT (experiments / tests)
-    if (split < 0) { const char* e = getenv("UPSIDE_HIP_SLOT_SPLIT"); split = e ? atoi(e) : 0; if (split < 0 || split > 16) split = 0; }
+    static const int split_env = env_int("UPSIDE_HIP_SLOT_SPLIT", 0);    // (experiments / tests)
+    const int split = (split_env < 0 || split_env > 16) ? 0 : split_env;
     const int K = split ? split : ((L->n_system <= 256 && R->n_node > 64) ? 4 : 1);
     if (batch_add(L, BK_BUILD_SLOTS, K, L->n_system < wgs ? L->n_system : wgs, lds, R, sizeof(*R))) return 0;
     UPK_FLUSH(L);
@@ -587,25 +587,19 @@ __global__ void __launch_bounds__(1024) PG_KERNEL_ATTR k_rotamer_grad2(upk_rotam
     }
 }
 
-static bool rot_pair2_enabled() {          // UPSIDE_HIP_PAIR2=0: the scalar passes (one partner per lane) -- A/B and tests
-    static int v = -1;
-    if (v < 0) { const char* e = getenv("UPSIDE_HIP_PAIR2"); v = (e && !atoi(e)) ? 0 : 1; }
-    return v != 0;
-}
 static int rot_geometry(const upk_launch_t* L, const upk_rotamer_t* R, bool want_acc, int& tab_floats, size_t& lds_bytes, dim3& grid, dim3& block,
                         bool poly = false, bool pair2 = false) {
     const int nt = R->G.n_type1;
     tab_floats = (nt * (nt + 1) / 2) * (poly ? R->n_poly : R->G.n_param);
     const size_t fixed = ((size_t)((tab_floats + 3) & ~3) + PG_WALK_LDS_WORDS(R->G.n1) + 4) * sizeof(float);
-    static int force_unstaged = -1;   // UPSIDE_HIP_ROT_UNSTAGED=1 exercises the large-system path
-    if (force_unstaged < 0) { const char* e = getenv("UPSIDE_HIP_ROT_UNSTAGED"); force_unstaged = (e && atoi(e)) ? 1 : 0; }
+    static const bool force_unstaged = env_int("UPSIDE_HIP_ROT_UNSTAGED", 0) != 0;   // =1 exercises the large-system path
     int staged = 1;
     lds_bytes = fixed + (size_t)R->G.n1 * (want_acc ? 20 : 8) * sizeof(float) + (pair2 ? 32 : 0);
     if (lds_bytes > 158 * 1024 || force_unstaged || R->bead_pack) { staged = 0; lds_bytes = fixed; }   // (a system whose gradient pass needs the packed copy uses it in both passes)
     if (lds_bytes > 158 * 1024 || (!staged && !R->bead_pack)) return -1;
     int bps, threads;
-    if (pair2) pair2_geometry(L->n_system, R->G.n1, bps, threads);
-    else pair_geometry(L->n_system, R->G.n1, bps, threads);
+    if (pair2) pair_geometry(L->n_system, R->G.n1, P2_LANES, 256, bps, threads);
+    else pair_geometry(L->n_system, R->G.n1, PG_LANES, 128, bps, threads);
     grid = dim3(bps, L->n_system); block = dim3(threads);
     return staged;
 }
@@ -613,8 +607,7 @@ extern "C" int upk_rotamer_pair_energy(const upk_launch_t* L, const upk_rotamer_
     if (!list_words_match(&R->G)) return 9010;
     UPK_FLUSH(L);
     int tab_floats; size_t lds; dim3 grid, block;
-    static int no_poly = -1;      // UPSIDE_HIP_ROT_POLY=0 keeps the energy pass on the spline-coefficient table (A/B and the large-table path)
-    if (no_poly < 0) { const char* e = getenv("UPSIDE_HIP_ROT_POLY"); no_poly = (e && !atoi(e)) ? 1 : 0; }
+    static const bool no_poly = env_int("UPSIDE_HIP_ROT_POLY", 1) == 0;   // =0 keeps the energy pass on the spline-coefficient table (A/B and the large-table path)
     // (the packed two-partners-per-lane form of THIS pass was built in round 3 and removed in round 6: the pass is bound by its scattered
     //  pair-matrix stores, and 16 rows x 4 partners per store instruction touch 1.7x the cache lines of 8 rows x 8 partners: 1.45 against 1.26 ms)
     if (R->param_tri_poly && !no_poly && rot_geometry(L, R, false, tab_floats, lds, grid, block, true) == 1) {   // polynomial table + beads fit LDS
@@ -739,7 +732,7 @@ extern "C" int upk_rotamer_grad(const upk_launch_t* L, const upk_rotamer_t* R) {
     UPK_FLUSH(L);
     int tab_floats; size_t lds; dim3 grid, block;
     const double unit32 = 1.0 / 4294967296.0, unit22 = 1.0 / (double)(1 << P2_FIX_BITS);
-    if (rot_pair2_enabled()) {                     // packed passes: polynomial table if it fits beside the accumulators, else spline coefficients
+    if (pair2_enabled()) {                     // packed passes: polynomial table if it fits beside the accumulators, else spline coefficients
         for (int poly = 1; poly >= 0; --poly) {
             if (poly && !R->param_tri_poly) continue;
             if (rot_geometry(L, R, true, tab_floats, lds, grid, block, poly != 0, true) != 1) continue;
@@ -1005,9 +998,8 @@ template <int N, int NS> __device__ __forceinline__ void bp_load_nb(const float*
         for (int i = 0; i < N; ++i) v[i] = p[i];
     }
 }
-template <int NA, int NB, bool WT, int NS = 6, typename CTX = BpCtx>   // WT: messages leave through 16-byte write-through stores (cluster solve)
-__device__ __forceinline__ void bp_edge_slot(const CTX& C, int oa, int ob, int a, int b, const float (&P)[NA * NB], const float* __restrict__ nb_old,
-                                             __amdgpu_buffer_rsrc_t inbox_w) {
+template <int NA, int NB, int NS = 6, typename CTX = BpCtx>
+__device__ __forceinline__ void bp_edge_slot(const CTX& C, int oa, int ob, int a, int b, const float (&P)[NA * NB], const float* __restrict__ nb_old) {
     float* pa = C.msg(oa);
     float* pb = C.msg(ob);
     float ma[NA], mb[NB];
@@ -1032,22 +1024,11 @@ __device__ __forceinline__ void bp_edge_slot(const CTX& C, int oa, int ob, int a
     // (tried: both products on explicit v_pk_fma_f32 pairs -- the compiler's own pairing already issues as many packed
     //  operations, no change in time, and the re-associated row sums cost the bit-identity between the solve variants)
     const float ra = fast_rcp(sa), rb = fast_rcp(sb);
-    if (WT) {
 #pragma unroll
-        for (int i = 0; i < NA; ++i) ta[i] *= ra;
+    for (int i = 0; i < NA; ++i) ta[i] *= ra;
 #pragma unroll
-        for (int j = 0; j < NB; ++j) tb[j] *= rb;
-        st_wt16(inbox_w, oa, ta[0], ta[1], ta[2], NA == 6 ? ta[NA - 3] : 1.f);
-        if (NA == 6) st_wt16(inbox_w, oa + 4, ta[NA - 2], ta[NA - 1], 1.f, 1.f);
-        st_wt16(inbox_w, ob, tb[0], tb[1], tb[2], NB == 6 ? tb[NB - 3] : 1.f);
-        if (NB == 6) st_wt16(inbox_w, ob + 4, tb[NB - 2], tb[NB - 1], 1.f, 1.f);
-    } else {
-#pragma unroll
-        for (int i = 0; i < NA; ++i) ta[i] *= ra;
-#pragma unroll
-        for (int j = 0; j < NB; ++j) tb[j] *= rb;
-        bp_store_row<NA, CTX::W3>(pa, ta); bp_store_row<NB, CTX::W3>(pb, tb);
-    }
+    for (int j = 0; j < NB; ++j) tb[j] *= rb;
+    bp_store_row<NA, CTX::W3>(pa, ta); bp_store_row<NB, CTX::W3>(pb, tb);
 }
 // the NA x NB entries of one slot, row-major, from the [36][cap] table
 template <int NA, int NB>
@@ -1060,9 +1041,8 @@ __device__ __forceinline__ void bp_load_matrix(const BpCtx& C, int sl, float (&P
         else P[i * NB + 2] = ((const float*)r)[2];
     }
 }
-template <int NA, int NB, bool WT, int NS = 6, typename CTX = BpCtx>
-__device__ __forceinline__ void bp_edge_range_impl(const CTX& C, int lo, int hi, const float* __restrict__ nb_old, int tid, int nt,
-                                                   __amdgpu_buffer_rsrc_t inbox_w) {
+template <int NA, int NB, int NS = 6, typename CTX = BpCtx>
+__device__ __forceinline__ void bp_edge_range(const CTX& C, int lo, int hi, const float* __restrict__ nb_old, int tid, int nt) {
     // (measured and rejected: fetching the next slot's flag and message offsets one trip ahead.  In the 6x6 instance it
     // spills 58 VGPRs (sweep 34.5 -> 47.7 us at 1024 systems); in the 3x3 / 3x6 instances alone it costs 1 % of the
     // benchmark -- under load the sweep is limited by memory throughput, not by the two-trip chain)
@@ -1071,7 +1051,7 @@ __device__ __forceinline__ void bp_edge_range_impl(const CTX& C, int lo, int hi,
         if (!act) continue;
         float P[NA * NB];
         bp_load_matrix<NA, NB>(C, sl, P);
-        bp_edge_slot<NA, NB, WT, NS>(C, oa, ob, C.slot_a[sl], C.slot_b[sl], P, nb_old, inbox_w);
+        bp_edge_slot<NA, NB, NS>(C, oa, ob, C.slot_a[sl], C.slot_b[sl], P, nb_old);
     }
 }
 // Active slots of the multi-state classes, packed once per solve: the sweeps then read one 16-byte record per ACTIVE slot
@@ -1102,8 +1082,7 @@ __device__ __forceinline__ void bp_pack_active(const BpCtx& C, int4* __restrict_
     }
 }
 template <int NA, int NB, int NS = 6, typename CTX = BpCtx>
-__device__ __forceinline__ void bp_edge_packed(const CTX& C, int first, int end, const float* __restrict__ nb_old, int tid, int nt,
-                                               __amdgpu_buffer_rsrc_t rs) {
+__device__ __forceinline__ void bp_edge_packed(const CTX& C, int first, int end, const float* __restrict__ nb_old, int tid, int nt) {
 #ifndef BP_REC_AHEAD
 #define BP_REC_AHEAD 1
 #endif
@@ -1126,7 +1105,7 @@ __device__ __forceinline__ void bp_edge_packed(const CTX& C, int first, int end,
             if (idx + 2 * nt < end) r2 = C.rec[idx + 2 * nt];
             float P1[NA * NB];
             bp_load_matrix<NA, NB>(C, r1.w, P1);                  // (the last trip re-reads its own matrix: harmless)
-            bp_edge_slot<NA, NB, false, NS>(C, r0.x, r0.y, r0.z & 0xffff, r0.z >> 16, P0, nb_old, rs);
+            bp_edge_slot<NA, NB, NS>(C, r0.x, r0.y, r0.z & 0xffff, r0.z >> 16, P0, nb_old);
             r0 = r1; r1 = r2;
 #pragma unroll
             for (int e = 0; e < NA * NB; ++e) P0[e] = P1[e];
@@ -1140,13 +1119,9 @@ __device__ __forceinline__ void bp_edge_packed(const CTX& C, int first, int end,
         if (BP_REC_AHEAD && idx + nt < end) rn = C.rec[idx + nt];
         float P[NA * NB];
         bp_load_matrix<NA, NB>(C, r.w, P);
-        bp_edge_slot<NA, NB, false, NS>(C, r.x, r.y, r.z & 0xffff, r.z >> 16, P, nb_old, rs);
+        bp_edge_slot<NA, NB, NS>(C, r.x, r.y, r.z & 0xffff, r.z >> 16, P, nb_old);
         if (BP_REC_AHEAD) r = rn; else if (idx + nt < end) r = C.rec[idx + nt];
     }
-}
-template <int NA, int NB, int NS = 6, typename CTX = BpCtx>
-__device__ __forceinline__ void bp_edge_range(const CTX& C, int lo, int hi, const float* __restrict__ nb_old, int tid, int nt) {
-    bp_edge_range_impl<NA, NB, false, NS>(C, lo, hi, nb_old, tid, nt, make_rsrc(C.inbox, 0u));
 }
 // energies -> probabilities, in place, for slots [lo, hi) of one class (rotamer.cpp:835)
 // One slot per lane and trip: all NA*NB loads of the slot are issued before the first store, so a trip costs one
@@ -1287,10 +1262,10 @@ struct BpResident {
             }
         }
     }
-    template <int NS, typename CTX> __device__ __forceinline__ void edge(const CTX& C, const float* __restrict__ nb_old, __amdgpu_buffer_rsrc_t rs) const {
+    template <int NS, typename CTX> __device__ __forceinline__ void edge(const CTX& C, const float* __restrict__ nb_old) const {
 #pragma unroll
         for (int k = 0; k < K; ++k)
-            if (ab[k] >= 0) bp_edge_slot<NA, NB, false, NS>(C, oa[k], ob[k], ab[k] & 0xffff, ab[k] >> 16, P[k], nb_old, rs);
+            if (ab[k] >= 0) bp_edge_slot<NA, NB, NS>(C, oa[k], ob[k], ab[k] & 0xffff, ab[k] >> 16, P[k], nb_old);
     }
     template <int NS, typename CTX> __device__ __forceinline__ float marginal(const CTX& C, const float* __restrict__ nbm, bool want_energy) const {
         float en = 0.f;
@@ -1649,7 +1624,6 @@ __global__ void __launch_bounds__(BLOCK) k_rotamer_bp(upk_rotamer_t R, int want_
     const int e33 = cls[CL33] + n_act[CL33], e36 = cls[CL36] + n_act[CL36], e66 = cls[CL66] + n_act[CL66];   // ends of the packed records
     r33.load(C, cls[CL33], e33, tid, nt); r36.load(C, cls[CL36], e36, tid, nt); r66.load(C, cls[CL66], e66, tid, nt);
     BP_STAMP(4);
-    const __amdgpu_buffer_rsrc_t inbox_rs = make_rsrc(C.inbox, 0u);
 
     float* nb_old = nb0; float* nb_cur = nb1;
     int iter = 0;
@@ -1663,16 +1637,16 @@ __global__ void __launch_bounds__(BLOCK) k_rotamer_bp(upk_rotamer_t R, int want_
         // ---- edge phase: every residue pair rewrites its two messages in place from the old node beliefs
         // (measured and rejected: dealing 64-slot chunks of all classes to the wavefronts round-robin, heavy classes first, to
         // even out the trip counts -- 1 % slower: the phase is limited by bytes, not by trips)
-        r33.template edge<NS>(C, nb_old, inbox_rs); r36.template edge<NS>(C, nb_old, inbox_rs); r66.template edge<NS>(C, nb_old, inbox_rs);
+        r33.template edge<NS>(C, nb_old); r36.template edge<NS>(C, nb_old); r66.template edge<NS>(C, nb_old);
         if (PACK) {
             // (no barrier separates the classes: a wavefront's edge phase is the sum of its trips through all of them.  A class of
             //  n slots gives its first n mod nt lanes one slot more; dealt from lane 0 in every class the extra trips pile up on the
             //  first wavefronts -- 8 trips there, 5 on the last one for the benchmark protein.  The streamed 3x3 and 3x6 classes are
             //  dealt from the LAST lane instead: 7 at most.  Which lane serves a slot changes nothing in its arithmetic.)
             const int tid_r = BP_EDGE_REVERSE ? nt - 1 - tid : tid;
-            bp_edge_packed<3, 3, NS>(C, cls[CL33] + K33 * nt, e33, nb_old, tid_r, nt, inbox_rs);
-            bp_edge_packed<3, 6, NS>(C, cls[CL36] + K36 * nt, e36, nb_old, tid_r, nt, inbox_rs);
-            bp_edge_packed<6, 6, NS>(C, cls[CL66] + K66 * nt, e66, nb_old, tid, nt, inbox_rs);
+            bp_edge_packed<3, 3, NS>(C, cls[CL33] + K33 * nt, e33, nb_old, tid_r, nt);
+            bp_edge_packed<3, 6, NS>(C, cls[CL36] + K36 * nt, e36, nb_old, tid_r, nt);
+            bp_edge_packed<6, 6, NS>(C, cls[CL66] + K66 * nt, e66, nb_old, tid, nt);
         } else {
             bp_edge_range<3, 3, NS>(C, cls[CL33], cls[CL33 + 1], nb_old, tid, nt);
             bp_edge_range<3, 6, NS>(C, cls[CL36], cls[CL36 + 1], nb_old, tid, nt);
@@ -2035,11 +2009,6 @@ __device__ __forceinline__ float bpc_marginal(const BpcSlot<NA, NB>& st, const f
 #define BPC_GROUP 16  // lanes cooperating on one node
 
 #define BPC_BLOCK 512   // 8 waves: 256 VGPRs per lane keep the three slot states + a 6x6 matrix out of scratch
-// RESIDENT = true: the form described above (512 lanes, needs C large enough for the matrices to fit LDS).
-// RESIDENT = false ("split" solve, 1024 lanes): the same exchange protocol, but the matrices stay in global memory and
-// a lane loops over its share of the slots like the one-workgroup kernel does -- any C works; used for mid-size
-// batches that leave CUs idle under the one-workgroup solve.
-template <bool RESIDENT>
 __global__ void __launch_bounds__(BPC_BLOCK) k_rotamer_bp_cluster(upk_rotamer_t R, int want_energy, int C, int sys0, int n_sys, int p_cap) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
     if ((int)blockIdx.x >= n_sys) return;
@@ -2058,7 +2027,7 @@ __global__ void __launch_bounds__(BPC_BLOCK) k_rotamer_bp_cluster(upk_rotamer_t 
     const int need = n_own[0] * 9 + n_own[1] * 18 + n_own[2] * 36;
     // every workgroup of the cluster must reach the same verdict: test all shares, not only the own one
     bool fits = true;
-    for (int cc = 0; RESIDENT && cc < C; ++cc) {
+    for (int cc = 0; cc < C; ++cc) {
         int nd = 0;
 #pragma unroll
         for (int k = 0; k < 3; ++k) {
@@ -2100,33 +2069,12 @@ __global__ void __launch_bounds__(BPC_BLOCK) k_rotamer_bp_cluster(upk_rotamer_t 
     for (int i = tid; i < NN; i += nt) nrot[i] = R.node_nrot[i];
     for (int i = tid; i <= NN; i += nt) bp_start[i] = R.bp_start[(size_t)s * (NN + 1) + i];
     BpcSlot<3, 3> s33; BpcSlot<3, 6> s36; BpcSlot<6, 6> s66;
-    BpCtx Cx;                                  // split solve: slot data in global memory
-    Cx.cap = R.slot_cap;
-    Cx.slot_a = R.slot_a + (size_t)s * R.slot_cap; Cx.slot_b = R.slot_b + (size_t)s * R.slot_cap;
-    Cx.active = R.slot_active + (size_t)s * R.slot_cap; Cx.slot_off = R.slot_off + (size_t)s * R.slot_cap * 2;
-    Cx.P = R.P + (size_t)s * R.slot_cap * 36; Cx.inbox = R.msg_cur + (size_t)s * R.slot_cap * 16;
-    Cx.marg = R.marg + (size_t)s * R.slot_cap * 36;
-    if (RESIDENT) {
-        bpc_stage<3, 3>(Pl0, R, s, lo[0], n_own[0]);
-        bpc_stage<3, 6>(Pl1, R, s, lo[1], n_own[1]);
-        bpc_stage<6, 6>(Pl2, R, s, lo[2], n_own[2]);
-        bpc_init(s33, R, s, lo[0], n_own[0], X.inbox_w);
-        bpc_init(s36, R, s, lo[1], n_own[1], X.inbox_w);
-        bpc_init(s66, R, s, lo[2], n_own[2], X.inbox_w);
-    } else {
-        // exp(-E) in place for the own multi-state slots only: nobody else reads them (the 1-state classes stay
-        // energies: the fold below and the 1-1 energy term take exp / the energy themselves)
-        exp_class<3, 3>(Cx.P, Cx.cap, lo[0], lo[0] + n_own[0], tid, nt);
-        exp_class<3, 6>(Cx.P, Cx.cap, lo[1], lo[1] + n_own[1], tid, nt);
-        exp_class<6, 6>(Cx.P, Cx.cap, lo[2], lo[2] + n_own[2], tid, nt);
-        for (int k = 0; k < 3; ++k)            // old edge beliefs = 1 (rotamer.cpp:1015-1032), both rows of every own slot
-            for (int sl = lo[k] + tid; sl < lo[k] + n_own[k]; sl += nt) {
-                const int oa = Cx.slot_off[sl * 2], ob = Cx.slot_off[sl * 2 + 1];
-                st_wt16(X.inbox_w, oa, 1.f, 1.f, 1.f, 1.f); st_wt16(X.inbox_w, ob, 1.f, 1.f, 1.f, 1.f);
-                if (k == 2) st_wt16(X.inbox_w, oa + 4, 1.f, 1.f, 1.f, 1.f);
-                if (k >= 1) st_wt16(X.inbox_w, ob + 4, 1.f, 1.f, 1.f, 1.f);
-            }
-    }
+    bpc_stage<3, 3>(Pl0, R, s, lo[0], n_own[0]);
+    bpc_stage<3, 6>(Pl1, R, s, lo[1], n_own[1]);
+    bpc_stage<6, 6>(Pl2, R, s, lo[2], n_own[2]);
+    bpc_init(s33, R, s, lo[0], n_own[0], X.inbox_w);
+    bpc_init(s36, R, s, lo[1], n_own[1], X.inbox_w);
+    bpc_init(s66, R, s, lo[2], n_own[2], X.inbox_w);
     // fold the edges to 1-state partners into the probabilities of the own nodes (rotamer.cpp:378-385)
     if (R.node_prob_in_solve && c == 0)      // (the 1-state nodes' 1-body terms: read back by this workgroup's energy sum)
         for (int g = tid; g < e1; g += nt) { float p1[6]; rotamer_node_prob_one(R, s, g, p1); }
@@ -2170,15 +2118,9 @@ __global__ void __launch_bounds__(BPC_BLOCK) k_rotamer_bp_cluster(upk_rotamer_t 
     const int gl = tid % BPC_GROUP, n_grp = nt / BPC_GROUP;
     for (int sweep = -1;; ++sweep) {
         // ---- edge phase
-        if (RESIDENT) {
-            bpc_edge(s33, Pl0, n_own[0], nb, X.inbox_w);
-            bpc_edge(s36, Pl1, n_own[1], nb, X.inbox_w);
-            bpc_edge(s66, Pl2, n_own[2], nb, X.inbox_w);
-        } else {
-            bp_edge_range_impl<3, 3, true>(Cx, lo[0], lo[0] + n_own[0], nb, tid, nt, X.inbox_w);
-            bp_edge_range_impl<3, 6, true>(Cx, lo[1], lo[1] + n_own[1], nb, tid, nt, X.inbox_w);
-            bp_edge_range_impl<6, 6, true>(Cx, lo[2], lo[2] + n_own[2], nb, tid, nt, X.inbox_w);
-        }
+        bpc_edge(s33, Pl0, n_own[0], nb, X.inbox_w);
+        bpc_edge(s36, Pl1, n_own[1], nb, X.inbox_w);
+        bpc_edge(s66, Pl2, n_own[2], nb, X.inbox_w);
         if (!cluster_barrier(X.bar, phase, C, R.G.error_flag, fb, spin_limit)) return;      // (handed to the one-workgroup solve)
         // ---- node phase over the own nodes
         float dev = 0.f;
@@ -2278,15 +2220,9 @@ __global__ void __launch_bounds__(BPC_BLOCK) k_rotamer_bp_cluster(upk_rotamer_t 
     __syncthreads();
     float* marg = R.marg + (size_t)s * R.slot_cap * 36;
     float en = 0.f;
-    if (RESIDENT) {
-        en += bpc_marginal(s33, Pl0, n_own[0], nb, marg, R.slot_cap, want_energy);
-        en += bpc_marginal(s36, Pl1, n_own[1], nb, marg, R.slot_cap, want_energy);
-        en += bpc_marginal(s66, Pl2, n_own[2], nb, marg, R.slot_cap, want_energy);
-    } else {
-        en += bp_marginal_range<3, 3>(Cx, lo[0], lo[0] + n_own[0], nb, tid, nt, want_energy);
-        en += bp_marginal_range<3, 6>(Cx, lo[1], lo[1] + n_own[1], nb, tid, nt, want_energy);
-        en += bp_marginal_range<6, 6>(Cx, lo[2], lo[2] + n_own[2], nb, tid, nt, want_energy);
-    }
+    en += bpc_marginal(s33, Pl0, n_own[0], nb, marg, R.slot_cap, want_energy);
+    en += bpc_marginal(s36, Pl1, n_own[1], nb, marg, R.slot_cap, want_energy);
+    en += bpc_marginal(s66, Pl2, n_own[2], nb, marg, R.slot_cap, want_energy);
     // ---- leave the accumulators clean for the next force evaluation (every class, split over the cluster)
     float* P = R.P + (size_t)s * R.slot_cap * 36;
     int* active_w = R.slot_active + (size_t)s * R.slot_cap;
@@ -2338,8 +2274,7 @@ static void bp_launch(const upk_launch_t* L, const upk_rotamer_t* R, int want_en
     // and batch sizes; the losers are gone: `git log` has them).  (ii) 1024 lanes streaming every matrix over the CACHED inbox layout: the
     // hand-over solve behind a cluster launch, systems whose layout scratch does not fit, UPSIDE_HIP_BP_COMPACT=0 (tests).
     const dim3 grid(1, L->n_system);
-    static int compact = -1;  // UPSIDE_HIP_BP_COMPACT=0: the cached inbox layout (tests)
-    if (compact < 0) { const char* e = getenv("UPSIDE_HIP_BP_COMPACT"); compact = (e && !atoi(e)) ? 0 : 1; }
+    static const bool compact = env_int("UPSIDE_HIP_BP_COMPACT", 1) != 0;  // =0: the cached inbox layout (tests)
     // (the layout pass borrows the LDS inbox for an activity bit per cached row and a prefix per 32 rows: at most two rows per slot)
     const size_t layout_scratch = (((size_t)2 * R->slot_cap + 64) / 32 * 2 + 2) * sizeof(int);
     const bool dense = compact && R->slot_row && R->row_start && (size_t)lds_msg_floats * sizeof(float) >= layout_scratch;
@@ -2347,8 +2282,7 @@ static void bp_launch(const upk_launch_t* L, const upk_rotamer_t* R, int want_en
         upk_rotamer_t Rl = *R;
         // the dense layout as a launch of its own in front of the solve (R->bp_layout allocated by the host node: from 512 systems on),
         // when its scratch fits a quarter of a CU's LDS; else inside the solve
-        static int hand_back = -1;      // UPSIDE_HIP_BP_LAYOUT=2 (tests): no scratch at all, so that every system is handed back to its solve
-        if (hand_back < 0) { const char* e = getenv("UPSIDE_HIP_BP_LAYOUT"); hand_back = (e && atoi(e) == 2) ? 1 : 0; }
+        static const bool hand_back = env_int("UPSIDE_HIP_BP_LAYOUT", 0) == 2;      // (tests): no scratch at all, so that every system is handed back to its solve
         const int scratch_words = hand_back ? 1 : (int)((((size_t)2 * (R->slot_cap / 4 + 32) + 64) / 32) * 2 + 2);
         const size_t layout_lds = ((size_t)R->n_node * (BP_NODE_STRIDE + 1) + 64 + N_CLASS + 16) * sizeof(float) + (size_t)scratch_words * sizeof(int) + 64;
         if (R->bp_layout && layout_lds <= 40 * 1024)
@@ -2363,8 +2297,7 @@ extern "C" int upk_rotamer_bp(const upk_launch_t* L, const upk_rotamer_t* R, int
     const size_t lds_base = ((size_t)R->n_node * (BP_NODE_ARRAYS * BP_NODE_STRIDE + 2) + 64 + 8) * sizeof(float);
     if (lds_base > 155 * 1024) return 9004;
     // LDS left over holds the messages to the 3-state nodes (at most all of the inbox: 16 floats per slot)
-    static int lds_msg_kb = -1;   // UPSIDE_HIP_BP_LDS_MSG_KB (experiments): 0 keeps every message in global memory
-    if (lds_msg_kb < 0) { const char* e = getenv("UPSIDE_HIP_BP_LDS_MSG_KB"); lds_msg_kb = e ? atoi(e) : 160; }
+    static const int lds_msg_kb = env_int("UPSIDE_HIP_BP_LDS_MSG_KB", 160);   // (experiments): 0 keeps every message in global memory
     size_t msg_bytes = (size_t)lds_msg_kb * 1024;
     // LDS of the one-workgroup solve, beliefs + inbox: all 160 KB of the CU (the kernel has no static LDS)
     if (lds_base + msg_bytes > (size_t)160 * 1024) msg_bytes = lds_base >= (size_t)160 * 1024 ? 0 : (size_t)160 * 1024 - lds_base;
@@ -2380,7 +2313,6 @@ extern "C" int upk_rotamer_bp(const upk_launch_t* L, const upk_rotamer_t* R, int
         if (chunk >= 8) chunk &= ~7;
         if (chunk >= 1) {
             const int p_cap = upk_rotamer_bp_cluster_capacity(R);
-            const size_t split_lds = ((size_t)R->n_node * 14 + 64) * sizeof(float);
             for (int s0 = 0; s0 < L->n_system; s0 += chunk) {
                 const int n = L->n_system - s0 < chunk ? L->n_system - s0 : chunk;
                 // grid.x rounded up to a multiple of 8 (the surplus workgroups leave at once): workgroup b is dispatched to XCD b mod 8, so the C
@@ -2390,8 +2322,7 @@ extern "C" int upk_rotamer_bp(const upk_launch_t* L, const upk_rotamer_t* R, int
                 // fence, which is valid only while the cluster shares an L2: 180 us, 2 235 -> 2 287 steps/s -- 0.9 us per barrier; the rest of a
                 // 10 us sweep is the counter round trips and the phases' own dependent loads.)
                 const int gx = (n + 7) & ~7;
-                if (R->bp_resident) hipLaunchKernelGGL(k_rotamer_bp_cluster<true>, dim3(gx, C), dim3(BPC_BLOCK), 156 * 1024, ST(L), *R, want_energy, C, s0, n, p_cap);
-                else hipLaunchKernelGGL(k_rotamer_bp_cluster<false>, dim3(gx, C), dim3(BPC_BLOCK), split_lds, ST(L), *R, want_energy, C, s0, n, p_cap);
+                hipLaunchKernelGGL(k_rotamer_bp_cluster, dim3(gx, C), dim3(BPC_BLOCK), 156 * 1024, ST(L), *R, want_energy, C, s0, n, p_cap);
             }
             bp_launch(L, R, want_energy, 1, lds_base, 0);   // rare path: no LDS inbox, so that the (normally empty) launch does not wait for a whole CU's LDS
             return launch_status();

@@ -243,11 +243,10 @@ int upside_main_impl(int argc, const char* const* argv, int verbose) {
     // block of the configuration files on device LOCAL_RANK and replica exchange runs over RCCL inside the library
     // (upside_hip_comm_*, comm_rccl.cpp).  UPSIDE_HIP_COMM=1 takes the same path with a single process (tests).
     auto env_int_of = [](const char* a, const char* b, int dflt) {
-        const char* v = getenv(a); if (!v) v = getenv(b);
-        return v ? atoi(v) : dflt; };
+        return env_int(a, env_int(b, dflt)); };
     const int world = max(1, env_int_of("UPSIDE_HIP_WORLD", "WORLD_SIZE", 1));
     const int rank = env_int_of("UPSIDE_HIP_RANK", "RANK", 0), local_rank = env_int_of("UPSIDE_HIP_LOCAL_RANK", "LOCAL_RANK", 0);
-    const bool use_comm = world > 1 || (getenv("UPSIDE_HIP_COMM") && atoi(getenv("UPSIDE_HIP_COMM")));
+    const bool use_comm = world > 1 || env_int("UPSIDE_HIP_COMM", 0);
     if (rank < 0 || rank >= world) throw string("invalid rank");
     const int n_total = (int)files.size();
     if (n_total % world) throw to_string(n_total) + " systems do not divide over " + to_string(world) + " processes";
@@ -409,11 +408,11 @@ int upside_main_impl(int argc, const char* const* argv, int verbose) {
         // publishes with an exclusive create + rename and removes the file once every rank has joined.
         string launch;
         bool job_wide = false;      // the nonce is made of variables every rank of the job shares, on whatever node it runs
-        if (const char* x = getenv("UPSIDE_HIP_COMM_NONCE")) { launch = x; job_wide = true; }
+        if (const char* x = env_str("UPSIDE_HIP_COMM_NONCE")) { launch = x; job_wide = true; }
         else {
             for (const char* v : {"MASTER_ADDR", "MASTER_PORT", "TORCHELASTIC_RUN_ID", "TORCHELASTIC_RESTART_COUNT"}) {
-                if (getenv(v)) job_wide = true;
-                launch += string(getenv(v) ? getenv(v) : "") + "|";
+                if (env_set(v)) job_wide = true;
+                launch += string(env_set(v) ? env_str(v) : "") + "|";
             }
             launch += to_string(world) + "|";
             // the launcher's pid is the same for the ranks of ONE node only: it stands in for the job-wide variables where a launcher
@@ -423,10 +422,10 @@ int upside_main_impl(int argc, const char* const* argv, int verbose) {
         unsigned long long nonce = 1469598103934665603ull;               // FNV-1a
         for (unsigned char ch : launch) { nonce ^= ch; nonce *= 1099511628211ull; }
         string path;
-        if (const char* f = getenv("UPSIDE_HIP_COMM_FILE")) path = f;
+        if (const char* f = env_str("UPSIDE_HIP_COMM_FILE")) path = f;
         else {
-            path = string("/tmp/upside_hip_comm_") + (getenv("MASTER_PORT") ? getenv("MASTER_PORT") : "0") + "_" + to_string((long)getppid());
-            for (const char* v : {"TORCHELASTIC_RUN_ID", "TORCHELASTIC_RESTART_COUNT"}) if (const char* x = getenv(v)) path += string("_") + x;
+            path = string("/tmp/upside_hip_comm_") + (env_set("MASTER_PORT") ? env_str("MASTER_PORT") : "0") + "_" + to_string((long)getppid());
+            for (const char* v : {"TORCHELASTIC_RUN_ID", "TORCHELASTIC_RESTART_COUNT"}) if (const char* x = env_str(v)) path += string("_") + x;
         }
         // Two attempts started one after the other from the same shell share nonce and file name: the record also carries the wall-clock
         // second it was written, and a rank takes only records written after (its own start - UPSIDE_HIP_COMM_SKEW_S, default 20 s:
@@ -435,8 +434,8 @@ int upside_main_impl(int argc, const char* const* argv, int verbose) {
         memset(&rec, 0, sizeof(rec));
         // (default = the wait window below: a rank that starts late -- a staggered multi-node launch -- or whose node clock lags still accepts
         //  rank 0's record for as long as rank 0 waits for it)
-        const int wait_s = getenv("UPSIDE_HIP_COMM_WAIT_S") ? max(1, atoi(getenv("UPSIDE_HIP_COMM_WAIT_S"))) : 120;
-        const long long skew_s = getenv("UPSIDE_HIP_COMM_SKEW_S") ? max(0, atoi(getenv("UPSIDE_HIP_COMM_SKEW_S"))) : wait_s;
+        const int wait_s = env_set("UPSIDE_HIP_COMM_WAIT_S") ? max(1, env_int("UPSIDE_HIP_COMM_WAIT_S", 0)) : 120;
+        const long long skew_s = env_set("UPSIDE_HIP_COMM_SKEW_S") ? max(0, env_int("UPSIDE_HIP_COMM_SKEW_S", 0)) : wait_s;
         if (rank == 0) {
             remove(path.c_str());                                   // a stale record of an earlier attempt under this name
             if (upside_hip_comm_get_unique_id(rec.id)) throw string(upside_hip_last_error());

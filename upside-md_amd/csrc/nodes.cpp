@@ -25,9 +25,6 @@ template <class T> struct Builtin : T {
 
 vector<int> iota_targets(int n) { vector<int> v(n); for (int i = 0; i < n; ++i) v[i] = i; return v; }
 
-int env_int(const char* name, int dflt) { const char* e = getenv(name); return e ? atoi(e) : dflt; }
-float env_float(const char* name, float dflt) { const char* e = getenv(name); return e ? (float)atof(e) : dflt; }
-
 void require_injective(const vector<int>& loc, int n_target, const char* what) {
     vector<char> seen(n_target, 0);
     for (int x : loc) {
@@ -1466,7 +1463,7 @@ struct RotamerSidechain : public PotentialNode, BatchedParamDeriv {
         }
         R.bp_trace = nullptr;
         prepare_deps.push_back(ig.node1);   // the list upkeep reads the bead positions only, not the 1-body energies
-        if (getenv("UPSIDE_HIP_BP_TRACE")) { bp_trace.alloc((size_t)ctx->n_system * 32); R.bp_trace = bp_trace.p; }
+        if (env_set("UPSIDE_HIP_BP_TRACE")) { bp_trace.alloc((size_t)ctx->n_system * 32); R.bp_trace = bp_trace.p; }
     }
     bool has_prepare() const override { return true; }
     void prepare() override {   // pair list + residue-pair slots of the systems that moved (depends on the bead positions only)
@@ -1485,7 +1482,6 @@ struct RotamerSidechain : public PotentialNode, BatchedParamDeriv {
         bp_C_chosen = true;
         ctx->flush();
         const int want = env_int("UPSIDE_HIP_BP_CLUSTER", -1);   // 1 disables, >1 forces
-        R.bp_resident = 1;
         if (want == 1) { R.bp_C = 1; set_matrix_form(); return; }
         hip_check(hipStreamSynchronize(ctx->stream), "sync");
         auto cs = class_start.download();
@@ -1500,16 +1496,15 @@ struct RotamerSidechain : public PotentialNode, BatchedParamDeriv {
         C = max(C, (int)((widest * 115 / 100 + lanes - 1) / lanes));   // one slot per class per lane
         if (want > 1) C = want;
         if (C > 16 || n_node - R.n_node1 < C) C = 1;             // too large for a co-resident cluster: one-workgroup solve
-        R.bp_resident = 1;
         // The cluster solve trades HBM/L2 traffic for two device-scope barriers per sweep.  Re-measured after the
         // one-workgroup kernel got its batched loads and the short list margin (BP ms, cluster vs one workgroup):
-        //   300 residues / 10 A (C = 8):  1 system 0.19 vs 0.31, 8: 0.23 vs 0.35, 32: 0.35 vs 0.43, 48 (two launches or the
-        //                                 split form): 0.63 vs 0.47, 64: 0.56 vs 0.48
+        //   300 residues / 10 A (C = 8):  1 system 0.19 vs 0.31, 8: 0.23 vs 0.35, 32: 0.35 vs 0.43, 48 (two launches):
+        //                                 0.63 vs 0.47, 64: 0.56 vs 0.48
         //   300 residues / 7 A, 150 residues / 10 A (C = 3..4): 0.22 vs 0.19 at 1 system, 0.31 vs 0.24 at 32
         //   56 and 20 residues (C = 1): the one-workgroup solve by construction
-        // so the resident cluster is used when the pair matrices need many workgroups (C >= 6) and the batch fits one
-        // launch (CUs / C systems) or a quarter more; everything else takes the one-workgroup solve.  The split form
-        // (cluster over global-memory matrices) no longer wins anywhere; UPSIDE_HIP_BP_SPLIT keeps it testable.
+        // so the cluster is used when the pair matrices need many workgroups (C >= 6) and the batch fits 4/5 of one
+        // launch (CUs / C systems); everything else takes the one-workgroup solve.  (A second cluster form that kept the
+        // matrices in global memory won nowhere after these measurements and is gone: `git log` has it.)
         const int n_cu = upk_device_cu_count();
         int per_launch = C > 1 ? n_cu / C : 0;
         if (per_launch >= 8) per_launch &= ~7;
@@ -1517,7 +1512,6 @@ struct RotamerSidechain : public PotentialNode, BatchedParamDeriv {
         //  0.61 vs 0.39 -- the cluster up to 4/5 of one launch)
         const int resident_limit = C >= 6 ? per_launch * 4 / 5 : 0;
         if (want <= 1 && ctx->n_system > resident_limit) C = 1;
-        if (env_int("UPSIDE_HIP_BP_SPLIT", 0) > 1) { C = env_int("UPSIDE_HIP_BP_SPLIT", 0); R.bp_resident = 0; }   // experiments / tests
         R.bp_C = C < 1 ? 1 : C;
         R.bp_test_abort = env_int("UPSIDE_HIP_BP_CLUSTER_TEST_ABORT", 0);
         set_matrix_form();
@@ -1875,7 +1869,7 @@ double engine_bp_bytes(DerivEngine& e) {
                 }
                 total += per_sweep * (it[s] + 1);
             }
-            if (getenv("UPSIDE_HIP_BP_STATS")) {   // diagnostics: slot occupancy of the last launch
+            if (env_set("UPSIDE_HIP_BP_STATS")) {   // diagnostics: slot occupancy of the last launch
                 long n_slot[6] = {0}, n_act[6] = {0}, sweeps = 0;
                 for (int s = 0; s < S; ++s) {
                     sweeps += it[s];

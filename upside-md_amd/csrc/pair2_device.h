@@ -310,18 +310,9 @@ __device__ __forceinline__ void group2_batch_loop(Op& op, int n_rows, const unsi
     }
 }
 
-// launch geometry as pair_geometry, for 16-row batches
-static inline void pair2_geometry(int n_system, int n_rows, int& wgs_per_system, int& threads) {
-    static int target = 0;
-    if (!target) { const char* e = getenv("UPSIDE_HIP_IG_WGS"); target = e ? atoi(e) : 256; if (target < 1) target = 256; }
-    int bps = (target + n_system - 1) / n_system;
-    const int max_bps = (n_rows + 255) / 256;                    // one 16-row batch per wavefront of a 1024-lane workgroup = 256 rows
-    if (bps > max_bps) bps = max_bps;
-    if (bps < 1) bps = 1;
-    const int rows_per_wg = (n_rows + bps - 1) / bps;
-    int t = ((rows_per_wg * P2_LANES + 63) / 64) * 64;
-    threads = t < 256 ? 256 : (t > 1024 ? 1024 : t);
-    wgs_per_system = bps;
+static inline bool pair2_enabled() {   // UPSIDE_HIP_PAIR2=0: the scalar passes (one partner per lane) -- A/B and tests
+    static const bool on = env_int("UPSIDE_HIP_PAIR2", 1) != 0;
+    return on;
 }
 
 }  // namespace up
