@@ -254,6 +254,11 @@ int upside_hip_cv_compute(DerivEngine* engine, float* out /* host (n_system, n_c
 int upside_hip_cv_record(DerivEngine* engine, int every_n_round, int capacity);
 int upside_hip_cv_read(DerivEngine* engine, int first, int n, float* out /* (n, n_system, n_cv) */, long long* n_stored,
                        long long* n_attempted, int reset);
+/* The CV values a cv_restraint node saw in the last force pass: out is host (n_system, n_cv of the
+ * node).  They are the bits upside_hip_cv_compute gives for the same definition at the same positions.  System 0's row is also
+ * get_value_by_name(node, "cv_value").  Returns the node's n_cv, or -1 on error (the node is no cv_restraint); out may be NULL to
+ * ask for n_cv alone. */
+int upside_hip_cv_restraint_values(DerivEngine* engine, const char* node_name, float* out);
 
 /* Per-kernel timing hooks used by bench.py.  With profiling enabled every interaction-graph / BP kernel
  * launch is bracketed by HIP events on the engine's stream.  upside_hip_profile_dump writes one text line per

@@ -518,6 +518,17 @@ int upk_cv_compute(const upk_launch_t* L, upk_coord_t pos, const upk_cv_t* C, fl
  * entries), so the launch replays unchanged from a captured graph. */
 typedef struct { unsigned long long* rounds; int* n_attempt; int every, capacity; float* samples; } upk_cv_record_t;
 int upk_cv_record(const upk_launch_t* L, upk_coord_t pos, const upk_cv_t* C, const upk_cv_record_t* R);
+/* cv_restraint (node of the force pass): E[s] = sum_c 1/2 k u^2 with u = max(0, |v_c - center| - flat_width) over the CVs of C, v_c
+ * the very bits upk_cv_compute reports.  par + s * par_stride is system s's row [center | spring_const | flat_width] (3 n_cv floats;
+ * stride 0: one row for all -- the cv_restraint node, the only caller, always passes a full table with stride 3 n_cv, so the
+ * shared row is not exercised).  Writes dE/dx of every list entry to contrib[s][entry][3] (entry = index into C->atoms: a scatter
+ * source of pos with one slot per entry; every slot is written on every launch), the CV values to values[s][n_cv] and, unless
+ * pot_terms is NULL, the n_cv energy terms to pot_terms[s][n_cv].  Same kernel shape as upk_cv_compute: one workgroup per system,
+ * fp64 sums in one order, no atomics.  An rg, rmsd or distance below UPK_CV_RESTRAINT_VMIN (Angstrom) and a contact pair at r = 0
+ * contribute zero force (the energy is still counted). */
+#define UPK_CV_RESTRAINT_VMIN 1e-6
+int upk_cv_restraint(const upk_launch_t* L, upk_coord_t pos, const upk_cv_t* C, const float* par, long par_stride, float* contrib,
+                     long contrib_stride, float* values, float* pot_terms);
 
 #ifdef __cplusplus
 }

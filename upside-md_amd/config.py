@@ -800,6 +800,102 @@ def add_collective_variables(path, specs):
     return p
 
 
+CV_RESTRAINT_VALUES = ('center', 'spring_const', 'flat_width')     # the datasets that may differ between the windows of one engine
+CV_MAX_LIST = 1 << 24                                              # UPK_CV_MAX_LIST of include/upside_hip_kernels.h
+
+
+def _restraint_values(center, spring_const, flat_width, n_cv, who='cv_restraint'):
+    out = {}
+    for nm, v in zip(CV_RESTRAINT_VALUES, (center, spring_const, flat_width)):
+        v = np.asarray(v, 'f8').reshape(-1)
+        if len(v) != n_cv:
+            raise ValueError('%s: %s holds %d entries, the node has %d CVs' % (who, nm, len(v), n_cv))
+        if not np.isfinite(v).all():
+            raise ValueError('%s: %s is not finite' % (who, nm))
+        if nm != 'center' and (v < 0).any():
+            raise ValueError('%s: %s must not be negative' % (who, nm))
+        out[nm] = v.astype('f4')
+    return out
+
+
+def add_cv_restraint(path, specs, name='cv_restraint'):
+    """add an umbrella bias on collective variables (node type cv_restraint, argument pos) to an existing configuration:
+         E = sum_c 1/2 spring_const_c u_c^2,   u_c = max(0, |v_c - center_c| - flat_width_c)
+    specs: the dicts of pack_collective_variables, each with the further keys 'center' (required), 'spring_const' (required) and
+    'flat_width' (default 0: the plain harmonic umbrella).  name must start with 'cv_restraint'; several such nodes may coexist
+    ('cv_restraint_q', 'cv_restraint_rg').  center, spring_const and flat_width may differ between the files of one engine
+    (write_umbrella_windows); everything else of the node must agree.  Returns the packed arrays."""
+    if not str(name).startswith('cv_restraint'):
+        raise ValueError("add_cv_restraint: the node name must start with 'cv_restraint', got %r" % (name,))
+    specs = list(specs)
+    if not specs:
+        raise ValueError('add_cv_restraint: no collective variables')
+    bare, val = [], dict((k, []) for k in CV_RESTRAINT_VALUES)
+    for c, sp in enumerate(specs):
+        if not isinstance(sp, dict):
+            raise ValueError("collective variable %d: a dict with a 'kind' is expected" % c)
+        for k in ('center', 'spring_const'):
+            if k not in sp:
+                raise ValueError('collective variable %d: %r is missing' % (c, k))
+        for k in CV_RESTRAINT_VALUES:
+            v = sp.get(k, 0.)
+            if np.ndim(v) != 0:
+                raise ValueError('collective variable %d: %s must be one number' % (c, k))
+            val[k].append(float(v))
+        bare.append(dict((k, v) for k, v in sp.items() if k not in CV_RESTRAINT_VALUES))
+    with h5lite.open_file(path) as f:      # everything is checked before the file is opened for writing
+        n_atom = f.group('input').shape('pos')[0]
+    p = pack_collective_variables(bare, n_atom)
+    n_list = np.diff(p['atom_start'])
+    if len(n_list) and n_list.max() > CV_MAX_LIST:
+        raise ValueError('collective variable %d: %d list entries exceed the limit of %d' % (int(n_list.argmax()), int(n_list.max()), CV_MAX_LIST))
+    p.update(_restraint_values(val['center'], val['spring_const'], val['flat_width'], len(specs), name))
+    with h5lite.open_file(path, 'r+') as f:
+        inp = f.group('input')
+        pot = inp.group('potential')
+        if name in pot:
+            pot.delete(name)
+        g = pot.create_group(name); _args(g, ['pos'])
+        for k in ('kind', 'atom_start', 'atoms', 'ref_pos', 'contact_r0', 'contact_beta', 'contact_lambda', 'names') + CV_RESTRAINT_VALUES:
+            g.write(k, p[k])
+    return p
+
+
+def write_umbrella_windows(base_path, out_paths, node_name, centers, spring_consts=None, flat_widths=None):
+    """one copy of the configuration base_path per window, differing from it in the values of its cv_restraint node `node_name`
+    only: centers (n_window, n_cv) (or (n_window,) for a node of one CV); spring_consts and flat_widths likewise, None keeps the
+    base file's.  The files group into one engine (Ensemble.from_files, upside_hip with several configurations)."""
+    import shutil
+    out_paths = [str(p) for p in out_paths]
+    with h5lite.open_file(base_path) as f:
+        pot = f.group('input').group('potential')
+        if node_name not in pot:
+            raise ValueError('write_umbrella_windows: %s has no node %r' % (base_path, node_name))
+        g = pot.group(node_name)
+        base = dict((k, g.read(k, 'f4')) for k in CV_RESTRAINT_VALUES)
+    n_cv = len(base['center'])
+    rows = {}
+    for nm, v in zip(CV_RESTRAINT_VALUES, (centers, spring_consts, flat_widths)):
+        if v is None:
+            rows[nm] = np.broadcast_to(base[nm], (len(out_paths), n_cv))
+            continue
+        v = np.asarray(v, 'f8')
+        if v.ndim == 1 and n_cv == 1:
+            v = v[:, None]
+        if v.shape != (len(out_paths), n_cv):
+            raise ValueError('write_umbrella_windows: %s must be (%d windows, %d CVs), got %r' % (nm, len(out_paths), n_cv, v.shape))
+        rows[nm] = v
+    for i, p in enumerate(out_paths):
+        val = _restraint_values(rows['center'][i], rows['spring_const'][i], rows['flat_width'][i], n_cv, 'window %d' % i)
+        shutil.copyfile(str(base_path), p)
+        with h5lite.open_file(p, 'r+') as f:
+            g = f.group('input').group('potential').group(node_name)
+            for k in CV_RESTRAINT_VALUES:
+                g.delete(k)
+                g.write(k, val[k])
+    return out_paths
+
+
 def default_collective_variables(pos, contact_cutoff=8.0, min_seq_sep=4, beta=5., lam=1.8):
     """the standard folding observables over the CA atoms (atom 3 r + 1) against the structure `pos` (n_atom,3): Rg, RMSD and
     fraction of native contacts Q to it, end-to-end distance (what `make_config.py --collective-variables` writes)"""

@@ -1,0 +1,225 @@
+// Device code shared by the kernels that evaluate collective variables (kernels_cv.hip: k_collective_variables, k_cv_restraint).
+// Both compute a CV by cv_evaluate below, so a restraint acts on exactly the number the observable reports: the same sums in the
+// same order, bit for bit.
+//   - every sum is accumulated in fp64 and has ONE order: lane t adds elements t, t + CV_BLOCK, ... ascending; the 64 lanes of a
+//     wavefront combine in a fixed butterfly of DPP / permlane exchanges (the two 32-bit halves of a double travel side by side);
+//     the four wavefront totals meet in LDS and every lane adds them 0, 1, 2, 3.  No atomics.
+//   - the largest eigenvalue of Horn's 4x4 quaternion matrix comes from cyclic Jacobi rotations in fp64 (one lane; 4x4); where the
+//     gradient is wanted, its eigenvector is read off the cofactors of K - lambda I (the eigenvalue itself is untouched by that).
+#pragma once
+#include "device_math.h"
+#include "../../include/upside_hip_kernels.h"
+
+#define CV_BLOCK 256
+#define CV_WAVES (CV_BLOCK / 64)
+#define CV_MAX_SUMS 10       // rmsd: Ga + the 3x3 correlation matrix
+
+namespace up {
+
+template <int CTRL>
+__device__ __forceinline__ double dpp_mov64(double v) {
+    const int lo = __builtin_amdgcn_update_dpp(0, __double2loint(v), CTRL, 0xf, 0xf, false);
+    const int hi = __builtin_amdgcn_update_dpp(0, __double2hiint(v), CTRL, 0xf, 0xf, false);
+    return __hiloint2double(hi, lo);
+}
+// every lane ends with the sum of all 64, by the butterfly of device_math.h's wave_reduce (each step adds a lane and its partner:
+// commutative, so all lanes hold the same bits)
+__device__ __forceinline__ double wave_sum64(double v) {
+    v += dpp_mov64<UP_DPP_XOR1>(v);
+    v += dpp_mov64<UP_DPP_XOR2>(v);
+    v += dpp_mov64<UP_DPP_HALF_MIRROR>(v);
+    v += dpp_mov64<UP_DPP_ROW_MIRROR>(v);
+    {   const unsigned lo = (unsigned)__double2loint(v), hi = (unsigned)__double2hiint(v);
+        const auto rl = __builtin_amdgcn_permlane16_swap(lo, lo, false, false);
+        const auto rh = __builtin_amdgcn_permlane16_swap(hi, hi, false, false);
+        v = __hiloint2double((int)rh[0], (int)rl[0]) + __hiloint2double((int)rh[1], (int)rl[1]); }
+    {   const unsigned lo = (unsigned)__double2loint(v), hi = (unsigned)__double2hiint(v);
+        const auto rl = __builtin_amdgcn_permlane32_swap(lo, lo, false, false);
+        const auto rh = __builtin_amdgcn_permlane32_swap(hi, hi, false, false);
+        v = __hiloint2double((int)rh[0], (int)rl[0]) + __hiloint2double((int)rh[1], (int)rl[1]); }
+    return v;
+}
+// v[0..K) summed over the workgroup; every lane receives the totals.  Called by all lanes.
+template <int K>
+__device__ __forceinline__ void block_sum(double (&v)[K], double (*part)[CV_MAX_SUMS]) {
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    __syncthreads();          // (the previous totals have been read)
+#pragma unroll
+    for (int k = 0; k < K; ++k) {
+        const double w = wave_sum64(v[k]);
+        if (lane == 0) part[wave][k] = w;
+    }
+    __syncthreads();
+#pragma unroll
+    for (int k = 0; k < K; ++k) {
+        double t = part[0][k];
+#pragma unroll
+        for (int w = 1; w < CV_WAVES; ++w) t += part[w][k];
+        v[k] = t;
+    }
+}
+
+// largest eigenvalue of the symmetric 4x4 matrix a (upper triangle used): cyclic Jacobi, eigenvalues only
+__device__ inline double jacobi4_max_eigenvalue(double (&a)[4][4]) {
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+        for (int j = 0; j < i; ++j) a[i][j] = a[j][i];
+    double scale = 0.;
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) scale += a[i][j] * a[i][j];
+    for (int sweep = 0; sweep < 50; ++sweep) {
+        const double off = a[0][1] * a[0][1] + a[0][2] * a[0][2] + a[0][3] * a[0][3] + a[1][2] * a[1][2] + a[1][3] * a[1][3] + a[2][3] * a[2][3];
+        if (!(off > 1e-40 * scale)) break;       // (also leaves on a NaN)
+#pragma unroll
+        for (int p = 0; p < 3; ++p)
+#pragma unroll
+            for (int q = p + 1; q < 4; ++q) {
+                const double apq = a[p][q];
+                if (apq == 0.) continue;
+                const double theta = (a[q][q] - a[p][p]) / (2. * apq);
+                const double t = (theta >= 0. ? 1. : -1.) / (fabs(theta) + sqrt(theta * theta + 1.));
+                const double c = 1. / sqrt(t * t + 1.), s = t * c;
+#pragma unroll
+                for (int k = 0; k < 4; ++k) {      // A <- A J
+                    const double akp = a[k][p], akq = a[k][q];
+                    a[k][p] = c * akp - s * akq; a[k][q] = s * akp + c * akq;
+                }
+#pragma unroll
+                for (int k = 0; k < 4; ++k) {      // A <- J^T A
+                    const double apk = a[p][k], aqk = a[q][k];
+                    a[p][k] = c * apk - s * aqk; a[q][k] = s * apk + c * aqk;
+                }
+            }
+    }
+    return fmax(fmax(a[0][0], a[1][1]), fmax(a[2][2], a[3][3]));
+}
+
+// unit eigenvector of the symmetric 4x4 matrix k (full) at its eigenvalue lam: K - lam I is singular, so every row of its adjugate
+// is a multiple of the eigenvector; the row of largest norm is taken (its relative error is eps x |K| / gap to the next eigenvalue,
+// the conditioning of the eigenvector itself).  A degenerate eigenvalue (adjugate 0) gives the identity quaternion.
+__device__ inline void cofactor_eigenvector4(const double (&k)[4][4], double lam, double (&q)[4]) {
+    double m[4][4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) m[i][j] = k[i][j] - (i == j ? lam : 0.);
+    double best = 0.;
+    q[0] = 1.; q[1] = 0.; q[2] = 0.; q[3] = 0.;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        double row[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {      // cofactor (i, j): the matrix without row i and column j
+            const int r0 = 0 + (0 >= i), r1 = 1 + (1 >= i), r2 = 2 + (2 >= i), c0 = 0 + (0 >= j), c1 = 1 + (1 >= j), c2 = 2 + (2 >= j);
+            const double d = m[r0][c0] * (m[r1][c1] * m[r2][c2] - m[r1][c2] * m[r2][c1])
+                           - m[r0][c1] * (m[r1][c0] * m[r2][c2] - m[r1][c2] * m[r2][c0])
+                           + m[r0][c2] * (m[r1][c0] * m[r2][c1] - m[r1][c1] * m[r2][c0]);
+            row[j] = ((i + j) & 1) ? -d : d;
+        }
+        const double n2 = row[0] * row[0] + row[1] * row[1] + row[2] * row[2] + row[3] * row[3];
+        if (n2 > best) { best = n2; q[0] = row[0]; q[1] = row[1]; q[2] = row[2]; q[3] = row[3]; }
+    }
+    if (best > 0.) { const double inv = 1. / sqrt(best); q[0] *= inv; q[1] *= inv; q[2] *= inv; q[3] *= inv; }
+}
+
+__device__ __forceinline__ void ld3d(const float* __restrict__ x, int atom, int stride, double& px, double& py, double& pz) {
+    const float* p = x + (size_t)atom * stride;
+    px = (double)p[0]; py = (double)p[1]; pz = (double)p[2];
+}
+
+// Value of CV c of the system whose positions start at x.  Called by all lanes of the workgroup; the value is valid on lane 0
+// (on every lane for rg and contacts).  cen receives the selection's centroid (rg, rmsd; every lane).  WANT_ROT: on lane 0 an
+// rmsd also leaves in rot the optimal proper rotation R taking the centred reference onto the centred selection
+// (row-major: a_i ~ sum_j rot[3 i + j] b_j).
+template <bool WANT_ROT>
+__device__ __forceinline__ double cv_evaluate(const float* __restrict__ x, int stride, const upk_cv_t& C, int c, double (*part)[CV_MAX_SUMS],
+                                              double (&cen)[3], double (&rot)[9]) {
+    const int tid = threadIdx.x;
+    const int kind = C.kind[c], a0 = C.atom_start[c], n = C.atom_start[c + 1] - a0;
+    const int* __restrict__ atoms = C.atoms + a0;
+    double value = 0.;
+    if (kind == UPK_CV_RG || kind == UPK_CV_RMSD) {
+        cen[0] = 0.; cen[1] = 0.; cen[2] = 0.;
+        for (int i = tid; i < n; i += CV_BLOCK) { double px, py, pz; ld3d(x, atoms[i], stride, px, py, pz); cen[0] += px; cen[1] += py; cen[2] += pz; }
+        block_sum<3>(cen, part);
+        const double inv_n = 1. / (double)n;
+        cen[0] *= inv_n; cen[1] *= inv_n; cen[2] *= inv_n;
+        if (kind == UPK_CV_RG) {
+            double g[1] = {0.};
+            for (int i = tid; i < n; i += CV_BLOCK) {
+                double px, py, pz; ld3d(x, atoms[i], stride, px, py, pz);
+                px -= cen[0]; py -= cen[1]; pz -= cen[2];
+                g[0] += px * px + py * py + pz * pz;
+            }
+            block_sum<1>(g, part);
+            value = sqrt(g[0] * inv_n);
+        } else {
+            const double* __restrict__ ref = C.ref + (size_t)C.aux_start[c] * 3;      // centred on the host
+            double m[10] = {0., 0., 0., 0., 0., 0., 0., 0., 0., 0.};       // Ga, then S[i][j] = sum a_i b_j
+            for (int i = tid; i < n; i += CV_BLOCK) {
+                double a[3]; ld3d(x, atoms[i], stride, a[0], a[1], a[2]);
+                a[0] -= cen[0]; a[1] -= cen[1]; a[2] -= cen[2];
+                const double b[3] = {ref[3 * i], ref[3 * i + 1], ref[3 * i + 2]};
+                m[0] += a[0] * a[0] + a[1] * a[1] + a[2] * a[2];
+#pragma unroll
+                for (int u = 0; u < 3; ++u)
+#pragma unroll
+                    for (int v = 0; v < 3; ++v) m[1 + 3 * u + v] += a[u] * b[v];
+            }
+            block_sum<10>(m, part);
+            if (tid == 0) {       // Horn 1987: the largest eigenvalue of the quaternion matrix is the best proper rotation's sum a . R b
+                const double Sxx = m[1], Sxy = m[2], Sxz = m[3], Syx = m[4], Syy = m[5], Syz = m[6], Szx = m[7], Szy = m[8], Szz = m[9];
+                double K[4][4];
+                K[0][0] = Sxx + Syy + Szz; K[0][1] = Syz - Szy; K[0][2] = Szx - Sxz; K[0][3] = Sxy - Syx;
+                K[1][1] = Sxx - Syy - Szz; K[1][2] = Sxy + Syx; K[1][3] = Szx + Sxz;
+                K[2][2] = -Sxx + Syy - Szz; K[2][3] = Syz + Szy;
+                K[3][3] = -Sxx - Syy + Szz;
+                double K0[4][4];
+                if (WANT_ROT) {
+#pragma unroll
+                    for (int i = 0; i < 4; ++i)
+#pragma unroll
+                        for (int j = i; j < 4; ++j) K0[i][j] = K0[j][i] = K[i][j];
+                }
+                const double lam = jacobi4_max_eigenvalue(K);
+                value = sqrt(fmax(0., (m[0] + C.ref_g[c] - 2. * lam) * inv_n));
+                if (WANT_ROT) {      // K is built from S[u][v] = sum a_u b_v, whose eigenvector is the quaternion of R transposed
+                    double q[4]; cofactor_eigenvector4(K0, lam, q);
+                    const double w = q[0], qx = q[1], qy = q[2], qz = q[3];
+                    rot[0] = w * w + qx * qx - qy * qy - qz * qz; rot[1] = 2. * (qx * qy + w * qz);           rot[2] = 2. * (qx * qz - w * qy);
+                    rot[3] = 2. * (qx * qy - w * qz);           rot[4] = w * w - qx * qx + qy * qy - qz * qz; rot[5] = 2. * (qy * qz + w * qx);
+                    rot[6] = 2. * (qx * qz + w * qy);           rot[7] = 2. * (qy * qz - w * qx);           rot[8] = w * w - qx * qx - qy * qy + qz * qz;
+                }
+            }
+        }
+    } else if (kind == UPK_CV_CONTACTS) {
+        const int n_pair = n / 2;
+        const float* __restrict__ r0 = C.r0 + C.aux_start[c];
+        const double beta = (double)C.beta[c], lambda = (double)C.lambda[c];
+        double q[1] = {0.};
+        for (int i = tid; i < n_pair; i += CV_BLOCK) {
+            double ax, ay, az, bx, by, bz;
+            ld3d(x, atoms[2 * i], stride, ax, ay, az); ld3d(x, atoms[2 * i + 1], stride, bx, by, bz);
+            ax -= bx; ay -= by; az -= bz;
+            const double arg = beta * (sqrt(ax * ax + ay * ay + az * az) - lambda * (double)r0[i]);
+            // 1 / (1 + exp(arg)) without an overflowing exponential: a pair 1e3 A apart contributes exactly 0
+            const double e = exp(-fabs(arg));
+            q[0] += (arg > 0. ? e : 1.) / (1. + e);
+        }
+        block_sum<1>(q, part);
+        value = q[0] / (double)n_pair;
+    } else {      // UPK_CV_DISTANCE
+        if (tid == 0) {
+            double ax, ay, az, bx, by, bz;
+            ld3d(x, atoms[0], stride, ax, ay, az); ld3d(x, atoms[1], stride, bx, by, bz);
+            ax -= bx; ay -= by; az -= bz;
+            value = sqrt(ax * ax + ay * ay + az * az);
+        }
+    }
+    return value;
+}
+
+}  // namespace up

@@ -742,16 +742,17 @@ void DerivEngine::param_deriv_accumulate(int node, const float* weights) {
 }
 
 // ---- collective variables (upside_hip_cv_define / _compute / _record / _read) -----------------------------------------------------
-void DerivEngine::cv_define(int n_cv, const int* kind, const int* atom_start, const int* atoms, const float* ref_pos, const float* contact_r0,
-                            const float* contact_beta, const float* contact_lambda) {
+CvHostDefinition cv_check_definition(int n_atom, int n_cv, const int* kind, const int* atom_start, const int* atoms, const float* ref_pos,
+                                     const float* contact_r0, const float* contact_beta, const float* contact_lambda) {
     static const char* kind_name[] = {"rg", "rmsd", "contacts", "distance"};
     if (n_cv < 0) throw string("collective variables: n_cv is negative");
     if (n_cv > UPK_CV_MAX) throw string("collective variables: ") + to_string(n_cv) + " CVs exceed the kernel's limit of " + to_string(UPK_CV_MAX) + " (UPK_CV_MAX)";
     if (n_cv && (!kind || !atom_start || !atoms)) throw string("collective variables: kind, atom_start and atoms must be given");
-    // everything is checked and built on the host before the first device array is touched: a refusal leaves the old definition in force
-    vector<int> h_kind, h_start, h_atoms, h_aux((size_t)n_cv, 0);
-    vector<double> h_ref, h_ref_g((size_t)n_cv, 0.);
-    vector<float> h_r0, h_beta((size_t)n_cv, 0.f), h_lambda((size_t)n_cv, 0.f);
+    CvHostDefinition def; def.n_cv = n_cv;
+    vector<int>&h_kind = def.kind, &h_start = def.atom_start, &h_atoms = def.atoms, &h_aux = def.aux_start;
+    vector<double>&h_ref = def.ref, &h_ref_g = def.ref_g;
+    vector<float>&h_r0 = def.r0, &h_beta = def.beta, &h_lambda = def.lambda;
+    h_aux.assign((size_t)n_cv, 0); h_ref_g.assign((size_t)n_cv, 0.); h_beta.assign((size_t)n_cv, 0.f); h_lambda.assign((size_t)n_cv, 0.f);
     if (n_cv) {
         h_kind.assign(kind, kind + n_cv); h_start.assign(atom_start, atom_start + n_cv + 1);
         if (h_start[0] != 0) throw string("collective variables: atom_start[0] must be 0");
@@ -765,7 +766,7 @@ void DerivEngine::cv_define(int n_cv, const int* kind, const int* atom_start, co
             if (n == 0) throw whok + ": empty selection";
             if (n > UPK_CV_MAX_LIST) throw whok + ": " + to_string(n) + " list entries exceed the limit of " + to_string(UPK_CV_MAX_LIST) + " (UPK_CV_MAX_LIST)";
             for (long i = h_start[c]; i < h_start[c + 1]; ++i)
-                if (atoms[i] < 0 || atoms[i] >= pos->n_atom) throw whok + ": atom " + to_string(atoms[i]) + " out of range (n_atom " + to_string(pos->n_atom) + ")";
+                if (atoms[i] < 0 || atoms[i] >= n_atom) throw whok + ": atom " + to_string(atoms[i]) + " out of range (n_atom " + to_string(n_atom) + ")";
             if (h_kind[c] == UPK_CV_RMSD) {
                 if (n < 3) throw whok + ": an rmsd selection needs at least 3 atoms";
                 if (!ref_pos) throw whok + ": ref_pos must be given";
@@ -792,15 +793,51 @@ void DerivEngine::cv_define(int n_cv, const int* kind, const int* atom_start, co
             h_ref_g[c] = g;
         }
     }
+    return def;
+}
+CvHostDefinition cv_read_definition(hid_t_compat group, int n_atom, const string& where) {
+    const hid_t g = (hid_t)group;
+    auto kind = h5u::read<int>(g, "kind", 1);
+    const size_t n_cv = kind.size();
+    auto atom_start = h5u::read<int>(g, "atom_start", 1);
+    if (atom_start.size() != n_cv + 1) throw where + ": atom_start must have n_cv + 1 entries";
+    auto atoms = h5u::read<int>(g, "atoms", 1);
+    if (atom_start.back() != (int)atoms.size() || atom_start[0] != 0) throw where + ": atom_start does not span atoms";
+    vector<hsize_t> d;
+    auto ref_pos = h5u::read<float>(g, "ref_pos", 2, &d);
+    if (d[0] && d[1] != 3) throw where + ": ref_pos must be (n, 3)";
+    auto r0 = h5u::read<float>(g, "contact_r0", 1);
+    auto beta = h5u::read<float>(g, "contact_beta", 1), lambda = h5u::read<float>(g, "contact_lambda", 1);
+    if (beta.size() != n_cv || lambda.size() != n_cv) throw where + ": contact_beta and contact_lambda must have n_cv entries";
+    // the packed arrays must be as long as the kinds say (cv_check_definition reads them by those counts)
+    size_t n_ref = 0, n_pair = 0;
+    for (size_t c = 0; c < n_cv; ++c) {
+        const long n = (long)atom_start[c + 1] - atom_start[c];
+        if (n < 0) throw where + ": atom_start must not decrease";
+        if (kind[c] == UPK_CV_RMSD) n_ref += (size_t)n; else if (kind[c] == UPK_CV_CONTACTS) n_pair += (size_t)(n / 2);
+    }
+    if (ref_pos.size() != n_ref * 3) throw where + ": ref_pos holds " + to_string(ref_pos.size() / 3) + " rows, the rmsd selections " + to_string(n_ref);
+    if (r0.size() != n_pair) throw where + ": contact_r0 holds " + to_string(r0.size()) + " entries, the contacts lists " + to_string(n_pair) + " pairs";
+    return cv_check_definition(n_atom, (int)n_cv, kind.data(), atom_start.data(), atoms.data(), ref_pos.data(), r0.data(), beta.data(), lambda.data());
+}
+void CvDeviceDefinition::upload(const CvHostDefinition& d) {
+    kind.upload(d.kind); atom_start.upload(d.atom_start); atoms.upload(d.atoms); aux_start.upload(d.aux_start);
+    ref.upload(d.ref); ref_g.upload(d.ref_g); r0.upload(d.r0); beta.upload(d.beta); lambda.upload(d.lambda);
+    C.n_cv = d.n_cv; C.kind = kind.p; C.atom_start = atom_start.p; C.atoms = atoms.p; C.aux_start = aux_start.p;
+    C.ref = ref.p; C.ref_g = ref_g.p; C.r0 = r0.p; C.beta = beta.p; C.lambda = lambda.p;
+}
+void DerivEngine::cv_define(int n_cv, const int* kind, const int* atom_start, const int* atoms, const float* ref_pos, const float* contact_r0,
+                            const float* contact_beta, const float* contact_lambda) {
+    // everything is checked and built on the host before the first device array is touched: a refusal leaves the old definition in force
+    cv_install(cv_check_definition(pos->n_atom, n_cv, kind, atom_start, atoms, ref_pos, contact_r0, contact_beta, contact_lambda));
+}
+void DerivEngine::cv_install(const CvHostDefinition& def) {
     sync();
     invalidate_graph();
     cv_record(0, 0);                       // samples of another definition have another width
     cv.names.clear();
-    cv.kind.upload(h_kind); cv.atom_start.upload(h_start); cv.atoms.upload(h_atoms); cv.aux_start.upload(h_aux);
-    cv.ref.upload(h_ref); cv.ref_g.upload(h_ref_g); cv.r0.upload(h_r0); cv.beta.upload(h_beta); cv.lambda.upload(h_lambda);
-    cv.out.alloc((size_t)ctx.n_system * n_cv);
-    cv.C.n_cv = n_cv; cv.C.kind = cv.kind.p; cv.C.atom_start = cv.atom_start.p; cv.C.atoms = cv.atoms.p; cv.C.aux_start = cv.aux_start.p;
-    cv.C.ref = cv.ref.p; cv.C.ref_g = cv.ref_g.p; cv.C.r0 = cv.r0.p; cv.C.beta = cv.beta.p; cv.C.lambda = cv.lambda.p;
+    cv.upload(def);
+    cv.out.alloc((size_t)ctx.n_system * def.n_cv);
 }
 void DerivEngine::cv_compute(float* out_host) {
     if (!cv.C.n_cv) throw string("no collective variables defined (upside_hip_cv_define / upside_hip_cv_load)");

@@ -52,6 +52,23 @@ struct PerSystemValues {
     virtual std::vector<float> get_param_system(int) const { throw std::string("this node has no per-system parameters"); }
 };
 
+// A checked definition of collective variables (the CSR arrays of upside_hip_cv_define, the rmsd references centred in double) and
+// its device copy: shared by the engine's observables (upside_hip_cv_*) and the cv_restraint nodes.
+struct CvHostDefinition {
+    int n_cv = 0;
+    std::vector<int> kind, atom_start, atoms, aux_start; std::vector<double> ref, ref_g; std::vector<float> r0, beta, lambda;
+};
+// throws a message naming the CV and what is wrong with it; touches no device memory
+CvHostDefinition cv_check_definition(int n_atom, int n_cv, const int* kind, const int* atom_start, const int* atoms, const float* ref_pos,
+                                     const float* contact_r0, const float* contact_beta, const float* contact_lambda);
+// the same from a group with the datasets of /input/collective_variables (`where` names it in messages; `names` is not read)
+CvHostDefinition cv_read_definition(hid_t_compat group, int n_atom, const std::string& where);
+struct CvDeviceDefinition {
+    upk_cv_t C{};
+    DevBuf<int> kind, atom_start, atoms, aux_start; DevBuf<double> ref, ref_g; DevBuf<float> r0, beta, lambda;
+    void upload(const CvHostDefinition& d);
+};
+
 struct DerivEngine {   // deriv_engine.h:145-237
     struct Node {
         std::string name;
@@ -150,15 +167,15 @@ struct DerivEngine {   // deriv_engine.h:145-237
     void hamiltonian_swap(int n_pair, const int* pairs, uint32_t base_seed, uint64_t round, int draw0, int* accepted);
     // collective variables of every system (upside_hip_cv_*; kernels_cv.hip).  A definition is replaced whole; recording appends one
     // (n_system, n_cv) sample per `every` completed rounds from inside md_step, the decision taken on the device (captured graphs replay it)
-    struct CollectiveVariables {
-        upk_cv_t C{}; std::vector<std::string> names;
-        DevBuf<int> kind, atom_start, atoms, aux_start; DevBuf<double> ref, ref_g; DevBuf<float> r0, beta, lambda;
+    struct CollectiveVariables : CvDeviceDefinition {
+        std::vector<std::string> names;
         DevBuf<float> out;                      // [S][n_cv] of upside_hip_cv_compute
         upk_cv_record_t R{};                    // R.every > 0: recording
         DevBuf<unsigned long long> rounds; DevBuf<int> n_attempt; DevBuf<float> samples;
     } cv;
     void cv_define(int n_cv, const int* kind, const int* atom_start, const int* atoms, const float* ref_pos, const float* contact_r0,
                    const float* contact_beta, const float* contact_lambda);      // throws, leaving the previous definition in force
+    void cv_install(const CvHostDefinition& def);      // a checked definition
     void cv_compute(float* out_host);
     void cv_record(int every_n_round, int capacity);
     void cv_read(int first, int n, float* out_host, long long* n_stored, long long* n_attempted, int reset);

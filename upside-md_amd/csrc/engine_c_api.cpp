@@ -17,6 +17,7 @@ using namespace std;
 
 int engine_pairlist(DerivEngine& e, const string& node_name, int sys, vector<pair<int, int>>& out);
 int engine_rotamer_iterations(DerivEngine& e, vector<int>& iters);
+int engine_cv_restraint_values(DerivEngine& e, const string& node_name, vector<float>* out);
 int engine_rebuild_flags(DerivEngine& e, const string& node_name, vector<int>& flags);
 int engine_igraph_stats(DerivEngine& e, const string& node_name, double* out);
 double engine_bp_bytes(DerivEngine& e);
@@ -517,30 +518,11 @@ extern "C" int upside_hip_cv_load(DerivEngine* e, const char* config_file) {
     auto input = h5u::open_group(config, "/input");
     if (!h5u::exists(input, "collective_variables")) return 0;
     auto g = h5u::open_group(input, "collective_variables");
-    auto kind = h5u::read<int>(g, "kind", 1);
-    const size_t n_cv = kind.size();
-    auto atom_start = h5u::read<int>(g, "atom_start", 1);
-    if (atom_start.size() != n_cv + 1) throw string("/input/collective_variables: atom_start must have n_cv + 1 entries");
-    auto atoms = h5u::read<int>(g, "atoms", 1);
-    if (atom_start.back() != (int)atoms.size() || atom_start[0] != 0) throw string("/input/collective_variables: atom_start does not span atoms");
-    vector<hsize_t> d;
-    auto ref_pos = h5u::read<float>(g, "ref_pos", 2, &d);
-    if (d[0] && d[1] != 3) throw string("/input/collective_variables: ref_pos must be (n, 3)");
-    auto r0 = h5u::read<float>(g, "contact_r0", 1);
-    auto beta = h5u::read<float>(g, "contact_beta", 1), lambda = h5u::read<float>(g, "contact_lambda", 1);
-    if (beta.size() != n_cv || lambda.size() != n_cv) throw string("/input/collective_variables: contact_beta and contact_lambda must have n_cv entries");
+    const CvHostDefinition def = cv_read_definition((hid_t_compat)(hid_t)g, e->pos->n_atom, "/input/collective_variables");
+    const size_t n_cv = (size_t)def.n_cv;
     auto names = read_string_dataset(g, "names");
     if (names.size() != n_cv) throw string("/input/collective_variables: names must have n_cv entries");
-    // the packed arrays must be as long as the kinds say (upside_hip_cv_define reads them by those counts)
-    size_t n_ref = 0, n_pair = 0;
-    for (size_t c = 0; c < n_cv; ++c) {
-        const long n = (long)atom_start[c + 1] - atom_start[c];
-        if (n < 0) throw string("/input/collective_variables: atom_start must not decrease");
-        if (kind[c] == UPK_CV_RMSD) n_ref += (size_t)n; else if (kind[c] == UPK_CV_CONTACTS) n_pair += (size_t)(n / 2);
-    }
-    if (ref_pos.size() != n_ref * 3) throw string("/input/collective_variables: ref_pos holds ") + to_string(ref_pos.size() / 3) + " rows, the rmsd selections " + to_string(n_ref);
-    if (r0.size() != n_pair) throw string("/input/collective_variables: contact_r0 holds ") + to_string(r0.size()) + " entries, the contacts lists " + to_string(n_pair) + " pairs";
-    e->cv_define((int)n_cv, kind.data(), atom_start.data(), atoms.data(), ref_pos.data(), r0.data(), beta.data(), lambda.data());
+    e->cv_install(def);
     e->cv.names = names;
     return (int)n_cv;
     API_CATCH(-1)
@@ -550,6 +532,16 @@ extern "C" int upside_hip_cv_compute(DerivEngine* e, float* out) { API_TRY e->cv
 extern "C" int upside_hip_cv_record(DerivEngine* e, int every_n_round, int capacity) { API_TRY e->cv_record(every_n_round, capacity); return 0; API_CATCH(1) }
 extern "C" int upside_hip_cv_read(DerivEngine* e, int first, int n, float* out, long long* n_stored, long long* n_attempted, int reset) {
     API_TRY e->cv_read(first, n, out, n_stored, n_attempted, reset); return 0; API_CATCH(1)
+}
+extern "C" int upside_hip_cv_restraint_values(DerivEngine* e, const char* node_name, float* out) {
+    API_TRY
+    if (!e || !node_name) throw string("engine or node name is NULL");
+    vector<float> v;
+    const int n_cv = engine_cv_restraint_values(*e, string(node_name), out ? &v : nullptr);
+    if (n_cv < 0) throw string("node ") + node_name + " is not a cv_restraint";
+    copy(v.begin(), v.end(), out);
+    return n_cv;
+    API_CATCH(-1)
 }
 // ---- Monte-Carlo pivot moves (monte_carlo_sampler.cpp; main.cpp:628-630) ---------------------------------
 extern "C" int upside_hip_load_mc(DerivEngine* e, const char* config_file) {

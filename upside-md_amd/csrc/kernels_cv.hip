@@ -1,5 +1,7 @@
-// gfx950 kernel of the collective variables (upside_hip_cv_*): radius of gyration, RMSD after optimal superposition, fraction of
-// native contacts and plain distances of EVERY system in one launch.
+// gfx950 kernels of the collective variables: radius of gyration, RMSD after optimal superposition, fraction of native contacts
+// and plain distances of EVERY system in one launch -- as observables (upside_hip_cv_*, k_collective_variables) and as the
+// coordinates of an umbrella bias in the force pass (node cv_restraint, k_cv_restraint at the end of this file).  The value of a
+// CV is computed by cv_device.h for both.
 //
 // One workgroup of CV_BLOCK lanes owns one system (blockIdx.x) and walks the system's CVs one after the other; a CV is a handful of
 // sums over its atom list, read through the engine's position layout ([S][n_atom][stride]).  Nothing here is large: 300 CA atoms
@@ -12,106 +14,16 @@
 //     in LDS and every lane adds them 0, 1, 2, 3.  No atomics.  A system's values are therefore bit-identical run to run, whatever
 //     the batch size, the system's place in the batch, or the way the launch was issued (eagerly or from a captured graph).
 //   - the largest eigenvalue of Horn's 4x4 quaternion matrix comes from cyclic Jacobi rotations in fp64 (one lane; 4x4).
+// (The sums, the butterfly and the eigenvalue solver are in cv_device.h.)
 // Recording (upk_cv_record) is the same kernel behind a sample decision taken on the device: each system's workgroup advances its
 // own round counter (equal entries, like the thermostat's n_invocations) and stores a row on every `every`-th round while the
 // buffer has room, so a captured MD graph replays it unchanged.
-#include "device_math.h"
-#include "../../include/upside_hip_kernels.h"
+#include "cv_device.h"
 
 using namespace up;
 
 #define ST(L) ((hipStream_t)(L)->stream)
 static inline int launch_status() { return (int)hipGetLastError(); }
-
-#define CV_BLOCK 256
-#define CV_WAVES (CV_BLOCK / 64)
-#define CV_MAX_SUMS 10       // rmsd: Ga + the 3x3 correlation matrix
-
-template <int CTRL>
-__device__ __forceinline__ double dpp_mov64(double v) {
-    const int lo = __builtin_amdgcn_update_dpp(0, __double2loint(v), CTRL, 0xf, 0xf, false);
-    const int hi = __builtin_amdgcn_update_dpp(0, __double2hiint(v), CTRL, 0xf, 0xf, false);
-    return __hiloint2double(hi, lo);
-}
-// every lane ends with the sum of all 64, by the butterfly of device_math.h's wave_reduce (each step adds a lane and its partner:
-// commutative, so all lanes hold the same bits)
-__device__ __forceinline__ double wave_sum64(double v) {
-    v += dpp_mov64<UP_DPP_XOR1>(v);
-    v += dpp_mov64<UP_DPP_XOR2>(v);
-    v += dpp_mov64<UP_DPP_HALF_MIRROR>(v);
-    v += dpp_mov64<UP_DPP_ROW_MIRROR>(v);
-    {   const unsigned lo = (unsigned)__double2loint(v), hi = (unsigned)__double2hiint(v);
-        const auto rl = __builtin_amdgcn_permlane16_swap(lo, lo, false, false);
-        const auto rh = __builtin_amdgcn_permlane16_swap(hi, hi, false, false);
-        v = __hiloint2double((int)rh[0], (int)rl[0]) + __hiloint2double((int)rh[1], (int)rl[1]); }
-    {   const unsigned lo = (unsigned)__double2loint(v), hi = (unsigned)__double2hiint(v);
-        const auto rl = __builtin_amdgcn_permlane32_swap(lo, lo, false, false);
-        const auto rh = __builtin_amdgcn_permlane32_swap(hi, hi, false, false);
-        v = __hiloint2double((int)rh[0], (int)rl[0]) + __hiloint2double((int)rh[1], (int)rl[1]); }
-    return v;
-}
-// v[0..K) summed over the workgroup; every lane receives the totals.  Called by all lanes.
-template <int K>
-__device__ __forceinline__ void block_sum(double (&v)[K], double (*part)[CV_MAX_SUMS]) {
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    __syncthreads();          // (the previous totals have been read)
-#pragma unroll
-    for (int k = 0; k < K; ++k) {
-        const double w = wave_sum64(v[k]);
-        if (lane == 0) part[wave][k] = w;
-    }
-    __syncthreads();
-#pragma unroll
-    for (int k = 0; k < K; ++k) {
-        double t = part[0][k];
-#pragma unroll
-        for (int w = 1; w < CV_WAVES; ++w) t += part[w][k];
-        v[k] = t;
-    }
-}
-
-// largest eigenvalue of the symmetric 4x4 matrix a (upper triangle used): cyclic Jacobi, eigenvalues only
-__device__ double jacobi4_max_eigenvalue(double (&a)[4][4]) {
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int j = 0; j < i; ++j) a[i][j] = a[j][i];
-    double scale = 0.;
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) scale += a[i][j] * a[i][j];
-    for (int sweep = 0; sweep < 50; ++sweep) {
-        const double off = a[0][1] * a[0][1] + a[0][2] * a[0][2] + a[0][3] * a[0][3] + a[1][2] * a[1][2] + a[1][3] * a[1][3] + a[2][3] * a[2][3];
-        if (!(off > 1e-40 * scale)) break;       // (also leaves on a NaN)
-#pragma unroll
-        for (int p = 0; p < 3; ++p)
-#pragma unroll
-            for (int q = p + 1; q < 4; ++q) {
-                const double apq = a[p][q];
-                if (apq == 0.) continue;
-                const double theta = (a[q][q] - a[p][p]) / (2. * apq);
-                const double t = (theta >= 0. ? 1. : -1.) / (fabs(theta) + sqrt(theta * theta + 1.));
-                const double c = 1. / sqrt(t * t + 1.), s = t * c;
-#pragma unroll
-                for (int k = 0; k < 4; ++k) {      // A <- A J
-                    const double akp = a[k][p], akq = a[k][q];
-                    a[k][p] = c * akp - s * akq; a[k][q] = s * akp + c * akq;
-                }
-#pragma unroll
-                for (int k = 0; k < 4; ++k) {      // A <- J^T A
-                    const double apk = a[p][k], aqk = a[q][k];
-                    a[p][k] = c * apk - s * aqk; a[q][k] = s * apk + c * aqk;
-                }
-            }
-    }
-    return fmax(fmax(a[0][0], a[1][1]), fmax(a[2][2], a[3][3]));
-}
-
-__device__ __forceinline__ void ld3d(const float* __restrict__ x, int atom, int stride, double& px, double& py, double& pz) {
-    const float* p = x + (size_t)atom * stride;
-    px = (double)p[0]; py = (double)p[1]; pz = (double)p[2];
-}
 
 __global__ void __launch_bounds__(CV_BLOCK) k_collective_variables(upk_coord_t pos, upk_cv_t C, upk_cv_record_t R, float* __restrict__ out) {
     __shared__ double part[CV_WAVES][CV_MAX_SUMS];
@@ -130,73 +42,8 @@ __global__ void __launch_bounds__(CV_BLOCK) k_collective_variables(upk_coord_t p
     const int stride = pos.stride;
 
     for (int c = 0; c < C.n_cv; ++c) {
-        const int kind = C.kind[c], a0 = C.atom_start[c], n = C.atom_start[c + 1] - a0;
-        const int* __restrict__ atoms = C.atoms + a0;
-        double value = 0.;
-        if (kind == UPK_CV_RG || kind == UPK_CV_RMSD) {
-            double cen[3] = {0., 0., 0.};
-            for (int i = tid; i < n; i += CV_BLOCK) { double px, py, pz; ld3d(x, atoms[i], stride, px, py, pz); cen[0] += px; cen[1] += py; cen[2] += pz; }
-            block_sum<3>(cen, part);
-            const double inv_n = 1. / (double)n;
-            cen[0] *= inv_n; cen[1] *= inv_n; cen[2] *= inv_n;
-            if (kind == UPK_CV_RG) {
-                double g[1] = {0.};
-                for (int i = tid; i < n; i += CV_BLOCK) {
-                    double px, py, pz; ld3d(x, atoms[i], stride, px, py, pz);
-                    px -= cen[0]; py -= cen[1]; pz -= cen[2];
-                    g[0] += px * px + py * py + pz * pz;
-                }
-                block_sum<1>(g, part);
-                value = sqrt(g[0] * inv_n);
-            } else {
-                const double* __restrict__ ref = C.ref + (size_t)C.aux_start[c] * 3;      // centred on the host
-                double m[10] = {0., 0., 0., 0., 0., 0., 0., 0., 0., 0.};       // Ga, then S[i][j] = sum a_i b_j
-                for (int i = tid; i < n; i += CV_BLOCK) {
-                    double a[3]; ld3d(x, atoms[i], stride, a[0], a[1], a[2]);
-                    a[0] -= cen[0]; a[1] -= cen[1]; a[2] -= cen[2];
-                    const double b[3] = {ref[3 * i], ref[3 * i + 1], ref[3 * i + 2]};
-                    m[0] += a[0] * a[0] + a[1] * a[1] + a[2] * a[2];
-#pragma unroll
-                    for (int u = 0; u < 3; ++u)
-#pragma unroll
-                        for (int v = 0; v < 3; ++v) m[1 + 3 * u + v] += a[u] * b[v];
-                }
-                block_sum<10>(m, part);
-                if (tid == 0) {       // Horn 1987: the largest eigenvalue of the quaternion matrix is the best proper rotation's sum a . R b
-                    const double Sxx = m[1], Sxy = m[2], Sxz = m[3], Syx = m[4], Syy = m[5], Syz = m[6], Szx = m[7], Szy = m[8], Szz = m[9];
-                    double K[4][4];
-                    K[0][0] = Sxx + Syy + Szz; K[0][1] = Syz - Szy; K[0][2] = Szx - Sxz; K[0][3] = Sxy - Syx;
-                    K[1][1] = Sxx - Syy - Szz; K[1][2] = Sxy + Syx; K[1][3] = Szx + Sxz;
-                    K[2][2] = -Sxx + Syy - Szz; K[2][3] = Syz + Szy;
-                    K[3][3] = -Sxx - Syy + Szz;
-                    const double lam = jacobi4_max_eigenvalue(K);
-                    value = sqrt(fmax(0., (m[0] + C.ref_g[c] - 2. * lam) * inv_n));
-                }
-            }
-        } else if (kind == UPK_CV_CONTACTS) {
-            const int n_pair = n / 2;
-            const float* __restrict__ r0 = C.r0 + C.aux_start[c];
-            const double beta = (double)C.beta[c], lambda = (double)C.lambda[c];
-            double q[1] = {0.};
-            for (int i = tid; i < n_pair; i += CV_BLOCK) {
-                double ax, ay, az, bx, by, bz;
-                ld3d(x, atoms[2 * i], stride, ax, ay, az); ld3d(x, atoms[2 * i + 1], stride, bx, by, bz);
-                ax -= bx; ay -= by; az -= bz;
-                const double arg = beta * (sqrt(ax * ax + ay * ay + az * az) - lambda * (double)r0[i]);
-                // 1 / (1 + exp(arg)) without an overflowing exponential: a pair 1e3 A apart contributes exactly 0
-                const double e = exp(-fabs(arg));
-                q[0] += (arg > 0. ? e : 1.) / (1. + e);
-            }
-            block_sum<1>(q, part);
-            value = q[0] / (double)n_pair;
-        } else {      // UPK_CV_DISTANCE
-            if (tid == 0) {
-                double ax, ay, az, bx, by, bz;
-                ld3d(x, atoms[0], stride, ax, ay, az); ld3d(x, atoms[1], stride, bx, by, bz);
-                ax -= bx; ay -= by; az -= bz;
-                value = sqrt(ax * ax + ay * ay + az * az);
-            }
-        }
+        double cen[3], rot[9];
+        const double value = cv_evaluate<false>(x, stride, C, c, part, cen, rot);
         if (tid == 0) row[c] = (float)value;
     }
 }
@@ -215,4 +62,98 @@ extern "C" int upk_cv_compute(const upk_launch_t* L, upk_coord_t pos, const upk_
 extern "C" int upk_cv_record(const upk_launch_t* L, upk_coord_t pos, const upk_cv_t* C, const upk_cv_record_t* R) {
     if (!R->rounds || !R->n_attempt || !R->samples || R->every < 1 || R->capacity < 1) return 9303;
     return cv_launch(L, pos, C, *R, nullptr);
+}
+
+// ---- cv_restraint: E = sum_c 1/2 k_c u_c^2, u_c = max(0, |v_c - center_c| - flat_width_c), per system ------------------------------
+// The shape of the kernel above: one workgroup per system walks the node's CVs.  Per CV the value v comes from cv_evaluate (the
+// bits k_collective_variables reports), lane 0 turns it into dE/dv with this system's row [center | spring_const | flat_width]
+// at par + s * par_stride and hands v, dE/dv and (rmsd) the rotation to the other lanes through LDS; a second lane-strided pass
+// writes dE/dv * dv/dx of every list entry, as one fp32 3-vector, into the entry's own slot of the scatter source of pos
+// (contrib[s][entry][3]: one writer per slot, every slot written on every launch; the parent gathers in its fixed order, so an
+// atom may sit in several CVs and many pairs).  Small values: an rg, rmsd or distance below UPK_CV_RESTRAINT_VMIN and a contact
+// pair at r = 0 have no direction; they contribute zero force (their energy is counted).
+__global__ void __launch_bounds__(CV_BLOCK) k_cv_restraint(upk_coord_t pos, upk_cv_t C, const float* __restrict__ par, long par_stride,
+                                                           float* __restrict__ contrib, long contrib_stride, float* __restrict__ values,
+                                                           float* __restrict__ pot_terms) {
+    __shared__ double part[CV_WAVES][CV_MAX_SUMS];
+    __shared__ double bc[2][11];      // v, dE/dv, R; by CV parity (a lane may still read CV c's while lane 0 writes CV c+1's)
+    const int s = blockIdx.x, tid = threadIdx.x;
+    const float* __restrict__ x = pos.out + (size_t)s * pos.n_elem * pos.stride;
+    const int stride = pos.stride;
+    const float* __restrict__ row = par + (size_t)s * par_stride;
+    float* __restrict__ out = contrib + (size_t)s * contrib_stride;
+
+    for (int c = 0; c < C.n_cv; ++c) {
+        double cen[3], rot[9];
+        const double value = cv_evaluate<true>(x, stride, C, c, part, cen, rot);
+        const int kind = C.kind[c], a0 = C.atom_start[c], n = C.atom_start[c + 1] - a0;
+        double* b = bc[c & 1];
+        if (tid == 0) {
+            const double d = value - (double)row[c], k = (double)row[C.n_cv + c], w = (double)row[2 * C.n_cv + c];
+            const double u = fmax(0., fabs(d) - w);
+            b[0] = value; b[1] = d < 0. ? -(k * u) : k * u;
+            if (kind == UPK_CV_RMSD) {
+#pragma unroll
+                for (int i = 0; i < 9; ++i) b[2 + i] = rot[i];
+            }
+            values[(size_t)s * C.n_cv + c] = (float)value;
+            if (pot_terms) pot_terms[(size_t)s * C.n_cv + c] = (float)(0.5 * k * u * u);
+        }
+        __syncthreads();
+        const double v = b[0], dEdv = b[1];
+        const int* __restrict__ atoms = C.atoms + a0;
+        float* __restrict__ o = out + (size_t)a0 * 3;
+        if (kind == UPK_CV_RG || kind == UPK_CV_RMSD) {
+            const double f = v < UPK_CV_RESTRAINT_VMIN ? 0. : dEdv / ((double)n * v);
+            if (kind == UPK_CV_RG) {
+                for (int i = tid; i < n; i += CV_BLOCK) {
+                    double px, py, pz; ld3d(x, atoms[i], stride, px, py, pz);
+                    o[3 * i] = (float)(f * (px - cen[0])); o[3 * i + 1] = (float)(f * (py - cen[1])); o[3 * i + 2] = (float)(f * (pz - cen[2]));
+                }
+            } else {
+                const double* __restrict__ ref = C.ref + (size_t)C.aux_start[c] * 3;
+                double R[9];
+#pragma unroll
+                for (int i = 0; i < 9; ++i) R[i] = b[2 + i];
+                for (int i = tid; i < n; i += CV_BLOCK) {
+                    double px, py, pz; ld3d(x, atoms[i], stride, px, py, pz);
+                    const double bx = ref[3 * i], by = ref[3 * i + 1], bz = ref[3 * i + 2];
+                    o[3 * i]     = (float)(f * (px - cen[0] - (R[0] * bx + R[1] * by + R[2] * bz)));
+                    o[3 * i + 1] = (float)(f * (py - cen[1] - (R[3] * bx + R[4] * by + R[5] * bz)));
+                    o[3 * i + 2] = (float)(f * (pz - cen[2] - (R[6] * bx + R[7] * by + R[8] * bz)));
+                }
+            }
+        } else if (kind == UPK_CV_CONTACTS) {
+            const int n_pair = n / 2;
+            const float* __restrict__ r0 = C.r0 + C.aux_start[c];
+            const double beta = (double)C.beta[c], lambda = (double)C.lambda[c];
+            const double f = -dEdv * beta / (double)n_pair;
+            for (int i = tid; i < n_pair; i += CV_BLOCK) {
+                double ax, ay, az, bx, by, bz;
+                ld3d(x, atoms[2 * i], stride, ax, ay, az); ld3d(x, atoms[2 * i + 1], stride, bx, by, bz);
+                ax -= bx; ay -= by; az -= bz;
+                const double r = sqrt(ax * ax + ay * ay + az * az);
+                const double e = exp(-fabs(beta * (r - lambda * (double)r0[i])));      // q (1 - q) = e / (1 + e)^2, either sign of the argument
+                const double g = r > 0. ? f * e / ((1. + e) * (1. + e) * r) : 0.;
+                const float gx = (float)(g * ax), gy = (float)(g * ay), gz = (float)(g * az);
+                o[6 * i] = gx; o[6 * i + 1] = gy; o[6 * i + 2] = gz; o[6 * i + 3] = -gx; o[6 * i + 4] = -gy; o[6 * i + 5] = -gz;
+            }
+        } else if (tid == 0) {      // UPK_CV_DISTANCE
+            double ax, ay, az, bx, by, bz;
+            ld3d(x, atoms[0], stride, ax, ay, az); ld3d(x, atoms[1], stride, bx, by, bz);
+            const double f = v < UPK_CV_RESTRAINT_VMIN ? 0. : dEdv / v;
+            const float gx = (float)(f * (ax - bx)), gy = (float)(f * (ay - by)), gz = (float)(f * (az - bz));
+            o[0] = gx; o[1] = gy; o[2] = gz; o[3] = -gx; o[4] = -gy; o[5] = -gz;
+        }
+    }
+}
+
+extern "C" int upk_cv_restraint(const upk_launch_t* L, upk_coord_t pos, const upk_cv_t* C, const float* par, long par_stride, float* contrib,
+                                long contrib_stride, float* values, float* pot_terms) {
+    UPK_FLUSH(L);
+    if (C->n_cv < 1 || C->n_cv > UPK_CV_MAX || pos.width < 3) return 9301;
+    if (!par || !contrib || !values) return 9304;
+    hipLaunchKernelGGL(k_cv_restraint, dim3((unsigned)L->n_system), dim3(CV_BLOCK), 0, ST(L), pos, *C, par, par_stride, contrib, contrib_stride,
+                       values, pot_terms);
+    return launch_status();
 }

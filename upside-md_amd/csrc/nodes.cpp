@@ -1811,9 +1811,96 @@ struct ScaledSum : public PotentialNode, BatchedParamDeriv {
 };
 RegisterNodeType<Builtin<ScaledSum>, 1> scaled_sum_node("scaled_sum");
 
+// cv_restraint: an umbrella bias on collective variables (this project's own node; the reference has none).  The group holds a CV
+// definition in the datasets of /input/collective_variables plus center, spring_const and flat_width (n_cv each):
+//   E = sum_c 1/2 k_c u_c^2,  u_c = max(0, |v_c - center_c| - flat_width_c)
+// with v_c the very number upside_hip_cv_compute reports (kernels_cv.hip: k_cv_restraint).  The values [center | spring_const |
+// flat_width] are a device table of one row per system, rewritten in place by stream-ordered copies (like hbond_energy's E_dev):
+// no kernel argument ever changes, so a captured MD graph reads the values of the moment it is replayed.
+// (The launcher takes a row stride like the other per-system launchers; this node, its only caller, always passes the full table's
+// 3 n_cv, so a shared single row -- stride 0 -- is not a path the library or its tests exercise.)
+struct CVRestraint : public PotentialNode, PerSystemValues {
+    CoordNode& pos; int n_cv = 0, n_entry = 0, src = -1;
+    CvDeviceDefinition def;
+    vector<float> par_sys, par_staging; DevBuf<float> par, values;      // [S][3 n_cv], [S][n_cv]
+    static void check_values(const vector<float>& p, size_t n_cv) {
+        if (p.size() != 3 * n_cv) throw string("expected ") + to_string(3 * n_cv) + " values [center | spring_const | flat_width] but got " + to_string(p.size());
+        for (size_t c = 0; c < n_cv; ++c) {
+            if (!std::isfinite(p[c])) throw string("center of CV ") + to_string(c) + " is not finite";
+            if (!(p[n_cv + c] >= 0.f) || !std::isfinite(p[n_cv + c])) throw string("spring_const of CV ") + to_string(c) + " must be finite and not negative";
+            if (!(p[2 * n_cv + c] >= 0.f) || !std::isfinite(p[2 * n_cv + c])) throw string("flat_width of CV ") + to_string(c) + " must be finite and not negative";
+        }
+    }
+    vector<float> read_values(hid_t_compat g) const {
+        vector<float> p;
+        for (const char* nm : {"center", "spring_const", "flat_width"}) {
+            auto v = read<float>(H(g), nm, 1);
+            if ((int)v.size() != n_cv) throw string(nm) + " holds " + to_string(v.size()) + " entries, the node has " + to_string(n_cv) + " CVs";
+            p.insert(p.end(), v.begin(), v.end());
+        }
+        check_values(p, (size_t)n_cv);
+        return p;
+    }
+    CVRestraint(DeviceCtx* c, hid_t_compat grp, CoordNode& pos_) : PotentialNode(c), pos(pos_) {
+        check_elem_width_lower_bound(pos, 3);
+        // everything is read and checked on the host before the first device array is touched
+        const CvHostDefinition h = cv_read_definition(grp, pos.n_elem, "cv_restraint");
+        if (h.n_cv < 1) throw string("cv_restraint: no collective variables");
+        n_cv = h.n_cv; n_entry = h.atom_start[n_cv];
+        const auto row0 = read_values(grp);
+        def.upload(h);
+        par_sys.resize((size_t)c->n_system * row0.size());
+        for (int s = 0; s < c->n_system; ++s) copy(row0.begin(), row0.end(), par_sys.begin() + (size_t)s * row0.size());
+        par.upload(par_sys); values.alloc((size_t)c->n_system * n_cv);
+        src = pos.scatter.add_source(n_entry, 1, 3, h.atoms);
+        alloc_terms(n_cv);
+    }
+    void compute_value(ComputeMode mode) override {
+        upk_check(upk_cv_restraint(&ctx->L, pos.coord(), &def.C, par.p, 3L * n_cv, pos.scatter.source_ptr(src), pos.scatter.arena_size, values.p,
+                                   mode == PotentialAndDerivMode ? pot_terms.p : nullptr), "cv_restraint");
+        if (mode == PotentialAndDerivMode) reduce_terms();
+    }
+    void write_par() {      // the staging row may be rewritten only once the previous copy has left it
+        hip_check(hipStreamSynchronize(ctx->stream), "hipStreamSynchronize");
+        par_staging = par_sys;
+        hip_check(hipMemcpyAsync(par.p, par_staging.data(), par_sys.size() * sizeof(float), hipMemcpyHostToDevice, ctx->stream), "H2D cv_restraint values");
+    }
+    void load_system_values(int s, hid_t_compat g) override { const auto p = read_values(g); copy(p.begin(), p.end(), par_sys.begin() + (size_t)s * p.size()); }
+    bool values_differ() const override { for (int s = 1; s < ctx->n_system; ++s) if (memcmp(&par_sys[(size_t)s * 3 * n_cv], &par_sys[0], 3 * n_cv * sizeof(float))) return true; return false; }
+    void finish_system_values() override { write_par(); }
+    void set_param_system(int s, const vector<float>& p) override {
+        check_values(p, (size_t)n_cv);
+        copy(p.begin(), p.end(), par_sys.begin() + (size_t)s * p.size());
+        write_par();
+    }
+    vector<float> get_param_system(int s) const override { return vector<float>(par_sys.begin() + (size_t)s * 3 * n_cv, par_sys.begin() + (size_t)(s + 1) * 3 * n_cv); }
+    vector<float> get_param() const override { return get_param_system(0); }
+    void set_param(const vector<float>& p) override {      // every system, as the reference's set_param
+        check_values(p, (size_t)n_cv);
+        for (int s = 0; s < ctx->n_system; ++s) copy(p.begin(), p.end(), par_sys.begin() + (size_t)s * p.size());
+        write_par();
+    }
+    vector<float> all_values() {      // [S][n_cv] of the last force pass
+        hip_check(hipStreamSynchronize(ctx->stream), "hipStreamSynchronize");
+        return values.download();
+    }
+    vector<float> get_value_by_name(const char* log_name) override {
+        if (string(log_name) != "cv_value") throw string("cv_restraint: no value named ") + log_name + " (cv_value)";
+        auto v = all_values(); v.resize((size_t)n_cv);
+        return v;
+    }
+};
+RegisterNodeType<Builtin<CVRestraint>, 1> cv_restraint_node("cv_restraint");
+
 }  // namespace
 
 // accessors used by the C-ABI layer (engine_c_api.cpp)
+int engine_cv_restraint_values(DerivEngine& e, const string& node_name, vector<float>* out) {      // n_cv; out (may be NULL): [S][n_cv]
+    auto* r = dynamic_cast<CVRestraint*>(e.get(node_name).computation.get());
+    if (!r) return -1;
+    if (out) *out = r->all_values();
+    return r->n_cv;
+}
 int engine_pairlist(DerivEngine& e, const string& node_name, int sys, vector<pair<int, int>>& out) {
     auto* c = e.get(node_name).computation.get();
     IGraphHost* ig = nullptr;
@@ -1945,6 +2032,7 @@ const vector<PerSystemValueSpec>& per_system_value_table() {
         {"z_flat_bottom", {"z0", "radius", "spring_constant"}, {}},
         {"contact", {"energy", "distance", "width"}, {}},
         {"hbond_energy", {}, {"protein_hbond_energy"}},
+        {"cv_restraint", {"center", "spring_const", "flat_width"}, {}},
     };
     return t;
 }

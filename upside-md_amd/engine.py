@@ -287,6 +287,7 @@ class Ensemble(object):
         c.upside_hip_cv_compute.argtypes = [vp, vp]
         c.upside_hip_cv_record.argtypes = [vp, i32, i32]
         c.upside_hip_cv_read.argtypes = [vp, i32, i32, vp, vp, vp, i32]
+        c.upside_hip_cv_restraint_values.argtypes = [vp, ct.c_char_p, vp]
         c._ensemble_bound = True
 
     def _check(self, rc, what):
@@ -462,6 +463,15 @@ class Ensemble(object):
         out = np.zeros((ns, self.n_system, self.n_cv), 'f4')
         self._check(self.calc.upside_hip_cv_read(self.engine, 0, ns, out.ctypes.data, None, None, int(bool(reset))), 'cv_read')
         return (out, ns, na) if with_counts else out
+
+    def restraint_values(self, node_name):
+        """(n_system, n_cv) CV values the cv_restraint node `node_name` saw in the last force pass (energies(), MD steps): the bits
+        cvs() gives for the same definition at the same positions"""
+        n_cv = int(self.calc.upside_hip_cv_restraint_values(self.engine, _b(node_name), None))      # (no out: the node's n_cv)
+        out = np.zeros((self.n_system, max(n_cv, 0)), 'f4')
+        if n_cv < 0 or self.calc.upside_hip_cv_restraint_values(self.engine, _b(node_name), out.ctypes.data) < 0:
+            raise RuntimeError('cv_restraint_values failed: %s' % self.calc.upside_hip_last_error().decode())
+        return out
 
     # -- replica exchange across the engines of a job, inside the library (comm_rccl.cpp) -------------
     COMM_ID_BYTES = 128
