@@ -259,6 +259,19 @@ int upside_hip_cv_read(DerivEngine* engine, int first, int n, float* out /* (n, 
  * get_value_by_name(node, "cv_value").  Returns the node's n_cv, or -1 on error (the node is no cv_restraint); out may be NULL to
  * ask for n_cv alone. */
 int upside_hip_cv_restraint_values(DerivEngine* engine, const char* node_name, float* out);
+/* cv_metadynamics nodes: the hills live on the device in n_list lists of `capacity` slots (shared = 0: one
+ * list per system, list = system; shared = 1: one list, list = 0, deposit k of system s in slot k * n_system + s).  d is the number
+ * of CVs of the node.  All return 0, or 1 on error (upside_hip_last_error); any out pointer may be NULL.
+ * _read: the visible hills of a list, centers (n_hill, d) and weights (n_hill) into host arrays of at least `capacity` rows, and
+ *   n_attempt, the deposits attempted (it runs on when the list is full: n_attempt > deposits stored tells of the overflow).
+ * _write: replaces a list by n_hill hills through stream-ordered copies (a captured MD graph sees them in its next replay) and
+ *   sets the counters so that deposition continues after them; refuses n_hill > capacity, values that are not finite and, for a
+ *   shared list, n_hill that is no multiple of n_system.
+ * _values: out (n_system, d), the CV values of the last force pass (the bits upside_hip_cv_compute gives). */
+int upside_hip_metad_info(DerivEngine* engine, const char* node_name, int* d, int* capacity, int* n_list);
+int upside_hip_metad_read(DerivEngine* engine, const char* node_name, int list, float* centers, float* weights, int* n_hill, long long* n_attempt);
+int upside_hip_metad_write(DerivEngine* engine, const char* node_name, int list, const float* centers, const float* weights, int n_hill);
+int upside_hip_metad_values(DerivEngine* engine, const char* node_name, float* out);
 
 /* Per-kernel timing hooks used by bench.py.  With profiling enabled every interaction-graph / BP kernel
  * launch is bracketed by HIP events on the engine's stream.  upside_hip_profile_dump writes one text line per

@@ -529,6 +529,31 @@ int upk_cv_record(const upk_launch_t* L, upk_coord_t pos, const upk_cv_t* C, con
 #define UPK_CV_RESTRAINT_VMIN 1e-6
 int upk_cv_restraint(const upk_launch_t* L, upk_coord_t pos, const upk_cv_t* C, const float* par, long par_stride, float* contrib,
                      long contrib_stride, float* values, float* pot_terms);
+/* cv_metadynamics (node of the force pass + a deposit per completed MD round): the d = C->n_cv <= UPK_METAD_MAX_DIM CVs of C span
+ * one space and the bias is a sum of Gaussian hills,
+ *   V(v) = sum_h w_h exp(-sum_c (v_c - s_hc)^2 / (2 sigma_c^2)),   dV/dv_c = sum_h -w_h (v_c - s_hc) / sigma_c^2 exp(...)
+ * over ALL hills of the system's list (no cutoff, no grid), accumulated in fp64 in one order: lane t takes hills t, t + 256, ...
+ * ascending, then the workgroup's fixed-order sum.  v_c is the fp64 value behind the bits upk_cv_compute reports.
+ * Hills: hills[list][d + 1][capacity] floats (rows 0..d-1 the centres, row d the weights; consecutive lanes read consecutive
+ * hills).  shared = 0: list = system, n_deposit[s] hills visible.  shared = 1: one list for all systems (walkers); deposit k of
+ * system s is slot k * n_system + s and n_deposit[s] * n_system hills are visible (the entries of n_deposit are equal).
+ * rounds[S], n_deposit[S], n_attempt[S] are device counters each system's workgroup advances for itself: no kernel argument
+ * ever changes, so eager launches and a replayed graph give the same series. */
+#define UPK_METAD_MAX_DIM 4
+typedef struct {
+    float* hills; int* n_deposit; int* n_attempt; unsigned long long* rounds;
+    const float* sigma;                  /* [d] */
+    int capacity, pace, shared; float height, kdT;
+} upk_cv_metad_t;
+/* force pass: contrib[s][entry][3] = dV/dv_c * dv_c/dx of every list entry (every slot written on every launch, zeros without
+ * hills; the small-value rules of upk_cv_restraint), values[s][d], and unless NULL pot_terms[s][1] = V */
+int upk_cv_metad(const upk_launch_t* L, upk_coord_t pos, const upk_cv_t* C, const upk_cv_metad_t* M, float* contrib, long contrib_stride,
+                 float* values, float* pot_terms);
+/* one completed MD round: system s advances rounds[s]; on every pace-th round it counts an attempt and, while its deposit fits
+ * (shared: while the deposits of ALL walkers fit), appends a hill centred on the float bits upk_cv_compute would report, of weight
+ * height (kdT == 0) or height * exp(-V(centre) / kdT) (well-tempered), V over the hills visible before this launch.  A launch
+ * reads only slots of earlier deposits and writes its own: no atomics. */
+int upk_cv_metad_deposit(const upk_launch_t* L, upk_coord_t pos, const upk_cv_t* C, const upk_cv_metad_t* M);
 
 #ifdef __cplusplus
 }

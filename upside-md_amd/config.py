@@ -896,6 +896,125 @@ def write_umbrella_windows(base_path, out_paths, node_name, centers, spring_cons
     return out_paths
 
 
+METAD_MAX_DIM = 4                  # UPK_METAD_MAX_DIM of include/upside_hip_kernels.h
+METAD_MAX_CAPACITY = 1 << 24
+
+
+def _metad_hills(centers, weights, d, capacity=None, who='metadynamics hills'):
+    w = np.asarray(weights, 'f8').reshape(-1)
+    c = np.asarray(centers, 'f8')
+    if c.ndim == 1 and d == 1:
+        c = c[:, None]
+    if c.shape != (len(w), d):
+        raise ValueError('%s: centers must be (%d hills, %d CVs), got %r' % (who, len(w), d, c.shape))
+    if not (np.isfinite(c).all() and np.isfinite(w).all()):
+        raise ValueError('%s: centers and weights must be finite' % who)
+    if capacity is not None and len(w) > capacity:
+        raise ValueError('%s: %d hills exceed the capacity of %d' % (who, len(w), capacity))
+    return c.astype('f4'), w.astype('f4')
+
+
+def add_cv_metadynamics(path, specs, sigma, height, pace, capacity, kdT=0., shared=False, name='cv_metadynamics'):
+    """add a metadynamics bias on collective variables (node type cv_metadynamics, argument pos) to an existing configuration.
+    The d = len(specs) <= 4 CVs (the dicts of pack_collective_variables) span one space in which a Gaussian hill is deposited
+    every `pace` MD rounds at the current CV values:
+         V(v) = sum_h w_h exp(-sum_c (v_c - s_hc)^2 / (2 sigma_c^2))
+    sigma: the d widths; height: the weight of a hill (plain) or of the first one (well-tempered); capacity: hill slots per list
+    -- when a list is full, deposits are dropped (and counted); kdT: k_B Delta T of well-tempered metadynamics in the engine's
+    energy unit, w_h = height exp(-V(s_h) / kdT), 0 = plain; shared: all systems of one engine deposit into ONE list (multiple
+    walkers; capacity then counts the hills of all of them).  The sum over hills has no cutoff.  name must start with
+    'cv_metadynamics'.  The files of one engine must agree on the whole node.  Returns the packed arrays."""
+    if not str(name).startswith('cv_metadynamics'):
+        raise ValueError("add_cv_metadynamics: the node name must start with 'cv_metadynamics', got %r" % (name,))
+    specs = list(specs)
+    if not specs:
+        raise ValueError('add_cv_metadynamics: no collective variables')
+    if len(specs) > METAD_MAX_DIM:
+        raise ValueError('add_cv_metadynamics: %d CVs span more dimensions than the limit of %d' % (len(specs), METAD_MAX_DIM))
+    for c, sp in enumerate(specs):
+        if not isinstance(sp, dict):
+            raise ValueError("collective variable %d: a dict with a 'kind' is expected" % c)
+    sigma = np.asarray(sigma, 'f8').reshape(-1)
+    if len(sigma) != len(specs):
+        raise ValueError('%s: sigma holds %d entries, the node has %d CVs' % (name, len(sigma), len(specs)))
+    if not (np.isfinite(sigma).all() and (sigma > 0).all()):
+        raise ValueError('%s: sigma must be finite and positive' % name)
+    if not (np.ndim(height) == 0 and np.isfinite(height) and height > 0):
+        raise ValueError('%s: height must be finite and positive' % name)
+    if not (np.ndim(kdT) == 0 and np.isfinite(kdT) and kdT >= 0):
+        raise ValueError('%s: kdT must be finite and not negative' % name)
+    if int(pace) != pace or pace < 1:
+        raise ValueError('%s: pace must be a whole number of MD rounds, at least 1' % name)
+    if int(capacity) != capacity or not 1 <= capacity <= METAD_MAX_CAPACITY:
+        raise ValueError('%s: capacity must be a whole number between 1 and %d' % (name, METAD_MAX_CAPACITY))
+    with h5lite.open_file(path) as f:      # everything is checked before the file is opened for writing
+        n_atom = f.group('input').shape('pos')[0]
+    p = pack_collective_variables(specs, n_atom)
+    n_list = np.diff(p['atom_start'])
+    if len(n_list) and n_list.max() > CV_MAX_LIST:
+        raise ValueError('collective variable %d: %d list entries exceed the limit of %d' % (int(n_list.argmax()), int(n_list.max()), CV_MAX_LIST))
+    p['sigma'] = sigma.astype('f4')
+    with h5lite.open_file(path, 'r+') as f:
+        pot = f.group('input').group('potential')
+        if name in pot:
+            pot.delete(name)
+        g = pot.create_group(name); _args(g, ['pos'])
+        for k in ('kind', 'atom_start', 'atoms', 'ref_pos', 'contact_r0', 'contact_beta', 'contact_lambda', 'names', 'sigma'):
+            g.write(k, p[k])
+        g.set_attr('height', float(height)); g.set_attr('kdT', float(kdT))
+        g.set_attr('pace', int(pace)); g.set_attr('capacity', int(capacity)); g.set_attr('shared', int(bool(shared)))
+    return p
+
+
+def _metad_node_shape(path, node):
+    """(d, capacity) of the cv_metadynamics node of a configuration (its handles are released on return)"""
+    with h5lite.open_file(path) as f:
+        pot = f.group('input').group('potential')
+        if node not in pot:
+            raise ValueError('set_metadynamics_hills: %s has no node %r' % (path, node))
+        g = pot.group(node)
+        return len(g.read('kind')), int(np.asarray(g.get_attr('capacity')).ravel()[0])
+
+
+def set_metadynamics_hills(path, node, centers, weights):
+    """the hills a run of `upside_hip` starts from: /input/metadynamics/<node>/{hill_center (n, d), hill_weight (n)} of the
+    configuration (outside /input/potential: files are grouped into engines without regard to it).  To continue a run, pass what
+    it left under /output/metadynamics/<node>.  With a shared list the engine's first file is the one that is read."""
+    d, capacity = _metad_node_shape(path, node)
+    c, w = _metad_hills(centers, weights, d, capacity, 'set_metadynamics_hills')
+    with h5lite.open_file(path, 'r+') as f:
+        m = f.group('input').require_group('metadynamics')
+        if node in m:
+            m.delete(node)
+        g = m.create_group(node)
+        g.write('hill_center', c); g.write('hill_weight', w)
+    return c, w
+
+
+def metadynamics_free_energy(centers, weights, sigma, grid_points, kT=None, kdT=0.):
+    """the free-energy estimate of a metadynamics run at grid_points (m, d) (or (m,) for d = 1), float64, up to a constant:
+    -V for plain metadynamics (kdT = 0), -(kT + kdT) / kdT V for well-tempered (kT: the run's temperature in energy units)"""
+    sigma = np.asarray(sigma, 'f8').reshape(-1)
+    d = len(sigma)
+    w = np.asarray(weights, 'f8').reshape(-1)
+    c = np.asarray(centers, 'f8').reshape(len(w), d)
+    x = np.asarray(grid_points, 'f8')
+    x = x[:, None] if (x.ndim == 1 and d == 1) else x
+    if x.ndim != 2 or x.shape[1] != d:
+        raise ValueError('metadynamics_free_energy: grid_points must be (m, %d)' % d)
+    if not (sigma > 0).all():
+        raise ValueError('metadynamics_free_energy: sigma must be positive')
+    z = (x[:, None, :] - c[None, :, :]) / sigma
+    v = (w[None, :] * np.exp(-0.5 * (z * z).sum(2))).sum(1)
+    if kdT > 0.:
+        if kT is None or not kT > 0.:
+            raise ValueError('metadynamics_free_energy: well-tempered (kdT > 0) needs kT > 0')
+        return -(float(kT) + float(kdT)) / float(kdT) * v
+    if kdT < 0.:
+        raise ValueError('metadynamics_free_energy: kdT must not be negative')
+    return -v
+
+
 def default_collective_variables(pos, contact_cutoff=8.0, min_seq_sep=4, beta=5., lam=1.8):
     """the standard folding observables over the CA atoms (atom 3 r + 1) against the structure `pos` (n_atom,3): Rg, RMSD and
     fraction of native contacts Q to it, end-to-end distance (what `make_config.py --collective-variables` writes)"""

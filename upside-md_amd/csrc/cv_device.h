@@ -1,6 +1,6 @@
-// Device code shared by the kernels that evaluate collective variables (kernels_cv.hip: k_collective_variables, k_cv_restraint).
-// Both compute a CV by cv_evaluate below, so a restraint acts on exactly the number the observable reports: the same sums in the
-// same order, bit for bit.
+// Device code shared by the kernels that evaluate collective variables (kernels_cv.hip: k_collective_variables, k_cv_restraint,
+// k_cv_metad, k_cv_metad_deposit).  All compute a CV by cv_evaluate below, so a bias acts on exactly the number the observable
+// reports: the same sums in the same order, bit for bit.  The two biases write their forces by cv_write_gradient.
 //   - every sum is accumulated in fp64 and has ONE order: lane t adds elements t, t + CV_BLOCK, ... ascending; the 64 lanes of a
 //     wavefront combine in a fixed butterfly of DPP / permlane exchanges (the two 32-bit halves of a double travel side by side);
 //     the four wavefront totals meet in LDS and every lane adds them 0, 1, 2, 3.  No atomics.
@@ -220,6 +220,60 @@ __device__ __forceinline__ double cv_evaluate(const float* __restrict__ x, int s
         }
     }
     return value;
+}
+
+// dE/dv * dv/dx of CV c, one fp32 3-vector per list entry, into the entry's own slot out[(atom_start[c] + entry) * 3 ..]: lane t
+// writes entries t, t + CV_BLOCK, ... (a distance: lane 0).  v is the CV's value, cen the centroid cv_evaluate left (rg, rmsd) and
+// rot nine doubles in LDS holding its rotation (rmsd only; read inside that branch).  Small values: an rg, rmsd or distance below
+// UPK_CV_RESTRAINT_VMIN and a contact pair at r = 0 have no direction and receive zero.  Every slot of the CV is written.
+__device__ __forceinline__ void cv_write_gradient(const float* __restrict__ x, int stride, const upk_cv_t& C, int c, double v, double dEdv,
+                                                  const double (&cen)[3], const double* rot, float* __restrict__ out) {
+    const int tid = threadIdx.x;
+    const int kind = C.kind[c], a0 = C.atom_start[c], n = C.atom_start[c + 1] - a0;
+    const int* __restrict__ atoms = C.atoms + a0;
+    float* __restrict__ o = out + (size_t)a0 * 3;
+    if (kind == UPK_CV_RG || kind == UPK_CV_RMSD) {
+        const double f = v < UPK_CV_RESTRAINT_VMIN ? 0. : dEdv / ((double)n * v);
+        if (kind == UPK_CV_RG) {
+            for (int i = tid; i < n; i += CV_BLOCK) {
+                double px, py, pz; ld3d(x, atoms[i], stride, px, py, pz);
+                o[3 * i] = (float)(f * (px - cen[0])); o[3 * i + 1] = (float)(f * (py - cen[1])); o[3 * i + 2] = (float)(f * (pz - cen[2]));
+            }
+        } else {
+            const double* __restrict__ ref = C.ref + (size_t)C.aux_start[c] * 3;
+            double R[9];
+#pragma unroll
+            for (int i = 0; i < 9; ++i) R[i] = rot[i];
+            for (int i = tid; i < n; i += CV_BLOCK) {
+                double px, py, pz; ld3d(x, atoms[i], stride, px, py, pz);
+                const double bx = ref[3 * i], by = ref[3 * i + 1], bz = ref[3 * i + 2];
+                o[3 * i]     = (float)(f * (px - cen[0] - (R[0] * bx + R[1] * by + R[2] * bz)));
+                o[3 * i + 1] = (float)(f * (py - cen[1] - (R[3] * bx + R[4] * by + R[5] * bz)));
+                o[3 * i + 2] = (float)(f * (pz - cen[2] - (R[6] * bx + R[7] * by + R[8] * bz)));
+            }
+        }
+    } else if (kind == UPK_CV_CONTACTS) {
+        const int n_pair = n / 2;
+        const float* __restrict__ r0 = C.r0 + C.aux_start[c];
+        const double beta = (double)C.beta[c], lambda = (double)C.lambda[c];
+        const double f = -dEdv * beta / (double)n_pair;
+        for (int i = tid; i < n_pair; i += CV_BLOCK) {
+            double ax, ay, az, bx, by, bz;
+            ld3d(x, atoms[2 * i], stride, ax, ay, az); ld3d(x, atoms[2 * i + 1], stride, bx, by, bz);
+            ax -= bx; ay -= by; az -= bz;
+            const double r = sqrt(ax * ax + ay * ay + az * az);
+            const double e = exp(-fabs(beta * (r - lambda * (double)r0[i])));      // q (1 - q) = e / (1 + e)^2, either sign of the argument
+            const double g = r > 0. ? f * e / ((1. + e) * (1. + e) * r) : 0.;
+            const float gx = (float)(g * ax), gy = (float)(g * ay), gz = (float)(g * az);
+            o[6 * i] = gx; o[6 * i + 1] = gy; o[6 * i + 2] = gz; o[6 * i + 3] = -gx; o[6 * i + 4] = -gy; o[6 * i + 5] = -gz;
+        }
+    } else if (tid == 0) {      // UPK_CV_DISTANCE
+        double ax, ay, az, bx, by, bz;
+        ld3d(x, atoms[0], stride, ax, ay, az); ld3d(x, atoms[1], stride, bx, by, bz);
+        const double f = v < UPK_CV_RESTRAINT_VMIN ? 0. : dEdv / v;
+        const float gx = (float)(f * (ax - bx)), gy = (float)(f * (ay - by)), gz = (float)(f * (az - bz));
+        o[0] = gx; o[1] = gy; o[2] = gz; o[3] = -gx; o[4] = -gy; o[5] = -gz;
+    }
 }
 
 }  // namespace up

@@ -283,6 +283,8 @@ int DerivEngine::get_idx(const string& name, bool must_exist) {
 
 void DerivEngine::finalize() {
     for (auto& n : nodes) { n.computation->finalize(); if (!n.computation->capturable()) graph_failed = true; }
+    round_end_work.clear();
+    for (auto& n : nodes) if (auto* w = dynamic_cast<RoundEndWork*>(n.computation.get())) round_end_work.push_back(w);
     // Unroll the level-synchronous sweep of deriv_engine.cpp:124-169 once; the order of events is static.
     schedule.clear();
     for (auto& n : nodes) n.germ_exec_level = n.deriv_exec_level = -1;
@@ -552,6 +554,7 @@ void DerivEngine::md_step() {
     if (++stage_num == 3) {
         stage_num = 0; ++round_num;
         if (cv.R.every > 0) upk_check(upk_cv_record(&ctx.L, pos->coord(), &cv.C, &cv.R), "cv_record");      // a completed round (recording off: no launch)
+        for (auto* w : round_end_work) w->round_end();
     }
     ++steps_done;
 }

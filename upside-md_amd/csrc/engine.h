@@ -69,6 +69,14 @@ struct CvDeviceDefinition {
     void upload(const CvHostDefinition& d);
 };
 
+// A node with work at the end of every completed MD round (cv_metadynamics deposits its hills there).  Engine-internal, found by
+// dynamic_cast at finalize(); md_step() enqueues round_end() next to the CV recording, so a captured graph holds the launch, and no
+// force pass outside MD (energies, swap sets) ever issues it.  An engine without such a node issues no launch for it.
+struct RoundEndWork {
+    virtual ~RoundEndWork() {}
+    virtual void round_end() = 0;
+};
+
 struct DerivEngine {   // deriv_engine.h:145-237
     struct Node {
         std::string name;
@@ -98,6 +106,7 @@ struct DerivEngine {   // deriv_engine.h:145-237
     std::map<int, Side> side;                  // node index -> side stream of its prepare() (empty when disabled)
     int last_prepare_step = -1;                // index in `schedule` of the last prepare step
     DevBuf<float*> zero_ptrs; DevBuf<long> zero_sizes; int n_zero = 0;   // every CoordNode's sens, cleared by one launch per force pass
+    std::vector<RoundEndWork*> round_end_work;  // in node order (usually empty)
 
     DerivEngine(int n_atom, int n_system);
     ~DerivEngine();

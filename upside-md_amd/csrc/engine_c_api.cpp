@@ -18,6 +18,10 @@ using namespace std;
 int engine_pairlist(DerivEngine& e, const string& node_name, int sys, vector<pair<int, int>>& out);
 int engine_rotamer_iterations(DerivEngine& e, vector<int>& iters);
 int engine_cv_restraint_values(DerivEngine& e, const string& node_name, vector<float>* out);
+void engine_metad_info(DerivEngine& e, const string& node_name, int* d, int* capacity, int* n_list);
+void engine_metad_read(DerivEngine& e, const string& node_name, int list, float* centers, float* weights, int* n_hill, long long* n_attempt);
+void engine_metad_write(DerivEngine& e, const string& node_name, int list, const float* centers, const float* weights, int n_hill);
+vector<float> engine_metad_values(DerivEngine& e, const string& node_name);
 int engine_rebuild_flags(DerivEngine& e, const string& node_name, vector<int>& flags);
 int engine_igraph_stats(DerivEngine& e, const string& node_name, double* out);
 double engine_bp_bytes(DerivEngine& e);
@@ -542,6 +546,37 @@ extern "C" int upside_hip_cv_restraint_values(DerivEngine* e, const char* node_n
     copy(v.begin(), v.end(), out);
     return n_cv;
     API_CATCH(-1)
+}
+// ---- cv_metadynamics: the hills of a node (nodes.cpp: CVMetadynamics) ---------------------------------------------------------------
+extern "C" int upside_hip_metad_info(DerivEngine* e, const char* node_name, int* d, int* capacity, int* n_list) {
+    API_TRY
+    if (!e || !node_name) throw string("engine or node name is NULL");
+    engine_metad_info(*e, string(node_name), d, capacity, n_list);
+    return 0;
+    API_CATCH(1)
+}
+extern "C" int upside_hip_metad_read(DerivEngine* e, const char* node_name, int list, float* centers, float* weights, int* n_hill, long long* n_attempt) {
+    API_TRY
+    if (!e || !node_name) throw string("engine or node name is NULL");
+    engine_metad_read(*e, string(node_name), list, centers, weights, n_hill, n_attempt);
+    return 0;
+    API_CATCH(1)
+}
+extern "C" int upside_hip_metad_write(DerivEngine* e, const char* node_name, int list, const float* centers, const float* weights, int n_hill) {
+    API_TRY
+    if (!e || !node_name) throw string("engine or node name is NULL");
+    engine_metad_write(*e, string(node_name), list, centers, weights, n_hill);
+    e->swap_energy.clear();
+    return 0;
+    API_CATCH(1)
+}
+extern "C" int upside_hip_metad_values(DerivEngine* e, const char* node_name, float* out) {
+    API_TRY
+    if (!e || !node_name || !out) throw string("engine, node name or out is NULL");
+    const auto v = engine_metad_values(*e, string(node_name));
+    copy(v.begin(), v.end(), out);
+    return 0;
+    API_CATCH(1)
 }
 // ---- Monte-Carlo pivot moves (monte_carlo_sampler.cpp; main.cpp:628-630) ---------------------------------
 extern "C" int upside_hip_load_mc(DerivEngine* e, const char* config_file) {

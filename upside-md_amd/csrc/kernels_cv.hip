@@ -1,7 +1,8 @@
 // gfx950 kernels of the collective variables: radius of gyration, RMSD after optimal superposition, fraction of native contacts
 // and plain distances of EVERY system in one launch -- as observables (upside_hip_cv_*, k_collective_variables) and as the
-// coordinates of an umbrella bias in the force pass (node cv_restraint, k_cv_restraint at the end of this file).  The value of a
-// CV is computed by cv_device.h for both.
+// coordinates of a bias in the force pass (node cv_restraint: k_cv_restraint, an umbrella; node cv_metadynamics: k_cv_metad and
+// k_cv_metad_deposit at the end of this file, Gaussian hills deposited during MD).  The value of a CV is computed by cv_device.h for
+// all of them, and its gradient for the two biases.
 //
 // One workgroup of CV_BLOCK lanes owns one system (blockIdx.x) and walks the system's CVs one after the other; a CV is a handful of
 // sums over its atom list, read through the engine's position layout ([S][n_atom][stride]).  Nothing here is large: 300 CA atoms
@@ -68,7 +69,7 @@ extern "C" int upk_cv_record(const upk_launch_t* L, upk_coord_t pos, const upk_c
 // The shape of the kernel above: one workgroup per system walks the node's CVs.  Per CV the value v comes from cv_evaluate (the
 // bits k_collective_variables reports), lane 0 turns it into dE/dv with this system's row [center | spring_const | flat_width]
 // at par + s * par_stride and hands v, dE/dv and (rmsd) the rotation to the other lanes through LDS; a second lane-strided pass
-// writes dE/dv * dv/dx of every list entry, as one fp32 3-vector, into the entry's own slot of the scatter source of pos
+// (cv_write_gradient) writes dE/dv * dv/dx of every list entry, as one fp32 3-vector, into the entry's own slot of the scatter source of pos
 // (contrib[s][entry][3]: one writer per slot, every slot written on every launch; the parent gathers in its fixed order, so an
 // atom may sit in several CVs and many pairs).  Small values: an rg, rmsd or distance below UPK_CV_RESTRAINT_VMIN and a contact
 // pair at r = 0 have no direction; they contribute zero force (their energy is counted).
@@ -86,7 +87,7 @@ __global__ void __launch_bounds__(CV_BLOCK) k_cv_restraint(upk_coord_t pos, upk_
     for (int c = 0; c < C.n_cv; ++c) {
         double cen[3], rot[9];
         const double value = cv_evaluate<true>(x, stride, C, c, part, cen, rot);
-        const int kind = C.kind[c], a0 = C.atom_start[c], n = C.atom_start[c + 1] - a0;
+        const int kind = C.kind[c];
         double* b = bc[c & 1];
         if (tid == 0) {
             const double d = value - (double)row[c], k = (double)row[C.n_cv + c], w = (double)row[2 * C.n_cv + c];
@@ -100,51 +101,7 @@ __global__ void __launch_bounds__(CV_BLOCK) k_cv_restraint(upk_coord_t pos, upk_
             if (pot_terms) pot_terms[(size_t)s * C.n_cv + c] = (float)(0.5 * k * u * u);
         }
         __syncthreads();
-        const double v = b[0], dEdv = b[1];
-        const int* __restrict__ atoms = C.atoms + a0;
-        float* __restrict__ o = out + (size_t)a0 * 3;
-        if (kind == UPK_CV_RG || kind == UPK_CV_RMSD) {
-            const double f = v < UPK_CV_RESTRAINT_VMIN ? 0. : dEdv / ((double)n * v);
-            if (kind == UPK_CV_RG) {
-                for (int i = tid; i < n; i += CV_BLOCK) {
-                    double px, py, pz; ld3d(x, atoms[i], stride, px, py, pz);
-                    o[3 * i] = (float)(f * (px - cen[0])); o[3 * i + 1] = (float)(f * (py - cen[1])); o[3 * i + 2] = (float)(f * (pz - cen[2]));
-                }
-            } else {
-                const double* __restrict__ ref = C.ref + (size_t)C.aux_start[c] * 3;
-                double R[9];
-#pragma unroll
-                for (int i = 0; i < 9; ++i) R[i] = b[2 + i];
-                for (int i = tid; i < n; i += CV_BLOCK) {
-                    double px, py, pz; ld3d(x, atoms[i], stride, px, py, pz);
-                    const double bx = ref[3 * i], by = ref[3 * i + 1], bz = ref[3 * i + 2];
-                    o[3 * i]     = (float)(f * (px - cen[0] - (R[0] * bx + R[1] * by + R[2] * bz)));
-                    o[3 * i + 1] = (float)(f * (py - cen[1] - (R[3] * bx + R[4] * by + R[5] * bz)));
-                    o[3 * i + 2] = (float)(f * (pz - cen[2] - (R[6] * bx + R[7] * by + R[8] * bz)));
-                }
-            }
-        } else if (kind == UPK_CV_CONTACTS) {
-            const int n_pair = n / 2;
-            const float* __restrict__ r0 = C.r0 + C.aux_start[c];
-            const double beta = (double)C.beta[c], lambda = (double)C.lambda[c];
-            const double f = -dEdv * beta / (double)n_pair;
-            for (int i = tid; i < n_pair; i += CV_BLOCK) {
-                double ax, ay, az, bx, by, bz;
-                ld3d(x, atoms[2 * i], stride, ax, ay, az); ld3d(x, atoms[2 * i + 1], stride, bx, by, bz);
-                ax -= bx; ay -= by; az -= bz;
-                const double r = sqrt(ax * ax + ay * ay + az * az);
-                const double e = exp(-fabs(beta * (r - lambda * (double)r0[i])));      // q (1 - q) = e / (1 + e)^2, either sign of the argument
-                const double g = r > 0. ? f * e / ((1. + e) * (1. + e) * r) : 0.;
-                const float gx = (float)(g * ax), gy = (float)(g * ay), gz = (float)(g * az);
-                o[6 * i] = gx; o[6 * i + 1] = gy; o[6 * i + 2] = gz; o[6 * i + 3] = -gx; o[6 * i + 4] = -gy; o[6 * i + 5] = -gz;
-            }
-        } else if (tid == 0) {      // UPK_CV_DISTANCE
-            double ax, ay, az, bx, by, bz;
-            ld3d(x, atoms[0], stride, ax, ay, az); ld3d(x, atoms[1], stride, bx, by, bz);
-            const double f = v < UPK_CV_RESTRAINT_VMIN ? 0. : dEdv / v;
-            const float gx = (float)(f * (ax - bx)), gy = (float)(f * (ay - by)), gz = (float)(f * (az - bz));
-            o[0] = gx; o[1] = gy; o[2] = gz; o[3] = -gx; o[4] = -gy; o[5] = -gz;
-        }
+        cv_write_gradient(x, stride, C, c, b[0], b[1], cen, b + 2, out);
     }
 }
 
@@ -155,5 +112,150 @@ extern "C" int upk_cv_restraint(const upk_launch_t* L, upk_coord_t pos, const up
     if (!par || !contrib || !values) return 9304;
     hipLaunchKernelGGL(k_cv_restraint, dim3((unsigned)L->n_system), dim3(CV_BLOCK), 0, ST(L), pos, *C, par, par_stride, contrib, contrib_stride,
                        values, pot_terms);
+    return launch_status();
+}
+
+// ---- cv_metadynamics: V(v) = sum_h w_h exp(-sum_c (v_c - s_hc)^2 / (2 sigma_c^2)) over the node's D CVs, per system ------------------
+// The CVs are coupled through the hills, so the kernel cannot go CV by CV as k_cv_restraint does.  Three phases in one workgroup per
+// system: (1) all D values by cv_evaluate, kept with centroid and rotation in LDS (13 doubles per CV); (2) the sum over ALL visible
+// hills of the system's list -- no cutoff, no grid -- of V and its D partial derivatives in one order (lane t: hills t, t + CV_BLOCK,
+// ... ascending, then block_sum<D + 1>); (3) dV/dv_c * dv_c/dx into the list entries' own scatter slots by cv_write_gradient, every
+// slot on every launch (zeros while the list is empty).  Hills are stored [list][D + 1][capacity], so consecutive lanes read
+// consecutive floats of each row.
+template <int D>
+__device__ __forceinline__ void metad_hill_sum(const float* __restrict__ hills, int capacity, int n_hill, const double (&v)[D], const double (&inv_s2)[D],
+                                               double (&acc)[D + 1]) {
+#pragma unroll
+    for (int k = 0; k <= D; ++k) acc[k] = 0.;
+    for (int h = threadIdx.x; h < n_hill; h += CV_BLOCK) {
+        double diff[D], e = 0.;
+#pragma unroll
+        for (int c = 0; c < D; ++c) { diff[c] = v[c] - (double)hills[(size_t)c * capacity + h]; e += diff[c] * diff[c] * inv_s2[c]; }
+        const double g = (double)hills[(size_t)D * capacity + h] * exp(-0.5 * e);
+        acc[0] += g;
+#pragma unroll
+        for (int c = 0; c < D; ++c) acc[1 + c] -= g * diff[c] * inv_s2[c];
+    }
+}
+// where a system's list starts in M.hills (floats) and how many of its hills are visible
+__device__ __forceinline__ size_t metad_list(const upk_cv_metad_t& M, int d, int s, int n_system, int n_deposit, int& n_hill) {
+    n_hill = M.shared ? n_deposit * n_system : n_deposit;
+    return M.shared ? (size_t)0 : (size_t)s * (d + 1) * M.capacity;
+}
+
+template <int D>
+__global__ void __launch_bounds__(CV_BLOCK) k_cv_metad(upk_coord_t pos, upk_cv_t C, upk_cv_metad_t M, float* __restrict__ contrib, long contrib_stride,
+                                                       float* __restrict__ values, float* __restrict__ pot_terms) {
+    __shared__ double part[CV_WAVES][CV_MAX_SUMS];
+    __shared__ double st[D][13];      // per CV: v, centroid, R
+    const int s = blockIdx.x, tid = threadIdx.x;
+    const float* __restrict__ x = pos.out + (size_t)s * pos.n_elem * pos.stride;
+    const int stride = pos.stride;
+    float* __restrict__ out = contrib + (size_t)s * contrib_stride;
+
+#pragma unroll 1
+    for (int c = 0; c < D; ++c) {
+        double cen[3], rot[9];
+        const double value = cv_evaluate<true>(x, stride, C, c, part, cen, rot);
+        if (tid == 0) {
+            const int kind = C.kind[c];
+            st[c][0] = value;
+            if (kind == UPK_CV_RG || kind == UPK_CV_RMSD) { st[c][1] = cen[0]; st[c][2] = cen[1]; st[c][3] = cen[2]; }
+            if (kind == UPK_CV_RMSD) {
+#pragma unroll
+                for (int i = 0; i < 9; ++i) st[c][4 + i] = rot[i];
+            }
+            values[(size_t)s * D + c] = (float)value;
+        }
+    }
+    __syncthreads();
+    double v[D], inv_s2[D], acc[D + 1];
+#pragma unroll
+    for (int c = 0; c < D; ++c) { v[c] = st[c][0]; const double sg = (double)M.sigma[c]; inv_s2[c] = 1. / (sg * sg); }
+    int n_hill;
+    const float* __restrict__ hills = M.hills + metad_list(M, D, s, (int)gridDim.x, M.n_deposit[s], n_hill);
+    metad_hill_sum<D>(hills, M.capacity, n_hill, v, inv_s2, acc);
+    block_sum<D + 1>(acc, part);
+    if (tid == 0 && pot_terms) pot_terms[s] = (float)acc[0];
+#pragma unroll 1
+    for (int c = 0; c < D; ++c) {
+        const double cen[3] = {st[c][1], st[c][2], st[c][3]};
+        cv_write_gradient(x, stride, C, c, v[c], acc[1 + c], cen, &st[c][4], out);
+    }
+}
+
+// One completed MD round (the decision of k_collective_variables' recording, on this node's own counters).  On a pace-th round
+// the system counts an attempt and, while the deposit fits, appends a hill: the centre is (float) of cv_evaluate<false>'s value --
+// the bits upk_cv_compute reports -- and the weight height, or height * exp(-V(centre) / kdT) with V from metad_hill_sum over the
+// hills visible before this launch, evaluated at the stored (rounded) centre so that the weights follow from the stored hills.
+// shared: the workgroup of system s reads slots < k * n_system (earlier launches) and writes slot k * n_system + s.
+template <int D>
+__global__ void __launch_bounds__(CV_BLOCK) k_cv_metad_deposit(upk_coord_t pos, upk_cv_t C, upk_cv_metad_t M) {
+    __shared__ double part[CV_WAVES][CV_MAX_SUMS];
+    __shared__ double st[D];
+    const int s = blockIdx.x, tid = threadIdx.x, n_system = (int)gridDim.x;
+    const unsigned long long r = M.rounds[s] + 1ull;
+    const int k = M.n_deposit[s], na = M.n_attempt[s];
+    __syncthreads();
+    const bool take = !(r % (unsigned long long)M.pace);
+    if (tid == 0) { M.rounds[s] = r; if (take) M.n_attempt[s] = na + 1; }
+    const long need = M.shared ? ((long)k + 1) * n_system : (long)k + 1;      // slots in use once this deposit is in
+    if (!take || need > (long)M.capacity) return;
+    const float* __restrict__ x = pos.out + (size_t)s * pos.n_elem * pos.stride;
+    const int stride = pos.stride;
+#pragma unroll 1
+    for (int c = 0; c < D; ++c) {
+        double cen[3], rot[9];
+        const double value = cv_evaluate<false>(x, stride, C, c, part, cen, rot);
+        if (tid == 0) st[c] = (double)(float)value;
+    }
+    __syncthreads();
+    double v[D], inv_s2[D], acc[D + 1];
+#pragma unroll
+    for (int c = 0; c < D; ++c) { v[c] = st[c]; const double sg = (double)M.sigma[c]; inv_s2[c] = 1. / (sg * sg); }
+    int n_hill;
+    const size_t list = metad_list(M, D, s, n_system, k, n_hill);
+    if (M.kdT > 0.f) {      // (uniform over the workgroup)
+        metad_hill_sum<D>(M.hills + list, M.capacity, n_hill, v, inv_s2, acc);
+        block_sum<D + 1>(acc, part);
+    } else acc[0] = 0.;
+    if (tid == 0) {
+        float* mine = M.hills + list + (M.shared ? (size_t)k * n_system + s : (size_t)k);
+#pragma unroll
+        for (int c = 0; c < D; ++c) mine[(size_t)c * M.capacity] = (float)v[c];
+        mine[(size_t)D * M.capacity] = M.kdT > 0.f ? (float)((double)M.height * exp(-acc[0] / (double)M.kdT)) : M.height;
+        M.n_deposit[s] = k + 1;
+    }
+}
+
+static int metad_check(const upk_launch_t* L, upk_coord_t pos, const upk_cv_t* C, const upk_cv_metad_t* M) {
+    if (C->n_cv < 1 || C->n_cv > UPK_METAD_MAX_DIM || pos.width < 3) return 9301;
+    if (!M->hills || !M->n_deposit || !M->n_attempt || !M->rounds || !M->sigma || M->capacity < 1 || M->pace < 1) return 9305;
+    return 0;
+}
+extern "C" int upk_cv_metad(const upk_launch_t* L, upk_coord_t pos, const upk_cv_t* C, const upk_cv_metad_t* M, float* contrib, long contrib_stride,
+                            float* values, float* pot_terms) {
+    UPK_FLUSH(L);
+    if (const int rc = metad_check(L, pos, C, M)) return rc;
+    if (!contrib || !values) return 9304;
+    const dim3 grid((unsigned)L->n_system), block(CV_BLOCK);
+    switch (C->n_cv) {
+        case 1: hipLaunchKernelGGL(k_cv_metad<1>, grid, block, 0, ST(L), pos, *C, *M, contrib, contrib_stride, values, pot_terms); break;
+        case 2: hipLaunchKernelGGL(k_cv_metad<2>, grid, block, 0, ST(L), pos, *C, *M, contrib, contrib_stride, values, pot_terms); break;
+        case 3: hipLaunchKernelGGL(k_cv_metad<3>, grid, block, 0, ST(L), pos, *C, *M, contrib, contrib_stride, values, pot_terms); break;
+        default: hipLaunchKernelGGL(k_cv_metad<4>, grid, block, 0, ST(L), pos, *C, *M, contrib, contrib_stride, values, pot_terms); break;
+    }
+    return launch_status();
+}
+extern "C" int upk_cv_metad_deposit(const upk_launch_t* L, upk_coord_t pos, const upk_cv_t* C, const upk_cv_metad_t* M) {
+    UPK_FLUSH(L);
+    if (const int rc = metad_check(L, pos, C, M)) return rc;
+    const dim3 grid((unsigned)L->n_system), block(CV_BLOCK);
+    switch (C->n_cv) {
+        case 1: hipLaunchKernelGGL(k_cv_metad_deposit<1>, grid, block, 0, ST(L), pos, *C, *M); break;
+        case 2: hipLaunchKernelGGL(k_cv_metad_deposit<2>, grid, block, 0, ST(L), pos, *C, *M); break;
+        case 3: hipLaunchKernelGGL(k_cv_metad_deposit<3>, grid, block, 0, ST(L), pos, *C, *M); break;
+        default: hipLaunchKernelGGL(k_cv_metad_deposit<4>, grid, block, 0, ST(L), pos, *C, *M); break;
+    }
     return launch_status();
 }

@@ -27,6 +27,11 @@
 
 using namespace std;
 
+vector<string> engine_metad_nodes(DerivEngine& e);      // nodes.cpp: the names of the engine's cv_metadynamics nodes
+void engine_metad_info(DerivEngine& e, const string& node_name, int* d, int* capacity, int* n_list);
+void engine_metad_read(DerivEngine& e, const string& node_name, int list, float* centers, float* weights, int* n_hill, long long* n_attempt);
+void engine_metad_write(DerivEngine& e, const string& node_name, int list, const float* centers, const float* weights, int n_hill);
+
 // ---- /output logger ------------------------------------------------------------------------------------------
 namespace {
 struct EArray {   // h5_support.cpp:199-274: extensible along dimension 0, chunked (100 frames), shuffle + fletcher32 (+ deflate 1)
@@ -155,6 +160,19 @@ struct OutputLogger {   // one per system / configuration file (H5Logger, state_
         for (auto& x : extra) x.flush();
         if (log_cv) cv.flush();
         if (file >= 0) H5Fflush(file, H5F_SCOPE_LOCAL);
+    }
+    // the hills of a cv_metadynamics node at the end of the run: /output/metadynamics/<node>/{hill_center (n, d), hill_weight (n),
+    // n_attempt (1)}; copied to /input/metadynamics/<node> of the next configuration they continue the run
+    void write_metadynamics(const string& node, int d, const vector<float>& centers, const vector<float>& weights, long n_attempt) {
+        if (H5Lexists(group, "metadynamics", H5P_DEFAULT) <= 0) { hid_t g = H5Gcreate2(group, "metadynamics", H5P_DEFAULT, H5P_DEFAULT, H5P_DEFAULT); if (g < 0) throw string("unable to create /output/metadynamics"); H5Gclose(g); }
+        h5u::Handle mg(H5Gopen2(group, "metadynamics", H5P_DEFAULT), H5Gclose);
+        h5u::Handle ng(H5Gcreate2(mg, node.c_str(), H5P_DEFAULT, H5P_DEFAULT, H5P_DEFAULT), H5Gclose);
+        if (ng < 0) throw string("unable to create /output/metadynamics/") + node;
+        EArray c, w, a;
+        c.create(ng, "hill_center", H5T_NATIVE_FLOAT, 4, {(hsize_t)d}); w.create(ng, "hill_weight", H5T_NATIVE_FLOAT, 4, {}); a.create(ng, "n_attempt", H5T_NATIVE_LONG, sizeof(long), {});
+        for (size_t i = 0; i < weights.size(); ++i) { c.push(&centers[i * d]); w.push(&weights[i]); }
+        a.push(&n_attempt);
+        c.close(); w.close(); a.close();
     }
     void close() {
         if (file < 0) return;
@@ -361,6 +379,30 @@ int upside_main_impl(int argc, const char* const* argv, int verbose) {
                 applied = true;
             }
             if (!applied) throw string("--set-param: no node named ") + node_name;
+        }
+    }
+    // cv_metadynamics: a run continues from the hills under /input/metadynamics/<node> (a system's own file; a shared list: the
+    // engine's first file), read before the first force pass so that frame 0 sees them
+    vector<vector<string>> metad_nodes(n_group);
+    for (int g = 0; g < n_group; ++g) {
+        metad_nodes[g] = engine_metad_nodes(*engines[g]);
+        for (const string& node : metad_nodes[g]) {
+            int d = 0, cap = 0, n_list = 0;
+            engine_metad_info(*engines[g], node, &d, &cap, &n_list);
+            for (int l = 0; l < n_list; ++l) {
+                const string& path = files[members[g][n_list == 1 ? 0 : l]];
+                hid_t f = H5Fopen(path.c_str(), H5F_ACC_RDONLY, H5P_DEFAULT);
+                if (f < 0) throw string("unable to open ") + path;
+                h5u::Handle fh(f, H5Fclose);
+                const string grp = "/input/metadynamics/" + node;
+                if (!h5u::exists(f, "/input/metadynamics") || !h5u::exists(f, grp)) continue;
+                vector<hsize_t> dc;
+                const auto centers = h5u::read<float>(f, grp + "/hill_center", 2, &dc); const auto weights = h5u::read<float>(f, grp + "/hill_weight", 1);
+                if (dc[0] != weights.size() || (dc[0] && (int)dc[1] != d))
+                    throw path + ": " + grp + ": hill_center must be (n_hill, " + to_string(d) + ") and hill_weight (n_hill)";
+                try { engine_metad_write(*engines[g], node, l, centers.data(), weights.data(), (int)weights.size()); }
+                catch (const string& err) { throw path + ": " + grp + ": " + err; }
+            }
         }
     }
     // main.cpp:548-564: recentring would fight a potential that is not translation invariant
@@ -690,6 +732,17 @@ int upside_main_impl(int argc, const char* const* argv, int verbose) {
         }
     }
     for (auto* x : engines) x->sync();
+    if (write_output) for (int ns = 0; ns < n_system; ++ns) {
+        const int g = group_of[ns];
+        for (const string& node : metad_nodes[g]) {
+            int d = 0, cap = 0, n_list = 0, n_hill = 0; long long n_att = 0;
+            engine_metad_info(*engines[g], node, &d, &cap, &n_list);
+            vector<float> centers((size_t)cap * d), weights((size_t)cap);
+            engine_metad_read(*engines[g], node, n_list == 1 ? 0 : local_of[ns], centers.data(), weights.data(), &n_hill, &n_att);
+            centers.resize((size_t)n_hill * d); weights.resize((size_t)n_hill);
+            loggers[ns].write_metadynamics(node, d, centers, weights, (long)n_att);
+        }
+    }
     for (auto& lg : loggers) lg.close();          // buffered frames reach the files also after an early stop (and before the communicator goes)
     if (use_comm) upside_hip_comm_free(e);
     stop_signal = g_received_signal;

@@ -1892,6 +1892,111 @@ struct CVRestraint : public PotentialNode, PerSystemValues {
 };
 RegisterNodeType<Builtin<CVRestraint>, 1> cv_restraint_node("cv_restraint");
 
+// cv_metadynamics: a history-dependent bias on collective variables (this project's own node, like cv_restraint).  The group
+// holds a CV definition in the datasets of /input/collective_variables; its d = n_cv <= UPK_METAD_MAX_DIM CVs span one space in
+// which Gaussian hills are deposited during MD:  V(v) = sum_h w_h exp(-sum_c (v_c - s_hc)^2 / (2 sigma_c^2)).
+// Further: sigma (d floats), attributes height, pace (MD rounds), capacity (hill slots per list), kdT (k_B Delta T of
+// well-tempered metadynamics in energy units; 0 = plain) and shared (1: all systems of the engine are walkers on one list).
+// Hills and counters live on the device (kernels_cv.hip: k_cv_metad in the force pass, k_cv_metad_deposit at the end of every
+// completed MD round), so no kernel argument ever changes and a captured MD graph replays the deposition.  Hills belong to the
+// system index: exchanging coordinates between systems leaves them where they are, as it leaves a Hamiltonian.
+// Not PerSystemValues: the files of one engine must agree on the whole group.
+struct CVMetadynamics : public PotentialNode, RoundEndWork {
+    CoordNode& pos; int n_cv = 0, n_entry = 0, src = -1, capacity = 0, n_list = 1; bool shared = false;
+    CvDeviceDefinition def; upk_cv_metad_t M{};
+    DevBuf<float> hills, sigma, values; DevBuf<int> n_deposit, n_attempt; DevBuf<unsigned long long> rounds;
+    vector<float> hill_staging; vector<int> count_staging;      // sources of the stream-ordered copies of write_hills
+    static float positive_attr(hid_t_compat grp, const char* nm, bool zero_ok) {
+        const float v = attr<float>(H(grp), ".", nm);
+        if (!std::isfinite(v) || v < 0.f || (!zero_ok && v == 0.f)) throw string("cv_metadynamics: ") + nm + " must be finite and " + (zero_ok ? "not negative" : "positive");
+        return v;
+    }
+    CVMetadynamics(DeviceCtx* c, hid_t_compat grp, CoordNode& pos_) : PotentialNode(c), pos(pos_) {
+        check_elem_width_lower_bound(pos, 3);
+        // everything is read and checked on the host before the first device array is touched
+        const CvHostDefinition h = cv_read_definition(grp, pos.n_elem, "cv_metadynamics");
+        if (h.n_cv < 1) throw string("cv_metadynamics: no collective variables");
+        if (h.n_cv > UPK_METAD_MAX_DIM)
+            throw string("cv_metadynamics: ") + to_string(h.n_cv) + " CVs span more dimensions than the limit of " + to_string(UPK_METAD_MAX_DIM) + " (UPK_METAD_MAX_DIM)";
+        n_cv = h.n_cv; n_entry = h.atom_start[n_cv];
+        const auto sg = read<float>(H(grp), "sigma", 1);
+        if ((int)sg.size() != n_cv) throw string("cv_metadynamics: sigma holds ") + to_string(sg.size()) + " entries, the node has " + to_string(n_cv) + " CVs";
+        for (int k = 0; k < n_cv; ++k) if (!std::isfinite(sg[k]) || !(sg[k] > 0.f)) throw string("cv_metadynamics: sigma of CV ") + to_string(k) + " must be finite and positive";
+        M.height = positive_attr(grp, "height", false);
+        M.kdT = positive_attr(grp, "kdT", true);
+        const int pace = attr<int>(H(grp), ".", "pace"), cap = attr<int>(H(grp), ".", "capacity"), sh = attr<int>(H(grp), ".", "shared");
+        if (pace < 1) throw string("cv_metadynamics: pace must be at least 1 (MD rounds)");
+        if (cap < 1 || cap > (1 << 24)) throw string("cv_metadynamics: capacity must be between 1 and ") + to_string(1 << 24) + " hills";
+        if (sh != 0 && sh != 1) throw string("cv_metadynamics: shared must be 0 or 1");
+        M.pace = pace; M.capacity = capacity = cap; M.shared = sh; shared = sh != 0;
+        n_list = shared ? 1 : c->n_system;
+        def.upload(h);
+        sigma.upload(sg);
+        hills.alloc((size_t)n_list * (n_cv + 1) * capacity);
+        n_deposit.alloc(c->n_system); n_attempt.alloc(c->n_system); rounds.alloc(c->n_system); values.alloc((size_t)c->n_system * n_cv);
+        M.hills = hills.p; M.sigma = sigma.p; M.n_deposit = n_deposit.p; M.n_attempt = n_attempt.p; M.rounds = rounds.p;
+        src = pos.scatter.add_source(n_entry, 1, 3, h.atoms);
+        alloc_terms(1);
+    }
+    void compute_value(ComputeMode mode) override {
+        upk_check(upk_cv_metad(&ctx->L, pos.coord(), &def.C, &M, pos.scatter.source_ptr(src), pos.scatter.arena_size, values.p,
+                               mode == PotentialAndDerivMode ? pot_terms.p : nullptr), "cv_metadynamics");
+        if (mode == PotentialAndDerivMode) reduce_terms();
+    }
+    void round_end() override { upk_check(upk_cv_metad_deposit(&ctx->L, pos.coord(), &def.C, &M), "cv_metadynamics deposit"); }
+    void check_list(int list) const { if (list < 0 || list >= n_list) throw string("cv_metadynamics: list ") + to_string(list) + " out of range (the node has " + to_string(n_list) + ")"; }
+    // centers [n][d] and weights [n] of list `list` (either may be NULL), the visible hills and the deposits attempted
+    void read_hills(int list, float* centers, float* weights, int* n_hill_out, long long* n_attempt_out) {
+        check_list(list);
+        hip_check(hipStreamSynchronize(ctx->stream), "hipStreamSynchronize");
+        const auto nd = n_deposit.download(); const auto na = n_attempt.download();
+        const int n = shared ? nd[0] * ctx->n_system : nd[list];
+        if (n_hill_out) *n_hill_out = n;
+        if (n_attempt_out) *n_attempt_out = na[shared ? 0 : list];
+        if (!n || (!centers && !weights)) return;
+        vector<float> h((size_t)(n_cv + 1) * capacity);
+        hip_check(hipMemcpy(h.data(), hills.p + (size_t)list * h.size(), h.size() * sizeof(float), hipMemcpyDeviceToHost), "D2H hills");
+        for (int i = 0; i < n; ++i) {
+            if (centers) for (int k = 0; k < n_cv; ++k) centers[(size_t)i * n_cv + k] = h[(size_t)k * capacity + i];
+            if (weights) weights[i] = h[(size_t)n_cv * capacity + i];
+        }
+    }
+    // replaces list `list` by n hills; deposition continues after them (n_attempt = the hills' deposits)
+    void write_hills(int list, const float* centers, const float* weights, int n) {
+        check_list(list);
+        const int S = ctx->n_system;
+        if (n < 0) throw string("cv_metadynamics: n_hill is negative");
+        if (n > capacity) throw string("cv_metadynamics: ") + to_string(n) + " hills exceed the capacity of " + to_string(capacity);
+        if (shared && n % S) throw string("cv_metadynamics: a shared list holds whole deposits: ") + to_string(n) + " hills are no multiple of " + to_string(S) + " systems";
+        if (n && (!centers || !weights)) throw string("cv_metadynamics: centers and weights must be given");
+        for (int i = 0; i < n; ++i) {
+            if (!std::isfinite(weights[i])) throw string("cv_metadynamics: weight of hill ") + to_string(i) + " is not finite";
+            for (int k = 0; k < n_cv; ++k) if (!std::isfinite(centers[(size_t)i * n_cv + k])) throw string("cv_metadynamics: centre of hill ") + to_string(i) + " is not finite";
+        }
+        hip_check(hipStreamSynchronize(ctx->stream), "hipStreamSynchronize");      // the staging arrays may be rewritten only once the previous copies have left them
+        hill_staging.assign((size_t)(n_cv + 1) * capacity, 0.f);
+        for (int i = 0; i < n; ++i) {
+            for (int k = 0; k < n_cv; ++k) hill_staging[(size_t)k * capacity + i] = centers[(size_t)i * n_cv + k];
+            hill_staging[(size_t)n_cv * capacity + i] = weights[i];
+        }
+        hip_check(hipMemcpyAsync(hills.p + (size_t)list * hill_staging.size(), hill_staging.data(), hill_staging.size() * sizeof(float), hipMemcpyHostToDevice, ctx->stream), "H2D hills");
+        const int first = shared ? 0 : list, count = shared ? S : 1;
+        count_staging.assign((size_t)count, shared ? n / S : n);
+        for (int* dst : {n_deposit.p, n_attempt.p})
+            hip_check(hipMemcpyAsync(dst + first, count_staging.data(), (size_t)count * sizeof(int), hipMemcpyHostToDevice, ctx->stream), "H2D hill counters");
+    }
+    vector<float> all_values() {      // [S][d] of the last force pass
+        hip_check(hipStreamSynchronize(ctx->stream), "hipStreamSynchronize");
+        return values.download();
+    }
+    vector<float> get_value_by_name(const char* log_name) override {
+        if (string(log_name) != "cv_value") throw string("cv_metadynamics: no value named ") + log_name + " (cv_value)";
+        auto v = all_values(); v.resize((size_t)n_cv);
+        return v;
+    }
+};
+RegisterNodeType<Builtin<CVMetadynamics>, 1> cv_metadynamics_node("cv_metadynamics");
+
 }  // namespace
 
 // accessors used by the C-ABI layer (engine_c_api.cpp)
@@ -1900,6 +2005,29 @@ int engine_cv_restraint_values(DerivEngine& e, const string& node_name, vector<f
     if (!r) return -1;
     if (out) *out = r->all_values();
     return r->n_cv;
+}
+static CVMetadynamics& metad_node(DerivEngine& e, const string& node_name) {
+    auto* m = dynamic_cast<CVMetadynamics*>(e.get(node_name).computation.get());
+    if (!m) throw string("node ") + node_name + " is not a cv_metadynamics";
+    return *m;
+}
+void engine_metad_info(DerivEngine& e, const string& node_name, int* d, int* capacity, int* n_list) {
+    auto& m = metad_node(e, node_name);
+    if (d) *d = m.n_cv;
+    if (capacity) *capacity = m.capacity;
+    if (n_list) *n_list = m.n_list;
+}
+void engine_metad_read(DerivEngine& e, const string& node_name, int list, float* centers, float* weights, int* n_hill, long long* n_attempt) {
+    metad_node(e, node_name).read_hills(list, centers, weights, n_hill, n_attempt);
+}
+void engine_metad_write(DerivEngine& e, const string& node_name, int list, const float* centers, const float* weights, int n_hill) {
+    metad_node(e, node_name).write_hills(list, centers, weights, n_hill);
+}
+vector<float> engine_metad_values(DerivEngine& e, const string& node_name) { return metad_node(e, node_name).all_values(); }
+vector<string> engine_metad_nodes(DerivEngine& e) {
+    vector<string> out;
+    for (auto& n : e.nodes) if (dynamic_cast<CVMetadynamics*>(n.computation.get())) out.push_back(n.name);
+    return out;
 }
 int engine_pairlist(DerivEngine& e, const string& node_name, int sys, vector<pair<int, int>>& out) {
     auto* c = e.get(node_name).computation.get();

@@ -288,6 +288,10 @@ class Ensemble(object):
         c.upside_hip_cv_record.argtypes = [vp, i32, i32]
         c.upside_hip_cv_read.argtypes = [vp, i32, i32, vp, vp, vp, i32]
         c.upside_hip_cv_restraint_values.argtypes = [vp, ct.c_char_p, vp]
+        c.upside_hip_metad_info.argtypes = [vp, ct.c_char_p, vp, vp, vp]
+        c.upside_hip_metad_read.argtypes = [vp, ct.c_char_p, i32, vp, vp, vp, vp]
+        c.upside_hip_metad_write.argtypes = [vp, ct.c_char_p, i32, vp, vp, i32]
+        c.upside_hip_metad_values.argtypes = [vp, ct.c_char_p, vp]
         c._ensemble_bound = True
 
     def _check(self, rc, what):
@@ -471,6 +475,44 @@ class Ensemble(object):
         out = np.zeros((self.n_system, max(n_cv, 0)), 'f4')
         if n_cv < 0 or self.calc.upside_hip_cv_restraint_values(self.engine, _b(node_name), out.ctypes.data) < 0:
             raise RuntimeError('cv_restraint_values failed: %s' % self.calc.upside_hip_last_error().decode())
+        return out
+
+    # -- cv_metadynamics: the hills of a node (they live on the device; deposition happens inside run_rounds / run_steps) -----
+    def metad_info(self, node_name):
+        """(d, capacity, n_list) of the cv_metadynamics node: n_list is n_system (shared = 0) or 1 (shared = 1)"""
+        v = np.zeros(3, 'i4')
+        self._check(self.calc.upside_hip_metad_info(self.engine, _b(node_name), v[0:].ctypes.data, v[1:].ctypes.data, v[2:].ctypes.data), 'metad_info')
+        return int(v[0]), int(v[1]), int(v[2])
+
+    def _metad_list(self, node_name, system):
+        d, cap, n_list = self.metad_info(node_name)
+        if not 0 <= int(system) < self.n_system:
+            raise ValueError('system %r out of range' % (system,))
+        return d, cap, (int(system) if n_list > 1 else 0)      # (a shared list serves every system)
+
+    def metad_hills(self, node_name, system=0):
+        """(centers (n, d) f4, weights (n,) f4, n_attempt): the hills system `system` sees (its own list, or the shared one in walker
+        order: deposit k of system s is row k * n_system + s) and the deposits attempted so far; n_attempt beyond the deposits
+        stored means the list ran full"""
+        d, cap, lst = self._metad_list(node_name, system)
+        c = np.zeros((cap, d), 'f4'); w = np.zeros(cap, 'f4'); n = np.zeros(1, 'i4'); na = np.zeros(1, 'i8')
+        self._check(self.calc.upside_hip_metad_read(self.engine, _b(node_name), lst, c.ctypes.data, w.ctypes.data, n.ctypes.data, na.ctypes.data), 'metad_read')
+        return c[:n[0]].copy(), w[:n[0]].copy(), int(na[0])
+
+    def set_metad_hills(self, node_name, centers, weights, system=0):
+        """replace the list system `system` sees by these hills (centers (n, d) or (n,) for d = 1, weights (n,)); deposition
+        continues after them.  Stream-ordered: the next force pass sees them, also from a captured graph."""
+        d, cap, lst = self._metad_list(node_name, system)
+        w = np.require(np.asarray(weights, 'f4').reshape(-1), dtype='f4', requirements='C')
+        c = np.require(np.asarray(centers, 'f4').reshape(len(w), d), dtype='f4', requirements='C')
+        self._check(self.calc.upside_hip_metad_write(self.engine, _b(node_name), lst, c.ctypes.data, w.ctypes.data, len(w)), 'metad_write')
+
+    def metad_values(self, node_name):
+        """(n_system, d) CV values the cv_metadynamics node saw in the last force pass: the bits cvs() gives for the same
+        definition at the same positions"""
+        d = self.metad_info(node_name)[0]
+        out = np.zeros((self.n_system, d), 'f4')
+        self._check(self.calc.upside_hip_metad_values(self.engine, _b(node_name), out.ctypes.data), 'metad_values')
         return out
 
     # -- replica exchange across the engines of a job, inside the library (comm_rccl.cpp) -------------
