@@ -206,7 +206,7 @@ int upside_hip_param_deriv_read(DerivEngine* engine, const char* node_name, int 
  *   _group_configurations: the grouping upside_main uses (HDF5 only, no device): group_of[i] = group of files[i], groups
  *     numbered by first appearance; returns the number of groups, -1 on failure.  Files that are identical or differ only
  *     in the table's values share a group; UPSIDE_HIP_HAMILTONIAN_BATCH=0 groups by the whole /input/potential instead.
- *   _set_param_system / _get_param_system: set_param / get_param of one system (nodes with parameters: hbond_energy).
+ *   _set_param_system / _get_param_system: set_param / get_param of one system (hbond_energy, cv_restraint).
  *     set_param keeps its meaning (every system); get_param returns system 0's values.
  *   _hamiltonian_swap: one swap set (main.cpp:251-273) on the engine's stream: energy pass, the pairs trade coordinates,
  *     energy pass, Metropolis verdicts of upside_replica_decide_lboltz (each system's own temperature), refused pairs trade

@@ -106,13 +106,8 @@ int upk_infer_bwd(const upk_launch_t* L, upk_coord_t infer, const float* bond_le
                   float* contrib, long contrib_stride);
 
 /* ---- bonded potentials (src/bonds.cpp:297-318, 457-487, 519-545, 350-372) -------------------------- */
-/* kind: 2 dist, 3 angle, 4 dihedral.  contrib: [term][kind][3]; pot_terms [S][n] (may be NULL)         */
-int upk_spring(const upk_launch_t* L, int kind, upk_coord_t pos, const int* id, const float* equil, const float* k, int n,
-               float* contrib, long contrib_stride, float* pot_terms);
-int upk_cavity_radial(const upk_launch_t* L, upk_coord_t pos, const int* id, const float* radius, const float* k, int n,
-                      float* contrib, long contrib_stride, float* pot_terms);
-/* the same with per-system parameter rows: system s reads equil / k / radius at base + s * par_stride (0 = one shared row;
- * the entry points above pass 0) */
+/* kind: 2 dist, 3 angle, 4 dihedral.  contrib: [term][kind][3]; pot_terms [S][n] (may be NULL).
+ * System s reads equil / k / radius at base + s * par_stride (0 = one row shared by every system, n = a row per system) */
 int upk_spring_strided(const upk_launch_t* L, int kind, upk_coord_t pos, const int* id, const float* equil, const float* k, long par_stride,
                        int n, float* contrib, long contrib_stride, float* pot_terms);
 int upk_cavity_radial_strided(const upk_launch_t* L, upk_coord_t pos, const int* id, const float* radius, const float* k, long par_stride,
@@ -143,9 +138,7 @@ int upk_weighted_pos_bwd(const upk_launch_t* L, upk_coord_t pos, upk_coord_t ene
 /* nonlinear_coupling (src/environment.cpp:358-369) */
 int upk_nonlinear_coupling(const upk_launch_t* L, upk_coord_t input, const int* types, const float* coeff, int n_coeff,
                            float offset, float inv_dx, float* pot_terms);
-/* hbond_energy (src/hbond.cpp:430-444) */
-int upk_hbond_energy(const upk_launch_t* L, upk_coord_t protein_hbond, float E_protein, float* pot_terms);
-/* the same with one energy scale per system: E_protein is a device array [S] */
+/* hbond_energy (src/hbond.cpp:430-444), one energy scale per system: E_protein is a device array [S] */
 int upk_hbond_energy_sys(const upk_launch_t* L, upk_coord_t protein_hbond, const float* E_protein, float* pot_terms);
 /* backbone_pairs (src/backbone_steric.cpp:81-145): gather form over residue pairs; aff_contrib [res][6]; pot_terms [S][n_res]
  * (each pair counted once).  cache (may be NULL: every residue scans all others each step, what the reference does): per-row lists
@@ -401,15 +394,12 @@ int upk_calibrate_valu(double* rates);
  *   kind 1 tension         (bonds.cpp:53-90)   tension_coeff[3]
  *   kind 2 AFM             (bonds.cpp:93-168)  k, starting_tip_pos[3], pulling_vel[3]; `time` = time_estimate
  *   kind 3 z_flat_bottom   (bonds.cpp:377-427) z0, radius, k
- * contrib: (n,3) contribution rows of pos' scatter plan */
-int upk_point_potential(const upk_launch_t* L, int kind, upk_coord_t pos, const int* id, const float* par, int n, float time,
-                        float* contrib, long contrib_stride, float* pot_terms);
-/* contact (sidechain_radial.cpp:139-205): id (n,2); par [n][4] = energy, dist, 1/width, cutoff; contrib (n,2,3) */
-int upk_contact(const upk_launch_t* L, upk_coord_t bead, const int* id, const float* par, int n, float* contrib, long contrib_stride,
-                float* pot_terms);
-/* per-system parameter rows: system s reads par + s * par_stride (0 = shared; the entry points above pass 0) */
+ * contrib: (n,3) contribution rows of pos' scatter plan.
+ * System s reads par + s * par_stride (0 = one row shared by every system, n * 8 = a row per system) */
 int upk_point_potential_strided(const upk_launch_t* L, int kind, upk_coord_t pos, const int* id, const float* par, long par_stride, int n,
                                 float time, float* contrib, long contrib_stride, float* pot_terms);
+/* contact (sidechain_radial.cpp:139-205): id (n,2); par [n][4] = energy, dist, 1/width, cutoff; contrib (n,2,3); par_stride as
+ * above (0 or n * 4) */
 int upk_contact_strided(const upk_launch_t* L, upk_coord_t bead, const int* id, const float* par, long par_stride, int n, float* contrib,
                         long contrib_stride, float* pot_terms);
 /* constant (bonds.cpp:550-587), slice (bonds.cpp:589-621) */

@@ -254,3 +254,62 @@ def test_ladder_md_under_graph_capture(lib, tmp_path):
     for k in ('mid', 'pos', 'mom', 'energy'):
         assert np.array_equal(res['1'][k], res['0'][k]), k
     assert not np.array_equal(res['1']['mid'], res['1']['pos'])
+
+
+def _add_cavity(path, ids, radius, spring_constant=5.):
+    with P.pkg.h5lite.open_file(path, 'r+') as t:
+        g = t.group('input/potential').create_group('cavity_radial')
+        g.set_attr('arguments', ['pos'])
+        g.write('id', np.asarray(ids, 'i4'))
+        g.write('radius', np.full(len(ids), radius, 'f4'))
+        g.write('spring_constant', np.full(len(ids), spring_constant, 'f4'))
+    return path
+
+
+def test_cavity_radial_ladder(lib, tmp_path):
+    """cavity_radial (in no fixture) on copies of trpcage20_7A, the radius at the median distance of the atoms from the origin.
+    Window 1 changes only spring_constant, window 2 only radius: each of the node's two arrays in turn is the one that makes the
+    table full.  Per window bitwise against an engine of three copies of its file and within RTOL of the oracle on its file;
+    three copies of window 0 keep the single shared row and are bitwise what construct computes; a differing id is refused."""
+    name = 'trpcage20_7A'
+    pos = P.golden(name)['pos'].astype('f4')
+    dist = np.sqrt((pos.reshape(-1, 3).astype('f8') ** 2).sum(axis=1))
+    n_atom, radius = len(dist), float(np.median(dist))
+    assert (dist > radius).any() and (dist < radius).any()
+    fs = [_add_cavity(H.copy_fixture(name, tmp_path / ('c%d.up' % i)), np.arange(n_atom), radius) for i in range(3)]
+    H.rewrite(fs[1], 'cavity_radial', 'spring_constant', lambda v: v * 1.5)
+    H.rewrite(fs[2], 'cavity_radial', 'radius', lambda v: v * 0.9)
+    big = E.Ensemble.from_files(fs, library=lib)
+    big.set_pos(pos)
+    e, d = big.energies_and_derivs()
+    big.close()
+    assert len(set(e.tolist())) == 3                 # the windows really differ
+    for i, f in enumerate(fs):
+        same = E.Ensemble(f, 3, library=lib)
+        same.set_pos(pos)
+        e3, d3 = same.energies_and_derivs()
+        same.close()
+        assert e3[i] == e[i], (i, e3[i], e[i])
+        assert np.array_equal(d3[i], d[i]), i
+        orc = P.pkg.Upside(f, library=P.oracle_library())
+        ref = dict(energy=np.float32(orc.energy(pos)), deriv=orc.deriv(pos))
+        node_energy = float(orc.get_output('cavity_radial')[0, 0])
+        orc.close()
+        assert node_energy != 0., i
+        bad = P.compare(ref, dict(energy=e[i], deriv=d[i]), rtol=P.RTOL, verbose=True)
+        assert not bad, (i, bad)
+    up = P.pkg.Upside(fs[0])
+    up.energy(pos)
+    assert float(up.get_output('cavity_radial')[0, 0]) != 0.
+    up.close()
+    a = E.Ensemble.from_files([fs[0]] * 3, library=lib); b = E.Ensemble(fs[0], 3, library=lib)
+    for x in (a, b):
+        x.set_pos(pos)
+    ea, da = a.energies_and_derivs(); eb, db = b.energies_and_derivs()
+    a.close(); b.close()
+    assert np.array_equal(ea, eb) and np.array_equal(da, db)
+    other = _add_cavity(H.copy_fixture(name, tmp_path / 'other_id.up'), np.arange(n_atom)[::-1], radius)
+    with pytest.raises(RuntimeError) as err:
+        E.Ensemble.from_files([fs[0], other], library=lib)
+    msg = str(err.value)
+    assert 'cavity_radial' in msg and 'id' in msg and 'other_id.up' in msg, msg

@@ -36,7 +36,8 @@ struct BatchedParamDeriv {
 // Hamiltonian ladders in one engine (upside_hip_construct_files): nodes whose parameter VALUES may differ per system while the
 // structure (node set, arguments, index datasets, shapes) is shared.  The table lists, per registry prefix, the datasets of the
 // node's group (and attributes of the group itself) that may differ; everything else of the node must be byte-identical to
-// system 0's file (checked by the engine before load_system_values is called).  Engine-internal, like BatchedParamDeriv.
+// system 0's file (checked by the engine before load_system_values is called).  Engine-internal, like BatchedParamDeriv; the nodes
+// implement it once, over their PerSystemTable (nodes.cpp).
 struct PerSystemValueSpec { std::string type; std::vector<std::string> datasets, attributes; };
 const std::vector<PerSystemValueSpec>& per_system_value_table();
 const PerSystemValueSpec* per_system_value_spec(const std::string& node_name);   // by the registry's prefix rule; NULL = not in the table
@@ -46,10 +47,9 @@ struct PerSystemValues {
     virtual void load_system_values(int system, hid_t_compat group) = 0;
     // after every system is loaded, before the first force pass: a node whose systems all agree keeps its single array (stride 0)
     virtual void finish_system_values() = 0;
-    virtual bool values_differ() const = 0;
-    // per-system set_param / get_param (nodes with parameters only)
-    virtual void set_param_system(int, const std::vector<float>&) { throw std::string("this node has no per-system parameters"); }
-    virtual std::vector<float> get_param_system(int) const { throw std::string("this node has no per-system parameters"); }
+    // per-system set_param / get_param; the nodes whose values come from files only refuse both
+    virtual void set_param_system(int system, const std::vector<float>& param) = 0;
+    virtual std::vector<float> get_param_system(int system) const = 0;
 };
 
 // A checked definition of collective variables (the CSR arrays of upside_hip_cv_define, the rmsd references centred in double) and

@@ -640,10 +640,6 @@ extern "C" int upk_spring_strided(const upk_launch_t* L, int kind, upk_coord_t p
     a.par_stride = par_stride;
     return fuse_submit(L, FOP_SPRING, a, n, {r_out(pos, false), r_slice(contrib, (size_t)n * kind * 12, (size_t)contrib_stride * 4, true), r_buf(pot_terms, pot_terms ? (size_t)n * 4 : 0, true)});
 }
-extern "C" int upk_spring(const upk_launch_t* L, int kind, upk_coord_t pos, const int* id, const float* equil, const float* k, int n,
-                          float* contrib, long contrib_stride, float* pot_terms) {
-    return upk_spring_strided(L, kind, pos, id, equil, k, 0, n, contrib, contrib_stride, pot_terms);
-}
 
 __global__ void k_cavity(upk_coord_t pos, const int* __restrict__ id, const float* __restrict__ radius, const float* __restrict__ kk, long par_stride,
                          int n, float* __restrict__ contrib, long contrib_stride, float* __restrict__ pot_terms) {   // bonds.cpp:350-372
@@ -668,10 +664,6 @@ extern "C" int upk_cavity_radial_strided(const upk_launch_t* L, upk_coord_t pos,
     UPK_FLUSH(L);
     hipLaunchKernelGGL(k_cavity, grid1(n, L->n_system), dim3(UPK_BLOCK), 0, ST(L), pos, id, radius, k, par_stride, n, contrib, contrib_stride, pot_terms);
     return launch_status();
-}
-extern "C" int upk_cavity_radial(const upk_launch_t* L, upk_coord_t pos, const int* id, const float* radius, const float* k, int n,
-                                 float* contrib, long contrib_stride, float* pot_terms) {
-    return upk_cavity_radial_strided(L, pos, id, radius, k, 0, n, contrib, contrib_stride, pot_terms);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -828,7 +820,8 @@ extern "C" int upk_nonlinear_coupling(const upk_launch_t* L, upk_coord_t input, 
 }
 
 // hbond_energy (hbond.cpp:430-444)
-// Ep_sys (may be NULL: Ep for every system): [S], one energy scale per system, read from the device so that a captured graph sees changes
+// Ep_sys: [S], one energy scale per system, read from the device so that a captured graph sees changes (the launcher always passes it;
+// the scalar Ep of a NULL Ep_sys is kept so that the fused kernel's code stays what it was)
 struct HBondEnergyArgs { upk_coord_t ph; float Ep; float* pot_terms; const float* Ep_sys; };
 __device__ __forceinline__ void b_hbond_energy(const int nv, const int s, upk_coord_t ph, float Ep, float* __restrict__ pot_terms, const float* __restrict__ Ep_sys) {
     if (nv >= ph.n_elem) return;
@@ -840,10 +833,6 @@ extern "C" int upk_hbond_energy_sys(const upk_launch_t* L, upk_coord_t protein_h
     FARGS(HBondEnergyArgs, a); a.ph = cz(protein_hbond); a.Ep_sys = E_protein; a.pot_terms = pot_terms;
     return fuse_submit(L, FOP_HBOND_ENERGY, a, protein_hbond.n_elem, {r_out(protein_hbond, false), r_sens(protein_hbond, true), r_buf(pot_terms, pot_terms ? (size_t)protein_hbond.n_elem * 4 : 0, true),
                                                                      r_slice(E_protein, 4, 4, false)});
-}
-extern "C" int upk_hbond_energy(const upk_launch_t* L, upk_coord_t protein_hbond, float E_protein, float* pot_terms) {
-    FARGS(HBondEnergyArgs, a); a.ph = cz(protein_hbond); a.Ep = E_protein; a.pot_terms = pot_terms;
-    return fuse_submit(L, FOP_HBOND_ENERGY, a, protein_hbond.n_elem, {r_out(protein_hbond, false), r_sens(protein_hbond, true), r_buf(pot_terms, pot_terms ? (size_t)protein_hbond.n_elem * 4 : 0, true)});
 }
 
 // protein_hbond helpers (hbond.cpp:320-335, 343-365)
@@ -1537,10 +1526,6 @@ extern "C" int upk_point_potential_strided(const upk_launch_t* L, int kind, upk_
                        contrib_stride, pot_terms);
     return launch_status();
 }
-extern "C" int upk_point_potential(const upk_launch_t* L, int kind, upk_coord_t pos, const int* id, const float* par, int n, float time,
-                                   float* contrib, long contrib_stride, float* pot_terms) {
-    return upk_point_potential_strided(L, kind, pos, id, par, 0, n, time, contrib, contrib_stride, pot_terms);
-}
 
 // contact (sidechain_radial.cpp:187-204): par is [n][4] = energy, dist, scale (1/width), cutoff
 __global__ void k_contact(upk_coord_t bead, const int* __restrict__ id, const float* __restrict__ par, long par_stride, int n, float* __restrict__ contrib,
@@ -1568,10 +1553,6 @@ extern "C" int upk_contact_strided(const upk_launch_t* L, upk_coord_t bead, cons
     UPK_FLUSH(L);
     hipLaunchKernelGGL(k_contact, grid1(n, L->n_system), dim3(UPK_BLOCK), 0, ST(L), bead, id, par, par_stride, n, contrib, contrib_stride, pot_terms);
     return launch_status();
-}
-extern "C" int upk_contact(const upk_launch_t* L, upk_coord_t bead, const int* id, const float* par, int n, float* contrib,
-                           long contrib_stride, float* pot_terms) {
-    return upk_contact_strided(L, bead, id, par, 0, n, contrib, contrib_stride, pot_terms);
 }
 
 // constant (bonds.cpp:550-587): the same values in every system;  slice (bonds.cpp:589-621)

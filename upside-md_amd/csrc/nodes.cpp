@@ -34,59 +34,99 @@ void require_injective(const vector<int>& loc, int n_target, const char* what) {
     }
 }
 
-// Per-system parameter values (PerSystemValues, engine.h): a node keeps the values of every system on the host, row 0 from its
-// own construction; only when some row differs from row 0 does the device array grow to [S][per] (stride per), otherwise it
-// stays the single row it was built with (stride 0: the same memory and arithmetic as an engine of identical systems).
-struct SysRows {
-    size_t per = 0; int S = 1; vector<float> host; bool differs = false;
-    void init(const vector<float>& row0, int n_system) { per = row0.size(); S = n_system; host.resize(per * (size_t)S); for (int s = 0; s < S; ++s) copy(row0.begin(), row0.end(), host.begin() + (size_t)s * per); }
-    void set_row(int s, const vector<float>& row) {
-        if (row.size() != per) throw string("per-system values of the wrong size");
-        copy(row.begin(), row.end(), host.begin() + (size_t)s * per);
-        if (memcmp(row.data(), host.data(), per * sizeof(float))) differs = true;
+// Per-system parameter values (PerSystemValues, engine.h) of the nodes in per_system_value_table(): the host values of every system,
+// row 0 from the node's own construction, behind one or two device arrays that the launcher reads with ONE row stride.  A row is the
+// node's arrays one after the other ([equil | k]); host and staging keep them as [n_array][S][per].  Two forms:
+//   shared until files differ: the device keeps the single construction row (stride 0: the memory and arithmetic of an engine of
+//     identical systems) unless a loaded row differs bytewise from row 0 in ANY array; then every array becomes [S][per] (stride per),
+//     once, in finish(), before the first force pass.  Such a table is never written afterwards.
+//   always full: [S][per] from construction on, pointer and stride fixed for the life of the node and rewritten in place by
+//     stream-ordered copies (write()), so a captured MD graph reads the values of the moment it is replayed.
+struct PerSystemTable {
+    DeviceCtx* ctx = nullptr; bool always_full = false, full = false; int n_array = 1, S = 1; size_t per = 0;
+    vector<float> host, staging;      // [n_array][S][per]; staging is the source of the copies of write()
+    DevBuf<float> dev[2];             // [S][per] each when full, else the one row [per]
+    void init(DeviceCtx* c, bool always_full_, int n_array_, const vector<float>& row0) {
+        ctx = c; always_full = full = always_full_; n_array = n_array_; S = c->n_system; per = row0.size() / n_array;
+        host.resize(row0.size() * (size_t)S);
+        for (int s = 0; s < S; ++s) set_row(s, row0);
+        for (int a = 0; a < n_array; ++a) dev[a].upload(vector<float>(block(a), block(a) + (full ? S : 1) * per));
     }
-    vector<float> row(int s) const { return vector<float>(host.begin() + (size_t)s * per, host.begin() + (size_t)(s + 1) * per); }
-    long stride() const { return differs ? (long)per : 0L; }
-    void upload_to(DevBuf<float>& d) const { if (differs) d.upload(host); }   // (unchanged single row otherwise)
+    const float* block(int a) const { return host.data() + (size_t)a * S * per; }
+    const float* ptr(int a = 0) const { return dev[a].p; }
+    long stride() const { return full ? (long)per : 0L; }
+    void set_row(int s, const vector<float>& row) {
+        if (row.size() != per * n_array) throw string("per-system values of the wrong size");
+        for (int a = 0; a < n_array; ++a) copy(row.begin() + a * per, row.begin() + (a + 1) * per, host.begin() + ((size_t)a * S + s) * per);
+    }
+    vector<float> row(int s) const {
+        vector<float> r;
+        for (int a = 0; a < n_array; ++a) r.insert(r.end(), block(a) + s * per, block(a) + (s + 1) * per);
+        return r;
+    }
+    void finish() {      // after every system's row is loaded
+        if (always_full) return write();
+        for (int a = 0; a < n_array; ++a) for (int s = 1; s < S; ++s) if (memcmp(block(a) + s * per, block(a), per * sizeof(float))) full = true;
+        if (full) for (int a = 0; a < n_array; ++a) dev[a].upload(vector<float>(block(a), block(a) + S * per));
+    }
+    void write() {       // (always full) the staging copy may be rewritten only once the previous copies have left it
+        hip_check(hipStreamSynchronize(ctx->stream), "hipStreamSynchronize");
+        staging = host;
+        for (int a = 0; a < n_array; ++a)
+            hip_check(hipMemcpyAsync(dev[a].p, staging.data() + (size_t)a * S * per, S * per * sizeof(float), hipMemcpyHostToDevice, ctx->stream), "H2D per-system values");
+    }
+};
+// datasets of n floats each, one after the other
+vector<float> read_columns(hid_t_compat g, initializer_list<const char*> names, int n) {
+    vector<float> row;
+    for (const char* nm : names) {
+        check_size(H(g), nm, {(size_t)n});
+        const auto v = read<float>(H(g), nm, 1);
+        row.insert(row.end(), v.begin(), v.end());
+    }
+    return row;
+}
+// A node of the table: it reads and checks one system's row from a group of its type (read_row); the always-full ones also take a
+// row through set_param_system (check_param refuses a malformed one).
+struct TableNode : PerSystemValues {
+    PerSystemTable tab;
+    virtual vector<float> read_row(hid_t_compat group) const = 0;
+    virtual void check_param(const vector<float>&) const {}
+    void load_system_values(int s, hid_t_compat g) override { tab.set_row(s, read_row(g)); }
+    void finish_system_values() override { tab.finish(); }
+    void require_settable() const { if (!tab.always_full) throw string("this node has no per-system parameters"); }
+    void set_param_system(int s, const vector<float>& p) override { require_settable(); check_param(p); tab.set_row(s, p); tab.write(); }
+    vector<float> get_param_system(int s) const override { require_settable(); return tab.row(s); }
+    void set_param_all(const vector<float>& p) {      // every system, as the reference's set_param
+        check_param(p);
+        for (int s = 0; s < tab.S; ++s) tab.set_row(s, p);
+        tab.write();
+    }
 };
 
 // ---------------------------------------------------------------------------------------------------
 // bonded springs: bonds.cpp:252-320 (dist_spring), 430-489 (angle_spring), 492-547 (dihedral_spring)
-struct SpringNode : public PotentialNode, PerSystemValues {
+struct SpringNode : public PotentialNode, TableNode {
     int kind, n_elem;
     CoordNode& pos;
-    DevBuf<int> id; DevBuf<float> equil, k;
+    DevBuf<int> id;      // (tab: [equil_dist | spring_const], n_elem each)
     int src = -1;
-    SysRows equil_rows, k_rows;      // [S][n_elem] each
-    void load_system_values(int s, hid_t_compat g) override {
-        check_size(H(g), "equil_dist", {(size_t)n_elem}); check_size(H(g), "spring_const", {(size_t)n_elem});
-        equil_rows.set_row(s, read<float>(H(g), "equil_dist", 1)); k_rows.set_row(s, read<float>(H(g), "spring_const", 1));
-    }
-    bool values_differ() const override { return equil_rows.differs || k_rows.differs; }
-    void finish_system_values() override {   // (one stride for both: both become [S][n] when either differs)
-        if (!values_differ()) return;
-        equil_rows.differs = k_rows.differs = true;
-        equil_rows.upload_to(equil); k_rows.upload_to(k);
-    }
+    vector<float> read_row(hid_t_compat g) const override { return read_columns(g, {"equil_dist", "spring_const"}, n_elem); }
     SpringNode(DeviceCtx* c, hid_t_compat grp, CoordNode& pos_, int kind_) : PotentialNode(c), kind(kind_), pos(pos_) {
         vector<hsize_t> dims;
         auto ids = read<int>(H(grp), "id", 2, &dims);
         n_elem = (int)dims[0];
         if ((int)dims[1] != kind) throw string("wrong width for id");
-        check_size(H(grp), "equil_dist", {(size_t)n_elem});
-        check_size(H(grp), "spring_const", {(size_t)n_elem});
         if (kind == 2) { check_size(H(grp), "bonded_atoms", {(size_t)n_elem}); bonded_atoms = read<int>(H(grp), "bonded_atoms", 1); }
         for (int x : ids) if (x < 0 || x >= pos.n_elem) throw string("atom index out of range");
         id.upload(ids);
-        equil.upload(read<float>(H(grp), "equil_dist", 1));
-        k.upload(read<float>(H(grp), "spring_const", 1));
-        equil_rows.init(equil.download(), c->n_system); k_rows.init(k.download(), c->n_system);
+        tab.init(c, false, 2, read_row(grp));
         src = pos.scatter.add_source(n_elem, kind, 3, ids);
         alloc_terms(n_elem);
         fused_forward = fused_backward = true;
     }
     void compute_value(ComputeMode mode) override {
-        upk_check(upk_spring_strided(&ctx->L, kind, pos.coord(), id.p, equil.p, k.p, equil_rows.stride(), n_elem, pos.scatter.source_ptr(src), pos.scatter.arena_size,
+        upk_check(upk_spring_strided(&ctx->L, kind, pos.coord(), id.p, tab.ptr(0), tab.ptr(1), tab.stride(), n_elem, pos.scatter.source_ptr(src), pos.scatter.arena_size,
                              mode == PotentialAndDerivMode ? pot_terms.p : nullptr), "spring");
         if (mode == PotentialAndDerivMode) reduce_terms();
     }
@@ -102,31 +142,19 @@ RegisterNodeType<Builtin<AngleSpring>, 1> angle_spring_node("angle_spring");
 RegisterNodeType<Builtin<DihedralSpring>, 1> dihedral_spring_node("dihedral_spring");
 
 // cavity_radial: bonds.cpp:323-374 (used to compact synthetic chains)
-struct CavityRadial : public PotentialNode, PerSystemValues {
+struct CavityRadial : public PotentialNode, TableNode {
     int n_term; CoordNode& pos;
-    DevBuf<int> id; DevBuf<float> radius, k; int src;
-    SysRows radius_rows, k_rows;
-    void load_system_values(int s, hid_t_compat g) override {
-        check_size(H(g), "radius", {(size_t)n_term}); check_size(H(g), "spring_constant", {(size_t)n_term});
-        radius_rows.set_row(s, read<float>(H(g), "radius", 1)); k_rows.set_row(s, read<float>(H(g), "spring_constant", 1));
-    }
-    bool values_differ() const override { return radius_rows.differs || k_rows.differs; }
-    void finish_system_values() override {
-        if (!values_differ()) return;
-        radius_rows.differs = k_rows.differs = true;
-        radius_rows.upload_to(radius); k_rows.upload_to(k);
-    }
+    DevBuf<int> id; int src;      // (tab: [radius | spring_constant], n_term each)
+    vector<float> read_row(hid_t_compat g) const override { return read_columns(g, {"radius", "spring_constant"}, n_term); }
     CavityRadial(DeviceCtx* c, hid_t_compat grp, CoordNode& pos_) : PotentialNode(c), pos(pos_) {
         auto ids = read<int>(H(grp), "id", 1);
         n_term = (int)ids.size();
-        check_size(H(grp), "radius", {(size_t)n_term}); check_size(H(grp), "spring_constant", {(size_t)n_term});
-        id.upload(ids); radius.upload(read<float>(H(grp), "radius", 1)); k.upload(read<float>(H(grp), "spring_constant", 1));
-        radius_rows.init(radius.download(), c->n_system); k_rows.init(k.download(), c->n_system);
+        id.upload(ids); tab.init(c, false, 2, read_row(grp));
         src = pos.scatter.add_source(n_term, 1, 3, ids);
         alloc_terms(n_term);
     }
     void compute_value(ComputeMode mode) override {
-        upk_check(upk_cavity_radial_strided(&ctx->L, pos.coord(), id.p, radius.p, k.p, radius_rows.stride(), n_term, pos.scatter.source_ptr(src), pos.scatter.arena_size,
+        upk_check(upk_cavity_radial_strided(&ctx->L, pos.coord(), id.p, tab.ptr(0), tab.ptr(1), tab.stride(), n_term, pos.scatter.source_ptr(src), pos.scatter.arena_size,
                                     mode == PotentialAndDerivMode ? pot_terms.p : nullptr), "cavity_radial");
         if (mode == PotentialAndDerivMode) reduce_terms();
     }
@@ -889,48 +917,28 @@ struct EnvironmentCoverage : public CoordNode, BatchedParamDeriv {
 RegisterNodeType<Builtin<EnvironmentCoverage>, 2> environment_coverage_node("environment_coverage");
 
 // hbond_energy: hbond.cpp:417-456
-// E_protein is a device array of one value per system (E_dev), written by stream-ordered copies: a captured MD graph reads the
-// values of the moment it is replayed, and set_param needs no new capture.
-struct HBondEnergy : public HBondCounter, BatchedParamDeriv, PerSystemValues {
-    CoordNode& protein_hbond; float E_protein;
-    vector<float> E_sys; DevBuf<float> E_dev;      // [S]
-    HBondEnergy(DeviceCtx* c, hid_t_compat grp, CoordNode& ph) : HBondCounter(c), protein_hbond(ph), E_protein(attr<float>(H(grp), ".", "protein_hbond_energy")) {
+// E_protein is an always-full table of one value per system: set_param needs no new capture of the MD graph.
+struct HBondEnergy : public HBondCounter, BatchedParamDeriv, TableNode {
+    CoordNode& protein_hbond;
+    vector<float> read_row(hid_t_compat g) const override { return vector<float>(1, attr<float>(H(g), ".", "protein_hbond_energy")); }
+    void check_param(const vector<float>& p) const override { if (p.size() != 1u) throw string("expected 1 param to hbond_energy but got " + to_string(p.size())); }
+    HBondEnergy(DeviceCtx* c, hid_t_compat grp, CoordNode& ph) : HBondCounter(c), protein_hbond(ph) {
         check_elem_width(ph, 7);
         alloc_terms(ph.n_elem);
         fused_forward = fused_backward = true;
-        E_sys.assign(c->n_system, E_protein); E_dev.upload(E_sys);
+        tab.init(c, true, 1, read_row(grp));
     }
     void compute_value(ComputeMode mode) override {
-        upk_check(upk_hbond_energy_sys(&ctx->L, protein_hbond.coord(), E_dev.p, mode == PotentialAndDerivMode ? pot_terms.p : nullptr), "hbond_energy");
+        upk_check(upk_hbond_energy_sys(&ctx->L, protein_hbond.coord(), tab.ptr(), mode == PotentialAndDerivMode ? pot_terms.p : nullptr), "hbond_energy");
         if (mode == PotentialAndDerivMode) reduce_terms();
     }
-    void write_E() {      // the host row may be rewritten only once the previous copy has left it
-        hip_check(hipStreamSynchronize(ctx->stream), "hipStreamSynchronize");
-        E_host_staging = E_sys;
-        hip_check(hipMemcpyAsync(E_dev.p, E_host_staging.data(), E_sys.size() * sizeof(float), hipMemcpyHostToDevice, ctx->stream), "H2D E_protein");
-    }
-    vector<float> E_host_staging;
-    void load_system_values(int s, hid_t_compat g) override { E_sys[s] = attr<float>(H(g), ".", "protein_hbond_energy"); }
-    bool values_differ() const override { for (float x : E_sys) if (memcmp(&x, &E_sys[0], sizeof(float))) return true; return false; }
-    void finish_system_values() override { E_dev.upload(E_sys); }
-    void set_param_system(int s, const vector<float>& p) override {
-        if (p.size() != 1u) throw string("expected 1 param to hbond_energy but got " + to_string(p.size()));
-        E_sys.at(s) = p[0];
-        write_E();
-    }
-    vector<float> get_param_system(int s) const override { return vector<float>(1, E_sys.at(s)); }
-    vector<float> get_param() const override { return vector<float>(1, E_sys[0]); }
+    vector<float> get_param() const override { return tab.row(0); }
     vector<float> get_param_deriv(int system) override {   // hbond.cpp:447-448: n_hbond of the last evaluation
         return param_deriv_table(ctx, 1, [&](float* t) { upk_check(upk_column_sum(&ctx->L, protein_hbond.coord(), 6, system, t), "hbond_energy param_deriv"); });
     }
     size_t param_deriv_size() const override { return 1; }
     void param_deriv_all(float* dev) override { upk_check(upk_column_sum_all(&ctx->L, protein_hbond.coord(), 6, dev), "hbond_energy param_deriv_all"); }
-    void set_param(const vector<float>& p) override {
-        if (p.size() != 1u) throw string("expected 1 param to hbond_energy but got " + to_string(p.size()));
-        E_protein = p[0];
-        fill(E_sys.begin(), E_sys.end(), E_protein);      // (every system, as the reference's set_param)
-        write_E();
-    }
+    void set_param(const vector<float>& p) override { set_param_all(p); }
 };
 RegisterNodeType<Builtin<HBondEnergy>, 1> hbond_energy_node("hbond_energy");
 
@@ -1000,11 +1008,10 @@ RegisterNodeType<Builtin<NonlinearCoupling>, 1> nonlinear_coupling_node("nonline
 // Optional restraint / external-field nodes (not emitted for the README force field)
 
 // atom_pos_spring (bonds.cpp:9-50), tension (:53-90), AFM (:93-168), z_flat_bottom (:377-427): one atom per term
-struct PointPotential : public PotentialNode, PerSystemValues {
-    int kind, n_term; CoordNode& pos; DevBuf<int> id; DevBuf<float> par; int src;
+struct PointPotential : public PotentialNode, TableNode {
+    int kind, n_term; CoordNode& pos; DevBuf<int> id; int src;      // (tab: [n_term][8])
     float time_initial = 0.f, time_step = 0.f; int round_num = 0;     // AFM only (the tip clock is the engine's: its attributes agree across systems)
-    SysRows par_rows;      // [S][n_term * 8]
-    vector<float> read_par(hid_t_compat grp) {
+    vector<float> read_row(hid_t_compat grp) const override {
         vector<float> p((size_t)n_term * 8, 0.f);
         auto col = [&](const char* name, int off) {
             check_size(H(grp), name, {(size_t)n_term});
@@ -1027,21 +1034,18 @@ struct PointPotential : public PotentialNode, PerSystemValues {
         auto ids = read<int>(H(grp), id_name, 1);
         n_term = (int)ids.size();
         for (int x : ids) if (x < 0 || x >= pos.n_elem) throw string("atom index out of range");
-        auto p = read_par(grp);
+        auto p = read_row(grp);
         if (kind == 2) { time_initial = attr<float>(H(grp), "pulling_vel", "time_initial"); time_step = attr<float>(H(grp), "pulling_vel", "time_step"); }
-        id.upload(ids); par.upload(p); par_rows.init(p, c->n_system);
+        id.upload(ids); tab.init(c, false, 1, p);
         src = pos.scatter.add_source(n_term, 1, 3, ids);
         alloc_terms(n_term);
     }
-    void load_system_values(int s, hid_t_compat g) override { par_rows.set_row(s, read_par(g)); }
-    bool values_differ() const override { return par_rows.differs; }
-    void finish_system_values() override { par_rows.upload_to(par); }
     bool capturable() const override { return kind != 2; }   // the AFM tip position travels as a kernel argument
     void add_loggers(vector<LogValue>& out) override {   // bonds.cpp:130-145 (AFM only, basic level)
         if (kind != 2) return;
         LogValue tip; tip.name = "tip_pos"; tip.dims = {(size_t)n_term, 3}; tip.level = 0;
         tip.fill = [this](int sys, float* b) {      // (the system's own row)
-            auto p = par_rows.row(sys); const float t = time_initial + time_step * round_num;
+            auto p = tab.row(sys); const float t = time_initial + time_step * round_num;
             for (int i = 0; i < n_term; ++i) for (int d = 0; d < 3; ++d) b[i * 3 + d] = p[(size_t)i * 8 + 1 + d] + p[(size_t)i * 8 + 4 + d] * t; };
         out.push_back(tip);
         LogValue te; te.name = "time_estimate"; te.dims = {1}; te.level = 0;
@@ -1054,7 +1058,7 @@ struct PointPotential : public PotentialNode, PerSystemValues {
             if (mode == DerivMode) round_num += 1;
             time = time_initial + time_step * round_num;
         }
-        upk_check(upk_point_potential_strided(&ctx->L, kind, pos.coord(), id.p, par.p, par_rows.stride(), n_term, time, pos.scatter.source_ptr(src), pos.scatter.arena_size,
+        upk_check(upk_point_potential_strided(&ctx->L, kind, pos.coord(), id.p, tab.ptr(), tab.stride(), n_term, time, pos.scatter.source_ptr(src), pos.scatter.arena_size,
                                       mode == PotentialAndDerivMode ? pot_terms.p : nullptr), "point_potential");
         if (mode == PotentialAndDerivMode) reduce_terms();
     }
@@ -1069,10 +1073,10 @@ RegisterNodeType<Builtin<AFMPotential>, 1> AFM_node("AFM");
 RegisterNodeType<Builtin<ZFlatBottom>, 1> z_flat_bottom_node("z_flat_bottom");
 
 // contact: sidechain_radial.cpp:139-205
-struct ContactEnergy : public PotentialNode, PerSystemValues {
-    int n_contact; CoordNode& bead_pos; DevBuf<int> id; DevBuf<float> par; int src; vector<int> host_id;
-    SysRows par_rows;      // [S][n_contact * 4]: the derived scale and cutoff columns per system too
-    vector<float> read_par(hid_t_compat grp) {
+struct ContactEnergy : public PotentialNode, TableNode {
+    int n_contact; CoordNode& bead_pos; DevBuf<int> id; int src; vector<int> host_id;
+    // (tab: [n_contact][4], the derived scale and cutoff columns per system too)
+    vector<float> read_row(hid_t_compat grp) const override {
         check_size(H(grp), "energy", {(size_t)n_contact}); check_size(H(grp), "distance", {(size_t)n_contact}); check_size(H(grp), "width", {(size_t)n_contact});
         auto en = read<float>(H(grp), "energy", 1), dist = read<float>(H(grp), "distance", 1), width = read<float>(H(grp), "width", 1);
         vector<float> p((size_t)n_contact * 4);
@@ -1082,9 +1086,6 @@ struct ContactEnergy : public PotentialNode, PerSystemValues {
         }
         return p;
     }
-    void load_system_values(int s, hid_t_compat g) override { par_rows.set_row(s, read_par(g)); }
-    bool values_differ() const override { return par_rows.differs; }
-    void finish_system_values() override { par_rows.upload_to(par); }
     ContactEnergy(DeviceCtx* c, hid_t_compat grp, CoordNode& bead_pos_) : PotentialNode(c), bead_pos(bead_pos_) {
         check_elem_width_lower_bound(bead_pos, 3);
         vector<hsize_t> dims;
@@ -1092,8 +1093,7 @@ struct ContactEnergy : public PotentialNode, PerSystemValues {
         n_contact = (int)dims[0];
         if ((int)dims[1] != 2) throw string("wrong width for id");
         for (int x : ids) if (x < 0 || x >= bead_pos.n_elem) throw string("contact index out of range");
-        auto p = read_par(grp);
-        id.upload(ids); par.upload(p); host_id = ids; par_rows.init(p, c->n_system);
+        id.upload(ids); host_id = ids; tab.init(c, false, 1, read_row(grp));
         src = bead_pos.scatter.add_source(n_contact, 2, 3, ids);
         alloc_terms(n_contact);
     }
@@ -1107,7 +1107,7 @@ struct ContactEnergy : public PotentialNode, PerSystemValues {
         out.push_back(l);
     }
     void compute_value(ComputeMode mode) override {
-        upk_check(upk_contact_strided(&ctx->L, bead_pos.coord(), id.p, par.p, par_rows.stride(), n_contact, bead_pos.scatter.source_ptr(src), bead_pos.scatter.arena_size,
+        upk_check(upk_contact_strided(&ctx->L, bead_pos.coord(), id.p, tab.ptr(), tab.stride(), n_contact, bead_pos.scatter.source_ptr(src), bead_pos.scatter.arena_size,
                               mode == PotentialAndDerivMode ? pot_terms.p : nullptr), "contact");
         if (mode == PotentialAndDerivMode) reduce_terms();
     }
@@ -1811,19 +1811,44 @@ struct ScaledSum : public PotentialNode, BatchedParamDeriv {
 };
 RegisterNodeType<Builtin<ScaledSum>, 1> scaled_sum_node("scaled_sum");
 
-// cv_restraint: an umbrella bias on collective variables (this project's own node; the reference has none).  The group holds a CV
-// definition in the datasets of /input/collective_variables plus center, spring_const and flat_width (n_cv each):
+// What cv_restraint and cv_metadynamics share: a CV definition in the datasets of /input/collective_variables, read and checked on
+// the host by the constructor; the node's type then checks the rest of its group and calls install(), so that nothing touches the
+// device or pos' scatter plan before every host-side check has passed.  v_c is the very number upside_hip_cv_compute reports.
+struct CVBiasNode : public PotentialNode {
+    const string type; CoordNode& pos; int n_cv = 0, n_entry = 0, src = -1;
+    CvHostDefinition host_def; CvDeviceDefinition def;
+    DevBuf<float> values;      // [S][n_cv] of the last force pass
+    CVBiasNode(DeviceCtx* c, hid_t_compat grp, CoordNode& pos_, const char* type_) : PotentialNode(c), type(type_), pos(pos_) {
+        check_elem_width_lower_bound(pos, 3);
+        host_def = cv_read_definition(grp, pos.n_elem, type);
+        if (host_def.n_cv < 1) throw type + ": no collective variables";
+        n_cv = host_def.n_cv; n_entry = host_def.atom_start[n_cv];
+    }
+    void install() {
+        def.upload(host_def);
+        values.alloc((size_t)ctx->n_system * n_cv);
+        src = pos.scatter.add_source(n_entry, 1, 3, host_def.atoms);
+    }
+    vector<float> all_values() {
+        hip_check(hipStreamSynchronize(ctx->stream), "hipStreamSynchronize");
+        return values.download();
+    }
+    vector<float> get_value_by_name(const char* log_name) override {
+        if (string(log_name) != "cv_value") throw type + ": no value named " + log_name + " (cv_value)";
+        auto v = all_values(); v.resize((size_t)n_cv);
+        return v;
+    }
+};
+
+// cv_restraint: an umbrella bias on collective variables (this project's own node; the reference has none).  Besides the CV
+// definition the group holds center, spring_const and flat_width (n_cv each):
 //   E = sum_c 1/2 k_c u_c^2,  u_c = max(0, |v_c - center_c| - flat_width_c)
-// with v_c the very number upside_hip_cv_compute reports (kernels_cv.hip: k_cv_restraint).  The values [center | spring_const |
-// flat_width] are a device table of one row per system, rewritten in place by stream-ordered copies (like hbond_energy's E_dev):
-// no kernel argument ever changes, so a captured MD graph reads the values of the moment it is replayed.
-// (The launcher takes a row stride like the other per-system launchers; this node, its only caller, always passes the full table's
-// 3 n_cv, so a shared single row -- stride 0 -- is not a path the library or its tests exercise.)
-struct CVRestraint : public PotentialNode, PerSystemValues {
-    CoordNode& pos; int n_cv = 0, n_entry = 0, src = -1;
-    CvDeviceDefinition def;
-    vector<float> par_sys, par_staging; DevBuf<float> par, values;      // [S][3 n_cv], [S][n_cv]
-    static void check_values(const vector<float>& p, size_t n_cv) {
+// (kernels_cv.hip: k_cv_restraint).  The values [center | spring_const | flat_width] are an always-full table of one row per system,
+// like hbond_energy's: no kernel argument ever changes.  (The launcher takes a row stride like the other per-system launchers; this
+// node, its only caller, always passes 3 n_cv, so a shared single row -- stride 0 -- is not a path the library or its tests exercise.)
+struct CVRestraint : public CVBiasNode, TableNode {
+    void check_param(const vector<float>& p) const override {
+        const size_t n_cv = (size_t)this->n_cv;
         if (p.size() != 3 * n_cv) throw string("expected ") + to_string(3 * n_cv) + " values [center | spring_const | flat_width] but got " + to_string(p.size());
         for (size_t c = 0; c < n_cv; ++c) {
             if (!std::isfinite(p[c])) throw string("center of CV ") + to_string(c) + " is not finite";
@@ -1831,64 +1856,29 @@ struct CVRestraint : public PotentialNode, PerSystemValues {
             if (!(p[2 * n_cv + c] >= 0.f) || !std::isfinite(p[2 * n_cv + c])) throw string("flat_width of CV ") + to_string(c) + " must be finite and not negative";
         }
     }
-    vector<float> read_values(hid_t_compat g) const {
+    vector<float> read_row(hid_t_compat g) const override {
         vector<float> p;
         for (const char* nm : {"center", "spring_const", "flat_width"}) {
             auto v = read<float>(H(g), nm, 1);
             if ((int)v.size() != n_cv) throw string(nm) + " holds " + to_string(v.size()) + " entries, the node has " + to_string(n_cv) + " CVs";
             p.insert(p.end(), v.begin(), v.end());
         }
-        check_values(p, (size_t)n_cv);
+        check_param(p);
         return p;
     }
-    CVRestraint(DeviceCtx* c, hid_t_compat grp, CoordNode& pos_) : PotentialNode(c), pos(pos_) {
-        check_elem_width_lower_bound(pos, 3);
-        // everything is read and checked on the host before the first device array is touched
-        const CvHostDefinition h = cv_read_definition(grp, pos.n_elem, "cv_restraint");
-        if (h.n_cv < 1) throw string("cv_restraint: no collective variables");
-        n_cv = h.n_cv; n_entry = h.atom_start[n_cv];
-        const auto row0 = read_values(grp);
-        def.upload(h);
-        par_sys.resize((size_t)c->n_system * row0.size());
-        for (int s = 0; s < c->n_system; ++s) copy(row0.begin(), row0.end(), par_sys.begin() + (size_t)s * row0.size());
-        par.upload(par_sys); values.alloc((size_t)c->n_system * n_cv);
-        src = pos.scatter.add_source(n_entry, 1, 3, h.atoms);
+    CVRestraint(DeviceCtx* c, hid_t_compat grp, CoordNode& pos_) : CVBiasNode(c, grp, pos_, "cv_restraint") {
+        const auto row0 = read_row(grp);
+        install();
+        tab.init(c, true, 1, row0);
         alloc_terms(n_cv);
     }
     void compute_value(ComputeMode mode) override {
-        upk_check(upk_cv_restraint(&ctx->L, pos.coord(), &def.C, par.p, 3L * n_cv, pos.scatter.source_ptr(src), pos.scatter.arena_size, values.p,
+        upk_check(upk_cv_restraint(&ctx->L, pos.coord(), &def.C, tab.ptr(), tab.stride(), pos.scatter.source_ptr(src), pos.scatter.arena_size, values.p,
                                    mode == PotentialAndDerivMode ? pot_terms.p : nullptr), "cv_restraint");
         if (mode == PotentialAndDerivMode) reduce_terms();
     }
-    void write_par() {      // the staging row may be rewritten only once the previous copy has left it
-        hip_check(hipStreamSynchronize(ctx->stream), "hipStreamSynchronize");
-        par_staging = par_sys;
-        hip_check(hipMemcpyAsync(par.p, par_staging.data(), par_sys.size() * sizeof(float), hipMemcpyHostToDevice, ctx->stream), "H2D cv_restraint values");
-    }
-    void load_system_values(int s, hid_t_compat g) override { const auto p = read_values(g); copy(p.begin(), p.end(), par_sys.begin() + (size_t)s * p.size()); }
-    bool values_differ() const override { for (int s = 1; s < ctx->n_system; ++s) if (memcmp(&par_sys[(size_t)s * 3 * n_cv], &par_sys[0], 3 * n_cv * sizeof(float))) return true; return false; }
-    void finish_system_values() override { write_par(); }
-    void set_param_system(int s, const vector<float>& p) override {
-        check_values(p, (size_t)n_cv);
-        copy(p.begin(), p.end(), par_sys.begin() + (size_t)s * p.size());
-        write_par();
-    }
-    vector<float> get_param_system(int s) const override { return vector<float>(par_sys.begin() + (size_t)s * 3 * n_cv, par_sys.begin() + (size_t)(s + 1) * 3 * n_cv); }
-    vector<float> get_param() const override { return get_param_system(0); }
-    void set_param(const vector<float>& p) override {      // every system, as the reference's set_param
-        check_values(p, (size_t)n_cv);
-        for (int s = 0; s < ctx->n_system; ++s) copy(p.begin(), p.end(), par_sys.begin() + (size_t)s * p.size());
-        write_par();
-    }
-    vector<float> all_values() {      // [S][n_cv] of the last force pass
-        hip_check(hipStreamSynchronize(ctx->stream), "hipStreamSynchronize");
-        return values.download();
-    }
-    vector<float> get_value_by_name(const char* log_name) override {
-        if (string(log_name) != "cv_value") throw string("cv_restraint: no value named ") + log_name + " (cv_value)";
-        auto v = all_values(); v.resize((size_t)n_cv);
-        return v;
-    }
+    vector<float> get_param() const override { return tab.row(0); }
+    void set_param(const vector<float>& p) override { set_param_all(p); }
 };
 RegisterNodeType<Builtin<CVRestraint>, 1> cv_restraint_node("cv_restraint");
 
@@ -1901,24 +1891,19 @@ RegisterNodeType<Builtin<CVRestraint>, 1> cv_restraint_node("cv_restraint");
 // completed MD round), so no kernel argument ever changes and a captured MD graph replays the deposition.  Hills belong to the
 // system index: exchanging coordinates between systems leaves them where they are, as it leaves a Hamiltonian.
 // Not PerSystemValues: the files of one engine must agree on the whole group.
-struct CVMetadynamics : public PotentialNode, RoundEndWork {
-    CoordNode& pos; int n_cv = 0, n_entry = 0, src = -1, capacity = 0, n_list = 1; bool shared = false;
-    CvDeviceDefinition def; upk_cv_metad_t M{};
-    DevBuf<float> hills, sigma, values; DevBuf<int> n_deposit, n_attempt; DevBuf<unsigned long long> rounds;
+struct CVMetadynamics : public CVBiasNode, RoundEndWork {
+    int capacity = 0, n_list = 1; bool shared = false;
+    upk_cv_metad_t M{};
+    DevBuf<float> hills, sigma; DevBuf<int> n_deposit, n_attempt; DevBuf<unsigned long long> rounds;
     vector<float> hill_staging; vector<int> count_staging;      // sources of the stream-ordered copies of write_hills
     static float positive_attr(hid_t_compat grp, const char* nm, bool zero_ok) {
         const float v = attr<float>(H(grp), ".", nm);
         if (!std::isfinite(v) || v < 0.f || (!zero_ok && v == 0.f)) throw string("cv_metadynamics: ") + nm + " must be finite and " + (zero_ok ? "not negative" : "positive");
         return v;
     }
-    CVMetadynamics(DeviceCtx* c, hid_t_compat grp, CoordNode& pos_) : PotentialNode(c), pos(pos_) {
-        check_elem_width_lower_bound(pos, 3);
-        // everything is read and checked on the host before the first device array is touched
-        const CvHostDefinition h = cv_read_definition(grp, pos.n_elem, "cv_metadynamics");
-        if (h.n_cv < 1) throw string("cv_metadynamics: no collective variables");
-        if (h.n_cv > UPK_METAD_MAX_DIM)
-            throw string("cv_metadynamics: ") + to_string(h.n_cv) + " CVs span more dimensions than the limit of " + to_string(UPK_METAD_MAX_DIM) + " (UPK_METAD_MAX_DIM)";
-        n_cv = h.n_cv; n_entry = h.atom_start[n_cv];
+    CVMetadynamics(DeviceCtx* c, hid_t_compat grp, CoordNode& pos_) : CVBiasNode(c, grp, pos_, "cv_metadynamics") {
+        if (n_cv > UPK_METAD_MAX_DIM)
+            throw string("cv_metadynamics: ") + to_string(n_cv) + " CVs span more dimensions than the limit of " + to_string(UPK_METAD_MAX_DIM) + " (UPK_METAD_MAX_DIM)";
         const auto sg = read<float>(H(grp), "sigma", 1);
         if ((int)sg.size() != n_cv) throw string("cv_metadynamics: sigma holds ") + to_string(sg.size()) + " entries, the node has " + to_string(n_cv) + " CVs";
         for (int k = 0; k < n_cv; ++k) if (!std::isfinite(sg[k]) || !(sg[k] > 0.f)) throw string("cv_metadynamics: sigma of CV ") + to_string(k) + " must be finite and positive";
@@ -1930,12 +1915,11 @@ struct CVMetadynamics : public PotentialNode, RoundEndWork {
         if (sh != 0 && sh != 1) throw string("cv_metadynamics: shared must be 0 or 1");
         M.pace = pace; M.capacity = capacity = cap; M.shared = sh; shared = sh != 0;
         n_list = shared ? 1 : c->n_system;
-        def.upload(h);
+        install();
         sigma.upload(sg);
         hills.alloc((size_t)n_list * (n_cv + 1) * capacity);
-        n_deposit.alloc(c->n_system); n_attempt.alloc(c->n_system); rounds.alloc(c->n_system); values.alloc((size_t)c->n_system * n_cv);
+        n_deposit.alloc(c->n_system); n_attempt.alloc(c->n_system); rounds.alloc(c->n_system);
         M.hills = hills.p; M.sigma = sigma.p; M.n_deposit = n_deposit.p; M.n_attempt = n_attempt.p; M.rounds = rounds.p;
-        src = pos.scatter.add_source(n_entry, 1, 3, h.atoms);
         alloc_terms(1);
     }
     void compute_value(ComputeMode mode) override {
@@ -1985,29 +1969,21 @@ struct CVMetadynamics : public PotentialNode, RoundEndWork {
         for (int* dst : {n_deposit.p, n_attempt.p})
             hip_check(hipMemcpyAsync(dst + first, count_staging.data(), (size_t)count * sizeof(int), hipMemcpyHostToDevice, ctx->stream), "H2D hill counters");
     }
-    vector<float> all_values() {      // [S][d] of the last force pass
-        hip_check(hipStreamSynchronize(ctx->stream), "hipStreamSynchronize");
-        return values.download();
-    }
-    vector<float> get_value_by_name(const char* log_name) override {
-        if (string(log_name) != "cv_value") throw string("cv_metadynamics: no value named ") + log_name + " (cv_value)";
-        auto v = all_values(); v.resize((size_t)n_cv);
-        return v;
-    }
 };
 RegisterNodeType<Builtin<CVMetadynamics>, 1> cv_metadynamics_node("cv_metadynamics");
 
 }  // namespace
 
 // accessors used by the C-ABI layer (engine_c_api.cpp)
+template <class T> static T* node_as(DerivEngine& e, const string& node_name) { return dynamic_cast<T*>(e.get(node_name).computation.get()); }
 int engine_cv_restraint_values(DerivEngine& e, const string& node_name, vector<float>* out) {      // n_cv; out (may be NULL): [S][n_cv]
-    auto* r = dynamic_cast<CVRestraint*>(e.get(node_name).computation.get());
+    auto* r = node_as<CVRestraint>(e, node_name);
     if (!r) return -1;
     if (out) *out = r->all_values();
     return r->n_cv;
 }
 static CVMetadynamics& metad_node(DerivEngine& e, const string& node_name) {
-    auto* m = dynamic_cast<CVMetadynamics*>(e.get(node_name).computation.get());
+    auto* m = node_as<CVMetadynamics>(e, node_name);
     if (!m) throw string("node ") + node_name + " is not a cv_metadynamics";
     return *m;
 }
@@ -2147,7 +2123,7 @@ double engine_igraph_bytes(DerivEngine& e) {
     return b;
 }
 
-// the values that may differ per system in one engine (upside_hip_construct_files); the nodes above implement PerSystemValues
+// the values that may differ per system in one engine (upside_hip_construct_files); the nodes above keep them in a PerSystemTable
 const vector<PerSystemValueSpec>& per_system_value_table() {
     static const vector<PerSystemValueSpec> t = {
         {"dist_spring", {"equil_dist", "spring_const"}, {}},
