@@ -109,7 +109,8 @@ int upside_hip_recenter_axes(DerivEngine* engine, int xy_only);
 
 /* Replica-exchange swap attempt among the systems of THIS engine (main.cpp:227-275): pairs (n_pair,2) are
  * one swap set; energies are evaluated, Metropolis tested with the REPLICA_EXCHANGE random stream
- * (random.h:26, keyed by round) and accepted pairs exchange coordinates.  accepted (n_pair) out. */
+ * (random.h:26, keyed by round) and accepted pairs exchange coordinates.  accepted (n_pair) out.  No system may appear
+ * twice in a set ("Overlapping indices in swap set.", as in the reference). */
 int upside_hip_replica_swap(DerivEngine* engine, int n_pair, const int* pairs, uint32_t base_seed,
                             uint64_t round, int* accepted);
 /* the same for the second and later swap sets of one attempt (main.cpp:249: ONE generator per attempt_swaps call):
@@ -117,7 +118,9 @@ int upside_hip_replica_swap(DerivEngine* engine, int n_pair, const int* pairs, u
 int upside_hip_replica_swap_from(DerivEngine* engine, int n_pair, const int* pairs, uint32_t base_seed,
                                  uint64_t round, int draw0, int* accepted);
 /* a later swap set of the SAME attempt without a new force evaluation: in a temperature-only exchange the accepted pairs
- * of the earlier sets merely traded their energies (the reference re-evaluates, main.cpp:251-259, and gets the same numbers) */
+ * of the earlier sets merely traded their energies (the reference re-evaluates, main.cpp:251-259, and gets the same numbers).
+ * Refused unless the first set of the same round came before with nothing evaluated and no coordinate or parameter written
+ * in between (the attempt's own swaps excepted). */
 int upside_hip_replica_swap_next(DerivEngine* engine, int n_pair, const int* pairs, uint32_t base_seed,
                                  uint64_t round, int draw0, int* accepted);
 

@@ -435,28 +435,24 @@ int upk_protein_hbond_bwd_pre(const upk_launch_t* L, upk_coord_t self, float* se
 int upk_protein_hbond_passthrough(const upk_launch_t* L, upk_coord_t self, upk_coord_t infer, const int* loc1, int n1,
                                   const int* loc2, int n2);
 
-/* device-side Metropolis for one swap set of replica exchange (src/main.cpp:251-273).  draw0 = number of
- * uniform 4-vectors already consumed from this round's generator; accepted has n_pair+1 entries, the last
- * one receives the generator position after this set. */
-int upk_replica_swap(const upk_launch_t* L, upk_coord_t pos, const float* energy, const float* beta, int n_pair,
-                     const int* pairs, uint32_t seed, uint64_t round, int draw0, int* accepted);
-/* replica exchange across GPUs (src/main.cpp:227-275 over a ladder spread across ranks; host side: csrc/comm_rccl.cpp).
- * Everything is device-resident and stream-ordered between the RCCL calls: total potentials (node order, fp32),
- * Metropolis verdicts over the all-gathered energies (identical on every rank; accepted pairs trade their gathered
- * energies; draw_io = generator position within the attempt), and the coordinate moves (plan[p] = {kind, a, b}: 1 = both
- * local, swap; 2 = local system a takes staging row b, the partner's coordinates received from its rank). */
+/* ---- replica exchange (src/main.cpp:227-275) ----
+ * One swap set, whoever issues it (the engine's temperature and Hamiltonian sets, csrc/comm_rccl.cpp over a ladder spread across
+ * ranks), is these launches on the engine's stream, everything device-resident:
+ * upk_sum_potentials: out[s] = total potential of system s (node order, fp32: the bits of the host sum).
+ * upk_exchange_decide: Metropolis verdicts of the pairs (device array (n_pair,2)) with the REPLICA_EXCHANGE stream of the round's
+ *   counter generator, one uniform per rejectable pair.  e_new == NULL: temperature exchange of one Hamiltonian on e_old; accepted
+ *   pairs trade their e_old entries, so the later sets of the attempt need no evaluation.  e_new given: Hamiltonian set, e_old / e_new
+ *   = energies before / after the pairs traded coordinates; nothing is traded.  beta = 1/T, indexed like the energies.
+ *   draw0 >= 0: first draw of the set, < 0: continue from *draw_io; accepted [n_pair + 1] (last = next draw), *draw_io = next draw.
+ * upk_swap_system_pairs: trade the coordinates of disjoint pairs of systems: all of them (accepted == NULL) or those with
+ *   accepted[p] == want.
+ * upk_replica_apply: the move of the accepted pairs where partners may live on another rank (plan[p] = {kind, a, b}: 1 = both local,
+ *   swap; 2 = local system a takes staging row b, the partner's coordinates received from its rank). */
 int upk_sum_potentials(const upk_launch_t* L, const float* const* node_pot, int n_node, float* out);
-int upk_replica_decide(const upk_launch_t* L, float* energy_all, const float* beta_all, int n_pair, const int* pairs,
-                       uint32_t seed, uint64_t round, int* draw_io, int* accepted);
+int upk_exchange_decide(const upk_launch_t* L, float* e_old, const float* e_new, const float* beta, int n_pair, const int* pairs,
+                        uint32_t seed, uint64_t round, int draw0, int* draw_io, int* accepted);
+int upk_swap_system_pairs(const upk_launch_t* L, upk_coord_t pos, int n_pair, const int* pairs, const int* accepted, int want);
 int upk_replica_apply(const upk_launch_t* L, upk_coord_t pos, int n_pair, const int* plan, const int* accepted, const float* staging);
-/* swap the coordinates of n_pair disjoint (s1, s2) pairs of systems; pairs is a device array */
-int upk_swap_system_pairs(const upk_launch_t* L, upk_coord_t pos, int n_pair, const int* pairs);
-/* Hamiltonian swap set: Metropolis verdicts from the energies before (e_old) and after (e_new) the pairs traded coordinates, beta [S];
- * draw0 >= 0: first draw of the set, < 0: continue from *draw_io; accepted [n_pair + 1] (last = next draw), *draw_io = next draw */
-int upk_hamiltonian_decide(const upk_launch_t* L, const float* e_old, const float* e_new, const float* beta, int n_pair, const int* pairs,
-                           uint32_t seed, uint64_t round, int draw0, int* draw_io, int* accepted);
-/* swap back the pairs whose accepted[p] is 0 */
-int upk_swap_refused_pairs(const upk_launch_t* L, upk_coord_t pos, int n_pair, const int* pairs, const int* accepted);
 
 /* ---- learned backbone potential (src/nn.cpp: backbone_featurizer, conv1d, scaled_sum), csrc/kernels_nn.hip ----
  * backbone_featurizer: out row r = (sin phi, cos phi, sin psi, cos psi, don, acc); phi, psi = columns 0, 1 of rama row rama_idx[r],

@@ -5,12 +5,14 @@
 // boundary cross GPUs).  One swap set, all on the engine's stream:
 //   1. (first set of an attempt) force pass, total potentials summed on the device, ncclAllGather of ONE fp32 per replica;
 //   2. every rank runs the identical Metropolis kernel on the identical gathered arrays with the shared counter RNG
-//      (k_replica_decide) -- no verdict is communicated; accepted pairs trade their gathered energies, so the later sets of
+//      (upk_exchange_decide) -- no verdict is communicated; accepted pairs trade their gathered energies, so the later sets of
 //      the attempt reuse them (a temperature exchange of one Hamiltonian permutes the energies);
 //   3. every pair that straddles two ranks sends its coordinates to the partner rank and receives the partner's into a
 //      staging row (one grouped ncclSend/ncclRecv of 3*n_atom floats per pair), whatever the verdict -- a couple of KB per
 //      rank and set buys a path with no host round trip; k_replica_apply then swaps accepted on-rank pairs in place and
 //      copies the staging row in for accepted cross-rank pairs.  Momenta and temperatures stay with the slot (main.cpp:244-247).
+// This is the engine's own temperature set (DerivEngine::replica_swap) with the all-gather between the energy sum and the verdicts,
+// and global indices: the potential sum, the validator, the decide launcher and the attempt record are the engine's.
 // librccl is loaded on first use (dlopen), so processes that never exchange across GPUs do not pay for it.
 #include "../../include/upside_engine_c.h"
 #include "engine.h"
@@ -102,12 +104,10 @@ struct ReplicaComm {
     ncclComm_t comm = nullptr;
     int rank = 0, world = 1;
     DevBuf<float> energy_local, energy_all, beta_all, staging;
-    DevBuf<const float*> node_pot;
     DevBuf<int> pairs_dev, plan_dev, accepted_dev, draw_dev;
     PinnedSet stage[2];              // [0] pair list, [1] plan; double use per call is serialised by the events
-    int n_node_pot = 0, pair_cap = 0, staging_rows = 0;
+    int pair_cap = 0, staging_rows = 0;
     bool broken = false;             // a collective failed part-way: the communicator is aborted, later calls are refused
-    uint64_t attempt_round = ~0ull; uint64_t attempt_compute = 0;   // the attempt the gathered energies belong to
     ~ReplicaComm() { if (comm) (void)((broken && rccl().CommAbort) ? rccl().CommAbort(comm) : rccl().CommDestroy(comm)); }
 };
 static void comm_deleter(void* p) { delete (ReplicaComm*)p; }
@@ -139,9 +139,6 @@ extern "C" int upside_hip_comm_init(DerivEngine* e, int rank, int world, const c
     vector<float> beta((size_t)world * S);
     for (size_t g = 0; g < beta.size(); ++g) beta[g] = 1.f / temperature_global[g];
     c->beta_all.upload(beta);
-    vector<const float*> ptrs;
-    for (auto& n : e->nodes) if (n.computation->potential_term) ptrs.push_back(static_cast<PotentialNode*>(n.computation.get())->potential_dev.p);
-    c->n_node_pot = (int)ptrs.size(); c->node_pot.upload(ptrs);
     if (e->comm) e->comm_free(e->comm);
     e->comm = c.release(); e->comm_free = comm_deleter;
     return 0;
@@ -183,16 +180,13 @@ extern "C" int upside_hip_comm_replica_swap(DerivEngine* e, int n_pair, const in
     const int S = e->ctx.n_system, G = S * c.world, lo = c.rank * S;
     hipStream_t st = e->ctx.stream;
     const int n_row = e->pos->n_elem * e->pos->stride;
+    check_swap_set(G, n_pair, pairs_global);
     // plan of this set for this rank (host arithmetic on the pair list only)
     vector<int> plan((size_t)n_pair * 3, 0);
     struct Cross { int local, peer, slot; };
     vector<Cross> cross;
-    vector<char> used((size_t)G, 0);
     for (int p = 0; p < n_pair; ++p) {
         const int g1 = pairs_global[2 * p], g2 = pairs_global[2 * p + 1];
-        if (g1 < 0 || g1 >= G || g2 < 0 || g2 >= G || g1 == g2) throw string("invalid system in swap set");
-        if (used[g1] || used[g2]) throw string("Overlapping indices in swap set.");
-        used[g1] = used[g2] = 1;
         const int r1 = g1 / S, r2 = g2 / S;
         if (r1 == c.rank && r2 == c.rank) { plan[3 * p] = 1; plan[3 * p + 1] = g1 - lo; plan[3 * p + 2] = g2 - lo; }
         else if (r1 == c.rank || r2 == c.rank) {
@@ -201,7 +195,7 @@ extern "C" int upside_hip_comm_replica_swap(DerivEngine* e, int n_pair, const in
             cross.push_back(Cross{mine - lo, peer, (int)cross.size()});
         }
     }
-    if (n_pair > c.pair_cap) { c.pair_cap = n_pair; c.pairs_dev.alloc((size_t)n_pair * 2); c.plan_dev.alloc((size_t)n_pair * 3); c.accepted_dev.alloc(n_pair); }
+    if (n_pair > c.pair_cap) { c.pair_cap = n_pair; c.pairs_dev.alloc((size_t)n_pair * 2); c.plan_dev.alloc((size_t)n_pair * 3); c.accepted_dev.alloc((size_t)n_pair + 1); }
     if ((int)cross.size() > c.staging_rows) { c.staging_rows = (int)cross.size(); c.staging.alloc((size_t)c.staging_rows * n_row); }
     if (n_pair) {      // through the communicator's pinned buffers: truly asynchronous, and the sources outlive the copies
         int* hp = c.stage[0].reserve((size_t)n_pair * 2); memcpy(hp, pairs_global, (size_t)n_pair * 2 * sizeof(int));
@@ -213,14 +207,14 @@ extern "C" int upside_hip_comm_replica_swap(DerivEngine* e, int n_pair, const in
     }
     if (first_set) {   // main.cpp:251-256: energies of every system, once per attempt
         e->compute(PotentialAndDerivMode);
-        upk_check(upk_sum_potentials(&e->ctx.L, c.node_pot.p, c.n_node_pot, c.energy_local.p), "sum_potentials");
+        e->sum_potentials_into(c.energy_local.p);
         { const ncclResult_t ag = rccl().AllGather(c.energy_local.p, c.energy_all.p, (size_t)S, ncclFloat, c.comm, st);
           if (ag != ncclSuccess) { c.broken = true; nccl_check(ag, "ncclAllGather"); } }
         hip_check(hipMemsetAsync(c.draw_dev.p, 0, sizeof(int), st), "memset");
-        c.attempt_round = round; c.attempt_compute = e->n_compute;
-    } else if (c.attempt_round != round || c.attempt_compute != e->n_compute)
-        throw string("a later swap set needs the first set of the same attempt (same round, no evaluation in between)");
-    if (n_pair) upk_check(upk_replica_decide(&e->ctx.L, c.energy_all.p, c.beta_all.p, n_pair, c.pairs_dev.p, base_seed, round, c.draw_dev.p, c.accepted_dev.p), "replica_decide");
+        e->begin_attempt(round, c.energy_all.p);
+    } else e->require_attempt(round, c.energy_all.p);
+    if (n_pair) upk_check(upk_exchange_decide(&e->ctx.L, c.energy_all.p, nullptr, c.beta_all.p, n_pair, c.pairs_dev.p, base_seed, round, -1, c.draw_dev.p,
+                                              c.accepted_dev.p), "exchange_decide");
     if (!cross.empty()) {   // coordinates of the straddling pairs, both directions, one group
         nccl_check(rccl().GroupStart(), "ncclGroupStart");
         try {

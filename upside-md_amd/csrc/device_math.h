@@ -225,6 +225,27 @@ __device__ __forceinline__ void boxmuller(float& a, float& b, uint32_t u0, uint3
     const float r = sqrtf(-2.f * logf(u01f(u1)));
     a = sinf(ang) * r; b = cosf(ang) * r;
 }
+// first uniform of the `draw`-th 4-vector of a round's generator: key {seed, stream, 0, 0}, counter {round lo, round hi, 0, draw}
+__device__ __forceinline__ float stream_uniform(uint32_t seed, uint32_t stream, uint64_t round, int draw) {
+    const uint32_t key[4] = {seed, stream, 0u, 0u};
+    uint32_t X[4] = {(uint32_t)(round & 0xffffffffu), (uint32_t)(round >> 32), 0u, (uint32_t)draw};
+    threefry4x32_20(X, key);
+    return u01f(X[0]);
+}
+// ---- the Metropolis rule of replica exchange (main.cpp:251-273), the one statement of it on the device.
+// lboltz_diff of a pair = (-b1 new1 - b2 new2) - (-b1 old1 - b2 old2) in the reference's fp32 order (callers are compiled without
+// contraction).  A temperature exchange of one Hamiltonian is the case new1 = old2, new2 = old1.
+__device__ __forceinline__ float exchange_lboltz_diff(float beta1, float beta2, float old1, float old2, float new1, float new2) {
+    const float old_lb = -beta1 * old1 + -beta2 * old2;
+    const float new_lb = -beta1 * new1 + -beta2 * new2;
+    return new_lb - old_lb;
+}
+// the verdict: the round's generator gives one uniform per REJECTABLE pair only (main.cpp:268 evaluates
+// `expf(lboltz_diff) < random.uniform_open_closed().x()` only when lboltz_diff < 0); draw = its position, advanced here
+__device__ __forceinline__ int exchange_accept(float lb, uint32_t seed, uint64_t round, int& draw) {
+    if (!(lb < 0.f)) return 1;
+    return !(expf(lb) < stream_uniform(seed, 1u /* REPLICA_EXCHANGE_RANDOM_STREAM */, round, draw++));
+}
 
 // fixed-point image of a float (|v| < 2^31): v * 2^32 as a 64-bit two's-complement integer, exact down to 2^-31.  Integer adds commute, so
 // sums accumulated through LDS atomics in any order are the EXACT sum of the contributions (and bit-reproducible); LDS integer

@@ -673,7 +673,7 @@ void DerivEngine::mc_step(uint64_t round) {   // MultipleMonteCarloSampler::exec
         hip_check(hipMemcpyAsync(b.p, v.data(), S * sizeof(float), hipMemcpyHostToDevice, ctx.stream), "H2D");
     };
     refresh(pivot.temperature, temperature);
-    swap_energy.clear();                                                // coordinates may move: no swap set can reuse older energies
+    invalidate_attempt();                                               // coordinates may move: no swap set can reuse older energies
     for (int sampler = 0; sampler < 2; ++sampler) {
         if (sampler == 0 ? !pivot.loaded : !jump.loaded) continue;
         compute(PotentialAndDerivMode); fetch_potentials();
@@ -980,48 +980,90 @@ DerivEngine* initialize_engine_from_hdf5(int n_atom, int n_system, hid_t_compat 
     return engine.release();
 }
 
-// One Hamiltonian swap set on the engine's stream (main.cpp:251-273 for systems of one engine whose parameter values differ):
-// energy pass, the pairs trade coordinates, energy pass, Metropolis verdicts on the device, refused pairs trade back.  Nothing
-// synchronises unless the caller wants the verdicts.
-void DerivEngine::hamiltonian_swap(int n_pair, const int* pairs, uint32_t base_seed, uint64_t round, int draw0, int* accepted) {
-    const int S = ctx.n_system;
-    if ((int)temperature.size() != S || (int)noise_scale.n != S) throw string("a Hamiltonian swap needs the systems' temperatures: call upside_hip_init_md first");
+// ---- replica exchange: one procedure for every swap set (engine.h: Exchange) ---------------------------------------------------
+void check_swap_set(int n_system, int n_pair, const int* pairs) {
     if (n_pair < 0 || (n_pair && !pairs)) throw string("invalid swap pairs");
-    vector<int> key(pairs, pairs + 2 * (size_t)n_pair);
-    vector<char> used(S, 0);
-    for (int x : key) {
-        if (x < 0 || x >= S) throw string("invalid system");
-        if (used[x]) throw string("Overlapping indices in swap set.");
-        used[x] = 1;
+    vector<char> used(n_system, 0);
+    for (int i = 0; i < 2 * n_pair; ++i) {
+        if (pairs[i] < 0 || pairs[i] >= n_system) throw string("invalid system");
+        if (used[pairs[i]]) throw string("Overlapping indices in swap set.");
+        used[pairs[i]] = 1;
     }
-    HSwap& H = hswap;
-    if (!H.e_old.n) {
-        H.e_old.alloc(S); H.e_new.alloc(S); H.draw.alloc(1);
+}
+void DerivEngine::sum_potentials_into(float* dev) {
+    Exchange& X = exchange;
+    if (X.n_node_pot < 0) {
         vector<const float*> ptrs;      // node order: the sum of fetch_potentials
         for (auto& n : nodes) if (n.computation->potential_term) ptrs.push_back(static_cast<PotentialNode*>(n.computation.get())->potential_dev.p);
-        H.n_node_pot = (int)ptrs.size(); H.node_pot.upload(ptrs);
+        X.n_node_pot = (int)ptrs.size(); X.node_pot.upload(ptrs);
     }
+    upk_check(upk_sum_potentials(&ctx.L, X.node_pot.p, X.n_node_pot, dev), "sum_potentials");
+}
+void DerivEngine::begin_attempt(uint64_t round, const float* energies) {
+    exchange.round = round; exchange.n_compute = n_compute; exchange.energies = energies; exchange.valid = true;
+}
+void DerivEngine::require_attempt(uint64_t round, const float* energies) const {
+    const Exchange& X = exchange;
+    if (!X.valid || X.round != round || X.n_compute != n_compute || X.energies != energies)
+        throw string("a later swap set needs the first set of the same attempt (same round, nothing evaluated or moved in between)");
+}
+const int* DerivEngine::exchange_set(int n_pair, const int* pairs) {
+    const int S = ctx.n_system;
+    check_swap_set(S, n_pair, pairs);
+    Exchange& X = exchange;
+    if (!X.e_old.n) { X.e_old.alloc(S); X.e_new.alloc(S); X.draw.alloc(1); }
     vector<float> beta(S);
     for (int s = 0; s < S; ++s) beta[s] = 1.f / temperature[s];
-    if (beta != H.beta_host) { sync(); H.beta.upload(beta); H.beta_host = beta; }
-    if (n_pair == 0) {
-        if (accepted) { sync(); accepted[0] = draw0 >= 0 ? draw0 : H.draw.download()[0]; }
-        return;
-    }
-    auto& dp = H.pairs[key];
-    if (!dp) { sync(); dp.reset(new DevBuf<int>()); dp->upload(key); }
-    if ((int)H.accepted.n < n_pair + 1) { sync(); H.accepted.alloc(n_pair + 1); }
-    compute(PotentialAndDerivMode);
-    upk_check(upk_sum_potentials(&ctx.L, H.node_pot.p, H.n_node_pot, H.e_old.p), "sum_potentials");
-    upk_check(upk_swap_system_pairs(&ctx.L, pos->coord(), n_pair, dp->p), "swap_system_pairs");
-    compute(PotentialAndDerivMode);
-    upk_check(upk_sum_potentials(&ctx.L, H.node_pot.p, H.n_node_pot, H.e_new.p), "sum_potentials");
-    upk_check(upk_hamiltonian_decide(&ctx.L, H.e_old.p, H.e_new.p, H.beta.p, n_pair, dp->p, base_seed, round, draw0, H.draw.p, H.accepted.p), "hamiltonian_decide");
-    upk_check(upk_swap_refused_pairs(&ctx.L, pos->coord(), n_pair, dp->p, H.accepted.p), "swap_refused_pairs");
-    swap_energy.clear();
-    if (accepted) {
-        check_device_errors();
-        hip_check(hipMemcpyAsync(accepted, H.accepted.p, (size_t)(n_pair + 1) * sizeof(int), hipMemcpyDeviceToHost, ctx.stream), "D2H accepted");
+    if (beta != X.beta_host) { sync(); X.beta.upload(beta); X.beta_host = beta; }
+    if ((int)X.accepted.n < n_pair + 1) { sync(); X.accepted.alloc(n_pair + 1); }
+    if (!n_pair) return nullptr;
+    // the device copies of the sets seen so far: a run alternates between a few.  A caller that keeps inventing sets starts over at 64
+    const vector<int> key(pairs, pairs + 2 * (size_t)n_pair);
+    auto it = X.pairs.find(key);
+    if (it == X.pairs.end()) {
         sync();
+        if (X.pairs.size() >= 64) X.pairs.clear();
+        it = X.pairs.emplace(key, unique_ptr<DevBuf<int>>(new DevBuf<int>())).first;
+        it->second->upload(key);
     }
+    return it->second->p;
+}
+void DerivEngine::read_verdicts(int n_pair, int* accepted) {
+    if (!accepted) return;
+    check_device_errors();
+    hip_check(hipMemcpyAsync(accepted, exchange.accepted.p, (size_t)(n_pair + 1) * sizeof(int), hipMemcpyDeviceToHost, ctx.stream), "D2H accepted");
+    sync();
+}
+// One temperature swap set of one Hamiltonian: the first set of an attempt evaluates, a later one finds the energies its
+// predecessors left (accepted pairs traded theirs along with their coordinates).  An empty set, here and in hamiltonian_swap, goes
+// through the verdict kernel like any other: it only sets or reports the draw counter (zero until a set has written it).
+void DerivEngine::replica_swap(int n_pair, const int* pairs, uint32_t base_seed, uint64_t round, int draw0, int* accepted, bool first_set) {
+    const int* dp = exchange_set(n_pair, pairs);
+    Exchange& X = exchange;
+    if (first_set) {
+        compute(PotentialAndDerivMode);
+        sum_potentials_into(X.e_old.p);
+        begin_attempt(round, X.e_old.p);
+    } else require_attempt(round, X.e_old.p);
+    upk_check(upk_exchange_decide(&ctx.L, X.e_old.p, nullptr, X.beta.p, n_pair, dp, base_seed, round, draw0, X.draw.p, X.accepted.p), "exchange_decide");
+    upk_check(upk_swap_system_pairs(&ctx.L, pos->coord(), n_pair, dp, X.accepted.p, 1), "swap_system_pairs");
+    read_verdicts(n_pair, accepted);
+}
+// One Hamiltonian swap set (systems of one engine whose parameter values differ): energy pass, the pairs trade coordinates, energy
+// pass, verdicts, refused pairs trade back.  Nothing synchronises unless the caller wants the verdicts.
+void DerivEngine::hamiltonian_swap(int n_pair, const int* pairs, uint32_t base_seed, uint64_t round, int draw0, int* accepted) {
+    if ((int)noise_scale.n != ctx.n_system) throw string("a Hamiltonian swap needs the systems' temperatures: call upside_hip_init_md first");
+    const int* dp = exchange_set(n_pair, pairs);
+    Exchange& X = exchange;
+    if (n_pair) {
+        compute(PotentialAndDerivMode);
+        sum_potentials_into(X.e_old.p);
+        upk_check(upk_swap_system_pairs(&ctx.L, pos->coord(), n_pair, dp, nullptr, 0), "swap_system_pairs");
+        compute(PotentialAndDerivMode);
+        sum_potentials_into(X.e_new.p);
+        invalidate_attempt();      // (e_old no longer holds a temperature attempt's energies)
+    }
+    upk_check(upk_exchange_decide(&ctx.L, X.e_old.p, X.e_new.p, X.beta.p, n_pair, dp, base_seed, round, draw0, X.draw.p, X.accepted.p), "exchange_decide");
+    upk_check(upk_swap_system_pairs(&ctx.L, pos->coord(), n_pair, dp, X.accepted.p, 0), "swap_system_pairs");
+    read_verdicts(n_pair, accepted);
 }

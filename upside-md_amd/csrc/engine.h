@@ -134,9 +134,7 @@ struct DerivEngine {   // deriv_engine.h:145-237
     // included, and replayed.  Invalidated by anything that changes a kernel argument.
     hipGraph_t md_graph = nullptr; hipGraphExec_t md_graph_exec = nullptr;
     bool md_graph_ready = false; int md_graph_parity = 0; uint64_t steps_done = 0, n_compute = 0;
-    DevBuf<float> swap_row;           // staging row of upside_hip_swap_between (exchange between engines of different potentials)
-    std::vector<float> swap_energy;   // energies seen by the last replica-swap set, accepted pairs already traded (upside_hip_replica_swap_next)
-    uint64_t swap_energy_round = ~0ull, swap_energy_compute = 0;   // the attempt they belong to: (round, force passes done when they were captured)
+    DevBuf<float> swap_row;           // staging row of upside_hip_swap_between (exchange between engines, or two systems of one)
     bool graph_failed = false;   // capture was refused once: stay on plain launches
     void invalidate_graph();
     bool capture_md_graph();
@@ -166,13 +164,24 @@ struct DerivEngine {   // deriv_engine.h:145-237
     ParamDeriv& param_deriv_state(int node);          // n_param known, nothing allocated yet
     const float* param_deriv_all(int node);            // enqueue every system's derivative; the device table [S][n_param]
     void param_deriv_accumulate(int node, const float* weights);   // enqueue sum += weights . table; no synchronisation
-    // device Hamiltonian swap sets (upside_hip_hamiltonian_swap): buffers allocated on first use, pairs uploaded once per distinct set
-    struct HSwap {
-        DevBuf<float> e_old, e_new, beta; std::vector<float> beta_host;
-        DevBuf<int> draw, accepted;
-        DevBuf<const float*> node_pot; int n_node_pot = 0;
-        std::map<std::vector<int>, std::unique_ptr<DevBuf<int>>> pairs;
-    } hswap;
+    // Replica exchange (main.cpp:227-275), one procedure for every swap set: energies summed on the device, upk_exchange_decide, one
+    // coordinate move.  replica_swap (temperature sets of one Hamiltonian), hamiltonian_swap (a second energy pass around the trade) and
+    // comm_rccl.cpp (the ladder spread over ranks: an all-gather between the sum and the verdicts) are its three callers.
+    struct Exchange {
+        DevBuf<const float*> node_pot; int n_node_pot = -1;     // the potential nodes' device arrays in node order, built once
+        DevBuf<float> beta, e_old, e_new; std::vector<float> beta_host;
+        DevBuf<int> draw, accepted;                             // draw counter of the attempt; verdicts [n_pair + 1] of the last set
+        std::map<std::vector<int>, std::unique_ptr<DevBuf<int>>> pairs;   // uploaded once per distinct set
+        // the attempt whose energies a later set may reuse: its round, the force passes done when they were summed, the array holding them
+        uint64_t round = ~0ull, n_compute = 0; const float* energies = nullptr; bool valid = false;
+    } exchange;
+    void sum_potentials_into(float* dev);                       // enqueue dev[s] = total potential of the last force pass
+    void begin_attempt(uint64_t round, const float* energies);
+    void require_attempt(uint64_t round, const float* energies) const;   // throws unless nothing was evaluated or moved since begin_attempt
+    void invalidate_attempt() { exchange.valid = false; }      // coordinates or parameters changed outside the attempt's own swaps
+    const int* exchange_set(int n_pair, const int* pairs);      // a checked set on the device, beta and the verdict buffers in place
+    void read_verdicts(int n_pair, int* accepted);              // accepted [n_pair + 1] of the last set (NULL: nothing, no synchronisation)
+    void replica_swap(int n_pair, const int* pairs, uint32_t base_seed, uint64_t round, int draw0, int* accepted, bool first_set);
     void hamiltonian_swap(int n_pair, const int* pairs, uint32_t base_seed, uint64_t round, int draw0, int* accepted);
     // collective variables of every system (upside_hip_cv_*; kernels_cv.hip).  A definition is replaced whole; recording appends one
     // (n_system, n_cv) sample per `every` completed rounds from inside md_step, the decision taken on the device (captured graphs replay it)
@@ -192,6 +201,8 @@ struct DerivEngine {   // deriv_engine.h:145-237
     void sync();
 };
 
+// a swap set over n_system systems: every index in range, no system twice (the reference's messages, main.cpp:171,181)
+void check_swap_set(int n_system, int n_pair, const int* pairs);
 DerivEngine* initialize_engine_from_hdf5(int n_atom, int n_system, hid_t_compat potential_group, bool quiet = false,
                                          const std::function<void(DerivEngine&)>& before_finalize = nullptr);
 

@@ -163,7 +163,7 @@ static PerSystemValues& per_system_node(DerivEngine* e, const char* node_name, i
 extern "C" int upside_hip_set_param_system(DerivEngine* e, const char* node_name, int system, int n_param, const float* param) {
     API_TRY
     per_system_node(e, node_name, system).set_param_system(system, vector<float>(param, param + n_param));
-    e->swap_energy.clear();
+    e->invalidate_attempt();
     return 0;
     API_CATCH(1)
 }
@@ -190,33 +190,36 @@ extern "C" void free_deriv_engine(DerivEngine* engine) { delete engine; }
 extern "C" int upside_hip_n_system(DerivEngine* engine) { return engine ? engine->ctx.n_system : 0; }
 
 // ---- positions / momenta ----------------------------------------------------------------------------
+// host rows [n][width] <-> device rows [n][stride] (stride >= width; the padding of a packed row is left as it was)
+static void pack_rows(const float* in, size_t n, int width, int stride, float* out) {
+    for (size_t i = 0; i < n; ++i) for (int d = 0; d < width; ++d) out[i * stride + d] = in[i * width + d];
+}
+static void unpack_rows(const float* in, size_t n, int stride, int width, float* out) {
+    for (size_t i = 0; i < n; ++i) for (int d = 0; d < width; ++d) out[i * width + d] = in[i * stride + d];
+}
 static void upload_pos(DerivEngine* e, const float* pos, int n_sys_in) {
     const int S = e->ctx.n_system, na = e->pos->n_atom, st = e->pos->stride;
     vector<float> buf((size_t)S * na * st, 0.f);
-    for (int s = 0; s < S; ++s) {
-        const float* p = pos + (size_t)(n_sys_in == 1 ? 0 : s) * na * 3;
-        for (int a = 0; a < na; ++a) for (int d = 0; d < 3; ++d) buf[((size_t)s * na + a) * st + d] = p[a * 3 + d];
-    }
+    for (int s = 0; s < S; ++s) pack_rows(pos + (size_t)(n_sys_in == 1 ? 0 : s) * na * 3, na, 3, st, buf.data() + (size_t)s * na * st);
     hip_check(hipMemcpyAsync(e->pos->output.p, buf.data(), buf.size() * sizeof(float), hipMemcpyHostToDevice, e->ctx.stream), "H2D pos");
     e->sync();
+    e->invalidate_attempt();
 }
 static void download_rows(DerivEngine* e, const float* dev, int n_elem, int stride, int width, float* out, int n_sys_out) {
-    const int S = e->ctx.n_system;
-    vector<float> buf((size_t)S * n_elem * stride);
+    vector<float> buf((size_t)n_sys_out * n_elem * stride);
     e->sync();
     hip_check(hipMemcpy(buf.data(), dev, buf.size() * sizeof(float), hipMemcpyDeviceToHost), "D2H");
-    for (int s = 0; s < n_sys_out; ++s) for (int i = 0; i < n_elem; ++i) for (int d = 0; d < width; ++d)
-        out[((size_t)s * n_elem + i) * width + d] = buf[((size_t)s * n_elem + i) * stride + d];
+    unpack_rows(buf.data(), (size_t)n_sys_out * n_elem, stride, width, out);
 }
 
-extern "C" int upside_hip_set_pos(DerivEngine* e, const float* pos) { API_TRY upload_pos(e, pos, e->ctx.n_system); e->swap_energy.clear(); return 0; API_CATCH(1) }
+extern "C" int upside_hip_set_pos(DerivEngine* e, const float* pos) { API_TRY upload_pos(e, pos, e->ctx.n_system); return 0; API_CATCH(1) }
 extern "C" int upside_hip_get_pos(DerivEngine* e, float* pos) {
     API_TRY download_rows(e, e->pos->output.p, e->pos->n_atom, e->pos->stride, 3, pos, e->ctx.n_system); return 0; API_CATCH(1) }
 extern "C" int upside_hip_set_mom(DerivEngine* e, const float* mom) {
     API_TRY
-    const int S = e->ctx.n_system, na = e->pos->n_atom;
-    vector<float> buf((size_t)S * na * 4, 0.f);
-    for (size_t i = 0; i < (size_t)S * na; ++i) for (int d = 0; d < 3; ++d) buf[i * 4 + d] = mom[i * 3 + d];
+    const size_t n = (size_t)e->ctx.n_system * e->pos->n_atom;
+    vector<float> buf(n * 4, 0.f);
+    pack_rows(mom, n, 3, 4, buf.data());
     hip_check(hipMemcpy(e->mom.p, buf.data(), buf.size() * sizeof(float), hipMemcpyHostToDevice), "H2D mom");
     return 0;
     API_CATCH(1)
@@ -566,7 +569,7 @@ extern "C" int upside_hip_metad_write(DerivEngine* e, const char* node_name, int
     API_TRY
     if (!e || !node_name) throw string("engine or node name is NULL");
     engine_metad_write(*e, string(node_name), list, centers, weights, n_hill);
-    e->swap_energy.clear();
+    e->invalidate_attempt();
     return 0;
     API_CATCH(1)
 }
@@ -614,91 +617,21 @@ extern "C" int upside_hip_recenter(DerivEngine* e) {
 extern "C" int upside_hip_recenter_axes(DerivEngine* e, int xy_only) {
     API_TRY upk_check(upk_recenter(&e->ctx.L, e->pos->coord(), xy_only ? 1 : 0), "recenter"); e->sync(); return 0; API_CATCH(1) }
 
-static int replica_swap_impl(DerivEngine* e, int n_pair, const int* pairs, uint32_t base_seed, uint64_t round, int draw0, int* accepted, bool reuse_energy) {
-    const int S = e->ctx.n_system;
-    for (int i = 0; i < 2 * n_pair; ++i) if (pairs[i] < 0 || pairs[i] >= S) throw string("invalid system");
-    if (reuse_energy) {
-        // the energies must be those of THIS attempt: captured in the same round with no force pass (MD, Monte Carlo, another
-        // evaluation) and no new coordinates since
-        if ((int)e->swap_energy.size() != S || e->swap_energy_round != round || e->swap_energy_compute != e->n_compute)
-            throw string("upside_hip_replica_swap_next needs a preceding upside_hip_replica_swap(_from) of the same attempt (same round, nothing evaluated or moved in between)");
-    } else {
-        e->compute(PotentialAndDerivMode);
-        e->fetch_potentials();
-        e->swap_energy = e->potential;
-        e->swap_energy_round = round; e->swap_energy_compute = e->n_compute;
-    }
-    if ((int)e->temperature.size() != S) throw string("replica exchange needs the systems' temperatures: call upside_hip_init_md first");
-    vector<float> beta(S);
-    for (int s = 0; s < S; ++s) beta[s] = 1.f / e->temperature[s];
-    DevBuf<float> d_en, d_beta; d_en.upload(e->swap_energy); d_beta.upload(beta);
-    DevBuf<int> d_pairs, d_acc; d_pairs.upload(vector<int>(pairs, pairs + 2 * n_pair)); d_acc.alloc(n_pair + 1);
-    upk_check(upk_replica_swap(&e->ctx.L, e->pos->coord(), d_en.p, d_beta.p, n_pair, d_pairs.p, base_seed, round, draw0, d_acc.p), "replica_swap");
-    e->sync();
-    auto acc = d_acc.download();
-    for (int i = 0; i <= n_pair; ++i) accepted[i] = acc[i];   // accepted[n_pair] = generator position for the next set
-    for (int i = 0; i < n_pair; ++i) if (acc[i]) swap(e->swap_energy[pairs[2 * i]], e->swap_energy[pairs[2 * i + 1]]);   // the coordinates traded places
-    return 0;
-}
+// ---- replica exchange among the systems of this engine (DerivEngine::replica_swap; main.cpp:227-275) -----------------------
 extern "C" int upside_hip_replica_swap_from(DerivEngine* e, int n_pair, const int* pairs, uint32_t base_seed, uint64_t round, int draw0, int* accepted) {
-    API_TRY
-    return replica_swap_impl(e, n_pair, pairs, base_seed, round, draw0, accepted, false);
-    API_CATCH(1)
+    API_TRY e->replica_swap(n_pair, pairs, base_seed, round, draw0, accepted, true); return 0; API_CATCH(1)
 }
 extern "C" int upside_hip_replica_swap_next(DerivEngine* e, int n_pair, const int* pairs, uint32_t base_seed, uint64_t round, int draw0, int* accepted) {
-    API_TRY
-    return replica_swap_impl(e, n_pair, pairs, base_seed, round, draw0, accepted, true);
-    API_CATCH(1)
+    API_TRY e->replica_swap(n_pair, pairs, base_seed, round, draw0, accepted, false); return 0; API_CATCH(1)
 }
 extern "C" int upside_hip_replica_swap(DerivEngine* e, int n_pair, const int* pairs, uint32_t base_seed, uint64_t round, int* accepted) {
-    std::vector<int> acc((size_t)n_pair + 1);
+    std::vector<int> acc((size_t)(n_pair > 0 ? n_pair : 0) + 1);
     const int rc = upside_hip_replica_swap_from(e, n_pair, pairs, base_seed, round, 0, acc.data());
     if (!rc) for (int i = 0; i < n_pair; ++i) accepted[i] = acc[i];
     return rc;
 }
 
-// ---- replica exchange across engines / GPUs (main.cpp:227-275) --------------------------------
-// Host arithmetic only: every rank holds the same all-gathered energies and reaches the same verdicts.
-namespace {
-inline uint32_t h_rotl32(uint32_t x, unsigned n) { return (x << (n & 31)) | (x >> ((32 - n) & 31)); }
-void h_threefry4x32_20(uint32_t X[4], const uint32_t key[4]) {   // Random123/threefry.h:110-117,172,296-430
-    static const unsigned R[8][2] = {{10, 26}, {11, 21}, {13, 27}, {23, 5}, {6, 20}, {17, 11}, {25, 10}, {18, 20}};
-    uint32_t ks[5]; ks[4] = 0x1BD11BDAu;
-    for (int i = 0; i < 4; ++i) { ks[i] = key[i]; ks[4] ^= key[i]; }
-    for (int i = 0; i < 4; ++i) X[i] += ks[i];
-    for (int r = 0; r < 20; ++r) {
-        if (r % 2 == 0) { X[0] += X[1]; X[1] = h_rotl32(X[1], R[r % 8][0]); X[1] ^= X[0]; X[2] += X[3]; X[3] = h_rotl32(X[3], R[r % 8][1]); X[3] ^= X[2]; }
-        else            { X[0] += X[3]; X[3] = h_rotl32(X[3], R[r % 8][0]); X[3] ^= X[0]; X[2] += X[1]; X[1] = h_rotl32(X[1], R[r % 8][1]); X[1] ^= X[2]; }
-        if (r % 4 == 3) { const int k = r / 4 + 1; for (int i = 0; i < 4; ++i) X[i] += ks[(k + i) % 5]; X[3] += k; }
-    }
-}
-float h_u01(uint32_t in) {   // uniform.hpp:145-179, the product and the sum rounded separately
-#pragma clang fp contract(off)
-    const float factor = 1.f / 4294967296.f;
-    volatile float t = (float)in * factor;
-    return t + 0.5f * factor;
-}
-}  // namespace
-// the Metropolis rule of main.cpp:262-272 on given log-Boltzmann differences (any mixture of Hamiltonians): a uniform of the
-// round's generator is drawn only for a rejectable pair; accepted[n_pair] = generator position after this set
-extern "C" int upside_replica_decide_lboltz(int n_pair, const float* lboltz_diff, uint32_t base_seed, uint64_t round, int draw0, int* accepted) {
-    API_TRY
-    int draw = draw0;
-    for (int p = 0; p < n_pair; ++p) {
-        int ok = 1;
-        if (lboltz_diff[p] < 0.f) {
-            const uint32_t key[4] = {base_seed, 1u /* REPLICA_EXCHANGE_RANDOM_STREAM */, 0u, 0u};
-            uint32_t X[4] = {(uint32_t)(round & 0xffffffffu), (uint32_t)(round >> 32), 0u, (uint32_t)draw};
-            h_threefry4x32_20(X, key);
-            ++draw;
-            if (expf(lboltz_diff[p]) < h_u01(X[0])) ok = 0;
-        }
-        accepted[p] = ok;
-    }
-    accepted[n_pair] = draw;
-    return 0;
-    API_CATCH(1)
-}
+// ---- coordinates of single systems; exchange across engines (main.cpp:227-275) ----------------------------------
 // trade the coordinates of system s1 of engine e1 and system s2 of engine e2 (same atom count; device to device)
 extern "C" int upside_hip_swap_between(DerivEngine* e1, int s1, DerivEngine* e2, int s2) {
     API_TRY
@@ -707,8 +640,8 @@ extern "C" int upside_hip_swap_between(DerivEngine* e1, int s1, DerivEngine* e2,
     if (e1 == e2 && s1 == s2) return 0;
     const size_t row = (size_t)e1->pos->n_elem * e1->pos->stride;
     // Both engines have drained their streams (their pending work reads or writes the rows); the three copies go through e1's
-    // stream into a staging row the engine keeps (an allocation and three blocking copies per pair before: a rejected pair of a
-    // Hamiltonian exchange attempt comes through here twice), and e2 is made to wait for them by the final synchronisation.
+    // stream into a staging row the engine keeps (a rejected pair of a Hamiltonian exchange attempt across engines comes through
+    // here twice), and e2 is made to wait for them by the final synchronisation.
     e1->sync(); e2->sync();
     if (e1->swap_row.n < row) e1->swap_row.alloc(row);
     float* a = e1->pos->output.p + (size_t)s1 * row; float* b = e2->pos->output.p + (size_t)s2 * row;
@@ -717,30 +650,19 @@ extern "C" int upside_hip_swap_between(DerivEngine* e1, int s1, DerivEngine* e2,
     hip_check(hipMemcpyAsync(a, b, row * sizeof(float), hipMemcpyDeviceToDevice, st), "D2D");
     hip_check(hipMemcpyAsync(b, e1->swap_row.p, row * sizeof(float), hipMemcpyDeviceToDevice, st), "D2D");
     hip_check(hipStreamSynchronize(st), "hipStreamSynchronize");
-    e1->swap_energy.clear(); e2->swap_energy.clear();
+    e1->invalidate_attempt(); e2->invalidate_attempt();
     return 0;
     API_CATCH(1)
 }
-extern "C" int upside_replica_decide(int n_pair, const int* pairs, const float* beta, const float* energy, uint32_t base_seed,
-                                     uint64_t round, int draw0, int* accepted) {
+extern "C" int upside_hip_swap_systems(DerivEngine* e, int s1, int s2) { return upside_hip_swap_between(e, s1, e, s2); }
+extern "C" int upside_hip_swap_system_pairs(DerivEngine* e, int n_pair, const int* pairs) {
     API_TRY
-    int draw = draw0;
-    for (int p = 0; p < n_pair; ++p) {
-        const int s1 = pairs[p * 2], s2 = pairs[p * 2 + 1];
-        if (s1 < 0 || s2 < 0) throw string("invalid system");
-        // temperature exchange of one Hamiltonian: (new_lboltz[s1]+new_lboltz[s2]) - (old_lboltz[s1]+old_lboltz[s2])
-        const float lb = (-beta[s1] * energy[s2] + -beta[s2] * energy[s1]) - (-beta[s1] * energy[s1] + -beta[s2] * energy[s2]);
-        int ok = 1;
-        if (lb < 0.f) {   // a uniform is drawn only for a rejectable pair (main.cpp:268)
-            const uint32_t key[4] = {base_seed, 1u /* REPLICA_EXCHANGE_RANDOM_STREAM */, 0u, 0u};
-            uint32_t X[4] = {(uint32_t)(round & 0xffffffffu), (uint32_t)(round >> 32), 0u, (uint32_t)draw};
-            h_threefry4x32_20(X, key);
-            ++draw;
-            if (expf(lb) < h_u01(X[0])) ok = 0;
-        }
-        accepted[p] = ok;
-    }
-    accepted[n_pair] = draw;   // generator position for the next swap set of this round
+    if (n_pair <= 0) return 0;
+    check_swap_set(e->ctx.n_system, n_pair, pairs);
+    DevBuf<int> d; d.upload(vector<int>(pairs, pairs + 2 * n_pair));
+    upk_check(upk_swap_system_pairs(&e->ctx.L, e->pos->coord(), n_pair, d.p, nullptr, 0), "swap_system_pairs");
+    e->sync();
+    e->invalidate_attempt();
     return 0;
     API_CATCH(1)
 }
@@ -751,7 +673,7 @@ extern "C" int upside_hip_get_system_pos(DerivEngine* e, int sys, float* pos) {
     vector<float> buf((size_t)na * st);
     e->sync();
     hip_check(hipMemcpy(buf.data(), e->pos->output.p + (size_t)sys * na * st, buf.size() * sizeof(float), hipMemcpyDeviceToHost), "D2H");
-    for (int a = 0; a < na; ++a) for (int d = 0; d < 3; ++d) pos[a * 3 + d] = buf[(size_t)a * st + d];
+    unpack_rows(buf.data(), na, st, 3, pos);
     return 0;
     API_CATCH(1)
 }
@@ -760,41 +682,10 @@ extern "C" int upside_hip_set_system_pos(DerivEngine* e, int sys, const float* p
     if (sys < 0 || sys >= e->ctx.n_system) throw string("invalid system");
     const int na = e->pos->n_atom, st = e->pos->stride;
     vector<float> buf((size_t)na * st, 0.f);
-    for (int a = 0; a < na; ++a) for (int d = 0; d < 3; ++d) buf[(size_t)a * st + d] = pos[a * 3 + d];
+    pack_rows(pos, na, 3, st, buf.data());
     e->sync();
     hip_check(hipMemcpy(e->pos->output.p + (size_t)sys * na * st, buf.data(), buf.size() * sizeof(float), hipMemcpyHostToDevice), "H2D");
-    return 0;
-    API_CATCH(1)
-}
-extern "C" int upside_hip_swap_system_pairs(DerivEngine* e, int n_pair, const int* pairs) {
-    API_TRY
-    const int S = e->ctx.n_system;
-    if (n_pair <= 0) return 0;
-    vector<char> used(S, 0);
-    for (int i = 0; i < 2 * n_pair; ++i) {
-        if (pairs[i] < 0 || pairs[i] >= S) throw string("invalid system");
-        if (used[pairs[i]]) throw string("Overlapping indices in swap set.");
-        used[pairs[i]] = 1;
-    }
-    DevBuf<int> d; d.upload(vector<int>(pairs, pairs + 2 * n_pair));
-    upk_check(upk_swap_system_pairs(&e->ctx.L, e->pos->coord(), n_pair, d.p), "swap_system_pairs");
-    e->sync();
-    return 0;
-    API_CATCH(1)
-}
-extern "C" int upside_hip_swap_systems(DerivEngine* e, int s1, int s2) {
-    API_TRY
-    const int S = e->ctx.n_system;
-    if (s1 < 0 || s1 >= S || s2 < 0 || s2 >= S) throw string("invalid system");
-    if (s1 == s2) return 0;
-    const size_t n = (size_t)e->pos->n_atom * e->pos->stride;
-    DevBuf<float> tmp; tmp.alloc(n);
-    float* a = e->pos->output.p + (size_t)s1 * n; float* b = e->pos->output.p + (size_t)s2 * n;
-    e->sync();
-    hip_check(hipMemcpy(tmp.p, a, n * sizeof(float), hipMemcpyDeviceToDevice), "D2D");
-    hip_check(hipMemcpy(a, b, n * sizeof(float), hipMemcpyDeviceToDevice), "D2D");
-    hip_check(hipMemcpy(b, tmp.p, n * sizeof(float), hipMemcpyDeviceToDevice), "D2D");
-    hip_check(hipDeviceSynchronize(), "sync");
+    e->invalidate_attempt();
     return 0;
     API_CATCH(1)
 }

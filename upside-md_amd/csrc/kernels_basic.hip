@@ -1203,10 +1203,7 @@ __global__ void k_mc_accept(upk_coord_t pos, const float* __restrict__ pos_copy,
         const float lb = delta_lprob[s] - (1.f / temperature[s]) * (e_new[s] - e_old[s]);   // monte_carlo_sampler.cpp:272
         int ok = 1;
         if (!(lb >= 0.f)) {
-            const uint32_t key[4] = {seed[s], (uint32_t)stream, 0u, 0u};
-            uint32_t X[4] = {(uint32_t)(round & 0xffffffffu), (uint32_t)(round >> 32), 0u, (uint32_t)accept_draw};   // next draw of the move's generator
-            threefry4x32_20(X, key);
-            ok = expf(lb) >= u01f(X[0]);
+            ok = expf(lb) >= stream_uniform(seed[s], (uint32_t)stream, round, accept_draw);   // next draw of the move's generator
         }
         accept = ok;
         stats[s * 2] += ok; stats[s * 2 + 1] += 1;
@@ -1227,48 +1224,8 @@ extern "C" int upk_mc_accept(const upk_launch_t* L, upk_coord_t pos, const float
 }
 
 // ------------------------------------------------------------------------------------------------
-// replica exchange Metropolis on the device (main.cpp:251-273); one lane per swap pair, pairs are disjoint.
-__global__ void k_replica_swap(upk_coord_t pos, const float* __restrict__ energy, const float* __restrict__ beta, int n_pair,
-                               const int* __restrict__ pairs, uint32_t seed, uint64_t round, int draw0, int* __restrict__ accepted) {
-    // uniforms are drawn sequentially from one generator, one 4-vector per REJECTABLE pair (main.cpp:268:
-    // `expf(lboltz_diff) < random.uniform_open_closed().x()` is only evaluated when lboltz_diff < 0)
-    __shared__ int draw_index[1024];
-    __shared__ int acc[1024];
-    if (threadIdx.x == 0) {
-        int draw = draw0;
-        for (int p = 0; p < n_pair; ++p) {
-            const int s1 = pairs[p * 2], s2 = pairs[p * 2 + 1];
-            // temperature exchange of one Hamiltonian: new_lboltz - old_lboltz = (beta1-beta2)(E1-E2)
-            const float lb = (-beta[s1] * energy[s2] + -beta[s2] * energy[s1]) - (-beta[s1] * energy[s1] + -beta[s2] * energy[s2]);
-            int ok = 1;
-            if (lb < 0.f) {
-                const uint32_t key[4] = {seed, 1u /* REPLICA_EXCHANGE_RANDOM_STREAM */, 0u, 0u};
-                uint32_t X[4] = {(uint32_t)(round & 0xffffffffu), (uint32_t)(round >> 32), 0u, (uint32_t)draw};
-                threefry4x32_20(X, key);
-                ++draw;
-                if (expf(lb) < u01f(X[0])) ok = 0;
-            }
-            acc[p] = ok; accepted[p] = ok; draw_index[p] = draw;
-        }
-        accepted[n_pair] = draw;   // generator position for the next swap set of this round
-    }
-    __syncthreads();
-    const int n = pos.n_elem * pos.stride;
-    for (int p = 0; p < n_pair; ++p) {
-        if (!acc[p]) continue;
-        float* a = C_OUT(pos, pairs[p * 2]); float* b = C_OUT(pos, pairs[p * 2 + 1]);
-        for (int i = threadIdx.x; i < n; i += blockDim.x) { const float t = a[i]; a[i] = b[i]; b[i] = t; }
-    }
-}
-extern "C" int upk_replica_swap(const upk_launch_t* L, upk_coord_t pos, const float* energy, const float* beta, int n_pair,
-                                const int* pairs, uint32_t seed, uint64_t round, int draw0, int* accepted) {
-    UPK_FLUSH(L);
-    if (n_pair > 1024) return 9002;
-    hipLaunchKernelGGL(k_replica_swap, dim3(1), dim3(UPK_BLOCK), 0, ST(L), pos, energy, beta, n_pair, pairs, seed, round, draw0, accepted);
-    return launch_status();
-}
-
-// ---- replica exchange across GPUs (comm_rccl.cpp): everything below runs on the engine's stream between RCCL calls --------
+// Replica exchange on the device (main.cpp:227-275): every swap set, whoever issues it (the engine's temperature and Hamiltonian sets,
+// comm_rccl.cpp's set over a ladder spread across ranks), is upk_sum_potentials, upk_exchange_decide and one coordinate move.
 // total potential of every system on the device: out[s] = sum over the potential nodes, in node order (the order and fp32
 // arithmetic of DerivEngine::fetch_potentials / deriv_engine.cpp:143-146, so the two give the same bits)
 __global__ void k_sum_potentials(const float* const* __restrict__ node_pot, int n_node, int S, float* __restrict__ out) {
@@ -1283,45 +1240,62 @@ extern "C" int upk_sum_potentials(const upk_launch_t* L, const float* const* nod
     hipLaunchKernelGGL(k_sum_potentials, grid1(L->n_system, 1), dim3(UPK_BLOCK), 0, ST(L), node_pot, n_node, L->n_system, out);
     return launch_status();
 }
-// Metropolis verdicts of one swap set over the GLOBAL ladder (main.cpp:251-273), identical on every rank: same gathered
-// energies, same temperatures, same counter RNG.  draw_io: generator position within this attempt (in/out, device);
-// accepted pairs trade their entries of energy_all (temperature exchange of one Hamiltonian), so the later sets of the
-// attempt need no new evaluation.
-__global__ void k_replica_decide(float* __restrict__ energy_all, const float* __restrict__ beta_all, int n_pair, const int* __restrict__ pairs,
-                                 uint32_t seed, uint64_t round, int* __restrict__ draw_io, int* __restrict__ accepted) {
+// Metropolis verdicts of one swap set (device_math.h: exchange_lboltz_diff, exchange_accept).  e_new == NULL: temperature exchange of
+// one Hamiltonian on e_old, accepted pairs trade their e_old entries, so the later sets of the attempt need no new evaluation.  e_new
+// given: Hamiltonian set after its two energy passes (e_old before the pairs traded coordinates, e_new after); nothing is traded.
+// draw0 >= 0 starts the set at that draw, draw0 < 0 continues from *draw_io (the previous set of the attempt).  accepted[n_pair] =
+// *draw_io = the draw after the set.  One thread: the draws of a set are sequential, and n_pair is small.
+__global__ void k_exchange_decide(float* __restrict__ e_old, const float* __restrict__ e_new, const float* __restrict__ beta, int n_pair,
+                                  const int* __restrict__ pairs, uint32_t seed, uint64_t round, int draw0, int* __restrict__ draw_io,
+                                  int* __restrict__ accepted) {
     if (threadIdx.x != 0 || blockIdx.x != 0) return;
-    int draw = *draw_io;
+    int draw = draw0 >= 0 ? draw0 : *draw_io;
     for (int p = 0; p < n_pair; ++p) {
         const int s1 = pairs[p * 2], s2 = pairs[p * 2 + 1];
-        const float lb = (-beta_all[s1] * energy_all[s2] + -beta_all[s2] * energy_all[s1]) - (-beta_all[s1] * energy_all[s1] + -beta_all[s2] * energy_all[s2]);
-        int ok = 1;
-        if (lb < 0.f) {
-            const uint32_t key[4] = {seed, 1u /* REPLICA_EXCHANGE_RANDOM_STREAM */, 0u, 0u};
-            uint32_t X[4] = {(uint32_t)(round & 0xffffffffu), (uint32_t)(round >> 32), 0u, (uint32_t)draw};
-            threefry4x32_20(X, key);
-            ++draw;
-            if (expf(lb) < u01f(X[0])) ok = 0;
-        }
+        const float old1 = e_old[s1], old2 = e_old[s2];
+        const float lb = exchange_lboltz_diff(beta[s1], beta[s2], old1, old2, e_new ? e_new[s1] : old2, e_new ? e_new[s2] : old1);
+        const int ok = exchange_accept(lb, seed, round, draw);
         accepted[p] = ok;
-        if (ok) { const float t = energy_all[s1]; energy_all[s1] = energy_all[s2]; energy_all[s2] = t; }
+        if (ok && !e_new) { e_old[s1] = old2; e_old[s2] = old1; }
     }
+    accepted[n_pair] = draw;
     *draw_io = draw;
 }
-extern "C" int upk_replica_decide(const upk_launch_t* L, float* energy_all, const float* beta_all, int n_pair, const int* pairs,
-                                  uint32_t seed, uint64_t round, int* draw_io, int* accepted) {
+extern "C" int upk_exchange_decide(const upk_launch_t* L, float* e_old, const float* e_new, const float* beta, int n_pair, const int* pairs,
+                                   uint32_t seed, uint64_t round, int draw0, int* draw_io, int* accepted) {
     UPK_FLUSH(L);
-    hipLaunchKernelGGL(k_replica_decide, dim3(1), dim3(64), 0, ST(L), energy_all, beta_all, n_pair, pairs, seed, round, draw_io, accepted);
+    hipLaunchKernelGGL(k_exchange_decide, dim3(1), dim3(64), 0, ST(L), e_old, e_new, beta, n_pair, pairs, seed, round, draw0, draw_io, accepted);
     return launch_status();
 }
-// apply the verdicts to this rank's coordinates.  plan[p] = {kind, a, b}: kind 1: both systems local (a, b = local ids:
-// swap in place); kind 2: system a is local, its partner lives on another rank and its coordinates arrived in staging row b
+// trade two coordinate rows of n floats; the launch's x dimension strides over the row
+__device__ __forceinline__ void swap_rows(float* a, float* b, int n) {
+    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) { const float t = a[i]; a[i] = b[i]; b[i] = t; }
+}
+// exchange the coordinates of disjoint pairs of systems in one launch (blockIdx.y = pair): every pair (accepted == NULL), or the
+// pairs whose verdict accepted[p] equals want (1: the accepted pairs of a temperature set; 0: the refused pairs of a Hamiltonian
+// set trade back)
+__global__ void k_swap_system_pairs(upk_coord_t pos, const int* __restrict__ pairs, const int* __restrict__ accepted, int want) {
+    const int p = blockIdx.y;
+    if (accepted && accepted[p] != want) return;
+    swap_rows(C_OUT(pos, pairs[p * 2]), C_OUT(pos, pairs[p * 2 + 1]), pos.n_elem * pos.stride);
+}
+extern "C" int upk_swap_system_pairs(const upk_launch_t* L, upk_coord_t pos, int n_pair, const int* pairs, const int* accepted, int want) {
+    UPK_FLUSH(L);
+    if (n_pair <= 0) return 0;
+    const int n = pos.n_elem * pos.stride;
+    hipLaunchKernelGGL(k_swap_system_pairs, dim3((unsigned)((n + UPK_BLOCK - 1) / UPK_BLOCK), (unsigned)n_pair), dim3(UPK_BLOCK), 0, ST(L), pos, pairs, accepted, want);
+    return launch_status();
+}
+// the coordinate move of a set over a ladder spread across ranks (comm_rccl.cpp), for the accepted pairs.  plan[p] = {kind, a, b}:
+// kind 1: both systems local (a, b = local ids: swap in place); kind 2: system a is local, its partner lives on another rank and its
+// coordinates arrived in staging row b
 __global__ void k_replica_apply(upk_coord_t pos, int n_pair, const int* __restrict__ plan, const int* __restrict__ accepted, const float* __restrict__ staging) {
     const int p = blockIdx.y;
     if (p >= n_pair || !accepted[p]) return;
     const int kind = plan[p * 3], a = plan[p * 3 + 1], b = plan[p * 3 + 2];
     const int n = pos.n_elem * pos.stride;
     float* xa = C_OUT(pos, a);
-    if (kind == 1) { float* xb = C_OUT(pos, b); for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) { const float t = xa[i]; xa[i] = xb[i]; xb[i] = t; } }
+    if (kind == 1) swap_rows(xa, C_OUT(pos, b), n);
     else if (kind == 2) { const float* in = staging + (size_t)b * n; for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) xa[i] = in[i]; }
 }
 extern "C" int upk_replica_apply(const upk_launch_t* L, upk_coord_t pos, int n_pair, const int* plan, const int* accepted, const float* staging) {
@@ -1329,70 +1303,6 @@ extern "C" int upk_replica_apply(const upk_launch_t* L, upk_coord_t pos, int n_p
     if (n_pair <= 0) return 0;
     const int n = pos.n_elem * pos.stride;
     hipLaunchKernelGGL(k_replica_apply, dim3((unsigned)((n + UPK_BLOCK - 1) / UPK_BLOCK), (unsigned)n_pair), dim3(UPK_BLOCK), 0, ST(L), pos, n_pair, plan, accepted, staging);
-    return launch_status();
-}
-
-// exchange the coordinates of disjoint pairs of systems in one launch (the accepted on-GPU pairs of a swap set)
-__global__ void k_swap_system_pairs(upk_coord_t pos, const int* __restrict__ pairs) {
-    const int p = blockIdx.y;
-    float* a = C_OUT(pos, pairs[p * 2]); float* b = C_OUT(pos, pairs[p * 2 + 1]);
-    const int n = pos.n_elem * pos.stride;
-    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) { const float t = a[i]; a[i] = b[i]; b[i] = t; }
-}
-extern "C" int upk_swap_system_pairs(const upk_launch_t* L, upk_coord_t pos, int n_pair, const int* pairs) {
-    UPK_FLUSH(L);
-    if (n_pair <= 0) return 0;
-    const int n = pos.n_elem * pos.stride;
-    hipLaunchKernelGGL(k_swap_system_pairs, dim3((unsigned)((n + UPK_BLOCK - 1) / UPK_BLOCK), (unsigned)n_pair), dim3(UPK_BLOCK), 0, ST(L), pos, pairs);
-    return launch_status();
-}
-
-// Hamiltonian swap set (main.cpp:251-273) after its two energy passes: e_old = energies before the pairs traded coordinates, e_new =
-// after.  lboltz_diff = (-b1 E1' - b2 E2') - (-b1 E1 - b2 E2) in the fp32 order of the host procedure; the Metropolis draw of
-// upside_replica_decide_lboltz on the round's counter-based stream.  draw0 >= 0 starts the set at that draw, draw0 < 0 continues
-// from *draw_io (the previous set of the attempt).  accepted[n_pair] = the draw after the set.  One thread: n_pair is small.
-__global__ void k_hamiltonian_decide(const float* __restrict__ e_old, const float* __restrict__ e_new, const float* __restrict__ beta, int n_pair,
-                                     const int* __restrict__ pairs, uint32_t seed, uint64_t round, int draw0, int* __restrict__ draw_io,
-                                     int* __restrict__ accepted) {
-    if (threadIdx.x != 0 || blockIdx.x != 0) return;
-    int draw = draw0 >= 0 ? draw0 : *draw_io;
-    for (int p = 0; p < n_pair; ++p) {
-        const int s1 = pairs[p * 2], s2 = pairs[p * 2 + 1];
-        const float old_lb = -beta[s1] * e_old[s1] + -beta[s2] * e_old[s2];
-        const float new_lb = -beta[s1] * e_new[s1] + -beta[s2] * e_new[s2];
-        const float lb = new_lb - old_lb;
-        int ok = 1;
-        if (lb < 0.f) {
-            const uint32_t key[4] = {seed, 1u /* REPLICA_EXCHANGE_RANDOM_STREAM */, 0u, 0u};
-            uint32_t X[4] = {(uint32_t)(round & 0xffffffffu), (uint32_t)(round >> 32), 0u, (uint32_t)draw};
-            threefry4x32_20(X, key);
-            ++draw;
-            if (expf(lb) < u01f(X[0])) ok = 0;
-        }
-        accepted[p] = ok;
-    }
-    accepted[n_pair] = draw;
-    *draw_io = draw;
-}
-extern "C" int upk_hamiltonian_decide(const upk_launch_t* L, const float* e_old, const float* e_new, const float* beta, int n_pair, const int* pairs,
-                                      uint32_t seed, uint64_t round, int draw0, int* draw_io, int* accepted) {
-    UPK_FLUSH(L);
-    hipLaunchKernelGGL(k_hamiltonian_decide, dim3(1), dim3(64), 0, ST(L), e_old, e_new, beta, n_pair, pairs, seed, round, draw0, draw_io, accepted);
-    return launch_status();
-}
-// trade back the coordinates of the pairs whose verdict was a refusal
-__global__ void k_swap_refused_pairs(upk_coord_t pos, const int* __restrict__ pairs, const int* __restrict__ accepted) {
-    const int p = blockIdx.y;
-    if (accepted[p]) return;
-    float* a = C_OUT(pos, pairs[p * 2]); float* b = C_OUT(pos, pairs[p * 2 + 1]);
-    const int n = pos.n_elem * pos.stride;
-    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) { const float t = a[i]; a[i] = b[i]; b[i] = t; }
-}
-extern "C" int upk_swap_refused_pairs(const upk_launch_t* L, upk_coord_t pos, int n_pair, const int* pairs, const int* accepted) {
-    UPK_FLUSH(L);
-    if (n_pair <= 0) return 0;
-    const int n = pos.n_elem * pos.stride;
-    hipLaunchKernelGGL(k_swap_refused_pairs, dim3((unsigned)((n + UPK_BLOCK - 1) / UPK_BLOCK), (unsigned)n_pair), dim3(UPK_BLOCK), 0, ST(L), pos, pairs, accepted);
     return launch_status();
 }
 
