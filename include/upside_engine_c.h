@@ -226,16 +226,24 @@ const char* upside_hip_last_error(void);
 
 /* Collective variables of every system, computed on the device in one launch (csrc/kernels_cv.hip) and recordable during MD with no
  * host round trip.  kind: 0 rg (radius of gyration of the selection), 1 rmsd (minimum over proper rigid motions to a reference given
- * for the same selection), 2 contacts (Q = mean over pairs of 1 / (1 + exp(beta (r_ij - lambda r0_ij)))), 3 distance.
+ * for the same selection), 2 contacts (Q = mean over pairs of 1 / (1 + exp(beta (r_ij - lambda r0_ij)))), 3 distance, 4 dihedral (the
+ * torsion of 4 atoms in radians, in (-pi, pi], with the sign of the backbone torsions: PERIODIC, period 2 pi -- cv_restraint and
+ * cv_metadynamics take its differences by the nearest image), 5 dihedral_similarity (mean over quadruples of
+ * 1/2 (1 + cos(phi_i - phi0_i)), in [0, 1]: helix content with phi0 = the helical (phi, psi), a torsional Q with the native angles).
  *   _cv_define: CSR layout -- atoms[atom_start[c] : atom_start[c+1]] is the selection of CV c (two atoms for a distance, interleaved
  *     pairs for contacts); ref_pos (rows of 3) holds the references of the rmsd CVs back to back in CV order, contact_r0 the r0 of the
  *     contacts CVs' pairs likewise; contact_beta / contact_lambda have n_cv entries (read for contacts CVs only).  Arrays a definition
  *     has no use for may be NULL.  Replaces any earlier definition (and stops a recording); n_cv = 0 clears it.  Refused, with
  *     upside_hip_last_error set and the earlier definition still in force: an unknown kind, an atom out of range, an empty selection,
  *     an rmsd selection under 3 atoms, an odd contacts list, a distance without exactly 2 atoms, r0 <= 0, more than 64 CVs
- *     (UPK_CV_MAX) or more than 2^24 entries in one list (UPK_CV_MAX_LIST).
+ *     (UPK_CV_MAX) or more than 2^24 entries in one list (UPK_CV_MAX_LIST); a kind 5 (this entry point carries no reference angles).
+ *   _cv_define2: the same with dihedral_ref, the reference angles (radians) of the dihedral_similarity CVs' quadruples back to back in
+ *     CV order; NULL where no CV is of that kind.  A dihedral's selection is its 4 atoms, a dihedral_similarity's is interleaved
+ *     quadruples.  Further refusals: a dihedral without exactly 4 atoms, a dihedral_similarity list that is no multiple of 4, a
+ *     quadruple with a repeated atom, dihedral_ref NULL or not finite where a dihedral_similarity exists.
  *   _cv_load: the same from the group /input/collective_variables of a configuration (datasets kind, atom_start, atoms, ref_pos (n,3),
- *     contact_r0, contact_beta, contact_lambda and the fixed-length string vector names; config.add_collective_variables writes it).
+ *     contact_r0, contact_beta, contact_lambda, the optional dihedral_ref -- absent means empty; its length must be the number of
+ *     dihedral_similarity quadruples -- and the fixed-length string vector names; config.add_collective_variables writes it).
  *     Returns the number of CVs, 0 without the group, -1 on error (the convention of upside_hip_load_mc).
  *   _cv_count: the number of CVs defined.
  *   _cv_compute: out is host (n_system, n_cv), at the current device positions; no force pass, pair lists untouched.
@@ -251,6 +259,9 @@ const char* upside_hip_last_error(void);
 int upside_hip_cv_define(DerivEngine* engine, int n_cv, const int* kind, const int* atom_start /* n_cv+1 */, const int* atoms,
                          const float* ref_pos, const float* contact_r0, const float* contact_beta /* n_cv */,
                          const float* contact_lambda /* n_cv */);
+int upside_hip_cv_define2(DerivEngine* engine, int n_cv, const int* kind, const int* atom_start /* n_cv+1 */, const int* atoms,
+                          const float* ref_pos, const float* contact_r0, const float* contact_beta /* n_cv */,
+                          const float* contact_lambda /* n_cv */, const float* dihedral_ref);
 int upside_hip_cv_load(DerivEngine* engine, const char* config_file);
 int upside_hip_cv_count(DerivEngine* engine);
 int upside_hip_cv_compute(DerivEngine* engine, float* out /* host (n_system, n_cv) */);

@@ -485,10 +485,15 @@ int upk_scaled_sum(const upk_launch_t* L, upk_coord_t in, const float* scale, fl
  *                    ref_g[c] = sum of their squared norms
  *   UPK_CV_CONTACTS  the list is interleaved pairs; mean over pairs of 1 / (1 + exp(beta[c] * (r - lambda[c] * r0))), r0 = r0[aux_start[c] + pair]
  *   UPK_CV_DISTANCE  |x(atoms[0]) - x(atoms[1])|
+ *   UPK_CV_DIHEDRAL  the torsion of the list's 4 atoms in radians, in (-pi, pi]: with F = r1 - r2, G = r2 - r3, H = r4 - r3, A = F x G,
+ *                    B = H x G it is atan2((B x A) . G, (A . B) |G|) (Blondel & Karplus; the backbone torsions' sign).  PERIODIC, period
+ *                    2 pi: the biases below take differences of its values by the nearest image, wrap(d) = d - 2 pi rint(d / 2 pi)
+ *   UPK_CV_DIHEDRAL_SIMILARITY  the list is interleaved quadruples; mean over quadruples of 1/2 (1 + cos(phi_i - phi0_i)), in [0, 1],
+ *                    phi0_i = dihedral_ref[aux_start[c] + quadruple] (radians).  Not periodic
  * One workgroup per system, every sum in fp64 and in one fixed order, no atomics: a system's row is bit-identical run to run and
  * whatever else shares its batch.  The lists are not staged anywhere, so the only limits are UPK_CV_MAX CVs per definition and
  * UPK_CV_MAX_LIST entries per list (what the launch checks and the 32-bit indices hold). */
-enum { UPK_CV_RG = 0, UPK_CV_RMSD = 1, UPK_CV_CONTACTS = 2, UPK_CV_DISTANCE = 3 };
+enum { UPK_CV_RG = 0, UPK_CV_RMSD = 1, UPK_CV_CONTACTS = 2, UPK_CV_DISTANCE = 3, UPK_CV_DIHEDRAL = 4, UPK_CV_DIHEDRAL_SIMILARITY = 5 };
 #define UPK_CV_MAX 64
 #define UPK_CV_MAX_LIST (1 << 24)   /* entries of one CV's list */
 typedef struct {
@@ -496,6 +501,7 @@ typedef struct {
     const int *kind, *atom_start, *atoms, *aux_start;   /* [n_cv], [n_cv+1], [atom_start[n_cv]], [n_cv] */
     const double *ref, *ref_g;                          /* [n_ref_atom][3], [n_cv] */
     const float *r0, *beta, *lambda;                    /* [n_contact_pair], [n_cv], [n_cv] */
+    const float* dihedral_ref;                          /* [n_similarity_quadruple] */
 } upk_cv_t;
 /* out [S][n_cv] at the current positions */
 int upk_cv_compute(const upk_launch_t* L, upk_coord_t pos, const upk_cv_t* C, float* out);
@@ -505,13 +511,15 @@ int upk_cv_compute(const upk_launch_t* L, upk_coord_t pos, const upk_cv_t* C, fl
 typedef struct { unsigned long long* rounds; int* n_attempt; int every, capacity; float* samples; } upk_cv_record_t;
 int upk_cv_record(const upk_launch_t* L, upk_coord_t pos, const upk_cv_t* C, const upk_cv_record_t* R);
 /* cv_restraint (node of the force pass): E[s] = sum_c 1/2 k u^2 with u = max(0, |v_c - center| - flat_width) over the CVs of C, v_c
- * the very bits upk_cv_compute reports.  par + s * par_stride is system s's row [center | spring_const | flat_width] (3 n_cv floats;
+ * the very bits upk_cv_compute reports (a dihedral: |wrap(v_c - center)|, so center may be any finite number).  par + s * par_stride is system s's row [center | spring_const | flat_width] (3 n_cv floats;
  * stride 0: one row for all -- the cv_restraint node, the only caller, always passes a full table with stride 3 n_cv, so the
  * shared row is not exercised).  Writes dE/dx of every list entry to contrib[s][entry][3] (entry = index into C->atoms: a scatter
  * source of pos with one slot per entry; every slot is written on every launch), the CV values to values[s][n_cv] and, unless
  * pot_terms is NULL, the n_cv energy terms to pot_terms[s][n_cv].  Same kernel shape as upk_cv_compute: one workgroup per system,
- * fp64 sums in one order, no atomics.  An rg, rmsd or distance below UPK_CV_RESTRAINT_VMIN (Angstrom) and a contact pair at r = 0
- * contribute zero force (the energy is still counted). */
+ * fp64 sums in one order, no atomics.  An rg, rmsd or distance below UPK_CV_RESTRAINT_VMIN (Angstrom), a contact pair at r = 0 and a
+ * torsion whose |G| is below UPK_CV_RESTRAINT_VMIN or whose first or last three atoms are collinear to within 1e-6 in the sine
+ * (|A|^2 not above 1e-12 |F|^2 |G|^2, or |B|^2 not above 1e-12 |H|^2 |G|^2; coincident end atoms included) contribute zero force
+ * (the energy is still counted; atan2(0, 0) = 0). */
 #define UPK_CV_RESTRAINT_VMIN 1e-6
 int upk_cv_restraint(const upk_launch_t* L, upk_coord_t pos, const upk_cv_t* C, const float* par, long par_stride, float* contrib,
                      long contrib_stride, float* values, float* pot_terms);
@@ -519,7 +527,9 @@ int upk_cv_restraint(const upk_launch_t* L, upk_coord_t pos, const upk_cv_t* C, 
  * one space and the bias is a sum of Gaussian hills,
  *   V(v) = sum_h w_h exp(-sum_c (v_c - s_hc)^2 / (2 sigma_c^2)),   dV/dv_c = sum_h -w_h (v_c - s_hc) / sigma_c^2 exp(...)
  * over ALL hills of the system's list (no cutoff, no grid), accumulated in fp64 in one order: lane t takes hills t, t + 256, ...
- * ascending, then the workgroup's fixed-order sum.  v_c is the fp64 value behind the bits upk_cv_compute reports.
+ * ascending, then the workgroup's fixed-order sum.  v_c is the fp64 value behind the bits upk_cv_compute reports.  In a dihedral's
+ * dimension v_c - s_hc is wrap(v_c - s_hc): the nearest image of the hill only, no sum over images, so sigma_c is expected to be
+ * well below pi.
  * Hills: hills[list][d + 1][capacity] floats (rows 0..d-1 the centres, row d the weights; consecutive lanes read consecutive
  * hills).  shared = 0: list = system, n_deposit[s] hills visible.  shared = 1: one list for all systems (walkers); deposit k of
  * system s is slot k * n_system + s and n_deposit[s] * n_system hills are visible (the entries of n_deposit are equal).

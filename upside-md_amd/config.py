@@ -686,8 +686,10 @@ def add_jump_moves(path, atom_ranges, sigma_trans, sigma_rot):
         g.write('sigma_rot', np.asarray(sigma_rot, 'f4').reshape(-1))
 
 
-CV_KINDS = ('rg', 'rmsd', 'contacts', 'distance')      # the kind codes of upside_hip_cv_define, in order
+CV_KINDS = ('rg', 'rmsd', 'contacts', 'distance', 'dihedral', 'dihedral_similarity')      # the kind codes of upside_hip_cv_define2, in order
 CV_MAX = 64                                            # UPK_CV_MAX of include/upside_hip_kernels.h
+# the period of each kind, 0 = not periodic: cv_restraint and cv_metadynamics take the differences of a periodic CV by the nearest image
+CV_PERIOD = dict((k, 2. * np.pi if k == 'dihedral' else 0.) for k in CV_KINDS)
 
 
 def native_contacts(pos, atoms, cutoff=8.0, min_seq_sep=4):
@@ -715,10 +717,12 @@ def pack_collective_variables(specs, n_atom):
          {'kind': 'rmsd', 'atoms': (n,), 'ref': (n,3)}                  reference positions of the SAME atoms, in order
          {'kind': 'contacts', 'pairs': (m,2), 'r0': (m,) or scalar, 'beta': 5., 'lambda': 1.8}
          {'kind': 'distance', 'pair': (a,b)}
+         {'kind': 'dihedral', 'atoms': (a,b,c,d)}                       the torsion in radians, in (-pi, pi]; periodic (CV_PERIOD)
+         {'kind': 'dihedral_similarity', 'quads': (m,4), 'ref': (m,) or scalar}     mean of 1/2 (1 + cos(phi_i - ref_i)), in [0, 1]
     'name' defaults to the kind, numbered when it repeats.  Raises ValueError naming the spec and what is wrong with it."""
     if len(specs) > CV_MAX:
         raise ValueError('%d collective variables exceed the limit of %d' % (len(specs), CV_MAX))
-    kind, atom_start, atoms, ref, r0, beta, lam, names = [], [0], [], [], [], [], [], []
+    kind, atom_start, atoms, ref, r0, beta, lam, names, dref = [], [0], [], [], [], [], [], [], []
     for c, sp in enumerate(specs):
         who = 'collective variable %d' % c
         if not isinstance(sp, dict) or 'kind' not in sp:
@@ -727,7 +731,8 @@ def pack_collective_variables(specs, n_atom):
         if k not in CV_KINDS:
             raise ValueError(who + ': unknown kind %r (one of %s)' % (k, ', '.join(CV_KINDS)))
         who += ' (%s)' % k
-        allowed = {'rg': ('atoms',), 'rmsd': ('atoms', 'ref'), 'contacts': ('pairs', 'r0', 'beta', 'lambda'), 'distance': ('pair',)}[k]
+        allowed = {'rg': ('atoms',), 'rmsd': ('atoms', 'ref'), 'contacts': ('pairs', 'r0', 'beta', 'lambda'), 'distance': ('pair',),
+                   'dihedral': ('atoms',), 'dihedral_similarity': ('quads', 'ref')}[k]
         extra = sorted(set(sp) - set(allowed) - set(('kind', 'name')))
         if extra:
             raise ValueError(who + ': unexpected key %r' % extra[0])
@@ -761,6 +766,22 @@ def pack_collective_variables(specs, n_atom):
             if not (np.isfinite(b) and np.isfinite(l)):
                 raise ValueError(who + ': beta and lambda must be finite')
             r0.append(r)
+        elif k == 'dihedral':
+            a = np.asarray(sp['atoms']).reshape(-1)
+            if len(a) != 4:
+                raise ValueError(who + ': atoms must hold exactly 4 atoms')
+        elif k == 'dihedral_similarity':
+            qd = np.asarray(sp['quads'])
+            if qd.ndim != 2 or qd.shape[1] != 4:
+                raise ValueError(who + ': quads must be (m, 4)')
+            a = qd.reshape(-1)
+            rf = np.asarray(sp['ref'], 'f8')
+            rf = np.full(len(qd), float(rf)) if rf.ndim == 0 else rf.reshape(-1)
+            if len(rf) != len(qd):
+                raise ValueError(who + ': ref must have one angle per quadruple')
+            if not np.isfinite(rf).all():
+                raise ValueError(who + ': ref is not finite')
+            dref.append(rf)
         else:
             a = np.asarray(sp['pair']).reshape(-1)
             if len(a) != 2:
@@ -771,6 +792,10 @@ def pack_collective_variables(specs, n_atom):
             raise ValueError(who + ': atom indices must be integers')
         if a.min() < 0 or a.max() >= n_atom:
             raise ValueError(who + ': atom %d out of range (n_atom %d)' % (int(a.min() if a.min() < 0 else a.max()), n_atom))
+        if k in ('dihedral', 'dihedral_similarity'):
+            for i, q in enumerate(a.reshape(-1, 4)):
+                if len(set(q.tolist())) != 4:
+                    raise ValueError(who + ': quadruple %d repeats an atom' % i)
         kind.append(CV_KINDS.index(k)); atoms.append(a.astype('i4')); atom_start.append(atom_start[-1] + len(a))
         beta.append(b); lam.append(l)
         names.append(str(sp.get('name', k)))
@@ -783,7 +808,50 @@ def pack_collective_variables(specs, n_atom):
     cat = lambda v, t, shape: (np.concatenate(v).astype(t) if v else np.zeros(shape, t))
     return dict(kind=np.asarray(kind, 'i4'), atom_start=np.asarray(atom_start, 'i4'), atoms=cat(atoms, 'i4', (0,)),
                 ref_pos=cat(ref, 'f4', (0, 3)), contact_r0=cat(r0, 'f4', (0,)), contact_beta=np.asarray(beta, 'f4'),
-                contact_lambda=np.asarray(lam, 'f4'), names=np.asarray(names, 'S') if names else np.zeros((0,), 'S1'))
+                contact_lambda=np.asarray(lam, 'f4'), names=np.asarray(names, 'S') if names else np.zeros((0,), 'S1'),
+                dihedral_ref=cat(dref, 'f4', (0,)))
+
+
+CV_DATASETS = ('kind', 'atom_start', 'atoms', 'ref_pos', 'contact_r0', 'contact_beta', 'contact_lambda', 'names')
+
+
+def _cv_datasets(p):
+    """the datasets of a CV definition's group: dihedral_ref only where a dihedral_similarity needs it, so that a definition of the
+    other kinds is written exactly as it always was"""
+    return CV_DATASETS + (('dihedral_ref',) if (np.asarray(p['kind']) == CV_KINDS.index('dihedral_similarity')).any() else ())
+
+
+def cv_periods(packed_or_specs):
+    """one period per CV (0 = not periodic) from the packed dict of pack_collective_variables or a list of specs: what
+    metadynamics_free_energy(periods=...) takes"""
+    if isinstance(packed_or_specs, dict):
+        return np.array([CV_PERIOD[CV_KINDS[int(k)]] for k in np.asarray(packed_or_specs['kind']).reshape(-1)], 'f8')
+    return np.array([CV_PERIOD[sp['kind']] for sp in packed_or_specs], 'f8')
+
+
+def backbone_dihedrals(path):
+    """(phi_quads (n,4), phi_res (n,), psi_quads (m,4), psi_res (m,)) of a configuration: the atoms of the backbone torsions as
+    /input/potential/rama_coord/id lists them (rows prevC, N, CA, C, nextN: columns 0-3 are phi, 1-4 psi; a row with a -1 among the
+    four -- a chain end -- is skipped) and the row (residue) each came from.  A `dihedral` over such a quadruple reports the phi or
+    psi of the rama_coord node."""
+    with h5lite.open_file(path) as f:
+        ids = np.asarray(f.group('input').group('potential').group('rama_coord').read('id'), 'i4').reshape(-1, 5)
+    res = np.arange(len(ids), dtype='i4')
+    ok_phi = (ids[:, 0:4] >= 0).all(1); ok_psi = (ids[:, 1:5] >= 0).all(1)
+    return ids[ok_phi, 0:4].copy(), res[ok_phi], ids[ok_psi, 1:5].copy(), res[ok_psi]
+
+
+def helix_content_spec(path, residues=None, phi0=-0.995, psi0=-0.820, name='helix_content'):
+    """a dihedral_similarity spec over the phi and psi of `residues` (rows of rama_coord; default: all that have the angle) with the
+    helical references (-57, -47 degrees): 1 for an ideal helix, 1/2 on average for random torsions"""
+    phi_q, phi_r, psi_q, psi_r = backbone_dihedrals(path)
+    if residues is not None:
+        residues = np.asarray(residues).reshape(-1)
+        phi_q = phi_q[np.isin(phi_r, residues)]; psi_q = psi_q[np.isin(psi_r, residues)]
+    if not len(phi_q) + len(psi_q):
+        raise ValueError('helix_content_spec: no backbone torsion in the selection')
+    return {'name': name, 'kind': 'dihedral_similarity', 'quads': np.concatenate((phi_q, psi_q)).astype('i4'),
+            'ref': np.concatenate((np.full(len(phi_q), float(phi0)), np.full(len(psi_q), float(psi0))))}
 
 
 def add_collective_variables(path, specs):
@@ -795,7 +863,7 @@ def add_collective_variables(path, specs):
         if 'collective_variables' in inp:
             inp.delete('collective_variables')
         g = inp.create_group('collective_variables')
-        for k in ('kind', 'atom_start', 'atoms', 'ref_pos', 'contact_r0', 'contact_beta', 'contact_lambda', 'names'):
+        for k in _cv_datasets(p):
             g.write(k, p[k])
     return p
 
@@ -821,6 +889,7 @@ def _restraint_values(center, spring_const, flat_width, n_cv, who='cv_restraint'
 def add_cv_restraint(path, specs, name='cv_restraint'):
     """add an umbrella bias on collective variables (node type cv_restraint, argument pos) to an existing configuration:
          E = sum_c 1/2 spring_const_c u_c^2,   u_c = max(0, |v_c - center_c| - flat_width_c)
+    (a dihedral: v_c - center_c folded into [-pi, pi], so a window next to +-pi acts on both sides of the cut)
     specs: the dicts of pack_collective_variables, each with the further keys 'center' (required), 'spring_const' (required) and
     'flat_width' (default 0: the plain harmonic umbrella).  name must start with 'cv_restraint'; several such nodes may coexist
     ('cv_restraint_q', 'cv_restraint_rg').  center, spring_const and flat_width may differ between the files of one engine
@@ -856,7 +925,7 @@ def add_cv_restraint(path, specs, name='cv_restraint'):
         if name in pot:
             pot.delete(name)
         g = pot.create_group(name); _args(g, ['pos'])
-        for k in ('kind', 'atom_start', 'atoms', 'ref_pos', 'contact_r0', 'contact_beta', 'contact_lambda', 'names') + CV_RESTRAINT_VALUES:
+        for k in _cv_datasets(p) + CV_RESTRAINT_VALUES:
             g.write(k, p[k])
     return p
 
@@ -922,7 +991,9 @@ def add_cv_metadynamics(path, specs, sigma, height, pace, capacity, kdT=0., shar
     sigma: the d widths; height: the weight of a hill (plain) or of the first one (well-tempered); capacity: hill slots per list
     -- when a list is full, deposits are dropped (and counted); kdT: k_B Delta T of well-tempered metadynamics in the engine's
     energy unit, w_h = height exp(-V(s_h) / kdT), 0 = plain; shared: all systems of one engine deposit into ONE list (multiple
-    walkers; capacity then counts the hills of all of them).  The sum over hills has no cutoff.  name must start with
+    walkers; capacity then counts the hills of all of them).  The sum over hills has no cutoff.  In the dimension of a dihedral
+    v_c - s_hc is folded into [-pi, pi] (the nearest image of each hill, no sum over images): keep its sigma well below pi.
+    name must start with
     'cv_metadynamics'.  The files of one engine must agree on the whole node.  Returns the packed arrays."""
     if not str(name).startswith('cv_metadynamics'):
         raise ValueError("add_cv_metadynamics: the node name must start with 'cv_metadynamics', got %r" % (name,))
@@ -959,7 +1030,7 @@ def add_cv_metadynamics(path, specs, sigma, height, pace, capacity, kdT=0., shar
         if name in pot:
             pot.delete(name)
         g = pot.create_group(name); _args(g, ['pos'])
-        for k in ('kind', 'atom_start', 'atoms', 'ref_pos', 'contact_r0', 'contact_beta', 'contact_lambda', 'names', 'sigma'):
+        for k in _cv_datasets(p) + ('sigma',):
             g.write(k, p[k])
         g.set_attr('height', float(height)); g.set_attr('kdT', float(kdT))
         g.set_attr('pace', int(pace)); g.set_attr('capacity', int(capacity)); g.set_attr('shared', int(bool(shared)))
@@ -991,9 +1062,11 @@ def set_metadynamics_hills(path, node, centers, weights):
     return c, w
 
 
-def metadynamics_free_energy(centers, weights, sigma, grid_points, kT=None, kdT=0.):
+def metadynamics_free_energy(centers, weights, sigma, grid_points, kT=None, kdT=0., periods=None):
     """the free-energy estimate of a metadynamics run at grid_points (m, d) (or (m,) for d = 1), float64, up to a constant:
-    -V for plain metadynamics (kdT = 0), -(kT + kdT) / kdT V for well-tempered (kT: the run's temperature in energy units)"""
+    -V for plain metadynamics (kdT = 0), -(kT + kdT) / kdT V for well-tempered (kT: the run's temperature in energy units).
+    periods (d,), as cv_periods gives them: in a dimension with a period > 0 the difference to a hill is taken by its nearest image,
+    as the node does; None: no dimension is periodic"""
     sigma = np.asarray(sigma, 'f8').reshape(-1)
     d = len(sigma)
     w = np.asarray(weights, 'f8').reshape(-1)
@@ -1004,7 +1077,14 @@ def metadynamics_free_energy(centers, weights, sigma, grid_points, kT=None, kdT=
         raise ValueError('metadynamics_free_energy: grid_points must be (m, %d)' % d)
     if not (sigma > 0).all():
         raise ValueError('metadynamics_free_energy: sigma must be positive')
-    z = (x[:, None, :] - c[None, :, :]) / sigma
+    diff = x[:, None, :] - c[None, :, :]
+    if periods is not None:
+        per = np.asarray(periods, 'f8').reshape(-1)
+        if len(per) != d or not (np.isfinite(per).all() and (per >= 0).all()):
+            raise ValueError('metadynamics_free_energy: periods must be %d numbers, not negative' % d)
+        for k in np.nonzero(per > 0)[0]:
+            diff[:, :, k] -= per[k] * np.rint(diff[:, :, k] / per[k])
+    z = diff / sigma
     v = (w[None, :] * np.exp(-0.5 * (z * z).sum(2))).sum(1)
     if kdT > 0.:
         if kT is None or not kT > 0.:

@@ -130,10 +130,55 @@ __device__ __forceinline__ void ld3d(const float* __restrict__ x, int atom, int 
     px = (double)p[0]; py = (double)p[1]; pz = (double)p[2];
 }
 
+// d folded into [-pi, pi]: the difference of two values of a periodic CV (period 2 pi) by its nearest image
+#define CV_TWO_PI 6.283185307179586476925286766559
+__device__ __forceinline__ double cv_wrap(double d) { return d - CV_TWO_PI * rint(d / CV_TWO_PI); }
+__device__ __forceinline__ bool cv_periodic(int kind) { return kind == UPK_CV_DIHEDRAL; }
+
+// The torsion of the atoms q[0..4) in the notation of Blondel & Karplus (1996): F = r1 - r2, G = r2 - r3, H = r4 - r3, A = F x G,
+// B = H x G, phi = atan2((B x A) . G, (A . B) |G|) in (-pi, pi] -- the sign convention of the reference's backbone torsions, so the
+// atoms of a rama_coord row give that node's phi or psi.  A quadruple without a direction gives atan2(0, 0) = 0 (signed zeros are
+// cleared first, so that neither -0 nor -pi can come out of a planar arrangement).
+struct cv_torsion_t { double F[3], G[3], H[3], A[3], B[3]; };
+__device__ __forceinline__ double cv_torsion(const float* __restrict__ x, int stride, const int* __restrict__ q, cv_torsion_t& t) {
+    double r1[3], r2[3], r3[3], r4[3];
+    ld3d(x, q[0], stride, r1[0], r1[1], r1[2]); ld3d(x, q[1], stride, r2[0], r2[1], r2[2]);
+    ld3d(x, q[2], stride, r3[0], r3[1], r3[2]); ld3d(x, q[3], stride, r4[0], r4[1], r4[2]);
+#pragma unroll
+    for (int d = 0; d < 3; ++d) { t.F[d] = r1[d] - r2[d]; t.G[d] = r2[d] - r3[d]; t.H[d] = r4[d] - r3[d]; }
+    t.A[0] = t.F[1] * t.G[2] - t.F[2] * t.G[1]; t.A[1] = t.F[2] * t.G[0] - t.F[0] * t.G[2]; t.A[2] = t.F[0] * t.G[1] - t.F[1] * t.G[0];
+    t.B[0] = t.H[1] * t.G[2] - t.H[2] * t.G[1]; t.B[1] = t.H[2] * t.G[0] - t.H[0] * t.G[2]; t.B[2] = t.H[0] * t.G[1] - t.H[1] * t.G[0];
+    const double c0 = t.B[1] * t.A[2] - t.B[2] * t.A[1], c1 = t.B[2] * t.A[0] - t.B[0] * t.A[2], c2 = t.B[0] * t.A[1] - t.B[1] * t.A[0];
+    const double gmag = sqrt(t.G[0] * t.G[0] + t.G[1] * t.G[1] + t.G[2] * t.G[2]);
+    double sn = c0 * t.G[0] + c1 * t.G[1] + c2 * t.G[2], cs = (t.A[0] * t.B[0] + t.A[1] * t.B[1] + t.A[2] * t.B[2]) * gmag;
+    if (sn == 0.) sn = 0.;
+    if (cs == 0.) cs = 0.;
+    return atan2(sn, cs);
+}
+// f * dphi/dx of the four atoms into o[0..12).  Small values: |G| < UPK_CV_RESTRAINT_VMIN, or three atoms collinear to within 1e-6
+// in the sine (|A|^2 not above 1e-12 |F|^2 |G|^2, or |B|^2 not above 1e-12 |H|^2 |G|^2): the torsion has no direction and all twelve
+// are zero.
+__device__ __forceinline__ void cv_torsion_gradient(const cv_torsion_t& t, double f, float* __restrict__ o) {
+    const double F2 = t.F[0] * t.F[0] + t.F[1] * t.F[1] + t.F[2] * t.F[2], G2 = t.G[0] * t.G[0] + t.G[1] * t.G[1] + t.G[2] * t.G[2];
+    const double H2 = t.H[0] * t.H[0] + t.H[1] * t.H[1] + t.H[2] * t.H[2];
+    const double A2 = t.A[0] * t.A[0] + t.A[1] * t.A[1] + t.A[2] * t.A[2], B2 = t.B[0] * t.B[0] + t.B[1] * t.B[1] + t.B[2] * t.B[2];
+    // (written as "not above": coincident end atoms, F = 0 or H = 0, make both sides 0 and have no direction either)
+    const bool none = G2 < UPK_CV_RESTRAINT_VMIN * UPK_CV_RESTRAINT_VMIN || !(A2 > 1e-12 * F2 * G2) || !(B2 > 1e-12 * H2 * G2);
+    const double gmag = sqrt(G2);
+    const double ka = none ? 0. : f * gmag / A2, kb = none ? 0. : f * gmag / B2;                 // dphi/dr1 = -ka A, dphi/dr4 = kb B
+    const double ma = none ? 0. : f * (t.F[0] * t.G[0] + t.F[1] * t.G[1] + t.F[2] * t.G[2]) / (A2 * gmag);
+    const double mb = none ? 0. : f * (t.H[0] * t.G[0] + t.H[1] * t.G[1] + t.H[2] * t.G[2]) / (B2 * gmag);
+#pragma unroll
+    for (int d = 0; d < 3; ++d) {
+        const double d1 = -ka * t.A[d], d4 = kb * t.B[d], mid = ma * t.A[d] - mb * t.B[d];
+        o[d] = (float)d1; o[3 + d] = (float)(mid - d1); o[6 + d] = (float)(-d4 - mid); o[9 + d] = (float)d4;
+    }
+}
+
 // Value of CV c of the system whose positions start at x.  Called by all lanes of the workgroup; the value is valid on lane 0
-// (on every lane for rg and contacts).  cen receives the selection's centroid (rg, rmsd; every lane).  WANT_ROT: on lane 0 an
-// rmsd also leaves in rot the optimal proper rotation R taking the centred reference onto the centred selection
-// (row-major: a_i ~ sum_j rot[3 i + j] b_j).
+// (on every lane for rg, contacts and dihedral_similarity).  cen receives the selection's centroid (rg, rmsd; every lane).
+// WANT_ROT: on lane 0 an rmsd also leaves in rot the optimal proper rotation R taking the centred reference onto the centred
+// selection (row-major: a_i ~ sum_j rot[3 i + j] b_j).
 template <bool WANT_ROT>
 __device__ __forceinline__ double cv_evaluate(const float* __restrict__ x, int stride, const upk_cv_t& C, int c, double (*part)[CV_MAX_SUMS],
                                               double (&cen)[3], double (&rot)[9]) {
@@ -211,6 +256,18 @@ __device__ __forceinline__ double cv_evaluate(const float* __restrict__ x, int s
         }
         block_sum<1>(q, part);
         value = q[0] / (double)n_pair;
+    } else if (kind == UPK_CV_DIHEDRAL_SIMILARITY) {
+        const int n_quad = n / 4;
+        const float* __restrict__ phi0 = C.dihedral_ref + C.aux_start[c];
+        double q[1] = {0.};
+        for (int i = tid; i < n_quad; i += CV_BLOCK) {
+            cv_torsion_t t;
+            q[0] += 0.5 * (1. + cos(cv_torsion(x, stride, atoms + 4 * i, t) - (double)phi0[i]));
+        }
+        block_sum<1>(q, part);
+        value = q[0] / (double)n_quad;
+    } else if (kind == UPK_CV_DIHEDRAL) {
+        if (tid == 0) { cv_torsion_t t; value = cv_torsion(x, stride, atoms, t); }
     } else {      // UPK_CV_DISTANCE
         if (tid == 0) {
             double ax, ay, az, bx, by, bz;
@@ -223,9 +280,11 @@ __device__ __forceinline__ double cv_evaluate(const float* __restrict__ x, int s
 }
 
 // dE/dv * dv/dx of CV c, one fp32 3-vector per list entry, into the entry's own slot out[(atom_start[c] + entry) * 3 ..]: lane t
-// writes entries t, t + CV_BLOCK, ... (a distance: lane 0).  v is the CV's value, cen the centroid cv_evaluate left (rg, rmsd) and
-// rot nine doubles in LDS holding its rotation (rmsd only; read inside that branch).  Small values: an rg, rmsd or distance below
-// UPK_CV_RESTRAINT_VMIN and a contact pair at r = 0 have no direction and receive zero.  Every slot of the CV is written.
+// writes entries t, t + CV_BLOCK, ... (a distance or dihedral: lane 0; a dihedral_similarity: quadruples t, t + CV_BLOCK, ...).
+// v is the CV's value, cen the centroid cv_evaluate left (rg, rmsd) and rot nine doubles in LDS holding its rotation (rmsd only;
+// read inside that branch).  Small values: an rg, rmsd or distance below
+// UPK_CV_RESTRAINT_VMIN, a contact pair at r = 0 and a torsion without a direction (cv_torsion_gradient) receive zero.  Every slot
+// of the CV is written.
 __device__ __forceinline__ void cv_write_gradient(const float* __restrict__ x, int stride, const upk_cv_t& C, int c, double v, double dEdv,
                                                   const double (&cen)[3], const double* rot, float* __restrict__ out) {
     const int tid = threadIdx.x;
@@ -267,6 +326,17 @@ __device__ __forceinline__ void cv_write_gradient(const float* __restrict__ x, i
             const float gx = (float)(g * ax), gy = (float)(g * ay), gz = (float)(g * az);
             o[6 * i] = gx; o[6 * i + 1] = gy; o[6 * i + 2] = gz; o[6 * i + 3] = -gx; o[6 * i + 4] = -gy; o[6 * i + 5] = -gz;
         }
+    } else if (kind == UPK_CV_DIHEDRAL_SIMILARITY) {      // dv/dphi_i = -1/2 sin(phi_i - phi0_i) / m, into the quadruple's own 4 slots
+        const int n_quad = n / 4;
+        const float* __restrict__ phi0 = C.dihedral_ref + C.aux_start[c];
+        const double f = -0.5 * dEdv / (double)n_quad;
+        for (int i = tid; i < n_quad; i += CV_BLOCK) {
+            cv_torsion_t t;
+            const double phi = cv_torsion(x, stride, atoms + 4 * i, t);
+            cv_torsion_gradient(t, f * sin(phi - (double)phi0[i]), o + 12 * i);
+        }
+    } else if (kind == UPK_CV_DIHEDRAL) {
+        if (tid == 0) { cv_torsion_t t; cv_torsion(x, stride, atoms, t); cv_torsion_gradient(t, dEdv, o); }
     } else if (tid == 0) {      // UPK_CV_DISTANCE
         double ax, ay, az, bx, by, bz;
         ld3d(x, atoms[0], stride, ax, ay, az); ld3d(x, atoms[1], stride, bx, by, bz);

@@ -746,23 +746,24 @@ void DerivEngine::param_deriv_accumulate(int node, const float* weights) {
 
 // ---- collective variables (upside_hip_cv_define / _compute / _record / _read) -----------------------------------------------------
 CvHostDefinition cv_check_definition(int n_atom, int n_cv, const int* kind, const int* atom_start, const int* atoms, const float* ref_pos,
-                                     const float* contact_r0, const float* contact_beta, const float* contact_lambda) {
-    static const char* kind_name[] = {"rg", "rmsd", "contacts", "distance"};
+                                     const float* contact_r0, const float* contact_beta, const float* contact_lambda, const float* dihedral_ref) {
+    static const char* kind_name[] = {"rg", "rmsd", "contacts", "distance", "dihedral", "dihedral_similarity"};
     if (n_cv < 0) throw string("collective variables: n_cv is negative");
     if (n_cv > UPK_CV_MAX) throw string("collective variables: ") + to_string(n_cv) + " CVs exceed the kernel's limit of " + to_string(UPK_CV_MAX) + " (UPK_CV_MAX)";
     if (n_cv && (!kind || !atom_start || !atoms)) throw string("collective variables: kind, atom_start and atoms must be given");
     CvHostDefinition def; def.n_cv = n_cv;
     vector<int>&h_kind = def.kind, &h_start = def.atom_start, &h_atoms = def.atoms, &h_aux = def.aux_start;
     vector<double>&h_ref = def.ref, &h_ref_g = def.ref_g;
-    vector<float>&h_r0 = def.r0, &h_beta = def.beta, &h_lambda = def.lambda;
+    vector<float>&h_r0 = def.r0, &h_beta = def.beta, &h_lambda = def.lambda, &h_dref = def.dihedral_ref;
     h_aux.assign((size_t)n_cv, 0); h_ref_g.assign((size_t)n_cv, 0.); h_beta.assign((size_t)n_cv, 0.f); h_lambda.assign((size_t)n_cv, 0.f);
     if (n_cv) {
         h_kind.assign(kind, kind + n_cv); h_start.assign(atom_start, atom_start + n_cv + 1);
         if (h_start[0] != 0) throw string("collective variables: atom_start[0] must be 0");
-        size_t n_ref = 0, n_pair = 0;
+        size_t n_ref = 0, n_pair = 0, n_quad = 0;
         for (int c = 0; c < n_cv; ++c) {
             const string who = "collective variable " + to_string(c);
-            if (h_kind[c] < 0 || h_kind[c] > UPK_CV_DISTANCE) throw who + ": unknown kind " + to_string(h_kind[c]) + " (0 rg, 1 rmsd, 2 contacts, 3 distance)";
+            if (h_kind[c] < 0 || h_kind[c] > UPK_CV_DIHEDRAL_SIMILARITY)
+                throw who + ": unknown kind " + to_string(h_kind[c]) + " (0 rg, 1 rmsd, 2 contacts, 3 distance, 4 dihedral, 5 dihedral_similarity)";
             const string whok = who + " (" + kind_name[h_kind[c]] + ")";
             const long n = (long)h_start[c + 1] - h_start[c];
             if (n < 0) throw whok + ": atom_start must not decrease";
@@ -781,10 +782,26 @@ CvHostDefinition cv_check_definition(int n_atom, int n_cv, const int* kind, cons
                 if (!std::isfinite(contact_beta[c]) || !std::isfinite(contact_lambda[c])) throw whok + ": beta and lambda must be finite";
                 h_aux[c] = (int)n_pair; n_pair += (size_t)(n / 2);
                 h_beta[c] = contact_beta[c]; h_lambda[c] = contact_lambda[c];
-            } else if (h_kind[c] == UPK_CV_DISTANCE && n != 2) throw whok + ": a distance needs exactly 2 atoms";
+            } else if (h_kind[c] == UPK_CV_DISTANCE) {
+                if (n != 2) throw whok + ": a distance needs exactly 2 atoms";
+            } else if (h_kind[c] == UPK_CV_DIHEDRAL || h_kind[c] == UPK_CV_DIHEDRAL_SIMILARITY) {
+                if (h_kind[c] == UPK_CV_DIHEDRAL && n != 4) throw whok + ": a dihedral needs exactly 4 atoms";
+                if (n % 4) throw whok + ": a dihedral_similarity list holds interleaved quadruples, its length must be a multiple of 4";
+                for (long i = 0; i < n / 4; ++i) {
+                    const int* q = atoms + h_start[c] + 4 * i;
+                    if (q[0] == q[1] || q[0] == q[2] || q[0] == q[3] || q[1] == q[2] || q[1] == q[3] || q[2] == q[3])
+                        throw whok + ": quadruple " + to_string(i) + " repeats an atom";
+                }
+                if (h_kind[c] == UPK_CV_DIHEDRAL_SIMILARITY) {
+                    if (!dihedral_ref) throw whok + ": dihedral_ref must be given (upside_hip_cv_define2)";
+                    for (long i = 0; i < n / 4; ++i) if (!std::isfinite(dihedral_ref[n_quad + i])) throw whok + ": dihedral_ref is not finite";
+                    h_aux[c] = (int)n_quad; n_quad += (size_t)(n / 4);
+                }
+            }
         }
         h_atoms.assign(atoms, atoms + h_start[n_cv]);
         h_r0.assign(contact_r0, contact_r0 + (contact_r0 ? n_pair : 0));
+        h_dref.assign(dihedral_ref, dihedral_ref + (dihedral_ref ? n_quad : 0));
         h_ref.resize(n_ref * 3);
         for (int c = 0; c < n_cv; ++c) if (h_kind[c] == UPK_CV_RMSD) {      // the reference centred in double, and its squared norm
             const size_t n = (size_t)(h_start[c + 1] - h_start[c]), o = (size_t)h_aux[c] * 3;
@@ -812,27 +829,33 @@ CvHostDefinition cv_read_definition(hid_t_compat group, int n_atom, const string
     auto r0 = h5u::read<float>(g, "contact_r0", 1);
     auto beta = h5u::read<float>(g, "contact_beta", 1), lambda = h5u::read<float>(g, "contact_lambda", 1);
     if (beta.size() != n_cv || lambda.size() != n_cv) throw where + ": contact_beta and contact_lambda must have n_cv entries";
+    vector<float> dref;      // optional: a file without it has no dihedral_similarity
+    if (h5u::exists(g, "dihedral_ref")) dref = h5u::read<float>(g, "dihedral_ref", 1);
     // the packed arrays must be as long as the kinds say (cv_check_definition reads them by those counts)
-    size_t n_ref = 0, n_pair = 0;
+    size_t n_ref = 0, n_pair = 0, n_quad = 0;
     for (size_t c = 0; c < n_cv; ++c) {
         const long n = (long)atom_start[c + 1] - atom_start[c];
         if (n < 0) throw where + ": atom_start must not decrease";
         if (kind[c] == UPK_CV_RMSD) n_ref += (size_t)n; else if (kind[c] == UPK_CV_CONTACTS) n_pair += (size_t)(n / 2);
+        else if (kind[c] == UPK_CV_DIHEDRAL_SIMILARITY) n_quad += (size_t)(n / 4);
     }
     if (ref_pos.size() != n_ref * 3) throw where + ": ref_pos holds " + to_string(ref_pos.size() / 3) + " rows, the rmsd selections " + to_string(n_ref);
     if (r0.size() != n_pair) throw where + ": contact_r0 holds " + to_string(r0.size()) + " entries, the contacts lists " + to_string(n_pair) + " pairs";
-    return cv_check_definition(n_atom, (int)n_cv, kind.data(), atom_start.data(), atoms.data(), ref_pos.data(), r0.data(), beta.data(), lambda.data());
+    if (dref.size() != n_quad)
+        throw where + ": dihedral_ref holds " + to_string(dref.size()) + " entries, the dihedral_similarity lists " + to_string(n_quad) + " quadruples";
+    return cv_check_definition(n_atom, (int)n_cv, kind.data(), atom_start.data(), atoms.data(), ref_pos.data(), r0.data(), beta.data(), lambda.data(),
+                               dref.data());
 }
 void CvDeviceDefinition::upload(const CvHostDefinition& d) {
     kind.upload(d.kind); atom_start.upload(d.atom_start); atoms.upload(d.atoms); aux_start.upload(d.aux_start);
-    ref.upload(d.ref); ref_g.upload(d.ref_g); r0.upload(d.r0); beta.upload(d.beta); lambda.upload(d.lambda);
+    ref.upload(d.ref); ref_g.upload(d.ref_g); r0.upload(d.r0); beta.upload(d.beta); lambda.upload(d.lambda); dihedral_ref.upload(d.dihedral_ref);
     C.n_cv = d.n_cv; C.kind = kind.p; C.atom_start = atom_start.p; C.atoms = atoms.p; C.aux_start = aux_start.p;
-    C.ref = ref.p; C.ref_g = ref_g.p; C.r0 = r0.p; C.beta = beta.p; C.lambda = lambda.p;
+    C.ref = ref.p; C.ref_g = ref_g.p; C.r0 = r0.p; C.beta = beta.p; C.lambda = lambda.p; C.dihedral_ref = dihedral_ref.p;
 }
 void DerivEngine::cv_define(int n_cv, const int* kind, const int* atom_start, const int* atoms, const float* ref_pos, const float* contact_r0,
-                            const float* contact_beta, const float* contact_lambda) {
+                            const float* contact_beta, const float* contact_lambda, const float* dihedral_ref) {
     // everything is checked and built on the host before the first device array is touched: a refusal leaves the old definition in force
-    cv_install(cv_check_definition(pos->n_atom, n_cv, kind, atom_start, atoms, ref_pos, contact_r0, contact_beta, contact_lambda));
+    cv_install(cv_check_definition(pos->n_atom, n_cv, kind, atom_start, atoms, ref_pos, contact_r0, contact_beta, contact_lambda, dihedral_ref));
 }
 void DerivEngine::cv_install(const CvHostDefinition& def) {
     sync();

@@ -498,7 +498,11 @@ extern "C" int upside_hip_run_steps(DerivEngine* e, int n_step) {
 // ---- collective variables of every system (kernels_cv.hip) ---------------------------------------------------
 extern "C" int upside_hip_cv_define(DerivEngine* e, int n_cv, const int* kind, const int* atom_start, const int* atoms, const float* ref_pos,
                                     const float* contact_r0, const float* contact_beta, const float* contact_lambda) {
-    API_TRY e->cv_define(n_cv, kind, atom_start, atoms, ref_pos, contact_r0, contact_beta, contact_lambda); return 0; API_CATCH(1)
+    return upside_hip_cv_define2(e, n_cv, kind, atom_start, atoms, ref_pos, contact_r0, contact_beta, contact_lambda, nullptr);
+}
+extern "C" int upside_hip_cv_define2(DerivEngine* e, int n_cv, const int* kind, const int* atom_start, const int* atoms, const float* ref_pos,
+                                     const float* contact_r0, const float* contact_beta, const float* contact_lambda, const float* dihedral_ref) {
+    API_TRY e->cv_define(n_cv, kind, atom_start, atoms, ref_pos, contact_r0, contact_beta, contact_lambda, dihedral_ref); return 0; API_CATCH(1)
 }
 namespace {
 vector<string> read_string_dataset(hid_t loc, const string& name) {      // fixed-length strings, one dimension

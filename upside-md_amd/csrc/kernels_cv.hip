@@ -1,5 +1,5 @@
-// gfx950 kernels of the collective variables: radius of gyration, RMSD after optimal superposition, fraction of native contacts
-// and plain distances of EVERY system in one launch -- as observables (upside_hip_cv_*, k_collective_variables) and as the
+// gfx950 kernels of the collective variables: radius of gyration, RMSD after optimal superposition, fraction of native contacts,
+// plain distances, torsions and torsional similarity of EVERY system in one launch -- as observables (upside_hip_cv_*, k_collective_variables) and as the
 // coordinates of a bias in the force pass (node cv_restraint: k_cv_restraint, an umbrella; node cv_metadynamics: k_cv_metad and
 // k_cv_metad_deposit at the end of this file, Gaussian hills deposited during MD).  The value of a CV is computed by cv_device.h for
 // all of them, and its gradient for the two biases.
@@ -65,14 +65,17 @@ extern "C" int upk_cv_record(const upk_launch_t* L, upk_coord_t pos, const upk_c
     return cv_launch(L, pos, C, *R, nullptr);
 }
 
-// ---- cv_restraint: E = sum_c 1/2 k_c u_c^2, u_c = max(0, |v_c - center_c| - flat_width_c), per system ------------------------------
+// ---- cv_restraint: E = sum_c 1/2 k_c u_c^2, u_c = max(0, |d_c| - flat_width_c), d_c = v_c - center_c, per system ---------------------
+// A periodic CV (a dihedral, period 2 pi) takes d_c = cv_wrap(v_c - center_c): the nearest image of the centre, which may be any
+// finite number.  The other kinds execute the plain difference.
 // The shape of the kernel above: one workgroup per system walks the node's CVs.  Per CV the value v comes from cv_evaluate (the
 // bits k_collective_variables reports), lane 0 turns it into dE/dv with this system's row [center | spring_const | flat_width]
 // at par + s * par_stride and hands v, dE/dv and (rmsd) the rotation to the other lanes through LDS; a second lane-strided pass
 // (cv_write_gradient) writes dE/dv * dv/dx of every list entry, as one fp32 3-vector, into the entry's own slot of the scatter source of pos
 // (contrib[s][entry][3]: one writer per slot, every slot written on every launch; the parent gathers in its fixed order, so an
-// atom may sit in several CVs and many pairs).  Small values: an rg, rmsd or distance below UPK_CV_RESTRAINT_VMIN and a contact
-// pair at r = 0 have no direction; they contribute zero force (their energy is counted).
+// atom may sit in several CVs and many pairs).  Small values: an rg, rmsd or distance below UPK_CV_RESTRAINT_VMIN, a contact
+// pair at r = 0 and a torsion with coincident or collinear atoms have no direction; they contribute zero force (their energy is
+// counted).
 __global__ void __launch_bounds__(CV_BLOCK) k_cv_restraint(upk_coord_t pos, upk_cv_t C, const float* __restrict__ par, long par_stride,
                                                            float* __restrict__ contrib, long contrib_stride, float* __restrict__ values,
                                                            float* __restrict__ pot_terms) {
@@ -90,7 +93,9 @@ __global__ void __launch_bounds__(CV_BLOCK) k_cv_restraint(upk_coord_t pos, upk_
         const int kind = C.kind[c];
         double* b = bc[c & 1];
         if (tid == 0) {
-            const double d = value - (double)row[c], k = (double)row[C.n_cv + c], w = (double)row[2 * C.n_cv + c];
+            double d = value - (double)row[c];
+            if (cv_periodic(kind)) d = cv_wrap(d);
+            const double k = (double)row[C.n_cv + c], w = (double)row[2 * C.n_cv + c];
             const double u = fmax(0., fabs(d) - w);
             b[0] = value; b[1] = d < 0. ? -(k * u) : k * u;
             if (kind == UPK_CV_RMSD) {
@@ -121,16 +126,22 @@ extern "C" int upk_cv_restraint(const upk_launch_t* L, upk_coord_t pos, const up
 // hills of the system's list -- no cutoff, no grid -- of V and its D partial derivatives in one order (lane t: hills t, t + CV_BLOCK,
 // ... ascending, then block_sum<D + 1>); (3) dV/dv_c * dv_c/dx into the list entries' own scatter slots by cv_write_gradient, every
 // slot on every launch (zeros while the list is empty).  Hills are stored [list][D + 1][capacity], so consecutive lanes read
-// consecutive floats of each row.
+// consecutive floats of each row.  In a periodic dimension (a dihedral; periodic[c], uniform over the launch) v_c - s_hc is folded
+// by cv_wrap: the nearest image of the hill only, no sum over images -- sigma is expected to be well below pi, where the next
+// image's exp(-(2 pi - |d|)^2 / (2 sigma^2)) is nothing.  The other dimensions execute the plain difference.
 template <int D>
 __device__ __forceinline__ void metad_hill_sum(const float* __restrict__ hills, int capacity, int n_hill, const double (&v)[D], const double (&inv_s2)[D],
-                                               double (&acc)[D + 1]) {
+                                               const bool (&periodic)[D], double (&acc)[D + 1]) {
 #pragma unroll
     for (int k = 0; k <= D; ++k) acc[k] = 0.;
     for (int h = threadIdx.x; h < n_hill; h += CV_BLOCK) {
         double diff[D], e = 0.;
 #pragma unroll
-        for (int c = 0; c < D; ++c) { diff[c] = v[c] - (double)hills[(size_t)c * capacity + h]; e += diff[c] * diff[c] * inv_s2[c]; }
+        for (int c = 0; c < D; ++c) {
+            diff[c] = v[c] - (double)hills[(size_t)c * capacity + h];
+            if (periodic[c]) diff[c] = cv_wrap(diff[c]);
+            e += diff[c] * diff[c] * inv_s2[c];
+        }
         const double g = (double)hills[(size_t)D * capacity + h] * exp(-0.5 * e);
         acc[0] += g;
 #pragma unroll
@@ -170,11 +181,12 @@ __global__ void __launch_bounds__(CV_BLOCK) k_cv_metad(upk_coord_t pos, upk_cv_t
     }
     __syncthreads();
     double v[D], inv_s2[D], acc[D + 1];
+    bool periodic[D];
 #pragma unroll
-    for (int c = 0; c < D; ++c) { v[c] = st[c][0]; const double sg = (double)M.sigma[c]; inv_s2[c] = 1. / (sg * sg); }
+    for (int c = 0; c < D; ++c) { v[c] = st[c][0]; const double sg = (double)M.sigma[c]; inv_s2[c] = 1. / (sg * sg); periodic[c] = cv_periodic(C.kind[c]); }
     int n_hill;
     const float* __restrict__ hills = M.hills + metad_list(M, D, s, (int)gridDim.x, M.n_deposit[s], n_hill);
-    metad_hill_sum<D>(hills, M.capacity, n_hill, v, inv_s2, acc);
+    metad_hill_sum<D>(hills, M.capacity, n_hill, v, inv_s2, periodic, acc);
     block_sum<D + 1>(acc, part);
     if (tid == 0 && pot_terms) pot_terms[s] = (float)acc[0];
 #pragma unroll 1
@@ -211,12 +223,13 @@ __global__ void __launch_bounds__(CV_BLOCK) k_cv_metad_deposit(upk_coord_t pos, 
     }
     __syncthreads();
     double v[D], inv_s2[D], acc[D + 1];
+    bool periodic[D];
 #pragma unroll
-    for (int c = 0; c < D; ++c) { v[c] = st[c]; const double sg = (double)M.sigma[c]; inv_s2[c] = 1. / (sg * sg); }
+    for (int c = 0; c < D; ++c) { v[c] = st[c]; const double sg = (double)M.sigma[c]; inv_s2[c] = 1. / (sg * sg); periodic[c] = cv_periodic(C.kind[c]); }
     int n_hill;
     const size_t list = metad_list(M, D, s, n_system, k, n_hill);
     if (M.kdT > 0.f) {      // (uniform over the workgroup)
-        metad_hill_sum<D>(M.hills + list, M.capacity, n_hill, v, inv_s2, acc);
+        metad_hill_sum<D>(M.hills + list, M.capacity, n_hill, v, inv_s2, periodic, acc);
         block_sum<D + 1>(acc, part);
     } else acc[0] = 0.;
     if (tid == 0) {

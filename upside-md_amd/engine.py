@@ -282,6 +282,7 @@ class Ensemble(object):
         c.upside_hip_hamiltonian_swap.argtypes = [vp, i32, vp, u32, u64, i32, vp]
         c.upside_hip_last_error.restype = ct.c_char_p
         c.upside_hip_cv_define.argtypes = [vp, i32, vp, vp, vp, vp, vp, vp, vp]
+        c.upside_hip_cv_define2.argtypes = [vp, i32, vp, vp, vp, vp, vp, vp, vp, vp]
         c.upside_hip_cv_load.argtypes = [vp, ct.c_char_p]
         c.upside_hip_cv_count.argtypes = [vp]
         c.upside_hip_cv_compute.argtypes = [vp, vp]
@@ -424,9 +425,12 @@ class Ensemble(object):
         n_cv = len(p['kind'])
         arr = dict((k, np.ascontiguousarray(p[k], t)) for k, t in (('kind', 'i4'), ('atom_start', 'i4'), ('atoms', 'i4'), ('ref_pos', 'f4'),
                                                                      ('contact_r0', 'f4'), ('contact_beta', 'f4'), ('contact_lambda', 'f4')))
-        self._check(self.calc.upside_hip_cv_define(self.engine, n_cv, *[arr[k].ctypes.data for k in
-                    ('kind', 'atom_start', 'atoms', 'ref_pos', 'contact_r0', 'contact_beta', 'contact_lambda')]), 'cv_define')
+        dref = np.ascontiguousarray(p['dihedral_ref'], 'f4') if 'dihedral_ref' in p else None      # (a dict packed before the kind existed)
+        self._check(self.calc.upside_hip_cv_define2(self.engine, n_cv, *([arr[k].ctypes.data for k in
+                    ('kind', 'atom_start', 'atoms', 'ref_pos', 'contact_r0', 'contact_beta', 'contact_lambda')] +
+                    [None if dref is None else dref.ctypes.data])), 'cv_define')
         self.cv_names = [x.decode() if isinstance(x, bytes) else str(x) for x in p['names']]
+        self._cv_periods = config.cv_periods(p)
 
     def load_cvs(self, path=None):
         """/input/collective_variables of a configuration (default: the engine's own); returns the number of CVs (0: no such group)"""
@@ -435,9 +439,18 @@ class Ensemble(object):
         if n < 0:
             raise RuntimeError('cv_load failed: %s' % self.calc.upside_hip_last_error().decode())
         if n:
+            from . import config
             with h5lite.open_file(path) as t:
-                self.cv_names = [x.decode() for x in t.group('input').group('collective_variables').read('names').ravel()]
+                g = t.group('input').group('collective_variables')
+                self.cv_names = [x.decode() for x in g.read('names').ravel()]
+                self._cv_periods = config.cv_periods(dict(kind=g.read('kind')))
+                del g      # (the handle is released before the file's)
         return n
+
+    @property
+    def cv_periods(self):
+        """one period per CV of the current definition (2 pi for a dihedral, 0 = not periodic)"""
+        return np.array(getattr(self, '_cv_periods', np.zeros(0)), 'f8')
 
     @property
     def n_cv(self):
