@@ -209,7 +209,7 @@ int upside_hip_param_deriv_read(DerivEngine* engine, const char* node_name, int 
  *   _group_configurations: the grouping upside_main uses (HDF5 only, no device): group_of[i] = group of files[i], groups
  *     numbered by first appearance; returns the number of groups, -1 on failure.  Files that are identical or differ only
  *     in the table's values share a group; UPSIDE_HIP_HAMILTONIAN_BATCH=0 groups by the whole /input/potential instead.
- *   _set_param_system / _get_param_system: set_param / get_param of one system (hbond_energy, cv_restraint).
+ *   _set_param_system / _get_param_system: set_param / get_param of one system (hbond_energy, cv_restraint, cv_steer).
  *     set_param keeps its meaning (every system); get_param returns system 0's values.
  *   _hamiltonian_swap: one swap set (main.cpp:251-273) on the engine's stream: energy pass, the pairs trade coordinates,
  *     energy pass, Metropolis verdicts of upside_replica_decide_lboltz (each system's own temperature), refused pairs trade
@@ -286,6 +286,21 @@ int upside_hip_metad_info(DerivEngine* engine, const char* node_name, int* d, in
 int upside_hip_metad_read(DerivEngine* engine, const char* node_name, int list, float* centers, float* weights, int* n_hill, long long* n_attempt);
 int upside_hip_metad_write(DerivEngine* engine, const char* node_name, int list, const float* centers, const float* weights, int n_hill);
 int upside_hip_metad_values(DerivEngine* engine, const char* node_name, float* out);
+/* cv_steer nodes: a cv_restraint whose centre moves with each system's own clock (completed MD rounds
+ * since the clock was last written) while the work of moving it is accumulated in float64 on the device.  All return 0, or 1 on
+ * error (upside_hip_last_error: the node is no cv_steer, ...); any out pointer may be NULL.
+ * _info: the node's number of CVs.
+ * _read: clock (n_system), work (n_system) and center (n_system, n_cv): the centres in force, as of the last force pass or
+ *   completed round (after _write: from the next force pass on).  Synchronises.
+ * _write: replaces every system's clock and / or work (NULL: kept) by stream-ordered copies; the next force pass, also one replayed
+ *   from a captured graph, sees them.  Refused: a negative clock, work that is not finite.
+ * _values: out (n_system, n_cv), the CV values of the last force pass (the bits upside_hip_cv_compute gives); system 0's row is also
+ *   get_value_by_name(node, "cv_value").
+ * Work and clock belong to the system index: a coordinate swap between systems leaves them where they are. */
+int upside_hip_steer_info(DerivEngine* engine, const char* node_name, int* n_cv);
+int upside_hip_steer_read(DerivEngine* engine, const char* node_name, long long* clock, double* work, double* center);
+int upside_hip_steer_write(DerivEngine* engine, const char* node_name, const long long* clock, const double* work);
+int upside_hip_steer_values(DerivEngine* engine, const char* node_name, float* out);
 
 /* Per-kernel timing hooks used by bench.py.  With profiling enabled every interaction-graph / BP kernel
  * launch is bracketed by HIP events on the engine's stream.  upside_hip_profile_dump writes one text line per

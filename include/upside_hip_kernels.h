@@ -523,6 +523,18 @@ int upk_cv_record(const upk_launch_t* L, upk_coord_t pos, const upk_cv_t* C, con
 #define UPK_CV_RESTRAINT_VMIN 1e-6
 int upk_cv_restraint(const upk_launch_t* L, upk_coord_t pos, const upk_cv_t* C, const float* par, long par_stride, float* contrib,
                      long contrib_stride, float* values, float* pot_terms);
+/* cv_steer (node of the force pass + an advance per completed MD round): upk_cv_restraint with a centre that moves on a schedule.
+ * par + s * par_stride is system s's row [center | rate | center_end | spring_const | flat_width] (5 n_cv floats; par_stride >= 5 n_cv)
+ * and clock[s] its completed MD rounds t.  The centre in force is c(t) = center + rate * t in fp64 (product and sum rounded
+ * separately), stopped at center_end on the side rate moves it to; d = v - c(t), wrapped for a periodic kind while c(t) itself
+ * stays on the unwrapped line.  Outputs as upk_cv_restraint, and centers[s][n_cv] = c(t).  No argument changes between launches. */
+int upk_cv_steer(const upk_launch_t* L, upk_coord_t pos, const upk_cv_t* C, const float* par, long par_stride, const unsigned long long* clock,
+                 float* contrib, long contrib_stride, float* values, float* pot_terms, double* centers);
+/* one completed MD round: work[s] += sum_c E_c(v_c, c_c(t + 1)) - E_c(v_c, c_c(t)) in fp64, CVs ascending, with v_c the bits
+ * upk_cv_compute reports at the current positions; then clock[s] = t + 1 and centers[s][n_cv] = c(t + 1).  Each system's workgroup
+ * owns its entries: no atomics. */
+int upk_cv_steer_advance(const upk_launch_t* L, upk_coord_t pos, const upk_cv_t* C, const float* par, long par_stride, unsigned long long* clock,
+                         double* work, double* centers);
 /* cv_metadynamics (node of the force pass + a deposit per completed MD round): the d = C->n_cv <= UPK_METAD_MAX_DIM CVs of C span
  * one space and the bias is a sum of Gaussian hills,
  *   V(v) = sum_h w_h exp(-sum_c (v_c - s_hc)^2 / (2 sigma_c^2)),   dV/dv_c = sum_h -w_h (v_c - s_hc) / sigma_c^2 exp(...)

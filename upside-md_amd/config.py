@@ -965,6 +965,132 @@ def write_umbrella_windows(base_path, out_paths, node_name, centers, spring_cons
     return out_paths
 
 
+CV_STEER_VALUES = ('center', 'rate', 'center_end', 'spring_const', 'flat_width')     # the datasets that may differ between the files of one engine
+
+
+def add_cv_steer(path, specs, name='cv_steer'):
+    """add a moving restraint on collective variables (node type cv_steer, argument pos) to an existing configuration: steered MD.
+         c_c(t) = center_c + rate_c t, stopped at center_end_c        t: the system's completed MD rounds
+         E = sum_c 1/2 spring_const_c u_c^2,   u_c = max(0, |v_c - c_c(t)| - flat_width_c)
+    (a dihedral: v_c - c_c(t) folded into [-pi, pi]; its centre travels on the unwrapped line and may pass +-pi and wind).  The
+    engine accumulates the work of moving the centres per system (Ensemble.steer_state; steer_work restates it from a recorded CV
+    series).  specs: the dicts of pack_collective_variables, each with the further keys 'center', 'center_end', 'spring_const'
+    (required), 'flat_width' (default 0) and exactly one of 'rate' (change of the centre per MD round; 0 needs center_end == center:
+    a cv_restraint) or 'n_round' (> 0: rate = (center_end - center) / n_round).  name must start with 'cv_steer'.  The five values
+    may differ between the files of one engine (each system pulls at its own speed); everything else of the node must agree.
+    Returns the packed arrays."""
+    if not str(name).startswith('cv_steer'):
+        raise ValueError("add_cv_steer: the node name must start with 'cv_steer', got %r" % (name,))
+    specs = list(specs)
+    if not specs:
+        raise ValueError('add_cv_steer: no collective variables')
+    extra = CV_STEER_VALUES + ('n_round',)
+    bare, val = [], dict((k, []) for k in CV_STEER_VALUES)
+    for c, sp in enumerate(specs):
+        who = 'collective variable %d' % c
+        if not isinstance(sp, dict):
+            raise ValueError(who + ": a dict with a 'kind' is expected")
+        for k in ('center', 'center_end', 'spring_const'):
+            if k not in sp:
+                raise ValueError(who + ': %r is missing' % k)
+        if ('rate' in sp) == ('n_round' in sp):
+            raise ValueError(who + ": exactly one of 'rate' and 'n_round' is expected")
+        v = {}
+        for k in ('center', 'center_end', 'spring_const', 'flat_width', 'rate', 'n_round'):
+            if k in sp or k == 'flat_width':
+                x = sp.get(k, 0.)
+                if np.ndim(x) != 0:
+                    raise ValueError(who + ': %s must be one number' % k)
+                v[k] = float(x)
+                if not np.isfinite(v[k]):
+                    raise ValueError(who + ': %s is not finite' % k)
+        if 'n_round' in v:
+            if not v['n_round'] > 0:
+                raise ValueError(who + ': n_round must be positive')
+            v['rate'] = (v['center_end'] - v['center']) / v['n_round']
+        for k in ('spring_const', 'flat_width'):
+            if v[k] < 0:
+                raise ValueError(who + ': %s must not be negative' % k)
+        # (judged on the float32 values the file holds, as the engine does)
+        c32, r32, e32 = (float(np.float32(v[k])) for k in ('center', 'rate', 'center_end'))
+        if (e32 - c32) * r32 < 0:
+            raise ValueError(who + ': center_end lies behind center (rate moves the centre away from it)')
+        if r32 == 0 and e32 != c32:
+            raise ValueError(who + ': rate is 0 but center_end differs from center')
+        for k in CV_STEER_VALUES:
+            val[k].append(v[k])
+        bare.append(dict((k, x) for k, x in sp.items() if k not in extra))
+    with h5lite.open_file(path) as f:      # everything is checked before the file is opened for writing
+        n_atom = f.group('input').shape('pos')[0]
+    p = pack_collective_variables(bare, n_atom)
+    n_list = np.diff(p['atom_start'])
+    if len(n_list) and n_list.max() > CV_MAX_LIST:
+        raise ValueError('collective variable %d: %d list entries exceed the limit of %d' % (int(n_list.argmax()), int(n_list.max()), CV_MAX_LIST))
+    for k in CV_STEER_VALUES:
+        p[k] = np.asarray(val[k], 'f4')
+    with h5lite.open_file(path, 'r+') as f:
+        pot = f.group('input').group('potential')
+        if name in pot:
+            pot.delete(name)
+        g = pot.create_group(name); _args(g, ['pos'])
+        for k in _cv_datasets(p) + CV_STEER_VALUES:
+            g.write(k, p[k])
+    return p
+
+
+def steer_center(center, rate, center_end, t):
+    """the centres of a cv_steer node after t completed MD rounds, float64: center + rate * t (product and sum rounded separately, as
+    the device does), stopped at center_end on the side rate moves it to.  center, rate, center_end: (n_cv,) or scalars; t: a scalar
+    or (n,), giving (n, n_cv)"""
+    c0, r, ce = (np.asarray(a, 'f8') for a in (center, rate, center_end))
+    t = np.asarray(t, 'f8')
+    c = c0 + r * (t[..., None] if (t.ndim and c0.ndim) else t)
+    return np.where(r > 0, np.minimum(c, ce), np.where(r < 0, np.maximum(c, ce), c))
+
+
+def _steer_energy(v, c, k, w, periods):
+    d = v - c
+    if periods is not None:
+        per = np.broadcast_to(np.asarray(periods, 'f8'), d.shape[-1:])
+        safe = np.where(per > 0, per, 1.)
+        d = np.where(per > 0, d - per * np.rint(d / safe), d)
+    u = np.maximum(0., np.abs(d) - w)
+    return 0.5 * k * u * u
+
+
+def steer_work(values, center, rate, center_end, spring_const, flat_width, periods=None, t0=0):
+    """the work a cv_steer node has accumulated after each MD round, float64 (n_round,), restated from the CV series: values
+    (n_round, n_cv) as recorded at the end of rounds t0 + 1, t0 + 2, ... (the engine's float32 bits, as record_cvs or /output/cv
+    hold them).  At the end of round n the centre is switched from c(n - 1) to c(n) at fixed coordinates:
+         W_n = W_{n-1} + sum_c E_c(v_n, c(n)) - E_c(v_n, c(n - 1))
+    periods (n_cv,) as cv_periods gives them (a dihedral's difference by its nearest image); None: no CV is periodic"""
+    v = np.asarray(values, 'f8')
+    if v.ndim == 1:
+        v = v[:, None]
+    k, w = np.asarray(spring_const, 'f8').reshape(-1), np.asarray(flat_width, 'f8').reshape(-1)
+    if v.ndim != 2 or v.shape[1] != len(k):
+        raise ValueError('steer_work: values must be (n_round, %d)' % len(k))
+    t = int(t0) + np.arange(len(v) + 1)
+    c = steer_center(np.asarray(center, 'f8').reshape(-1), np.asarray(rate, 'f8').reshape(-1), np.asarray(center_end, 'f8').reshape(-1), t)
+    dw = _steer_energy(v, c[1:], k, w, periods) - _steer_energy(v, c[:-1], k, w, periods)
+    total = np.zeros(len(v))
+    for col in range(dw.shape[1]):      # CVs in ascending order, as the device adds them
+        total = total + dw[:, col]
+    return np.cumsum(total)
+
+
+def jarzynski_free_energy(work, kT):
+    """-kT log mean exp(-W / kT) over the pulling trajectories (Jarzynski 1997), by log-sum-exp: safe for |W| >> kT"""
+    w = np.asarray(work, 'f8').reshape(-1)
+    if not len(w) or not np.isfinite(w).all():
+        raise ValueError('jarzynski_free_energy: work must be a non-empty set of finite numbers')
+    if not (np.ndim(kT) == 0 and np.isfinite(kT) and kT > 0):
+        raise ValueError('jarzynski_free_energy: kT must be finite and positive')
+    a = -w / float(kT)
+    m = a.max()
+    return -float(kT) * (m + np.log(np.mean(np.exp(a - m))))
+
+
 METAD_MAX_DIM = 4                  # UPK_METAD_MAX_DIM of include/upside_hip_kernels.h
 METAD_MAX_CAPACITY = 1 << 24
 

@@ -1,5 +1,5 @@
 // Device code shared by the kernels that evaluate collective variables (kernels_cv.hip: k_collective_variables, k_cv_restraint,
-// k_cv_metad, k_cv_metad_deposit).  All compute a CV by cv_evaluate below, so a bias acts on exactly the number the observable
+// k_cv_metad, k_cv_metad_deposit, k_cv_steer, k_cv_steer_advance).  All compute a CV by cv_evaluate below, so a bias acts on exactly the number the observable
 // reports: the same sums in the same order, bit for bit.  The two biases write their forces by cv_write_gradient.
 //   - every sum is accumulated in fp64 and has ONE order: lane t adds elements t, t + CV_BLOCK, ... ascending; the 64 lanes of a
 //     wavefront combine in a fixed butterfly of DPP / permlane exchanges (the two 32-bit halves of a double travel side by side);
@@ -134,6 +134,20 @@ __device__ __forceinline__ void ld3d(const float* __restrict__ x, int atom, int 
 #define CV_TWO_PI 6.283185307179586476925286766559
 __device__ __forceinline__ double cv_wrap(double d) { return d - CV_TWO_PI * rint(d / CV_TWO_PI); }
 __device__ __forceinline__ bool cv_periodic(int kind) { return kind == UPK_CV_DIHEDRAL; }
+// the response of a flat-bottomed harmonic restraint to the (wrapped) difference d: u = max(0, |d| - w), dE/dv = +-k u, E = 1/2 k u^2
+// (k_cv_steer, k_cv_steer_advance; k_cv_restraint keeps these three lines in its own body: through this function its instructions
+// come out in another order)
+__device__ __forceinline__ void cv_harmonic_response(double d, double k, double w, double& dEdv, double& E) {
+    const double u = fmax(0., fabs(d) - w);
+    dEdv = d < 0. ? -(k * u) : k * u;
+    E = 0.5 * k * u * u;
+}
+// the centre of a moving restraint after t completed rounds: center + rate * t in fp64, product and sum rounded separately (what
+// IEEE arithmetic on the host gives: no contraction), stopped at center_end on the side rate moves it to
+__device__ __forceinline__ double cv_steer_center(double center, double rate, double center_end, unsigned long long t) {
+    const double c = __dadd_rn(center, __dmul_rn(rate, (double)t));
+    return rate > 0. ? fmin(c, center_end) : (rate < 0. ? fmax(c, center_end) : c);
+}
 
 // The torsion of the atoms q[0..4) in the notation of Blondel & Karplus (1996): F = r1 - r2, G = r2 - r3, H = r4 - r3, A = F x G,
 // B = H x G, phi = atan2((B x A) . G, (A . B) |G|) in (-pi, pi] -- the sign convention of the reference's backbone torsions, so the

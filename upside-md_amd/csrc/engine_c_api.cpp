@@ -22,6 +22,10 @@ void engine_metad_info(DerivEngine& e, const string& node_name, int* d, int* cap
 void engine_metad_read(DerivEngine& e, const string& node_name, int list, float* centers, float* weights, int* n_hill, long long* n_attempt);
 void engine_metad_write(DerivEngine& e, const string& node_name, int list, const float* centers, const float* weights, int n_hill);
 vector<float> engine_metad_values(DerivEngine& e, const string& node_name);
+int engine_steer_n_cv(DerivEngine& e, const string& node_name);
+void engine_steer_read(DerivEngine& e, const string& node_name, long long* clock, double* work, double* center);
+void engine_steer_write(DerivEngine& e, const string& node_name, const long long* clock, const double* work);
+vector<float> engine_steer_values(DerivEngine& e, const string& node_name);
 int engine_rebuild_flags(DerivEngine& e, const string& node_name, vector<int>& flags);
 int engine_igraph_stats(DerivEngine& e, const string& node_name, double* out);
 double engine_bp_bytes(DerivEngine& e);
@@ -582,6 +586,38 @@ extern "C" int upside_hip_metad_values(DerivEngine* e, const char* node_name, fl
     if (!e || !node_name || !out) throw string("engine, node name or out is NULL");
     const auto v = engine_metad_values(*e, string(node_name));
     copy(v.begin(), v.end(), out);
+    return 0;
+    API_CATCH(1)
+}
+// ---- cv_steer: clocks, accumulated work and centres of a node (nodes.cpp: CVSteer) ---------------------------------------------------
+extern "C" int upside_hip_steer_info(DerivEngine* e, const char* node_name, int* n_cv) {
+    API_TRY
+    if (!e || !node_name) throw string("engine or node name is NULL");
+    const int n = engine_steer_n_cv(*e, string(node_name));
+    if (n_cv) *n_cv = n;
+    return 0;
+    API_CATCH(1)
+}
+extern "C" int upside_hip_steer_read(DerivEngine* e, const char* node_name, long long* clock, double* work, double* center) {
+    API_TRY
+    if (!e || !node_name) throw string("engine or node name is NULL");
+    engine_steer_read(*e, string(node_name), clock, work, center);
+    return 0;
+    API_CATCH(1)
+}
+extern "C" int upside_hip_steer_write(DerivEngine* e, const char* node_name, const long long* clock, const double* work) {
+    API_TRY
+    if (!e || !node_name) throw string("engine or node name is NULL");
+    engine_steer_write(*e, string(node_name), clock, work);
+    e->invalidate_attempt();
+    return 0;
+    API_CATCH(1)
+}
+extern "C" int upside_hip_steer_values(DerivEngine* e, const char* node_name, float* out) {
+    API_TRY
+    if (!e || !node_name) throw string("engine or node name is NULL");
+    const auto v = engine_steer_values(*e, string(node_name));
+    if (out) copy(v.begin(), v.end(), out);
     return 0;
     API_CATCH(1)
 }

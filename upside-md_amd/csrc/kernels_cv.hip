@@ -1,6 +1,7 @@
 // gfx950 kernels of the collective variables: radius of gyration, RMSD after optimal superposition, fraction of native contacts,
 // plain distances, torsions and torsional similarity of EVERY system in one launch -- as observables (upside_hip_cv_*, k_collective_variables) and as the
-// coordinates of a bias in the force pass (node cv_restraint: k_cv_restraint, an umbrella; node cv_metadynamics: k_cv_metad and
+// coordinates of a bias in the force pass (node cv_restraint: k_cv_restraint, an umbrella; node cv_steer: k_cv_steer and
+// k_cv_steer_advance, an umbrella whose centre moves while the work is accumulated; node cv_metadynamics: k_cv_metad and
 // k_cv_metad_deposit at the end of this file, Gaussian hills deposited during MD).  The value of a CV is computed by cv_device.h for
 // all of them, and its gradient for the two biases.
 //
@@ -117,6 +118,102 @@ extern "C" int upk_cv_restraint(const upk_launch_t* L, upk_coord_t pos, const up
     if (!par || !contrib || !values) return 9304;
     hipLaunchKernelGGL(k_cv_restraint, dim3((unsigned)L->n_system), dim3(CV_BLOCK), 0, ST(L), pos, *C, par, par_stride, contrib, contrib_stride,
                        values, pot_terms);
+    return launch_status();
+}
+
+// ---- cv_steer: cv_restraint with a centre that moves on a schedule, and the work that moving it does --------------------------------
+// System s has its own clock t_s (completed MD rounds, in device memory) and its own row [center | rate | center_end | spring_const |
+// flat_width] at par + s * par_stride (5 n_cv floats).  The centre in force is c_c(t_s) = cv_steer_center(...): fixed over the three
+// force passes of a round and switched between rounds, so no kernel argument ever changes and a captured graph replays the pulling.
+// k_cv_steer is k_cv_restraint with that centre (d is wrapped for a periodic kind; the centre itself travels on the unwrapped line
+// and may wind); it also reports the centres it used.
+__global__ void __launch_bounds__(CV_BLOCK) k_cv_steer(upk_coord_t pos, upk_cv_t C, const float* __restrict__ par, long par_stride,
+                                                       const unsigned long long* __restrict__ clock, float* __restrict__ contrib, long contrib_stride,
+                                                       float* __restrict__ values, float* __restrict__ pot_terms, double* __restrict__ centers) {
+    __shared__ double part[CV_WAVES][CV_MAX_SUMS];
+    __shared__ double bc[2][11];      // v, dE/dv, R; by CV parity (a lane may still read CV c's while lane 0 writes CV c+1's)
+    const int s = blockIdx.x, tid = threadIdx.x;
+    const float* __restrict__ x = pos.out + (size_t)s * pos.n_elem * pos.stride;
+    const int stride = pos.stride;
+    const float* __restrict__ row = par + (size_t)s * par_stride;
+    float* __restrict__ out = contrib + (size_t)s * contrib_stride;
+    const unsigned long long t = tid == 0 ? clock[s] : 0ull;      // (lane 0 alone turns values into forces)
+
+    for (int c = 0; c < C.n_cv; ++c) {
+        double cen[3], rot[9];
+        const double value = cv_evaluate<true>(x, stride, C, c, part, cen, rot);
+        const int kind = C.kind[c];
+        double* b = bc[c & 1];
+        if (tid == 0) {
+            const double centre = cv_steer_center((double)row[c], (double)row[C.n_cv + c], (double)row[2 * C.n_cv + c], t);
+            double d = value - centre;
+            if (cv_periodic(kind)) d = cv_wrap(d);
+            double dEdv, E;
+            cv_harmonic_response(d, (double)row[3 * C.n_cv + c], (double)row[4 * C.n_cv + c], dEdv, E);
+            b[0] = value; b[1] = dEdv;
+            if (kind == UPK_CV_RMSD) {
+#pragma unroll
+                for (int i = 0; i < 9; ++i) b[2 + i] = rot[i];
+            }
+            values[(size_t)s * C.n_cv + c] = (float)value;
+            centers[(size_t)s * C.n_cv + c] = centre;
+            if (pot_terms) pot_terms[(size_t)s * C.n_cv + c] = (float)E;
+        }
+        __syncthreads();
+        cv_write_gradient(x, stride, C, c, b[0], b[1], cen, b + 2, out);
+    }
+}
+
+// One completed MD round: the centre of system s switches from c(t_s) to c(t_s + 1) at the end-of-round positions.  The work of that
+// switch is the change of the bias energy at fixed coordinates, summed over the CVs in ascending order, with v_c the bits
+// upk_cv_compute reports ((float) of cv_evaluate<false>'s value), so that the accumulated work is a function of the recorded CV
+// series alone.  Lane 0 of the system's workgroup owns work[s] and clock[s]: no atomics.  centers receives c(t_s + 1), the centres
+// in force from now on.
+__global__ void __launch_bounds__(CV_BLOCK) k_cv_steer_advance(upk_coord_t pos, upk_cv_t C, const float* __restrict__ par, long par_stride,
+                                                               unsigned long long* __restrict__ clock, double* __restrict__ work, double* __restrict__ centers) {
+    __shared__ double part[CV_WAVES][CV_MAX_SUMS];
+    const int s = blockIdx.x, tid = threadIdx.x;
+    const float* __restrict__ x = pos.out + (size_t)s * pos.n_elem * pos.stride;
+    const int stride = pos.stride;
+    const float* __restrict__ row = par + (size_t)s * par_stride;
+    const unsigned long long t = tid == 0 ? clock[s] : 0ull;
+    double dw = 0.;
+
+    for (int c = 0; c < C.n_cv; ++c) {
+        double cen[3], rot[9];
+        const double value = cv_evaluate<false>(x, stride, C, c, part, cen, rot);
+        if (tid == 0) {
+            const double v = (double)(float)value;
+            const double c0 = (double)row[c], rate = (double)row[C.n_cv + c], c_end = (double)row[2 * C.n_cv + c];
+            const double k = (double)row[3 * C.n_cv + c], w = (double)row[4 * C.n_cv + c];
+            const double now = cv_steer_center(c0, rate, c_end, t), next = cv_steer_center(c0, rate, c_end, t + 1ull);
+            double d0 = v - now, d1 = v - next;
+            if (cv_periodic(C.kind[c])) { d0 = cv_wrap(d0); d1 = cv_wrap(d1); }
+            double f0, e0, f1, e1;
+            cv_harmonic_response(d0, k, w, f0, e0);
+            cv_harmonic_response(d1, k, w, f1, e1);
+            dw += e1 - e0;
+            centers[(size_t)s * C.n_cv + c] = next;
+        }
+    }
+    if (tid == 0) { work[s] += dw; clock[s] = t + 1ull; }
+}
+
+extern "C" int upk_cv_steer(const upk_launch_t* L, upk_coord_t pos, const upk_cv_t* C, const float* par, long par_stride, const unsigned long long* clock,
+                            float* contrib, long contrib_stride, float* values, float* pot_terms, double* centers) {
+    UPK_FLUSH(L);
+    if (C->n_cv < 1 || C->n_cv > UPK_CV_MAX || pos.width < 3) return 9301;
+    if (!par || !clock || !contrib || !values || !centers || par_stride < 5L * C->n_cv) return 9306;
+    hipLaunchKernelGGL(k_cv_steer, dim3((unsigned)L->n_system), dim3(CV_BLOCK), 0, ST(L), pos, *C, par, par_stride, clock, contrib, contrib_stride,
+                       values, pot_terms, centers);
+    return launch_status();
+}
+extern "C" int upk_cv_steer_advance(const upk_launch_t* L, upk_coord_t pos, const upk_cv_t* C, const float* par, long par_stride, unsigned long long* clock,
+                                    double* work, double* centers) {
+    UPK_FLUSH(L);
+    if (C->n_cv < 1 || C->n_cv > UPK_CV_MAX || pos.width < 3) return 9301;
+    if (!par || !clock || !work || !centers || par_stride < 5L * C->n_cv) return 9306;
+    hipLaunchKernelGGL(k_cv_steer_advance, dim3((unsigned)L->n_system), dim3(CV_BLOCK), 0, ST(L), pos, *C, par, par_stride, clock, work, centers);
     return launch_status();
 }
 

@@ -31,6 +31,9 @@ vector<string> engine_metad_nodes(DerivEngine& e);      // nodes.cpp: the names 
 void engine_metad_info(DerivEngine& e, const string& node_name, int* d, int* capacity, int* n_list);
 void engine_metad_read(DerivEngine& e, const string& node_name, int list, float* centers, float* weights, int* n_hill, long long* n_attempt);
 void engine_metad_write(DerivEngine& e, const string& node_name, int list, const float* centers, const float* weights, int n_hill);
+vector<string> engine_steer_nodes(DerivEngine& e);      // nodes.cpp: the names of the engine's cv_steer nodes
+int engine_steer_n_cv(DerivEngine& e, const string& node_name);
+void engine_steer_read(DerivEngine& e, const string& node_name, long long* clock, double* work, double* center);
 
 // ---- /output logger ------------------------------------------------------------------------------------------
 namespace {
@@ -159,6 +162,7 @@ struct OutputLogger {   // one per system / configuration file (H5Logger, state_
         if (log_jump) jump_stats.flush();
         for (auto& x : extra) x.flush();
         if (log_cv) cv.flush();
+        for (auto& x : steer) { x.work.flush(); x.clock.flush(); x.center.flush(); }
         if (file >= 0) H5Fflush(file, H5F_SCOPE_LOCAL);
     }
     // the hills of a cv_metadynamics node at the end of the run: /output/metadynamics/<node>/{hill_center (n, d), hill_weight (n),
@@ -174,8 +178,21 @@ struct OutputLogger {   // one per system / configuration file (H5Logger, state_
         a.push(&n_attempt);
         c.close(); w.close(); a.close();
     }
+    // a cv_steer node, at every frame: /output/cv_steer/<node>/{work (frame), clock (frame), center (frame, n_cv)} of the file's system
+    struct SteerLog { EArray work, clock, center; };
+    vector<SteerLog> steer;
+    void add_steer(const string& node, int n_cv) {
+        if (H5Lexists(group, "cv_steer", H5P_DEFAULT) <= 0) { hid_t g = H5Gcreate2(group, "cv_steer", H5P_DEFAULT, H5P_DEFAULT, H5P_DEFAULT); if (g < 0) throw string("unable to create /output/cv_steer"); H5Gclose(g); }
+        h5u::Handle sg(H5Gopen2(group, "cv_steer", H5P_DEFAULT), H5Gclose);
+        h5u::Handle ng(H5Gcreate2(sg, node.c_str(), H5P_DEFAULT, H5P_DEFAULT, H5P_DEFAULT), H5Gclose);
+        if (ng < 0) throw string("unable to create /output/cv_steer/") + node;
+        steer.emplace_back();
+        steer.back().work.create(ng, "work", H5T_NATIVE_DOUBLE, 8, {}); steer.back().clock.create(ng, "clock", H5T_NATIVE_LLONG, sizeof(long long), {});
+        steer.back().center.create(ng, "center", H5T_NATIVE_DOUBLE, 8, {(hsize_t)n_cv});
+    }
     void close() {
         if (file < 0) return;
+        for (auto& x : steer) { x.work.close(); x.clock.close(); x.center.close(); }
         pos.close(); kinetic.close(); potential.close(); time.close(); temperature.close(); replica_index.close(); replica_cumulative_swaps.close(); pivot_stats.close(); jump_stats.close();
         for (auto& x : extra) x.close();
         cv.close();
@@ -607,6 +624,10 @@ int upside_main_impl(int argc, const char* const* argv, int verbose) {
         for (int ns = 0; ns < n_system; ++ns) loggers[ns].add_node_loggers(node_loggers[group_of[ns]]);
     }
     if (write_output) for (int ns = 0; ns < n_system; ++ns) if (n_cv_of[group_of[ns]]) loggers[ns].add_cv(engines[group_of[ns]]->cv.names);
+    vector<vector<string>> steer_nodes(n_group);      // cv_steer: work, clock and centres of the file's system at every frame
+    for (int g = 0; g < n_group; ++g) steer_nodes[g] = engine_steer_nodes(*engines[g]);
+    if (write_output) for (int ns = 0; ns < n_system; ++ns)
+        for (const string& node : steer_nodes[group_of[ns]]) loggers[ns].add_steer(node, engine_steer_n_cv(*engines[group_of[ns]], node));
     vector<vector<float>> frame_cv(n_group);
     vector<int> replica_index(n_total);     // by GLOBAL slot; every rank keeps the whole table (the verdicts are identical everywhere)
     for (int ns = 0; ns < n_total; ++ns) replica_index[ns] = ns;
@@ -634,6 +655,15 @@ int upside_main_impl(int argc, const char* const* argv, int verbose) {
             for (int g = 0; g < n_group; ++g) if (n_cv_of[g]) {
                 frame_cv[g].resize(members[g].size() * (size_t)n_cv_of[g]);
                 if (upside_hip_cv_compute(engines[g], frame_cv[g].data())) throw string(upside_hip_last_error());
+            }
+            if (write_output) for (int g = 0; g < n_group; ++g) for (size_t k = 0; k < steer_nodes[g].size(); ++k) {
+                const int n_cv = engine_steer_n_cv(*engines[g], steer_nodes[g][k]);
+                vector<long long> clk(members[g].size()); vector<double> wrk(members[g].size()), cen(members[g].size() * (size_t)n_cv);
+                engine_steer_read(*engines[g], steer_nodes[g][k], clk.data(), wrk.data(), cen.data());
+                for (size_t l = 0; l < members[g].size(); ++l) {
+                    auto& lg = loggers[members[g][l]].steer[k];
+                    lg.work.push(&wrk[l]); lg.clock.push(&clk[l]); lg.center.push(&cen[l * n_cv]);
+                }
             }
             if (have_pivot && upside_hip_mc_stats(e, 0, mc_stats.data(), 1)) throw string(upside_hip_last_error());   // reset per frame
             if (have_jump && upside_hip_mc_stats(e, 1, mcj_stats.data(), 1)) throw string(upside_hip_last_error());

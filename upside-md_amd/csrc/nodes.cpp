@@ -1811,7 +1811,7 @@ struct ScaledSum : public PotentialNode, BatchedParamDeriv {
 };
 RegisterNodeType<Builtin<ScaledSum>, 1> scaled_sum_node("scaled_sum");
 
-// What cv_restraint and cv_metadynamics share: a CV definition in the datasets of /input/collective_variables, read and checked on
+// What cv_restraint, cv_steer and cv_metadynamics share: a CV definition in the datasets of /input/collective_variables, read and checked on
 // the host by the constructor; the node's type then checks the rest of its group and calls install(), so that nothing touches the
 // device or pos' scatter plan before every host-side check has passed.  v_c is the very number upside_hip_cv_compute reports.
 struct CVBiasNode : public PotentialNode {
@@ -1881,6 +1881,88 @@ struct CVRestraint : public CVBiasNode, TableNode {
     void set_param(const vector<float>& p) override { set_param_all(p); }
 };
 RegisterNodeType<Builtin<CVRestraint>, 1> cv_restraint_node("cv_restraint");
+
+// cv_steer: a cv_restraint whose centre moves on a schedule while the work done on the system is accumulated -- steered MD on the
+// device CVs, the input of Jarzynski and Crooks estimators (this project's own node).  Besides the CV definition the group holds
+// center, rate, center_end, spring_const and flat_width (n_cv each).  System s has its own clock t_s (completed MD rounds):
+//   c_c(t) = center_c + rate_c t (fp64), stopped at center_end_c;   E = sum_c 1/2 k_c max(0, |v_c - c_c(t_s)| - flat_width_c)^2
+// (kernels_cv.hip: k_cv_steer; the difference of a periodic CV is wrapped, the centre itself may wind).  rate is the change of the
+// centre per MD round; rate = 0 is a cv_restraint.  The centre is fixed over the three force passes of a round and switched at its
+// end, where k_cv_steer_advance adds the exact work of the switch, sum_c E_c(v_c, c_c(t + 1)) - E_c(v_c, c_c(t)) at the end-of-round
+// values (the bits the CV observable reports), to W_s and advances t_s: a RoundEndWork launch, never issued by a force pass outside
+// MD or by Monte-Carlo steps.  Rows, clocks and work live in device memory, so no kernel argument ever changes (capturable) and
+// every system may pull at its own speed.  Work and clock belong to the system index, like hills and Hamiltonians: exchanging
+// coordinates between systems leaves them where they are.
+struct CVSteer : public CVBiasNode, TableNode, RoundEndWork {
+    DevBuf<unsigned long long> clock; DevBuf<double> work, centers;      // [S], [S], [S][n_cv] (the centres in force)
+    vector<unsigned long long> clock_staging; vector<double> work_staging;      // sources of the stream-ordered copies of write_state
+    void check_param(const vector<float>& p) const override {
+        const size_t n_cv = (size_t)this->n_cv;
+        if (p.size() != 5 * n_cv)
+            throw string("expected ") + to_string(5 * n_cv) + " values [center | rate | center_end | spring_const | flat_width] but got " + to_string(p.size());
+        static const char* const names[5] = {"center", "rate", "center_end", "spring_const", "flat_width"};
+        for (size_t c = 0; c < n_cv; ++c) {
+            for (int a = 0; a < 5; ++a) if (!std::isfinite(p[a * n_cv + c])) throw string(names[a]) + " of CV " + to_string(c) + " is not finite";
+            for (int a = 3; a < 5; ++a) if (!(p[a * n_cv + c] >= 0.f)) throw string(names[a]) + " of CV " + to_string(c) + " must not be negative";
+            const double center = p[c], rate = p[n_cv + c], center_end = p[2 * n_cv + c];
+            if ((center_end - center) * rate < 0.) throw string("center_end of CV ") + to_string(c) + " lies behind center (rate moves the centre away from it)";
+            if (rate == 0. && center_end != center) throw string("rate of CV ") + to_string(c) + " is 0 but center_end differs from center";
+        }
+    }
+    vector<float> read_row(hid_t_compat g) const override {
+        vector<float> p;
+        for (const char* nm : {"center", "rate", "center_end", "spring_const", "flat_width"}) {
+            auto v = read<float>(H(g), nm, 1);
+            if ((int)v.size() != n_cv) throw string(nm) + " holds " + to_string(v.size()) + " entries, the node has " + to_string(n_cv) + " CVs";
+            p.insert(p.end(), v.begin(), v.end());
+        }
+        check_param(p);
+        return p;
+    }
+    CVSteer(DeviceCtx* c, hid_t_compat grp, CoordNode& pos_) : CVBiasNode(c, grp, pos_, "cv_steer") {
+        const auto row0 = read_row(grp);
+        install();
+        tab.init(c, true, 1, row0);
+        clock.alloc(c->n_system); work.alloc(c->n_system);
+        vector<double> c0((size_t)c->n_system * n_cv);
+        for (int s = 0; s < c->n_system; ++s) for (int k = 0; k < n_cv; ++k) c0[(size_t)s * n_cv + k] = row0[k];
+        centers.upload(c0);
+        alloc_terms(n_cv);
+    }
+    void compute_value(ComputeMode mode) override {
+        upk_check(upk_cv_steer(&ctx->L, pos.coord(), &def.C, tab.ptr(), tab.stride(), clock.p, pos.scatter.source_ptr(src), pos.scatter.arena_size, values.p,
+                               mode == PotentialAndDerivMode ? pot_terms.p : nullptr, centers.p), "cv_steer");
+        if (mode == PotentialAndDerivMode) reduce_terms();
+    }
+    void round_end() override { upk_check(upk_cv_steer_advance(&ctx->L, pos.coord(), &def.C, tab.ptr(), tab.stride(), clock.p, work.p, centers.p), "cv_steer advance"); }
+    vector<float> get_param() const override { return tab.row(0); }
+    void set_param(const vector<float>& p) override { set_param_all(p); }
+    // clocks [S], work [S] and the centres in force [S][n_cv] (of the last force pass or round end); any may be NULL
+    void read_state(long long* clock_out, double* work_out, double* center_out) {
+        hip_check(hipStreamSynchronize(ctx->stream), "hipStreamSynchronize");
+        if (clock_out) { const auto v = clock.download(); for (size_t i = 0; i < v.size(); ++i) clock_out[i] = (long long)v[i]; }
+        if (work_out) { const auto v = work.download(); copy(v.begin(), v.end(), work_out); }
+        if (center_out) { const auto v = centers.download(); copy(v.begin(), v.end(), center_out); }
+    }
+    // replaces every system's clock and / or work (NULL: kept); the next force pass, also a replayed one, sees them
+    void write_state(const long long* clock_in, const double* work_in) {
+        const int S = ctx->n_system;
+        for (int s = 0; s < S; ++s) {
+            if (clock_in && clock_in[s] < 0) throw string("cv_steer: clock of system ") + to_string(s) + " is negative";
+            if (work_in && !std::isfinite(work_in[s])) throw string("cv_steer: work of system ") + to_string(s) + " is not finite";
+        }
+        hip_check(hipStreamSynchronize(ctx->stream), "hipStreamSynchronize");      // the staging arrays may be rewritten only once the previous copies have left them
+        if (clock_in) {
+            clock_staging.assign(clock_in, clock_in + S);
+            hip_check(hipMemcpyAsync(clock.p, clock_staging.data(), (size_t)S * sizeof(unsigned long long), hipMemcpyHostToDevice, ctx->stream), "H2D steer clock");
+        }
+        if (work_in) {
+            work_staging.assign(work_in, work_in + S);
+            hip_check(hipMemcpyAsync(work.p, work_staging.data(), (size_t)S * sizeof(double), hipMemcpyHostToDevice, ctx->stream), "H2D steer work");
+        }
+    }
+};
+RegisterNodeType<Builtin<CVSteer>, 1> cv_steer_node("cv_steer");
 
 // cv_metadynamics: a history-dependent bias on collective variables (this project's own node, like cv_restraint).  The group
 // holds a CV definition in the datasets of /input/collective_variables; its d = n_cv <= UPK_METAD_MAX_DIM CVs span one space in
@@ -1981,6 +2063,20 @@ int engine_cv_restraint_values(DerivEngine& e, const string& node_name, vector<f
     if (!r) return -1;
     if (out) *out = r->all_values();
     return r->n_cv;
+}
+static CVSteer& steer_node(DerivEngine& e, const string& node_name) {
+    auto* m = node_as<CVSteer>(e, node_name);
+    if (!m) throw string("node ") + node_name + " is not a cv_steer";
+    return *m;
+}
+int engine_steer_n_cv(DerivEngine& e, const string& node_name) { return steer_node(e, node_name).n_cv; }
+void engine_steer_read(DerivEngine& e, const string& node_name, long long* clock, double* work, double* center) { steer_node(e, node_name).read_state(clock, work, center); }
+void engine_steer_write(DerivEngine& e, const string& node_name, const long long* clock, const double* work) { steer_node(e, node_name).write_state(clock, work); }
+vector<float> engine_steer_values(DerivEngine& e, const string& node_name) { return steer_node(e, node_name).all_values(); }
+vector<string> engine_steer_nodes(DerivEngine& e) {
+    vector<string> out;
+    for (auto& n : e.nodes) if (dynamic_cast<CVSteer*>(n.computation.get())) out.push_back(n.name);
+    return out;
 }
 static CVMetadynamics& metad_node(DerivEngine& e, const string& node_name) {
     auto* m = node_as<CVMetadynamics>(e, node_name);
@@ -2137,6 +2233,7 @@ const vector<PerSystemValueSpec>& per_system_value_table() {
         {"contact", {"energy", "distance", "width"}, {}},
         {"hbond_energy", {}, {"protein_hbond_energy"}},
         {"cv_restraint", {"center", "spring_const", "flat_width"}, {}},
+        {"cv_steer", {"center", "rate", "center_end", "spring_const", "flat_width"}, {}},
     };
     return t;
 }

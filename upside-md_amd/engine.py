@@ -293,6 +293,10 @@ class Ensemble(object):
         c.upside_hip_metad_read.argtypes = [vp, ct.c_char_p, i32, vp, vp, vp, vp]
         c.upside_hip_metad_write.argtypes = [vp, ct.c_char_p, i32, vp, vp, i32]
         c.upside_hip_metad_values.argtypes = [vp, ct.c_char_p, vp]
+        c.upside_hip_steer_info.argtypes = [vp, ct.c_char_p, vp]
+        c.upside_hip_steer_read.argtypes = [vp, ct.c_char_p, vp, vp, vp]
+        c.upside_hip_steer_write.argtypes = [vp, ct.c_char_p, vp, vp]
+        c.upside_hip_steer_values.argtypes = [vp, ct.c_char_p, vp]
         c._ensemble_bound = True
 
     def _check(self, rc, what):
@@ -526,6 +530,37 @@ class Ensemble(object):
         d = self.metad_info(node_name)[0]
         out = np.zeros((self.n_system, d), 'f4')
         self._check(self.calc.upside_hip_metad_values(self.engine, _b(node_name), out.ctypes.data), 'metad_values')
+        return out
+
+    # -- cv_steer: clocks, work and centres of a node (they live on the device and advance inside run_rounds / run_steps) ---------
+    def _steer_n_cv(self, node_name):
+        n = np.zeros(1, 'i4')
+        self._check(self.calc.upside_hip_steer_info(self.engine, _b(node_name), n.ctypes.data), 'steer_info')
+        return int(n[0])
+
+    def steer_state(self, node_name):
+        """dict(clock (n_system,) i8: completed MD rounds since the clock was last set; work (n_system,) f8: the accumulated work of
+        moving the centres; center (n_system, n_cv) f8: the centres in force, as of the last force pass or completed round).  Work
+        and clock belong to the system index: a coordinate swap leaves them where they are."""
+        n_cv = self._steer_n_cv(node_name)
+        clock = np.zeros(self.n_system, 'i8'); work = np.zeros(self.n_system, 'f8'); center = np.zeros((self.n_system, n_cv), 'f8')
+        self._check(self.calc.upside_hip_steer_read(self.engine, _b(node_name), clock.ctypes.data, work.ctypes.data, center.ctypes.data), 'steer_read')
+        return dict(clock=clock, work=work, center=center)
+
+    def set_steer_state(self, node_name, clock=None, work=None):
+        """replace the clocks and / or the work of every system (a scalar or (n_system,); None: kept).  Stream-ordered: the next
+        force pass sees them, also from a captured graph."""
+        self._steer_n_cv(node_name)
+        ck = None if clock is None else np.ascontiguousarray(np.broadcast_to(np.asarray(clock, 'i8'), (self.n_system,)))
+        wk = None if work is None else np.ascontiguousarray(np.broadcast_to(np.asarray(work, 'f8'), (self.n_system,)))
+        self._check(self.calc.upside_hip_steer_write(self.engine, _b(node_name), None if ck is None else ck.ctypes.data,
+                                                     None if wk is None else wk.ctypes.data), 'steer_write')
+
+    def steer_values(self, node_name):
+        """(n_system, n_cv) CV values the cv_steer node saw in the last force pass: the bits cvs() gives for the same definition at the
+        same positions"""
+        out = np.zeros((self.n_system, self._steer_n_cv(node_name)), 'f4')
+        self._check(self.calc.upside_hip_steer_values(self.engine, _b(node_name), out.ctypes.data), 'steer_values')
         return out
 
     # -- replica exchange across the engines of a job, inside the library (comm_rccl.cpp) -------------
