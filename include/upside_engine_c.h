@@ -302,6 +302,39 @@ int upside_hip_steer_read(DerivEngine* engine, const char* node_name, long long*
 int upside_hip_steer_write(DerivEngine* engine, const char* node_name, const long long* clock, const double* work);
 int upside_hip_steer_values(DerivEngine* engine, const char* node_name, float* out);
 
+/* MBAR (Shirts & Chodera 2008) on the device over the ladders the engine runs, from recorded series alone (csrc/kernels_mbar.hip):
+ * the free energies of n_state states ("windows") from n_sample samples, by self-consistent iteration in float64.  No engine is
+ * needed; every array is a HOST array; the call runs on a stream of its own on the current device and returns when it is done.
+ *   sample n: values[n][0..d) (float32: the recorded CV bits; d may be 0, values then unused) and energy[n] (the unbiased potential;
+ *     NULL = 0).  The samples are copied to the device once, not once per iteration.
+ *   state k: beta[k], the row rows[k][0..3d) = [center | spring_const | flat_width] in the layout of the cv_restraint per-system
+ *     table, and its sample count n_k[k] >= 0 (the samples need not be sorted by state; only the counts enter).
+ *   periods[c]: the period of CV c, 0 = not periodic (2 pi for a dihedral).
+ *   u_k(n) = beta[k] (energy[n] + sum_c 1/2 spring_const_kc max(0, |wrap_c(values[n][c] - center_kc)| - flat_width_kc)^2),
+ *     wrap_c(x) = x - periods[c] rint(x / periods[c]) where periods[c] > 0: the cv_restraint bias.  d = 0 with energy is a
+ *     temperature ladder, beta[k] = 1 / T_k.
+ *   one iteration from f:  D_n = logsumexp_{l : n_k[l] > 0} (ln n_k[l] + f_l - u_l(n)),  f'_k = -logsumexp_n (-u_k(n) - D_n) for
+ *     every k (also where n_k[k] = 0),  f' = f' - f'_0.  Starts from f0 (NULL = 0) and stops when max_k |f'_k - f_k| < tol or after
+ *     max_iter iterations (tol = 0: exactly max_iter).
+ *   out: f[n_state]; D[n_sample] (may be NULL), the denominators OF THE RETURNED f (one more pass after the last iteration);
+ *     *n_iter the iterations run and *last_delta the last max |f' - f| (either may be NULL).
+ *   target (has_target != 0): a state of its own with beta_target and row_target[3d] (NULL = no bias).  log_w[n_sample] receives
+ *     ln w_n = -u_t(n) - D_n - logsumexp_n (-u_t(n) - D_n), the normalised log-weights of the samples in the target state, and
+ *     *f_target = -logsumexp_n (-u_t(n) - D_n) on the scale of f.  has_target == 0: log_w and f_target are not touched.
+ * Every logsumexp subtracts its exact maximum (a state 1e5 kT away contributes 0: no overflow, no NaN); no atomics; every sum has
+ * one fixed order, so two calls on one input return the same bits.  No uncertainty estimate and no Newton solver.
+ * Returns 0, or 1 with upside_hip_last_error set.  Refused before anything is launched or copied: d < 0 or d > 8; n_state < 1;
+ * n_sample < 1; n_sample x n_state not below 2^62; beta, n_k or f NULL; values, rows or periods NULL with d > 0; a target without
+ * log_w and f_target; tol negative or not finite; max_iter < 1; an n_k below 0; every n_k equal to 0; the n_k not adding up to
+ * n_sample; a value, energy, beta, row entry, period, f0 or target entry that is not finite; a negative period, spring_const or
+ * flat_width.  Without a HIP device the call fails like every other (no CPU path).  One limit is met only at the first launch, after
+ * the samples have been copied: n_sample above 256 (2^31 - 1) (one lane per sample, 256 per workgroup; some 5e11 samples, beyond any
+ * device's memory) fails with "launch failed (9401: bad arguments)". */
+int upside_hip_mbar(long long n_sample, int n_state, int d, const float* values, const double* energy, const double* beta,
+                    const float* rows, const long long* n_k, const double* periods, double tol, int max_iter, const double* f0,
+                    int has_target, double beta_target, const float* row_target, double* f, double* D, double* log_w,
+                    double* f_target, int* n_iter, double* last_delta);
+
 /* Per-kernel timing hooks used by bench.py.  With profiling enabled every interaction-graph / BP kernel
  * launch is bracketed by HIP events on the engine's stream.  upside_hip_profile_dump writes one text line per
  * kernel: "<kind>:<node> <total ms> <launches> <total algorithmic bytes> <total pair evaluations>" (bytes as defined in

@@ -563,6 +563,53 @@ int upk_cv_metad(const upk_launch_t* L, upk_coord_t pos, const upk_cv_t* C, cons
  * reads only slots of earlier deposits and writes its own: no atomics. */
 int upk_cv_metad_deposit(const upk_launch_t* L, upk_coord_t pos, const upk_cv_t* C, const upk_cv_metad_t* M);
 
+/* ---- MBAR over umbrella and temperature ladders (upside_hip_mbar), csrc/kernels_mbar.hip ---------------------------------------------
+ * n_state states over n samples.  The reduced energy of sample n in state k is
+ *   u_k(n) = beta[k] * (energy[n] + sum_c 1/2 k_kc max(0, |wrap_c(values[n][c] - center_kc)| - w_kc)^2),
+ *   wrap_c(x) = x - period[c] * rint(x / period[c]) where period[c] > 0 (0: the plain difference),
+ * rows + k * 3 d = [center | spring_const | flat_width] of state k: the layout of the cv_restraint per-system table.  values are the
+ * recorded float32 CV bits; energy == NULL means 0; d = 0 (values, rows unused) with an energy is a temperature ladder.  All
+ * arithmetic is fp64; every logsumexp subtracts its exact maximum; no atomics; every sum has one order, so two launches give the same
+ * bits.  These three launchers take the stream itself (they belong to no engine) and return the launch's hipError_t, or 94xx for
+ * arguments they cannot run (d outside 0 .. UPK_MBAR_MAX_DIM, no state, no sample, a NULL array).
+ *   _denominator:  denom[n] = logsumexp over the states with a[l] > -inf, ascending, of a[l] - u_l(n); the caller passes
+ *                  a[l] = ln N_l + f_l, and -inf for a state without samples.  One lane per sample; the states pass through LDS in
+ *                  tiles of UPK_MBAR_STATE_TILE.
+ *   _free_energy:  f[k] = -logsumexp_n (-u_k(n) - denom[n]) for every state.  One workgroup per UPK_MBAR_FE_TILE states; lane t takes
+ *                  samples t, t + 256, ... ascending, then the workgroup's fixed-order sum.
+ *   _log_weights:  log_w[n] = -u_0(n) - denom[n] + f_target[0] for state 0 of S (the target, passed as a set of one state).
+ * upk_mbar_solve is the HOST side of upside_hip_mbar (include/upside_engine_c.h, which states the refusals): every pointer of
+ * upk_mbar_problem_t is a host pointer.  It checks the arguments before it touches the device, copies the samples once, iterates
+ * and fills the outputs; 0, or 1 with the reason in message. */
+#define UPK_MBAR_MAX_DIM 8
+#define UPK_MBAR_STATE_TILE 128
+#define UPK_MBAR_FE_TILE 4
+typedef struct {
+    int d, n_state;
+    const double* beta;                     /* [n_state] */
+    const float* rows;                      /* [n_state][3 d] */
+    double period[UPK_MBAR_MAX_DIM];
+} upk_mbar_states_t;
+typedef struct { long long n; const float* values; /* [n][d] */ const double* energy; /* [n] or NULL */ } upk_mbar_samples_t;
+int upk_mbar_denominator(void* stream, const upk_mbar_states_t* S, const upk_mbar_samples_t* X, const double* a, double* denom);
+int upk_mbar_free_energy(void* stream, const upk_mbar_states_t* S, const upk_mbar_samples_t* X, const double* denom, double* f);
+int upk_mbar_log_weights(void* stream, const upk_mbar_states_t* S, const upk_mbar_samples_t* X, const double* denom, const double* f_target,
+                         double* log_w);
+typedef struct {
+    long long n_sample; int n_state, d;
+    const float* values; const double* energy;                    /* host [n_sample][d], [n_sample] or NULL */
+    const double* beta; const float* rows; const long long* n_k;  /* host [n_state], [n_state][3 d], [n_state] */
+    const double* periods;                                        /* host [d] */
+    double tol; int max_iter;
+    const double* f0;                                             /* host [n_state] or NULL = 0 */
+    int has_target; double beta_target; const float* row_target;  /* host [3 d] or NULL = no bias */
+    double *f, *denominators, *log_w, *f_target;                  /* host out [n_state], [n_sample] or NULL, [n_sample], [1] */
+    int* n_iter; double* last_delta;                              /* host out, either may be NULL */
+} upk_mbar_problem_t;
+int upk_mbar_solve(const upk_mbar_problem_t* P, char* message /* host */, int message_len);
+int upk_mbar_state_tile(void);      /* UPK_MBAR_STATE_TILE and UPK_MBAR_FE_TILE of the library that was built */
+int upk_mbar_fe_tile(void);
+
 #ifdef __cplusplus
 }
 #endif

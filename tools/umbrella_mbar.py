@@ -1,0 +1,85 @@
+"""MBAR over the output files of an umbrella ladder run by `upside_hip`, on the GPU.
+
+    python tools/umbrella_mbar.py --temperature 0.85 [--node cv_restraint] [--bins 40] [--tol 1e-8] w00.up w01.up ...
+
+Every file is one window: its `cv_restraint` node (`--node`) holds the window's centre, spring constant and flat width, and its
+/output/cv holds the CV series the run recorded at the frames (the CVs of /input/collective_variables; samples follow the window,
+as /output does).  The node's CVs are found among the recorded ones by name; a CV of the node that was not recorded is an error that
+names it.  Prints the free energy f_k of every window (in kT, f_0 = 0) and the unbiased free-energy profile along the node's first
+CV (in energy units, lowest bin 0; `inf` where no sample fell)."""
+import argparse
+import os
+import sys
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+from __graft_entry__ import load_package  # noqa: E402
+
+
+def read_window(h5lite, config, path, node):
+    """(series (n_frame, n_recorded), recorded names, node names, node row [center | spring_const | flat_width], periods)"""
+    with h5lite.open_file(path) as t:
+        inp = t.group('input')
+        if 'collective_variables' not in inp:
+            raise SystemExit('%s: no /input/collective_variables, so the run recorded no /output/cv' % path)
+        recorded = [x.decode() for x in inp.group('collective_variables').read('names').ravel()]
+        pot = inp.group('potential')
+        if node not in pot:
+            raise SystemExit('%s: no node %r in /input/potential' % (path, node))
+        g = pot.group(node)
+        names = [x.decode() for x in g.read('names').ravel()]
+        row = np.concatenate([g.read(k, 'f4').ravel() for k in config.CV_RESTRAINT_VALUES])
+        periods = config.cv_periods(dict(kind=g.read('kind')))
+        out = t.group('output')
+        if 'cv' not in out:
+            raise SystemExit('%s: no /output/cv' % path)
+        series = out.read('cv', 'f4')
+        del g, pot, out, inp
+    return series.reshape(series.shape[0], -1), recorded, names, row, periods
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument('files', nargs='+')
+    ap.add_argument('--temperature', type=float, required=True, help='the one temperature of every window (energy units)')
+    ap.add_argument('--node', default='cv_restraint')
+    ap.add_argument('--skip', type=int, default=0, help='frames to leave out at the start of every window')
+    ap.add_argument('--bins', type=int, default=40)
+    ap.add_argument('--tol', type=float, default=1e-8)
+    ap.add_argument('--max-iter', type=int, default=10000)
+    args = ap.parse_args()
+    pkg = load_package()
+    values, rows, n_k, names0, periods0 = [], [], [], None, None
+    for path in args.files:
+        series, recorded, names, row, periods = read_window(pkg.h5lite, pkg.config, path, args.node)
+        for nm in names:
+            if nm not in recorded:
+                raise SystemExit('%s: the collective variable %r of node %r is not among the recorded ones %r' % (path, nm, args.node, recorded))
+        if names0 is None:
+            names0, periods0 = names, periods
+        elif names != names0:
+            raise SystemExit('%s: the CVs of node %r are %r, the first file has %r' % (path, args.node, names, names0))
+        v = series[args.skip:, [recorded.index(nm) for nm in names]]
+        values.append(v); rows.append(row); n_k.append(len(v))
+    kT = args.temperature
+    v = np.concatenate(values)
+    r = pkg.mbar.mbar(v, None, 1. / kT, np.stack(rows), np.array(n_k, 'i8'), periods0, args.tol, args.max_iter, target=(1. / kT, None))
+    print('# %d windows, %d samples, CVs %s; %d iterations, last max |df| = %.3e' % (len(rows), len(v), names0, r['n_iter'], r['last_delta']))
+    print('# window  centre(%s)  samples  f_k / kT' % names0[0])
+    for k, (row, n) in enumerate(zip(rows, n_k)):
+        print('%4d  %12.6g  %7d  %14.8f' % (k, row[0], n, r['f'][k]))
+    x = v[:, 0].astype('f8')
+    if periods0[0] > 0:
+        edges = np.linspace(-0.5 * periods0[0], 0.5 * periods0[0], args.bins + 1)
+    else:
+        edges = np.linspace(x.min(), np.nextafter(x.max(), np.inf), args.bins + 1)
+    prof = pkg.config.mbar_profile(x, r['log_w'], edges, kT, period=periods0[0])
+    prof = prof - prof[np.isfinite(prof)].min()
+    print('# unbiased profile along %s: bin centre, F' % names0[0])
+    for b in range(args.bins):
+        print('%12.6g  %12.6f' % (0.5 * (edges[b] + edges[b + 1]), prof[b]))
+
+
+if __name__ == '__main__':
+    main()

@@ -1091,6 +1091,29 @@ def jarzynski_free_energy(work, kT):
     return -float(kT) * (m + np.log(np.mean(np.exp(a - m))))
 
 
+def mbar_profile(values, log_w, edges, kT, period=0):
+    """the free-energy profile along one CV from the log-weights of mbar.mbar(target=...) / Ensemble.umbrella_mbar(target=...):
+         F_b = -kT ln sum_{n in bin b} w_n,   w_n = exp(log_w_n)
+    by a weighted histogram over the bins edges[b] <= v < edges[b + 1] (the last bin closed, as numpy.histogram); an empty bin is
+    +inf.  values (N,), log_w (N,), edges ascending.  period > 0: values are first folded into [edges[0], edges[0] + period).
+    Returns (n_bin,) float64."""
+    v = np.asarray(values, 'f8').reshape(-1)
+    lw = np.asarray(log_w, 'f8').reshape(-1)
+    e = np.asarray(edges, 'f8').reshape(-1)
+    if len(v) != len(lw) or not len(v):
+        raise ValueError('mbar_profile: values and log_w must be two non-empty arrays of one length')
+    if len(e) < 2 or not (np.diff(e) > 0).all():
+        raise ValueError('mbar_profile: edges must ascend')
+    if not (np.ndim(kT) == 0 and np.isfinite(kT) and kT > 0):
+        raise ValueError('mbar_profile: kT must be finite and positive')
+    if period > 0:
+        v = e[0] + np.mod(v - e[0], float(period))
+    m = lw.max()
+    h, _ = np.histogram(v, bins=e, weights=np.exp(lw - m))
+    with np.errstate(divide='ignore'):
+        return -float(kT) * (np.log(h) + m)
+
+
 METAD_MAX_DIM = 4                  # UPK_METAD_MAX_DIM of include/upside_hip_kernels.h
 METAD_MAX_CAPACITY = 1 << 24
 

@@ -45,6 +45,21 @@ void load_plugin_library(const string& path);   // engine.cpp
 extern "C" int upside_hip_load_plugin(const char* path) { API_TRY load_plugin_library(path); return 0; API_CATCH(1) }
 extern "C" int upside_hip_node_type_registered(const char* prefix) { API_TRY return node_creation_map().count(prefix) ? 1 : 0; API_CATCH(0) }
 extern "C" void upside_hip_set_last_error(const char* msg) { fail(msg); }   // (for the other translation units of the C-ABI)
+// MBAR over recorded series: engine-free; the checks, the staging and the iteration are upk_mbar_solve (kernels_mbar.hip)
+extern "C" int upside_hip_mbar(long long n_sample, int n_state, int d, const float* values, const double* energy, const double* beta,
+                               const float* rows, const long long* n_k, const double* periods, double tol, int max_iter, const double* f0,
+                               int has_target, double beta_target, const float* row_target, double* f, double* D, double* log_w,
+                               double* f_target, int* n_iter, double* last_delta) {
+    API_TRY
+    upk_mbar_problem_t P{};
+    P.n_sample = n_sample; P.n_state = n_state; P.d = d; P.values = values; P.energy = energy; P.beta = beta; P.rows = rows; P.n_k = n_k;
+    P.periods = periods; P.tol = tol; P.max_iter = max_iter; P.f0 = f0; P.has_target = has_target; P.beta_target = beta_target;
+    P.row_target = row_target; P.f = f; P.denominators = D; P.log_w = log_w; P.f_target = f_target; P.n_iter = n_iter; P.last_delta = last_delta;
+    char msg[256];
+    if (upk_mbar_solve(&P, msg, (int)sizeof(msg))) throw string(msg);
+    return 0;
+    API_CATCH(1)
+}
 
 // ---- construction ----------------------------------------------------------------------------------
 extern "C" int upside_hip_set_device(int device) {

@@ -1,0 +1,361 @@
+// gfx950 kernels and host driver of MBAR (Shirts & Chodera 2008) over the ladders this engine runs: K states ("windows") whose reduced
+// energy of sample n is
+//     u_k(n) = beta_k (E_n + sum_c 1/2 k_kc max(0, |wrap_c(v_nc - center_kc)| - w_kc)^2),   wrap_c(x) = x - P_c rint(x / P_c) for P_c > 0
+// -- the cv_restraint bias (cv_harmonic_response / cv_wrap of cv_device.h, restated here in fp64 with a general period) on the
+// recorded float32 CV bits v_n, plus an optional unbiased energy E_n.  d = 0 with E_n is a temperature ladder.  No force pass is
+// needed: the bias depends on the recorded numbers alone.  One self-consistent iteration from f is
+//     D_n  = logsumexp_{l : N_l > 0} (ln N_l + f_l - u_l(n))          k_mbar_denominator
+//     f'_k = -logsumexp_n (-u_k(n) - D_n),  every k                   k_mbar_free_energy
+//     f'   = f' - f'_0                                                 host (K doubles per iteration)
+// Everything is fp64.  Every logsumexp takes its EXACT maximum first (a pass of its own over the same expression) and then sums
+// exp(x - max), so a state 1e5 kT away contributes exp(-1e5) = 0 and neither overflows nor gives a NaN.  No atomics, and every sum
+// has ONE order, so two runs give the same bits:
+//   - k_mbar_denominator: one lane owns one sample (its d values and E_n stay in registers) and walks the states 0, 1, ... ascending.
+//     The states are staged in LDS in tiles of UPK_MBAR_STATE_TILE as doubles [a_l = ln N_l + f_l | beta_l | center | k | w]; all
+//     lanes read the same state, a broadcast.  a_l = -inf marks N_l = 0 and is skipped (uniform over the workgroup).  No cross-lane
+//     reduction.
+//   - k_mbar_free_energy: one workgroup owns UPK_MBAR_FE_TILE consecutive states, so a sample read serves that many; lane t takes
+//     samples t, t + 256, ... ascending; the workgroup's maximum first, then the sum, combined by block_sum of cv_device.h (the
+//     butterfly of every CV kernel, unchanged).  States past the last are clamped to it and not stored.
+//   - k_mbar_log_weights: ln w_n = -u_t(n) - D_n + f_t of a target state, one lane per sample.
+// The kernels are instantiated for d = 0 .. UPK_MBAR_MAX_DIM so that a sample's values are registers.
+// upk_mbar_solve is the host side: argument checks (every refusal returns before any device call), one copy of the samples to the
+// device, the iteration, the outputs.
+#include "cv_device.h"
+#include <hip/hip_runtime.h>
+#include <cmath>
+#include <cstdio>
+#include <vector>
+
+using namespace up;
+
+#define MBAR_BLOCK CV_BLOCK
+#define MBAR_TILE UPK_MBAR_STATE_TILE
+#define MBAR_FE UPK_MBAR_FE_TILE
+static_assert(MBAR_FE <= CV_MAX_SUMS, "block_sum holds CV_MAX_SUMS totals");
+
+namespace {
+
+// the doubles of one staged state: a, beta, then center, spring_const, flat_width of the D CVs
+template <int D> constexpr int mbar_state_doubles() { return 2 + 3 * D; }
+
+// state k of S into dst (one lane per double of the row; called by the lanes `lane`, `lane + stride`, ... of a workgroup)
+template <int D>
+__device__ __forceinline__ void mbar_stage_state(const upk_mbar_states_t& S, int k, double a, double* __restrict__ dst, int j) {
+    if (j == 0) dst[0] = a;
+    else if (j == 1) dst[1] = S.beta[k];
+    else dst[j] = (double)S.rows[(size_t)k * (3 * D) + (j - 2)];
+}
+
+// E + sum_c 1/2 k u^2 of the sample (v, E) under the staged state st; P = the periods
+template <int D>
+__device__ __forceinline__ double mbar_energy(const double (&v)[D ? D : 1], double E, const double* __restrict__ st, const upk_mbar_states_t& S) {
+    double e = E;
+#pragma unroll
+    for (int c = 0; c < D; ++c) {
+        double x = v[c] - st[2 + c];
+        const double P = S.period[c];
+        if (P > 0.) x = x - P * rint(x / P);
+        const double u = fmax(0., fabs(x) - st[2 + 2 * D + c]);
+        e += 0.5 * st[2 + D + c] * u * u;
+    }
+    return e;
+}
+
+template <int D>
+__device__ __forceinline__ void mbar_load_sample(const upk_mbar_samples_t& X, long long n, double (&v)[D ? D : 1], double& E) {
+    v[0] = 0.;
+#pragma unroll
+    for (int c = 0; c < D; ++c) v[c] = (double)X.values[(size_t)n * D + c];
+    E = X.energy ? X.energy[n] : 0.;
+}
+
+template <int D>
+__global__ void __launch_bounds__(MBAR_BLOCK) k_mbar_denominator(upk_mbar_states_t S, upk_mbar_samples_t X, const double* __restrict__ a,
+                                                                  double* __restrict__ denom) {
+    constexpr int W = mbar_state_doubles<D>();
+    __shared__ double tile[MBAR_TILE * W];
+    const int tid = threadIdx.x;
+    const long long n_raw = (long long)blockIdx.x * MBAR_BLOCK + tid;
+    const long long n = n_raw < X.n ? n_raw : X.n - 1;      // (a lane past the end repeats the last sample and stores nothing)
+    double v[D ? D : 1], E;
+    mbar_load_sample<D>(X, n, v, E);
+    double m = -INFINITY, sum = 0.;
+    for (int pass = 0; pass < 2; ++pass)
+        for (int k0 = 0; k0 < S.n_state; k0 += MBAR_TILE) {
+            const int nt = min(MBAR_TILE, S.n_state - k0);
+            __syncthreads();      // (the previous tile has been read)
+            for (int i = tid; i < nt * W; i += MBAR_BLOCK) { const int l = i / W, j = i - l * W; mbar_stage_state<D>(S, k0 + l, a[k0 + l], tile + l * W, j); }
+            __syncthreads();
+            for (int l = 0; l < nt; ++l) {
+                const double* __restrict__ st = tile + l * W;
+                if (st[0] == -INFINITY) continue;      // N_l = 0
+                const double x = st[0] - st[1] * mbar_energy<D>(v, E, st, S);
+                if (pass == 0) m = fmax(m, x); else sum += exp(x - m);
+            }
+        }
+    if (n_raw < X.n) denom[n] = m + log(sum);
+}
+
+// the largest of v[j] over the workgroup, for every j; every lane receives it
+template <int K>
+__device__ __forceinline__ void mbar_block_max(double (&v)[K], double (*part)[MBAR_FE]) {
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+#pragma unroll
+    for (int k = 0; k < K; ++k) {
+        double w = v[k];
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) w = fmax(w, __shfl_xor(w, o, 64));
+        if (lane == 0) part[wave][k] = w;
+    }
+    __syncthreads();
+#pragma unroll
+    for (int k = 0; k < K; ++k) {
+        double t = part[0][k];
+#pragma unroll
+        for (int w = 1; w < CV_WAVES; ++w) t = fmax(t, part[w][k]);
+        v[k] = t;
+    }
+}
+
+template <int D>
+__global__ void __launch_bounds__(MBAR_BLOCK) k_mbar_free_energy(upk_mbar_states_t S, upk_mbar_samples_t X, const double* __restrict__ denom,
+                                                                  double* __restrict__ f) {
+    constexpr int W = mbar_state_doubles<D>();
+    __shared__ double st[MBAR_FE][W];
+    __shared__ double part[CV_WAVES][CV_MAX_SUMS];
+    __shared__ double partm[CV_WAVES][MBAR_FE];
+    const int tid = threadIdx.x, k0 = blockIdx.x * MBAR_FE;
+    if (tid < MBAR_FE * W) { const int l = tid / W, j = tid - l * W; mbar_stage_state<D>(S, min(k0 + l, S.n_state - 1), 0., st[l], j); }
+    __syncthreads();
+    double m[MBAR_FE], s[MBAR_FE];
+#pragma unroll
+    for (int l = 0; l < MBAR_FE; ++l) { m[l] = -INFINITY; s[l] = 0.; }
+    for (long long n = tid; n < X.n; n += MBAR_BLOCK) {
+        double v[D ? D : 1], E;
+        mbar_load_sample<D>(X, n, v, E);
+        const double dn = denom[n];
+#pragma unroll
+        for (int l = 0; l < MBAR_FE; ++l) m[l] = fmax(m[l], -(st[l][1] * mbar_energy<D>(v, E, st[l], S)) - dn);
+    }
+    mbar_block_max<MBAR_FE>(m, partm);
+    for (long long n = tid; n < X.n; n += MBAR_BLOCK) {
+        double v[D ? D : 1], E;
+        mbar_load_sample<D>(X, n, v, E);
+        const double dn = denom[n];
+#pragma unroll
+        for (int l = 0; l < MBAR_FE; ++l) s[l] += exp(-(st[l][1] * mbar_energy<D>(v, E, st[l], S)) - dn - m[l]);
+    }
+    block_sum<MBAR_FE>(s, part);
+    if (tid == 0) {
+#pragma unroll
+        for (int l = 0; l < MBAR_FE; ++l) if (k0 + l < S.n_state) f[k0 + l] = -(m[l] + log(s[l]));
+    }
+}
+
+template <int D>
+__global__ void __launch_bounds__(MBAR_BLOCK) k_mbar_log_weights(upk_mbar_states_t S, upk_mbar_samples_t X, const double* __restrict__ denom,
+                                                                  const double* __restrict__ f_target, double* __restrict__ log_w) {
+    constexpr int W = mbar_state_doubles<D>();
+    __shared__ double st[W];
+    const int tid = threadIdx.x;
+    if (tid < W) mbar_stage_state<D>(S, 0, 0., st, tid);
+    __syncthreads();
+    const long long n = (long long)blockIdx.x * MBAR_BLOCK + tid;
+    if (n >= X.n) return;
+    double v[D ? D : 1], E;
+    mbar_load_sample<D>(X, n, v, E);
+    log_w[n] = -(st[1] * mbar_energy<D>(v, E, st, S)) - denom[n] + f_target[0];
+}
+
+static_assert(MBAR_FE * mbar_state_doubles<UPK_MBAR_MAX_DIM>() <= MBAR_BLOCK, "one lane stages one double of the free-energy tile");
+
+inline unsigned sample_blocks(long long n) { return (unsigned)((n + MBAR_BLOCK - 1) / MBAR_BLOCK); }
+inline int launch_status() { return (int)hipGetLastError(); }
+inline bool launch_args_ok(const upk_mbar_states_t* S, const upk_mbar_samples_t* X) {
+    return S && X && S->d >= 0 && S->d <= UPK_MBAR_MAX_DIM && S->n_state >= 1 && X->n >= 1 && S->beta && (S->d == 0 || (S->rows && X->values)) &&
+           (X->n + MBAR_BLOCK - 1) / MBAR_BLOCK <= 0x7fffffffll;
+}
+
+#define MBAR_DISPATCH(KERNEL, GRID, ...)                                                                                              \
+    switch (S->d) {                                                                                                                   \
+    case 0: hipLaunchKernelGGL(KERNEL<0>, dim3(GRID), dim3(MBAR_BLOCK), 0, (hipStream_t)stream, __VA_ARGS__); break;                  \
+    case 1: hipLaunchKernelGGL(KERNEL<1>, dim3(GRID), dim3(MBAR_BLOCK), 0, (hipStream_t)stream, __VA_ARGS__); break;                  \
+    case 2: hipLaunchKernelGGL(KERNEL<2>, dim3(GRID), dim3(MBAR_BLOCK), 0, (hipStream_t)stream, __VA_ARGS__); break;                  \
+    case 3: hipLaunchKernelGGL(KERNEL<3>, dim3(GRID), dim3(MBAR_BLOCK), 0, (hipStream_t)stream, __VA_ARGS__); break;                  \
+    case 4: hipLaunchKernelGGL(KERNEL<4>, dim3(GRID), dim3(MBAR_BLOCK), 0, (hipStream_t)stream, __VA_ARGS__); break;                  \
+    case 5: hipLaunchKernelGGL(KERNEL<5>, dim3(GRID), dim3(MBAR_BLOCK), 0, (hipStream_t)stream, __VA_ARGS__); break;                  \
+    case 6: hipLaunchKernelGGL(KERNEL<6>, dim3(GRID), dim3(MBAR_BLOCK), 0, (hipStream_t)stream, __VA_ARGS__); break;                  \
+    case 7: hipLaunchKernelGGL(KERNEL<7>, dim3(GRID), dim3(MBAR_BLOCK), 0, (hipStream_t)stream, __VA_ARGS__); break;                  \
+    default: hipLaunchKernelGGL(KERNEL<8>, dim3(GRID), dim3(MBAR_BLOCK), 0, (hipStream_t)stream, __VA_ARGS__); break;                 \
+    }
+static_assert(UPK_MBAR_MAX_DIM == 8, "MBAR_DISPATCH lists d = 0 .. 8");
+
+}  // namespace
+
+extern "C" int upk_mbar_denominator(void* stream, const upk_mbar_states_t* S, const upk_mbar_samples_t* X, const double* a, double* denom) {
+    if (!launch_args_ok(S, X) || !a || !denom) return 9401;
+    MBAR_DISPATCH(k_mbar_denominator, sample_blocks(X->n), *S, *X, a, denom)
+    return launch_status();
+}
+extern "C" int upk_mbar_free_energy(void* stream, const upk_mbar_states_t* S, const upk_mbar_samples_t* X, const double* denom, double* f) {
+    if (!launch_args_ok(S, X) || !denom || !f) return 9402;
+    MBAR_DISPATCH(k_mbar_free_energy, (unsigned)((S->n_state + MBAR_FE - 1) / MBAR_FE), *S, *X, denom, f)
+    return launch_status();
+}
+extern "C" int upk_mbar_log_weights(void* stream, const upk_mbar_states_t* S, const upk_mbar_samples_t* X, const double* denom,
+                                    const double* f_target, double* log_w) {
+    if (!launch_args_ok(S, X) || !denom || !f_target || !log_w) return 9403;
+    MBAR_DISPATCH(k_mbar_log_weights, sample_blocks(X->n), *S, *X, denom, f_target, log_w)
+    return launch_status();
+}
+
+// ---- host side -----------------------------------------------------------------------------------------------------------------------
+namespace {
+
+struct MbarRefusal { char text[256]; };
+#define MBAR_REFUSE(...) do { MbarRefusal r_; snprintf(r_.text, sizeof(r_.text), __VA_ARGS__); throw r_; } while (0)
+
+template <class T>
+bool all_finite(const T* p, size_t n, size_t* where) {
+    for (size_t i = 0; i < n; ++i) if (!std::isfinite((double)p[i])) { *where = i; return false; }
+    return true;
+}
+
+// every refusal of upside_hip_mbar; nothing here touches the device
+void mbar_check(const upk_mbar_problem_t& P) {
+    size_t at = 0;
+    if (P.d < 0 || P.d > UPK_MBAR_MAX_DIM) MBAR_REFUSE("mbar: d = %d, at most %d CVs are supported (and d >= 0)", P.d, UPK_MBAR_MAX_DIM);
+    if (P.n_state < 1) MBAR_REFUSE("mbar: n_state = %d, at least one state is needed", P.n_state);
+    if (P.n_sample < 1) MBAR_REFUSE("mbar: n_sample = %lld, at least one sample is needed", P.n_sample);
+    if (P.n_sample > ((1ll << 62) - 1) / P.n_state) MBAR_REFUSE("mbar: n_sample x n_state = %lld x %d is not below 2^62", P.n_sample, P.n_state);
+    if (!P.beta || !P.n_k || !P.f) MBAR_REFUSE("mbar: beta, n_k and f must be given");
+    if (P.d > 0 && (!P.values || !P.rows || !P.periods)) MBAR_REFUSE("mbar: values, rows and periods must be given when d > 0");
+    if (P.has_target && (!P.log_w || !P.f_target)) MBAR_REFUSE("mbar: a target state needs log_w and f_target");
+    if (!(P.tol >= 0.) || !std::isfinite(P.tol)) MBAR_REFUSE("mbar: tol must be finite and not negative");
+    if (P.max_iter < 1) MBAR_REFUSE("mbar: max_iter = %d, at least one iteration is needed", P.max_iter);
+    long long total = 0; bool any = false;
+    for (int k = 0; k < P.n_state; ++k) {
+        if (P.n_k[k] < 0) MBAR_REFUSE("mbar: n_k[%d] = %lld is negative", k, P.n_k[k]);
+        if (P.n_k[k] > P.n_sample - total) MBAR_REFUSE("mbar: the sample counts n_k add up to more than n_sample = %lld", P.n_sample);
+        total += P.n_k[k]; any = any || P.n_k[k] > 0;
+    }
+    if (!any) MBAR_REFUSE("mbar: no state has samples (every n_k is 0)");
+    if (total != P.n_sample) MBAR_REFUSE("mbar: the sample counts n_k add up to %lld, n_sample is %lld", total, P.n_sample);
+    if (!all_finite(P.beta, (size_t)P.n_state, &at)) MBAR_REFUSE("mbar: beta[%zu] is not finite", at);
+    if (P.f0 && !all_finite(P.f0, (size_t)P.n_state, &at)) MBAR_REFUSE("mbar: f0[%zu] is not finite", at);
+    if (P.has_target && !std::isfinite(P.beta_target)) MBAR_REFUSE("mbar: the target's beta is not finite");
+    const size_t d = (size_t)P.d;
+    for (size_t c = 0; c < d; ++c) {
+        if (!std::isfinite(P.periods[c])) MBAR_REFUSE("mbar: periods[%zu] is not finite", c);
+        if (P.periods[c] < 0.) MBAR_REFUSE("mbar: periods[%zu] is negative (0 = not periodic)", c);
+    }
+    for (int t = 0; t < (P.has_target && P.row_target && d ? 2 : 1); ++t) {
+        const float* rows = t ? P.row_target : P.rows;
+        const size_t n_row = t ? 1 : (size_t)P.n_state;
+        const char* who = t ? "the target's row" : "rows";
+        if (!d) break;
+        if (!all_finite(rows, n_row * 3 * d, &at)) MBAR_REFUSE("mbar: %s: state %zu, entry %zu is not finite", who, at / (3 * d), at % (3 * d));
+        for (size_t k = 0; k < n_row; ++k)
+            for (size_t c = 0; c < d; ++c) {
+                if (rows[k * 3 * d + d + c] < 0.f) MBAR_REFUSE("mbar: %s: spring_const of state %zu, CV %zu is negative", who, k, c);
+                if (rows[k * 3 * d + 2 * d + c] < 0.f) MBAR_REFUSE("mbar: %s: flat_width of state %zu, CV %zu is negative", who, k, c);
+            }
+    }
+    if (d && !all_finite(P.values, (size_t)P.n_sample * d, &at)) MBAR_REFUSE("mbar: values: sample %zu, CV %zu is not finite", at / d, at % d);
+    if (P.energy && !all_finite(P.energy, (size_t)P.n_sample, &at)) MBAR_REFUSE("mbar: energy[%zu] is not finite", at);
+}
+
+void hip_ok(hipError_t e, const char* what) { if (e != hipSuccess) MBAR_REFUSE("mbar: %s: %s", what, hipGetErrorString(e)); }
+void upk_ok(int code, const char* what) { if (code) MBAR_REFUSE("mbar: %s: launch failed (%d: %s)", what, code, code < 9000 ? hipGetErrorString((hipError_t)code) : "bad arguments"); }
+
+struct DeviceBuffer {
+    void* p = nullptr;
+    ~DeviceBuffer() { if (p) (void)hipFree(p); }
+    void alloc(size_t bytes, const char* what) { hip_ok(hipMalloc(&p, bytes ? bytes : 8), what); }
+    template <class T> T* as() const { return (T*)p; }
+};
+struct Stream {
+    hipStream_t s = nullptr;
+    ~Stream() { if (s) (void)hipStreamDestroy(s); }
+};
+
+void mbar_run(const upk_mbar_problem_t& P) {
+    mbar_check(P);
+    int n_dev = 0;
+    if (hipGetDeviceCount(&n_dev) != hipSuccess || n_dev < 1) MBAR_REFUSE("mbar: no HIP device (this library has no CPU path)");
+    const int K = P.n_state, d = P.d;
+    const size_t N = (size_t)P.n_sample;
+    Stream st; hip_ok(hipStreamCreate(&st.s), "hipStreamCreate");
+    DeviceBuffer values, energy, beta, rows, a, f_dev, denom, tbeta, trow, tf, lw;
+    // the samples and the states go to the device once
+    if (d) { values.alloc(N * d * sizeof(float), "samples"); hip_ok(hipMemcpyAsync(values.p, P.values, N * d * sizeof(float), hipMemcpyHostToDevice, st.s), "copy of values"); }
+    if (P.energy) { energy.alloc(N * sizeof(double), "energies"); hip_ok(hipMemcpyAsync(energy.p, P.energy, N * sizeof(double), hipMemcpyHostToDevice, st.s), "copy of energy"); }
+    beta.alloc(K * sizeof(double), "beta"); hip_ok(hipMemcpyAsync(beta.p, P.beta, K * sizeof(double), hipMemcpyHostToDevice, st.s), "copy of beta");
+    if (d) { rows.alloc((size_t)K * 3 * d * sizeof(float), "rows"); hip_ok(hipMemcpyAsync(rows.p, P.rows, (size_t)K * 3 * d * sizeof(float), hipMemcpyHostToDevice, st.s), "copy of rows"); }
+    a.alloc(K * sizeof(double), "a"); f_dev.alloc(K * sizeof(double), "f"); denom.alloc(N * sizeof(double), "denominators");
+
+    upk_mbar_states_t S{}; S.d = d; S.n_state = K; S.beta = beta.as<double>(); S.rows = rows.as<float>();
+    for (int c = 0; c < d; ++c) S.period[c] = P.periods[c];
+    upk_mbar_samples_t X{}; X.n = P.n_sample; X.values = values.as<float>(); X.energy = energy.as<double>();
+
+    std::vector<double> f(K, 0.), fn(K), av(K), ln_n(K);
+    if (P.f0) for (int k = 0; k < K; ++k) f[k] = P.f0[k];
+    for (int k = 0; k < K; ++k) ln_n[k] = P.n_k[k] > 0 ? std::log((double)P.n_k[k]) : -INFINITY;
+    auto denominators = [&]() {
+        for (int k = 0; k < K; ++k) av[k] = P.n_k[k] > 0 ? ln_n[k] + f[k] : -INFINITY;
+        hip_ok(hipMemcpyAsync(a.p, av.data(), K * sizeof(double), hipMemcpyHostToDevice, st.s), "copy of f");
+        hip_ok(hipStreamSynchronize(st.s), "hipStreamSynchronize");      // (av is pageable and rewritten by the next iteration)
+        upk_ok(upk_mbar_denominator(st.s, &S, &X, a.as<double>(), denom.as<double>()), "denominator pass");
+    };
+    int it = 0; double delta = INFINITY;
+    while (it < P.max_iter) {
+        denominators();
+        upk_ok(upk_mbar_free_energy(st.s, &S, &X, denom.as<double>(), f_dev.as<double>()), "free-energy pass");
+        hip_ok(hipMemcpyAsync(fn.data(), f_dev.p, K * sizeof(double), hipMemcpyDeviceToHost, st.s), "copy of f");
+        hip_ok(hipStreamSynchronize(st.s), "hipStreamSynchronize");
+        const double f0 = fn[0];
+        delta = 0.;
+        for (int k = 0; k < K; ++k) { fn[k] -= f0; const double dk = std::fabs(fn[k] - f[k]); if (!(dk <= delta)) delta = dk; }      // (a NaN is kept)
+        f.swap(fn); ++it;
+        if (delta < P.tol) break;
+    }
+    // the denominators of the returned f: D and the target's weights belong to it
+    if (P.denominators || P.has_target) denominators();
+    if (P.has_target) {
+        std::vector<float> zero(3 * (size_t)(d ? d : 1), 0.f);
+        tbeta.alloc(sizeof(double), "target"); hip_ok(hipMemcpyAsync(tbeta.p, &P.beta_target, sizeof(double), hipMemcpyHostToDevice, st.s), "copy of the target");
+        trow.alloc(3 * (size_t)(d ? d : 1) * sizeof(float), "target");
+        hip_ok(hipMemcpyAsync(trow.p, P.row_target && d ? P.row_target : zero.data(), 3 * (size_t)(d ? d : 1) * sizeof(float), hipMemcpyHostToDevice, st.s), "copy of the target");
+        hip_ok(hipStreamSynchronize(st.s), "hipStreamSynchronize");
+        tf.alloc(sizeof(double), "target"); lw.alloc(N * sizeof(double), "log-weights");
+        upk_mbar_states_t T = S; T.n_state = 1; T.beta = tbeta.as<double>(); T.rows = trow.as<float>();
+        upk_ok(upk_mbar_free_energy(st.s, &T, &X, denom.as<double>(), tf.as<double>()), "free-energy pass of the target");
+        upk_ok(upk_mbar_log_weights(st.s, &T, &X, denom.as<double>(), tf.as<double>(), lw.as<double>()), "log-weights");
+        hip_ok(hipMemcpyAsync(P.log_w, lw.p, N * sizeof(double), hipMemcpyDeviceToHost, st.s), "copy of log_w");
+        hip_ok(hipMemcpyAsync(P.f_target, tf.p, sizeof(double), hipMemcpyDeviceToHost, st.s), "copy of f_target");
+    }
+    if (P.denominators) hip_ok(hipMemcpyAsync(P.denominators, denom.p, N * sizeof(double), hipMemcpyDeviceToHost, st.s), "copy of D");
+    hip_ok(hipStreamSynchronize(st.s), "hipStreamSynchronize");
+    for (int k = 0; k < K; ++k) P.f[k] = f[k];
+    if (P.n_iter) *P.n_iter = it;
+    if (P.last_delta) *P.last_delta = delta;
+}
+
+}  // namespace
+
+extern "C" int upk_mbar_solve(const upk_mbar_problem_t* P, char* message, int message_len) {
+    if (message && message_len > 0) message[0] = 0;
+    try {
+        if (!P) MBAR_REFUSE("mbar: no problem given");
+        mbar_run(*P);
+        return 0;
+    } catch (const MbarRefusal& r) {
+        if (message && message_len > 0) snprintf(message, (size_t)message_len, "%s", r.text);
+    } catch (const std::exception& e) {
+        if (message && message_len > 0) snprintf(message, (size_t)message_len, "mbar: %s", e.what());
+    }
+    return 1;
+}
+extern "C" int upk_mbar_state_tile(void) { return MBAR_TILE; }
+extern "C" int upk_mbar_fe_tile(void) { return MBAR_FE; }

@@ -494,6 +494,52 @@ class Ensemble(object):
             raise RuntimeError('cv_restraint_values failed: %s' % self.calc.upside_hip_last_error().decode())
         return out
 
+    def umbrella_mbar(self, node_name, kT, tol=1e-8, max_iter=10000, f0=None, target=None, series=None):
+        """MBAR over the umbrella ladder of the cv_restraint node `node_name` from the recorded CV series (mbar.mbar on the device):
+        system s is window s with its own row [center | spring_const | flat_width] (get_param of system s) and beta = 1 / kT for all
+        (one temperature: the unbiased potential cancels and is not needed).  series: (n_stored, n_system, n_cv) as read_cvs gives it,
+        default read_cvs(reset=False); sample (i, s) belongs to window s and every window counts n_stored samples.  The node's CVs
+        are found among the recorded ones BY NAME (the names of the node's group against cv_names); a CV of the node that is not
+        recorded raises ValueError naming it.  target: None, 'unbiased' (no bias at beta) or a row (3 n_cv,).  Returns the dict of
+        mbar.mbar with values (N, d), rows (n_system, 3 d), periods (d,), n_k and names added; with a target, log_w feeds
+        config.mbar_profile."""
+        from . import config, mbar as _mbar
+        if not (np.ndim(kT) == 0 and np.isfinite(kT) and kT > 0):
+            raise ValueError('umbrella_mbar: kT must be one finite positive number (one temperature for every window)')
+        with h5lite.open_file(self.config_file_path) as t:
+            pot = t.group('input').group('potential')
+            if node_name not in pot:
+                raise ValueError('umbrella_mbar: %s has no node %r' % (self.config_file_path, node_name))
+            g = pot.group(node_name)
+            names = [x.decode() for x in g.read('names').ravel()]
+            periods = config.cv_periods(dict(kind=g.read('kind')))
+            del g, pot
+        recorded = list(getattr(self, 'cv_names', []))
+        cols = []
+        for nm in names:
+            if nm not in recorded:
+                raise ValueError('umbrella_mbar: the collective variable %r of node %r is not among the recorded ones %r' % (nm, node_name, recorded))
+            cols.append(recorded.index(nm))
+        d = len(names)
+        rows = np.stack([self.get_param((3 * d,), node_name, system=s) for s in range(self.n_system)])
+        if series is None:
+            series = self.read_cvs(reset=False)
+        series = np.asarray(series, 'f4')
+        if series.ndim != 3 or series.shape[1] != self.n_system or series.shape[2] != len(recorded):
+            raise ValueError('umbrella_mbar: the series must be (n_stored, %d systems, %d CVs), got %r' % (self.n_system, len(recorded), series.shape))
+        values = np.ascontiguousarray(series[:, :, cols].reshape(-1, d))
+        n_k = np.full(self.n_system, series.shape[0], 'i8')
+        beta = 1. / float(kT)
+        if isinstance(target, str):
+            if target != 'unbiased':
+                raise ValueError("umbrella_mbar: target must be None, 'unbiased' or a row")
+            tgt = (beta, None)
+        else:
+            tgt = None if target is None else (beta, target)
+        out = _mbar.mbar(values, None, beta, rows, n_k, periods, tol, max_iter, f0=f0, target=tgt, library=self.lib)
+        out.update(values=values, rows=rows, periods=periods, n_k=n_k, names=names)
+        return out
+
     # -- cv_metadynamics: the hills of a node (they live on the device; deposition happens inside run_rounds / run_steps) -----
     def metad_info(self, node_name):
         """(d, capacity, n_list) of the cv_metadynamics node: n_list is n_system (shared = 0) or 1 (shared = 1)"""
