@@ -322,7 +322,8 @@ int upside_hip_steer_values(DerivEngine* engine, const char* node_name, float* o
  *     ln w_n = -u_t(n) - D_n - logsumexp_n (-u_t(n) - D_n), the normalised log-weights of the samples in the target state, and
  *     *f_target = -logsumexp_n (-u_t(n) - D_n) on the scale of f.  has_target == 0: log_w and f_target are not touched.
  * Every logsumexp subtracts its exact maximum (a state 1e5 kT away contributes 0: no overflow, no NaN); no atomics; every sum has
- * one fixed order, so two calls on one input return the same bits.  No uncertainty estimate and no Newton solver.
+ * one fixed order, so two calls on one input return the same bits.  The iteration here is the self-consistent one; uncertainties and
+ * a Newton step come from upside_hip_mbar_gram below.
  * Returns 0, or 1 with upside_hip_last_error set.  Refused before anything is launched or copied: d < 0 or d > 8; n_state < 1;
  * n_sample < 1; n_sample x n_state not below 2^62; beta, n_k or f NULL; values, rows or periods NULL with d > 0; a target without
  * log_w and f_target; tol negative or not finite; max_iter < 1; an n_k below 0; every n_k equal to 0; the n_k not adding up to
@@ -334,6 +335,23 @@ int upside_hip_mbar(long long n_sample, int n_state, int d, const float* values,
                     const float* rows, const long long* n_k, const double* periods, double tol, int max_iter, const double* f0,
                     int has_target, double beta_target, const float* row_target, double* f, double* D, double* log_w,
                     double* f_target, int* n_iter, double* last_delta);
+
+/* The Gram matrix of the MBAR weight matrix (csrc/kernels_mbar_gram.hip), from which the asymptotic covariance of the free energies
+ * and of reweighted averages (Shirts & Chodera 2008, eq. D8/D9) and the Hessian of the MBAR objective follow.  Samples, states and
+ * periods are those of upside_hip_mbar; f[n_state] are the free energies (normally the ones upside_hip_mbar returned).  With
+ * D_n = logsumexp_{l : n_k[l] > 0} (ln n_k[l] + f_l - u_l(n)) the weight matrix has M = n_state + n_extra columns,
+ *   W[n][k] = exp(f_k - u_k(n) - D_n) for k < n_state,   W[n][n_state + j] = exp(log_extra[j * n_sample + n]),
+ * the explicit log-columns carrying target states, observables and profile bins (-inf = weight 0).
+ *   out: G[M * M] = W^T W (may be NULL: only colsum is computed, a cheap pass), colsum[M] = the column sums of W, D[n_sample] (may be
+ *   NULL).  Float64 throughout, no atomics, one summation order: two calls return the same bits, on any machine state -- the slab of
+ *   W that is formed at a time depends on M alone (at most 512 MB; W itself is never held).  G is bitwise symmetric.
+ * Limits: M <= 8192; the covariance built from G is the asymptotic one and assumes uncorrelated samples (subsample first).
+ * Returns 0, or 1 with upside_hip_last_error set.  Refused before anything is launched or copied: everything upside_hip_mbar refuses
+ * about samples, states, counts and periods; n_extra < 0; n_state + n_extra > 8192; colsum or f NULL; log_extra NULL with n_extra > 0;
+ * an f that is not finite; a log_extra entry that is NaN or +inf. */
+int upside_hip_mbar_gram(long long n_sample, int n_state, int d, const float* values, const double* energy, const double* beta,
+                         const float* rows, const long long* n_k, const double* periods, const double* f, int n_extra,
+                         const double* log_extra, double* G, double* colsum, double* D);
 
 /* Per-kernel timing hooks used by bench.py.  With profiling enabled every interaction-graph / BP kernel
  * launch is bracketed by HIP events on the engine's stream.  upside_hip_profile_dump writes one text line per

@@ -8,6 +8,7 @@
  */
 #ifndef UPSIDE_HIP_KERNELS_H
 #define UPSIDE_HIP_KERNELS_H
+#include <stddef.h>
 #include <stdint.h>
 
 #ifdef __cplusplus
@@ -609,6 +610,42 @@ typedef struct {
 int upk_mbar_solve(const upk_mbar_problem_t* P, char* message /* host */, int message_len);
 int upk_mbar_state_tile(void);      /* UPK_MBAR_STATE_TILE and UPK_MBAR_FE_TILE of the library that was built */
 int upk_mbar_fe_tile(void);
+
+/* ---- the MBAR Gram pass (upside_hip_mbar_gram), csrc/kernels_mbar_gram.hip ------------------------------------------------------------
+ * M = S->n_state + n_extra columns of the weight matrix over the X->n samples:
+ *   W[n][k]                = exp(f[k] - u_k(n) - denom[n])      k < n_state, u_k as above, denom from upk_mbar_denominator
+ *   W[n][n_state + j]      = exp(log_extra[j * n + n])          an explicit log-column; -inf is weight 0
+ * G[M][M] = W^T W and colsum[M] = the column sums of W, all fp64, no atomics, one summation order (two launches give the same bits),
+ * G bitwise symmetric (the upper triangle of UPK_MBAR_GRAM_TILE^2 tiles is computed with v_mfma_f64_16x16x4_f64 and mirrored).  W is
+ * generated in slabs of upk_mbar_gram_rows(M, workspace_bytes) samples into workspace (device memory) and never held whole:
+ * that is (workspace_bytes - upk_mbar_gram_partial_bytes(M)) / (8 * M rounded up to the tile) rounded down to UPK_MBAR_GRAM_GRANULE
+ * rows.  The partial bytes hold the partial sums of the ranges a slab is cut into where M < 2048 leaves too few tiles to fill the
+ * device (a function of M alone, 0 from M = 1985 on, at most 64 MB); they are added in ascending order.  With G == NULL only colsum is
+ * computed, and workspace is not used.  Every pointer but S and X is a device pointer.  Returns the launch's hipError_t, 9404 for
+ * arguments it cannot run (those of the launchers above; f or colsum NULL; n_extra < 0 or without log_extra; M above
+ * UPK_MBAR_GRAM_MAX_COLUMNS), 9405 for a workspace below one granule of rows when G is wanted.
+ * upk_mbar_gram_solve is the HOST side of upside_hip_mbar_gram (include/upside_engine_c.h states the refusals): host pointers, the
+ * checks before any device call, denominators from f and n_k, a workspace whose size depends on M alone; 0, or 1 with the reason. */
+#define UPK_MBAR_GRAM_TILE 64
+#define UPK_MBAR_GRAM_GRANULE 32
+#define UPK_MBAR_GRAM_MAX_COLUMNS 8192
+#define UPK_MBAR_GRAM_MAX_WORKSPACE 536870912ull      /* 512 MB */
+int upk_mbar_gram(void* stream, const upk_mbar_states_t* S, const upk_mbar_samples_t* X, const double* denom, const double* f,
+                  int n_extra, const double* log_extra /* [n_extra][n] */, double* G /* [M][M] or NULL */, double* colsum /* [M] */,
+                  void* workspace, size_t workspace_bytes);
+int upk_mbar_gram_tile(void);                                    /* UPK_MBAR_GRAM_TILE of the library that was built */
+size_t upk_mbar_gram_partial_bytes(int m);                       /* the front of the workspace that holds partial sums; 0 for large M */
+long long upk_mbar_gram_rows(int m, size_t workspace_bytes);     /* the slab length upk_mbar_gram takes from a workspace; 0: too small */
+typedef struct {
+    long long n_sample; int n_state, d;
+    const float* values; const double* energy;                    /* host, as in upk_mbar_problem_t */
+    const double* beta; const float* rows; const long long* n_k;
+    const double* periods;
+    const double* f;                                              /* host [n_state], finite */
+    int n_extra; const double* log_extra;                         /* host [n_extra][n_sample]; -inf allowed, NaN and +inf refused */
+    double *G, *colsum, *denominators;                            /* host out [M][M] or NULL, [M], [n_sample] or NULL */
+} upk_mbar_gram_problem_t;
+int upk_mbar_gram_solve(const upk_mbar_gram_problem_t* P, char* message /* host */, int message_len);
 
 #ifdef __cplusplus
 }

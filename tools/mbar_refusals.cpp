@@ -1,5 +1,6 @@
-// Stand-alone driver of the host side of upside_hip_mbar (upk_mbar_solve of csrc/kernels_mbar.hip: argument checks and staging) for a
-// sanitizer build: `make -C upside-md_amd/csrc mbar_sanitize` compiles kernels_mbar.hip's host code and this file with
+// Stand-alone driver of the host side of upside_hip_mbar and upside_hip_mbar_gram (upk_mbar_solve of csrc/kernels_mbar.hip and
+// upk_mbar_gram_solve of csrc/kernels_mbar_gram.hip: argument checks and staging) for a
+// sanitizer build: `make -C upside-md_amd/csrc mbar_sanitize` compiles the two files' host code and this file with
 // -fsanitize=address,undefined and runs the program.  It walks every refusal and nothing else: each returns before any device call,
 // so the program stays on the CPU whatever the machine holds (a good call after refusals is checked by tests/test_gpu_mbar.py).
 #include "../include/upside_hip_kernels.h"
@@ -13,6 +14,14 @@ static int n_bad = 0;
 static void expect(const upk_mbar_problem_t& P, const char* what, const char* fragment) {
     char msg[256];
     const int rc = upk_mbar_solve(&P, msg, (int)sizeof(msg));
+    const bool ok = rc == 1 && strstr(msg, fragment);
+    printf("%-34s %s: %s\n", what, ok ? "refused" : "NOT REFUSED AS EXPECTED", msg);
+    if (!ok) ++n_bad;
+}
+
+static void expect_gram(const upk_mbar_gram_problem_t& P, const char* what, const char* fragment) {
+    char msg[256];
+    const int rc = upk_mbar_gram_solve(&P, msg, (int)sizeof(msg));
     const bool ok = rc == 1 && strstr(msg, fragment);
     printf("%-34s %s: %s\n", what, ok ? "refused" : "NOT REFUSED AS EXPECTED", msg);
     if (!ok) ++n_bad;
@@ -60,6 +69,35 @@ int main() {
         printf("%-34s %s: %s\n", "no problem", rc == 1 ? "refused" : "NOT REFUSED", msg); if (rc != 1) ++n_bad; }
     {   char msg[8]; auto P = G; P.d = 9; const int rc = upk_mbar_solve(&P, msg, (int)sizeof(msg));      // a short message buffer is not overrun
         printf("%-34s rc %d: '%s'\n", "message buffer of 8 bytes", rc, msg); if (rc != 1 || strlen(msg) != 7) ++n_bad; }
+
+    // ---- upside_hip_mbar_gram: its own refusals, and those it shares with upside_hip_mbar reached through it
+    const int n_extra = 2;
+    std::vector<double> fk(K, 0.1), log_extra(n_extra * N, -1.), Gm((K + n_extra) * (K + n_extra)), colsum(K + n_extra);
+    log_extra[3] = -INFINITY;      // weight 0: allowed
+    upk_mbar_gram_problem_t Q{};
+    Q.n_sample = N; Q.n_state = K; Q.d = d; Q.values = values.data(); Q.energy = energy.data(); Q.beta = beta.data(); Q.rows = rows.data();
+    Q.n_k = n_k.data(); Q.periods = periods.data(); Q.f = fk.data(); Q.n_extra = n_extra; Q.log_extra = log_extra.data(); Q.G = Gm.data();
+    Q.colsum = colsum.data(); Q.denominators = D.data();
+    { auto P = Q; P.n_extra = -1; expect_gram(P, "gram: n_extra below 0", "n_extra = -1"); }
+    { auto P = Q; P.n_extra = 8192 - K + 1; expect_gram(P, "gram: M above 8192", "at most 8192"); }
+    { auto P = Q; P.n_state = 8193; P.n_extra = 0; expect_gram(P, "gram: n_state above 8192", "at most 8192"); }
+    { auto P = Q; P.n_state = 0; expect_gram(P, "gram: no state", "at least one state"); }
+    { auto P = Q; P.colsum = nullptr; expect_gram(P, "gram: colsum missing", "colsum must be given"); }
+    { auto P = Q; P.f = nullptr; expect_gram(P, "gram: f missing", "f must be given"); }
+    { auto P = Q; P.log_extra = nullptr; expect_gram(P, "gram: log_extra missing", "log_extra must be given"); }
+    { auto P = Q; auto x = fk; x[2] = nan; P.f = x.data(); expect_gram(P, "gram: f not a number", "f[2] is not finite"); }
+    { auto P = Q; auto x = fk; x[0] = -INFINITY; P.f = x.data(); expect_gram(P, "gram: f infinite", "f[0] is not finite"); }
+    { auto P = Q; auto x = log_extra; x[n_extra * N - 1] = nan; P.log_extra = x.data(); expect_gram(P, "gram: last log_extra not a number", "column 1, sample 29 is not a number"); }
+    { auto P = Q; auto x = log_extra; x[N] = INFINITY; P.log_extra = x.data(); expect_gram(P, "gram: a log_extra +inf", "column 1, sample 0 is +inf"); }
+    { auto P = Q; P.d = 9; expect_gram(P, "gram: d above 8", "at most 8"); }
+    { auto P = Q; P.n_sample = 0; expect_gram(P, "gram: no sample", "at least one sample"); }
+    { auto P = Q; auto c = n_k; c[2] = 9; P.n_k = c.data(); expect_gram(P, "gram: counts below n_sample", "add up"); }
+    { auto P = Q; auto v = values; v[0] = NAN; P.values = v.data(); expect_gram(P, "gram: a value not finite", "sample 0, CV 0"); }
+    { auto P = Q; auto r = rows; r[d] = -1.f; P.rows = r.data(); expect_gram(P, "gram: spring_const negative", "spring_const of state 0, CV 0"); }
+    {   char msg[256]; const int rc = upk_mbar_gram_solve(nullptr, msg, (int)sizeof(msg));
+        printf("%-34s %s: %s\n", "gram: no problem", rc == 1 ? "refused" : "NOT REFUSED", msg); if (rc != 1) ++n_bad; }
+    if (upk_mbar_gram_tile() != UPK_MBAR_GRAM_TILE || upk_mbar_gram_rows(K, 0) != 0 || upk_mbar_gram_rows(65, upk_mbar_gram_partial_bytes(65) + 128 * 8 * 33) != 32 || upk_mbar_gram_partial_bytes(4096) != 0 ||
+        upk_mbar_gram_rows(8193, (size_t)1 << 30) != 0) { printf("gram accessors NOT AS EXPECTED\n"); ++n_bad; }
     printf(n_bad ? "%d UNEXPECTED\n" : "all refusals as expected\n", n_bad);
     return n_bad ? 1 : 0;
 }

@@ -1,12 +1,14 @@
 """MBAR over the output files of an umbrella ladder run by `upside_hip`, on the GPU.
 
-    python tools/umbrella_mbar.py --temperature 0.85 [--node cv_restraint] [--bins 40] [--tol 1e-8] w00.up w01.up ...
+    python tools/umbrella_mbar.py --temperature 0.85 [--node cv_restraint] [--bins 40] [--tol 1e-8] [--solver newton] [--uncertainty] w00.up ...
 
 Every file is one window: its `cv_restraint` node (`--node`) holds the window's centre, spring constant and flat width, and its
 /output/cv holds the CV series the run recorded at the frames (the CVs of /input/collective_variables; samples follow the window,
 as /output does).  The node's CVs are found among the recorded ones by name; a CV of the node that was not recorded is an error that
 names it.  Prints the free energy f_k of every window (in kT, f_0 = 0) and the unbiased free-energy profile along the node's first
-CV (in energy units, lowest bin 0; `inf` where no sample fell)."""
+CV (in energy units, lowest bin 0; `inf` where no sample fell).  `--uncertainty` adds the asymptotic standard deviation of
+f_k - f_0 and a dF column to the profile (relative to the lowest bin; the frames are taken as uncorrelated, so `--skip`/subsample to
+the correlation time first); `--solver newton` converges a poorly overlapping ladder in a few steps."""
 import argparse
 import os
 import sys
@@ -48,6 +50,8 @@ def main():
     ap.add_argument('--bins', type=int, default=40)
     ap.add_argument('--tol', type=float, default=1e-8)
     ap.add_argument('--max-iter', type=int, default=10000)
+    ap.add_argument('--solver', choices=('self-consistent', 'newton'), default='self-consistent')
+    ap.add_argument('--uncertainty', action='store_true', help='print the standard deviation of f_k - f_0 and a dF column of the profile')
     args = ap.parse_args()
     pkg = load_package()
     values, rows, n_k, names0, periods0 = [], [], [], None, None
@@ -64,21 +68,28 @@ def main():
         values.append(v); rows.append(row); n_k.append(len(v))
     kT = args.temperature
     v = np.concatenate(values)
-    r = pkg.mbar.mbar(v, None, 1. / kT, np.stack(rows), np.array(n_k, 'i8'), periods0, args.tol, args.max_iter, target=(1. / kT, None))
-    print('# %d windows, %d samples, CVs %s; %d iterations, last max |df| = %.3e' % (len(rows), len(v), names0, r['n_iter'], r['last_delta']))
-    print('# window  centre(%s)  samples  f_k / kT' % names0[0])
+    problem = (v, None, 1. / kT, np.stack(rows), np.array(n_k, 'i8'))
+    r = pkg.mbar.mbar(*problem, periods0, args.tol, args.max_iter, target=(1. / kT, None), solver=args.solver)
+    print('# %d windows, %d samples, CVs %s; %d iterations%s, last max |df| = %.3e' %
+          (len(rows), len(v), names0, r['n_iter'], ' and %d Newton steps' % r['n_newton'] if 'n_newton' in r else '', r['last_delta']))
+    sigma = pkg.mbar.free_energy_uncertainty(*problem, r['f'], periods0) if args.uncertainty else None
+    print('# window  centre(%s)  samples  f_k / kT%s' % (names0[0], '  sigma(f_k - f_0)' if args.uncertainty else ''))
     for k, (row, n) in enumerate(zip(rows, n_k)):
-        print('%4d  %12.6g  %7d  %14.8f' % (k, row[0], n, r['f'][k]))
+        print('%4d  %12.6g  %7d  %14.8f%s' % (k, row[0], n, r['f'][k], '  %12.6f' % sigma[k, 0] if args.uncertainty else ''))
     x = v[:, 0].astype('f8')
     if periods0[0] > 0:
         edges = np.linspace(-0.5 * periods0[0], 0.5 * periods0[0], args.bins + 1)
     else:
         edges = np.linspace(x.min(), np.nextafter(x.max(), np.inf), args.bins + 1)
-    prof = pkg.config.mbar_profile(x, r['log_w'], edges, kT, period=periods0[0])
+    dF = None
+    if args.uncertainty:
+        prof, dF = pkg.mbar.profile(*problem, r['f'], edges, kT, period=periods0[0], target=(1. / kT, None), periods=periods0, cv=0)
+    else:
+        prof = pkg.config.mbar_profile(x, r['log_w'], edges, kT, period=periods0[0])
     prof = prof - prof[np.isfinite(prof)].min()
-    print('# unbiased profile along %s: bin centre, F' % names0[0])
+    print('# unbiased profile along %s: bin centre, F%s' % (names0[0], ', dF' if args.uncertainty else ''))
     for b in range(args.bins):
-        print('%12.6g  %12.6f' % (0.5 * (edges[b] + edges[b + 1]), prof[b]))
+        print('%12.6g  %12.6f%s' % (0.5 * (edges[b] + edges[b + 1]), prof[b], '  %12.6f' % dF[b] if args.uncertainty else ''))
 
 
 if __name__ == '__main__':

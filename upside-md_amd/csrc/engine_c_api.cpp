@@ -60,6 +60,19 @@ extern "C" int upside_hip_mbar(long long n_sample, int n_state, int d, const flo
     return 0;
     API_CATCH(1)
 }
+// the Gram pass of MBAR: the checks and the staging are upk_mbar_gram_solve (kernels_mbar_gram.hip)
+extern "C" int upside_hip_mbar_gram(long long n_sample, int n_state, int d, const float* values, const double* energy, const double* beta,
+                                    const float* rows, const long long* n_k, const double* periods, const double* f, int n_extra,
+                                    const double* log_extra, double* G, double* colsum, double* D) {
+    API_TRY
+    upk_mbar_gram_problem_t P{};
+    P.n_sample = n_sample; P.n_state = n_state; P.d = d; P.values = values; P.energy = energy; P.beta = beta; P.rows = rows; P.n_k = n_k;
+    P.periods = periods; P.f = f; P.n_extra = n_extra; P.log_extra = log_extra; P.G = G; P.colsum = colsum; P.denominators = D;
+    char msg[256];
+    if (upk_mbar_gram_solve(&P, msg, (int)sizeof(msg))) throw string(msg);
+    return 0;
+    API_CATCH(1)
+}
 
 // ---- construction ----------------------------------------------------------------------------------
 extern "C" int upside_hip_set_device(int device) {

@@ -494,7 +494,8 @@ class Ensemble(object):
             raise RuntimeError('cv_restraint_values failed: %s' % self.calc.upside_hip_last_error().decode())
         return out
 
-    def umbrella_mbar(self, node_name, kT, tol=1e-8, max_iter=10000, f0=None, target=None, series=None):
+    def umbrella_mbar(self, node_name, kT, tol=1e-8, max_iter=10000, f0=None, target=None, series=None, solver='self-consistent',
+                      n_sc=10, uncertainty=False):
         """MBAR over the umbrella ladder of the cv_restraint node `node_name` from the recorded CV series (mbar.mbar on the device):
         system s is window s with its own row [center | spring_const | flat_width] (get_param of system s) and beta = 1 / kT for all
         (one temperature: the unbiased potential cancels and is not needed).  series: (n_stored, n_system, n_cv) as read_cvs gives it,
@@ -502,7 +503,9 @@ class Ensemble(object):
         are found among the recorded ones BY NAME (the names of the node's group against cv_names); a CV of the node that is not
         recorded raises ValueError naming it.  target: None, 'unbiased' (no bias at beta) or a row (3 n_cv,).  Returns the dict of
         mbar.mbar with values (N, d), rows (n_system, 3 d), periods (d,), n_k and names added; with a target, log_w feeds
-        config.mbar_profile."""
+        config.mbar_profile.  solver, n_sc: as mbar.mbar ('newton' for a ladder that converges slowly).  uncertainty=True adds sigma
+        (n_system, n_system), the asymptotic standard deviation of f_i - f_j (mbar.free_energy_uncertainty: the samples are taken as
+        uncorrelated, so record or pass a series subsampled to its correlation time)."""
         from . import config, mbar as _mbar
         if not (np.ndim(kT) == 0 and np.isfinite(kT) and kT > 0):
             raise ValueError('umbrella_mbar: kT must be one finite positive number (one temperature for every window)')
@@ -536,7 +539,9 @@ class Ensemble(object):
             tgt = (beta, None)
         else:
             tgt = None if target is None else (beta, target)
-        out = _mbar.mbar(values, None, beta, rows, n_k, periods, tol, max_iter, f0=f0, target=tgt, library=self.lib)
+        out = _mbar.mbar(values, None, beta, rows, n_k, periods, tol, max_iter, f0=f0, target=tgt, library=self.lib, solver=solver, n_sc=n_sc)
+        if uncertainty:
+            out['sigma'] = _mbar.free_energy_uncertainty(values, None, beta, rows, n_k, out['f'], periods, library=self.lib)
         out.update(values=values, rows=rows, periods=periods, n_k=n_k, names=names)
         return out
 

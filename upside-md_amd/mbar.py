@@ -1,12 +1,18 @@
-"""MBAR on the device over the ladders the engine runs (upside_hip_mbar of include/upside_engine_c.h; csrc/kernels_mbar.hip): free
-energies of umbrella windows from the recorded CV series and of temperature ladders from recorded energies.  The profile along a CV
-from the returned log-weights is config.mbar_profile."""
+"""MBAR on the device over the ladders the engine runs (upside_hip_mbar and upside_hip_mbar_gram of include/upside_engine_c.h;
+csrc/kernels_mbar.hip, csrc/kernels_mbar_gram.hip): free energies of umbrella windows from the recorded CV series and of temperature
+ladders from recorded energies, by self-consistent iteration or with Newton steps; their asymptotic uncertainties, and averages and
+profiles in a target state with error bars, from the Gram matrix of the weight matrix (Shirts & Chodera 2008, eq. D8/D9).
+Limits of the uncertainties: at most 8192 columns (states + target + observables or bins); the covariance is the asymptotic one; the
+samples are taken as uncorrelated, so subsample a correlated series first."""
 import ctypes as ct
 import numpy as np
 
 MAX_DIM = 8              # UPK_MBAR_MAX_DIM of include/upside_hip_kernels.h
 STATE_TILE = 128         # UPK_MBAR_STATE_TILE: states staged in LDS per tile of the denominator pass
 FE_TILE = 4              # UPK_MBAR_FE_TILE: states per workgroup of the free-energy pass
+GRAM_TILE = 64           # UPK_MBAR_GRAM_TILE: the Gram pass computes G in tiles of 64 x 64
+GRAM_MAX_COLUMNS = 8192  # UPK_MBAR_GRAM_MAX_COLUMNS
+NULL_RCOND = 1e-10       # eigenvalues of I - Sigma V^T N V Sigma below this (relative) are its null space in covariance()
 
 
 def _bind(c):
@@ -15,6 +21,8 @@ def _bind(c):
     vp, i32, i64, f64 = ct.c_void_p, ct.c_int, ct.c_longlong, ct.c_double
     c.upside_hip_mbar.argtypes = [i64, i32, i32, vp, vp, vp, vp, vp, vp, f64, i32, vp, i32, f64, vp, vp, vp, vp, vp, vp, vp]
     c.upside_hip_mbar.restype = i32
+    c.upside_hip_mbar_gram.argtypes = [i64, i32, i32, vp, vp, vp, vp, vp, vp, vp, i32, vp, vp, vp, vp]
+    c.upside_hip_mbar_gram.restype = i32
     c.upside_hip_last_error.restype = ct.c_char_p
     c._mbar_bound = True
 
@@ -23,24 +31,8 @@ def _ptr(a):
     return None if a is None else a.ctypes.data
 
 
-def mbar(values, energy, beta, rows, n_k, periods=None, tol=1e-8, max_iter=10000, f0=None, target=None, want_denominators=True,
-         library=None):
-    """free energies f (K,) of K states from N samples, float64 on the device.
-      values   (N, d) float32 CV values as recorded, d <= 8; None or (N, 0) for d = 0
-      energy   (N,) unbiased potential, or None (= 0; it cancels when every beta is the same)
-      beta     (K,) or a scalar for all states
-      rows     (K, 3 d) = [center | spring_const | flat_width] per state: the cv_restraint per-system rows; None for d = 0
-      n_k      (K,) samples drawn from each state, summing to N (the order of the samples does not matter)
-      periods  (d,) period of each CV, 0 = not periodic (Ensemble.cv_periods, config.cv_periods); None: none is periodic
-      tol, max_iter   stops when max |f' - f| < tol or after max_iter iterations (tol = 0: exactly max_iter); f0: the start, default 0
-      target   None, or (beta_t, row_t) with row_t (3 d,) or None for no bias: the state to reweight to
-    Returns dict(f, D (N,) the denominators of the returned f, n_iter, last_delta) and with a target also log_w (N,), the normalised
-    log-weights of the samples in the target state, and f_target.  Every refusal of the entry point raises RuntimeError with its
-    message."""
-    from .engine import default_library
-    lib = library if library is not None else default_library()
-    c = lib.calc
-    _bind(c)
+def _problem(values, energy, beta, rows, n_k, periods):
+    """the arrays of a problem as the entry points take them: (v (N, d) f4, e (N,) f8 or None, b (K,), r (K, 3 d) f4, n_k i8, per (d,))"""
     n_k = np.ascontiguousarray(np.asarray(n_k).reshape(-1), 'i8')
     K = len(n_k)
     if values is None:
@@ -66,6 +58,39 @@ def mbar(values, energy, beta, rows, n_k, periods=None, tol=1e-8, max_iter=10000
     per = np.zeros(d) if periods is None else np.ascontiguousarray(np.asarray(periods, 'f8').reshape(-1))
     if len(per) != d:
         raise ValueError('mbar: %d periods for %d CVs' % (len(per), d))
+    return v, e, b, r, n_k, per
+
+
+def mbar(values, energy, beta, rows, n_k, periods=None, tol=1e-8, max_iter=10000, f0=None, target=None, want_denominators=True,
+         library=None, solver='self-consistent', n_sc=10):
+    """free energies f (K,) of K states from N samples, float64 on the device.
+      values   (N, d) float32 CV values as recorded, d <= 8; None or (N, 0) for d = 0
+      energy   (N,) unbiased potential, or None (= 0; it cancels when every beta is the same)
+      beta     (K,) or a scalar for all states
+      rows     (K, 3 d) = [center | spring_const | flat_width] per state: the cv_restraint per-system rows; None for d = 0
+      n_k      (K,) samples drawn from each state, summing to N (the order of the samples does not matter)
+      periods  (d,) period of each CV, 0 = not periodic (Ensemble.cv_periods, config.cv_periods); None: none is periodic
+      tol, max_iter   stops when max |f' - f| < tol or after max_iter iterations (tol = 0: exactly max_iter); f0: the start, default 0
+      target   None, or (beta_t, row_t) with row_t (3 d,) or None for no bias: the state to reweight to
+      solver   'self-consistent' (the default, unchanged), or 'newton': n_sc self-consistent iterations, then one self-consistent
+               iteration and one Newton step in turn (the step from gram() on the device, solved in numpy over the states with
+               samples, the first of them pinned) until an iteration's delta is below tol.  A Newton step that does not lower the
+               largest |gradient| is discarded and five self-consistent iterations run instead.  The result is always the output
+               of a self-consistent iteration, so every entry keeps its meaning; n_iter counts self-consistent iterations (at most
+               max_iter) and n_newton, the accepted Newton steps, is added.
+    Returns dict(f, D (N,) the denominators of the returned f, n_iter, last_delta) and with a target also log_w (N,), the normalised
+    log-weights of the samples in the target state, and f_target.  Every refusal of the entry point raises RuntimeError with its
+    message."""
+    from .engine import default_library
+    lib = library if library is not None else default_library()
+    c = lib.calc
+    _bind(c)
+    if solver == 'newton':
+        return _newton(values, energy, beta, rows, n_k, periods, tol, max_iter, f0, target, want_denominators, lib, n_sc)
+    if solver != 'self-consistent':
+        raise ValueError("mbar: solver must be 'self-consistent' or 'newton'")
+    v, e, b, r, n_k, per = _problem(values, energy, beta, rows, n_k, periods)
+    (N, d), K = v.shape, len(n_k)
     start = None
     if f0 is not None:
         start = np.ascontiguousarray(np.asarray(f0, 'f8').reshape(-1))
@@ -91,3 +116,183 @@ def mbar(values, energy, beta, rows, n_k, periods=None, tol=1e-8, max_iter=10000
     if target is not None:
         out['log_w'] = log_w; out['f_target'] = float(f_t[0])
     return out
+
+
+def _newton(values, energy, beta, rows, n_k, periods, tol, max_iter, f0, target, want_denominators, lib, n_sc):
+    """mbar(solver='newton'): every returned entry comes from the last self-consistent call; Newton steps only move its start"""
+    n_k = np.asarray(n_k).reshape(-1)
+    act = np.flatnonzero(n_k > 0)
+    free = act[1:]
+    cnt = n_k.astype('f8')
+
+    def sc(start, n):
+        return mbar(values, energy, beta, rows, n_k, periods, tol, n, f0=start, target=target, want_denominators=want_denominators, library=lib)
+
+    def gradient(c):
+        return cnt[act] * (1. - c[act])
+
+    if int(n_sc) < 1:
+        raise ValueError('mbar: n_sc must be at least 1')
+    out = sc(f0, min(int(n_sc), int(max_iter)))
+    n_iter, n_newton, n_next = out['n_iter'], 0, 1
+    while not out['last_delta'] < tol and n_iter < max_iter:
+        out = sc(out['f'], min(n_next, int(max_iter) - n_iter))
+        n_iter += out['n_iter']; n_next = 1
+        if out['last_delta'] < tol or n_iter >= max_iter:
+            break
+        if not len(free):      # one state with samples: nothing for a Newton step to move
+            continue
+        f = out['f']
+        g = gram(values, energy, beta, rows, n_k, f, periods, library=lib)
+        grad = gradient(g['colsum'])
+        H = np.diag(cnt[free] * g['colsum'][free]) - cnt[free, None] * g['G'][np.ix_(free, free)] * cnt[None, free]
+        trial = f.copy()
+        try:
+            trial[free] += np.linalg.solve(H, grad[1:])
+        except np.linalg.LinAlgError:
+            n_next = 5
+            continue
+        ok = np.isfinite(trial).all()
+        if ok:
+            c = gram(values, energy, beta, rows, n_k, trial, periods, want_gram=False, library=lib)['colsum']
+            ok = np.isfinite(c).all() and np.abs(gradient(c)).max() < np.abs(grad).max()
+        if ok:
+            out = dict(out, f=trial); n_newton += 1
+        else:
+            n_next = 5
+    out['n_iter'] = n_iter; out['n_newton'] = n_newton
+    return out
+
+
+def gram(values, energy, beta, rows, n_k, f, periods=None, log_columns=None, want_gram=True, library=None):
+    """the Gram matrix G = W^T W (M, M) and the column sums (M,) of the MBAR weight matrix at the free energies f, float64 on the
+    device (upside_hip_mbar_gram): M = K + n_extra columns, W[n, k] = exp(f_k - u_k(n) - D_n) for the K states of the problem (the
+    arguments of mbar()) and W[n, K + j] = exp(log_columns[j, n]) for each explicit log-column (-inf = weight 0; NaN and +inf are
+    refused).  want_gram=False computes the column sums only, a cheap pass.  Returns dict(G (or None), colsum, D (N,) the
+    denominators of f).  G is bitwise symmetric and two calls return the same bits.  M <= 8192."""
+    from .engine import default_library
+    lib = library if library is not None else default_library()
+    c = lib.calc
+    _bind(c)
+    v, e, b, r, n_k, per = _problem(values, energy, beta, rows, n_k, periods)
+    (N, d), K = v.shape, len(n_k)
+    fk = np.ascontiguousarray(np.asarray(f, 'f8').reshape(-1))
+    if len(fk) != K:
+        raise ValueError('mbar.gram: f holds %d entries for %d states' % (len(fk), K))
+    lc, n_extra = None, 0
+    if log_columns is not None:
+        lc = np.ascontiguousarray(np.asarray(log_columns, 'f8'))
+        if lc.ndim == 1:
+            lc = lc[None, :]
+        if lc.ndim != 2 or lc.shape[1] != N:
+            raise ValueError('mbar.gram: log_columns must be (n_extra, %d samples), got %r' % (N, lc.shape))
+        n_extra = lc.shape[0]
+    M = K + n_extra
+    if M > GRAM_MAX_COLUMNS:      # (before G is allocated; the entry point refuses it as well)
+        raise ValueError('mbar.gram: n_state + n_extra = %d + %d columns, at most %d are supported' % (K, n_extra, GRAM_MAX_COLUMNS))
+    G = np.zeros((M, M), 'f8') if want_gram else None
+    colsum = np.zeros(M, 'f8'); D = np.zeros(N, 'f8')
+    rc = c.upside_hip_mbar_gram(N, K, d, _ptr(v) if d else None, _ptr(e), _ptr(b), _ptr(r) if d else None, _ptr(n_k), _ptr(per) if d else None,
+                                _ptr(fk), n_extra, _ptr(lc) if n_extra else None, _ptr(G), _ptr(colsum), _ptr(D))
+    if rc:
+        raise RuntimeError('mbar.gram failed: %s' % c.upside_hip_last_error().decode())
+    return dict(G=G, colsum=colsum, D=D)
+
+
+def covariance(G, n_k):
+    """the asymptotic covariance Theta (M, M) of the log normalisation constants of the M columns of W from its Gram matrix
+    (Shirts & Chodera 2008, eq. D9), pure numpy:
+        s^2, V = eigh(G),  Sigma = sqrt(max(s^2, 0)),  Theta = V Sigma (I - Sigma V^T N V Sigma)^+ Sigma V^T,
+    N = diag(n_k) padded with 0 for the columns past len(n_k).  var(f_i - f_j) = Theta_ii + Theta_jj - 2 Theta_ij.  The pseudo-inverse
+    drops eigenvalues below NULL_RCOND of the largest (the constant shift of all f is an exact null direction)."""
+    G = np.asarray(G, 'f8')
+    if G.ndim != 2 or G.shape[0] != G.shape[1]:
+        raise ValueError('mbar.covariance: G must be square')
+    M = len(G)
+    n = np.zeros(M)
+    cnt = np.asarray(n_k, 'f8').reshape(-1)
+    if len(cnt) > M:
+        raise ValueError('mbar.covariance: %d counts for %d columns' % (len(cnt), M))
+    n[:len(cnt)] = cnt
+    s2, V = np.linalg.eigh(G)
+    VS = V * np.sqrt(np.maximum(s2, 0.))[None, :]
+    inner = np.eye(M) - VS.T @ (n[:, None] * VS)
+    inner = 0.5 * (inner + inner.T)
+    return VS @ np.linalg.pinv(inner, rcond=NULL_RCOND, hermitian=True) @ VS.T
+
+
+def _pair_sigma(theta):
+    dg = np.diag(theta)
+    return np.sqrt(np.maximum(dg[:, None] + dg[None, :] - 2. * theta, 0.))
+
+
+def free_energy_uncertainty(values, energy, beta, rows, n_k, f, periods=None, library=None):
+    """sigma (K, K): the asymptotic standard deviation of f_i - f_j, sqrt(Theta_ii + Theta_jj - 2 Theta_ij), at the converged
+    free energies f of the problem (the arguments of mbar())."""
+    g = gram(values, energy, beta, rows, n_k, f, periods, library=library)
+    return _pair_sigma(covariance(g['G'], n_k))
+
+
+def _target_weights(values, energy, beta, rows, n_k, f, periods, target, library):
+    """one self-consistent iteration from f with the target: (f', log_w) -- the weights belong to f', which equals f to within the
+    tolerance f was converged to"""
+    if target is None:
+        raise ValueError('mbar: a target (beta_t, row_t or None) is needed')
+    r = mbar(values, energy, beta, rows, n_k, periods, 0., 1, f0=f, target=target, want_denominators=False, library=library)
+    return r['f'], r['log_w']
+
+
+def expectation(values, energy, beta, rows, n_k, f, observables, target, periods=None, library=None):
+    """(mean (m,), sigma (m,)): the averages of m observables (N, m) (or (N,)) in the target state (beta_t, row_t or None) with their
+    asymptotic standard deviations, at the converged f.  Columns added to W: the target's weights w_t and, per observable,
+    w_t A' / <A'> with A' = A - min A + 1 > 0; var <A> = <A'>^2 (Theta_AA + Theta_tt - 2 Theta_At)."""
+    A = np.asarray(observables, 'f8')
+    if A.ndim == 1:
+        A = A[:, None]
+    if A.ndim != 2 or not np.isfinite(A).all():
+        raise ValueError('mbar.expectation: observables must be a finite (N, m) array')
+    f1, log_w = _target_weights(values, energy, beta, rows, n_k, f, periods, target, library)
+    if len(log_w) != len(A):
+        raise ValueError('mbar.expectation: %d observables for %d samples' % (len(A), len(log_w)))
+    shift = A.min(axis=0) - 1.
+    Ap = A - shift[None, :]
+    mean_p = (np.exp(log_w)[:, None] * Ap).sum(axis=0)
+    cols = np.concatenate((log_w[None, :], (log_w[:, None] + np.log(Ap) - np.log(mean_p)[None, :]).T))
+    K = len(np.asarray(n_k).reshape(-1))
+    theta = covariance(gram(values, energy, beta, rows, n_k, f1, periods, log_columns=cols, library=library)['G'], n_k)
+    t = K
+    a = K + 1 + np.arange(A.shape[1])
+    var = mean_p ** 2 * (theta[a, a] + theta[t, t] - 2. * theta[a, t])
+    return mean_p + shift, np.sqrt(np.maximum(var, 0.))
+
+
+def profile(values, energy, beta, rows, n_k, f, edges, kT, period=0, target=None, periods=None, cv=0, library=None):
+    """(F (n_bin,), dF (n_bin,)): the free-energy profile of the target state along one CV with its asymptotic standard deviation.
+    cv: the column of values to bin, or an (N,) array of its own.  F is config.mbar_profile of the target's weights.  One column is
+    added to W per non-empty bin, w_t 1[bin] / p_b; dF_b = kT sqrt(Theta_bb + Theta_rr - 2 Theta_br) relative to the lowest bin r
+    (dF_r = 0).  An empty bin has F = +inf and dF = nan."""
+    from . import config
+    f1, log_w = _target_weights(values, energy, beta, rows, n_k, f, periods, target, library)
+    x = np.asarray(values)[:, cv] if np.ndim(cv) == 0 else np.asarray(cv)
+    x = np.asarray(x, 'f8').reshape(-1)
+    F = config.mbar_profile(x, log_w, edges, kT, period)
+    e = np.asarray(edges, 'f8').reshape(-1)
+    if period > 0:
+        x = e[0] + np.mod(x - e[0], float(period))
+    b = np.searchsorted(e, x, 'right') - 1      # the bins of numpy.histogram: the last one is closed
+    b[x == e[-1]] = len(e) - 2
+    b[(x < e[0]) | (x > e[-1])] = -1
+    full = np.flatnonzero(np.isfinite(F))
+    dF = np.full(len(F), np.nan)
+    if not len(full):
+        return F, dF
+    cols = np.full((len(full), len(x)), -np.inf)
+    for i, bin_ in enumerate(full):
+        inside = b == bin_
+        cols[i, inside] = log_w[inside] + F[bin_] / float(kT)      # ln (w_n / p_b), p_b = exp(-F_b / kT)
+    K = len(np.asarray(n_k).reshape(-1))
+    theta = covariance(gram(values, energy, beta, rows, n_k, f1, periods, log_columns=cols, library=library)['G'], n_k)
+    idx = K + np.arange(len(full))
+    r = idx[np.argmin(F[full])]
+    dF[full] = float(kT) * np.sqrt(np.maximum(theta[idx, idx] + theta[r, r] - 2. * theta[idx, r], 0.))
+    return F, dF
