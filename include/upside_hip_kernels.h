@@ -479,6 +479,33 @@ int upk_conv1d_param_deriv_all(const upk_launch_t* L, const upk_conv1d_t* P, upk
 /* scaled_sum: in.sens[r] += *scale, pot_terms[s][r] = *scale * in[r] (pot_terms may be NULL); scale is a device value */
 int upk_scaled_sum(const upk_launch_t* L, upk_coord_t in, const float* scale, float* pot_terms);
 
+/* ---- TorusDBN backbone prior (src/hmm.cpp: torus_dbn :218-358, fixed_hmm :38-216), csrc/kernels_hmm.hip ----
+ * torus_dbn: out[r][s] = (prior[restypes[r]][s] + cs_to_emission[6][s]) + sum_{k<6} cs_k(r) * cs_to_emission[k][s], k ascending,
+ * cs = (cos phi, sin phi, cos psi, sin psi, cos(phi - psi), sin(phi - psi)), phi, psi = columns 0, 1 of rama row id[r]; n_state is
+ * out.width.  Rows 0..5 of cs_to_emission [7][n_state] are the reference constructor's matrix, row 6 the basins' log normalisation.
+ * The backward pass contracts self.sens with the matrix (state ascending) and ADDS the chain rule into columns 0, 1 of rama's sens
+ * row id[r] with plain read-modify-writes: id must be distinct and in range (checked by the node). */
+typedef struct { const int* id; const int* restypes; const float* prior; const float* cs_to_emission; int n_restype; } upk_torus_dbn_t;
+int upk_torus_dbn_fwd(const upk_launch_t* L, const upk_torus_dbn_t* P, upk_coord_t rama, upk_coord_t out);
+int upk_torus_dbn_bwd(const upk_launch_t* L, const upk_torus_dbn_t* P, upk_coord_t rama, upk_coord_t self);
+/* table[t][s] = sum over r (ascending) with restypes[r] == t of self.sens[r][s]: one system into table [n_restype * n_state], or every
+ * system into table [n_system][n_restype * n_state] */
+int upk_torus_dbn_param_deriv(const upk_launch_t* L, const upk_torus_dbn_t* P, upk_coord_t self, int system, float* table);
+int upk_torus_dbn_param_deriv_all(const upk_launch_t* L, const upk_torus_dbn_t* P, upk_coord_t self, float* table);
+/* fixed_hmm over the rows index[0 .. n_residue) of `in` (width n_state <= upk_fixed_hmm_max_state()): emission b_r = exp(e_min_r -
+ * in[index[r]]), scaled forward recursion f_r = normalise((f_{r-1} T) * b_r), T [n_state][n_state] and *offset device values;
+ * potential[s] = *offset * (n_residue - 1) + sum_r e_min_r - sum_r log(norm_r) (accumulated in fp64; potential may be NULL), and the
+ * posterior marginal of residue r is ADDED to in.sens row index[r] (index distinct and in range, checked by the node).  One wavefront
+ * per system; fwd [n_system][n_residue][row_stride] keeps the forward beliefs of the last call. */
+typedef struct { const float* T; const float* offset; const int* index; int n_residue, n_state, row_stride; float* fwd; float* w; } upk_fixed_hmm_t;
+int upk_fixed_hmm_max_state(void);
+int upk_fixed_hmm(const upk_launch_t* L, const upk_fixed_hmm_t* H, upk_coord_t in, float* potential);
+/* expected transition counts table[i][j] = sum over the edges of the normalised T[i][j] f_{r-1}[i] b_r[j] beta_r[j] (hmm.cpp:188-197),
+ * r ascending, from the beliefs and energies of the last upk_fixed_hmm call; w (as fwd) is scratch.  One system, or every system into
+ * table [n_system][n_state * n_state].  Off the MD path. */
+int upk_fixed_hmm_param_deriv(const upk_launch_t* L, const upk_fixed_hmm_t* H, upk_coord_t in, int system, float* table);
+int upk_fixed_hmm_param_deriv_all(const upk_launch_t* L, const upk_fixed_hmm_t* H, upk_coord_t in, float* table);
+
 /* ---- collective variables of every system (upside_hip_cv_*), csrc/kernels_cv.hip ---------------------------------------------
  * n_cv CVs, each over its own atom list atoms[atom_start[c] : atom_start[c+1]] (CSR):
  *   UPK_CV_RG        sqrt of the mean squared distance to the list's centroid

@@ -4,7 +4,7 @@ of upside_config.py; needs the reference's parameter directory, so it runs where
 
     python tools/make_config.py --pdb 1abc.pdb --chains A --out 1abc.up [--param-dir /root/reference/parameters]
                                 [--cutoff 7|10] [--cavity-radius R] [--contacts table] [--z-flat-bottom table]
-                                [--backbone-network net.npz] ...
+                                [--backbone-network net.npz] [--torus-dbn dbn.npz] ...
 
 The Ramachandran maps come from --rama-library (the README's rama.dat: neighbour-dependent coil / sheet maps, with
 --rama-sheet-mixing-energy, --rama-library-combining-rule, --secstr-bias as in py/upside_config.py) or, without one, are the
@@ -48,6 +48,8 @@ def main():
     ap.add_argument('--loose-hbond-criteria', action='store_true', help='permissive H-bond geometry (static structures only)')
     ap.add_argument('--backbone-network', default='', help='.npz with weights_k [W, C_in, C_out], bias_k [C_out], activation_k (ReLU | Tanh | '
                     'Identity) for k = 0, 1, ... and scale: appended as backbone_featurizer -> conv1d layers -> scaled_sum')
+    ap.add_argument('--torus-dbn', default='', help='.npz with basin_param [n_state, 6], aa_basin_energy [n_restype, n_state], '
+                    'transition_energy [n_state, n_state] and restype_order [n_restype]: appended as torus_dbn -> fixed_hmm')
     ap.add_argument('--collective-variables', action='store_true', help='also write /input/collective_variables: over the CA atoms, Rg, '
                     'RMSD and fraction of native contacts Q to the input structure, end-to-end distance (computed on the device; '
                     'upside_hip adds /output/cv)')
@@ -91,6 +93,10 @@ def main():
         layers = [(net['weights_%d' % k], net['bias_%d' % k], str(np.ravel(net['activation_%d' % k])[0])) for k in range(n_layer)]
         names = cfg.add_backbone_network(a.out, layers, float(np.ravel(net['scale'])[0]))
         print('backbone network: %s' % ' -> '.join(names))
+    if a.torus_dbn:
+        lib = np.load(a.torus_dbn)
+        names = cfg.add_torus_dbn(a.out, lib['basin_param'], lib['aa_basin_energy'], lib['transition_energy'], lib['restype_order'])
+        print('TorusDBN prior: %s' % ' -> '.join(names))
     if a.collective_variables:
         p = cfg.add_collective_variables(a.out, cfg.default_collective_variables(cfg.read_pos(a.out)))
         print('collective variables: %s' % ', '.join(x.decode() for x in p['names']))

@@ -1448,6 +1448,53 @@ def add_backbone_network(path, layers, scale, name='backbone_nn'):
     return names
 
 
+def add_torus_dbn(path, basin_param, aa_basin_energy, transition_energy, restype_order, name=''):
+    """append the reference's sequence-dependent backbone prior (src/hmm.cpp, write_torus_dbn of py/upside_config.py) to an
+    existing configuration:
+      torus_dbn<_name>   argument rama_coord; emission energy of every hidden state for the interior residues
+                         id = 1 .. n_res - 2 (the first and last residue have no complete phi / psi), restypes = the row of
+                         aa_basin_energy of each of them, prior_offset_energies = aa_basin_energy [n_restype, n_state],
+                         basin_param [n_state, 6] = (log normalisation, kappa_phi, mu_phi, kappa_psi, mu_psi, kappa_phi_minus_psi)
+      fixed_hmm<_name>   argument the node above; index = arange(len(id)), transition_energy [n_state, n_state]
+    restype_order lists the residue names of the rows of aa_basin_energy; the file's sequence is looked up in it.
+    Returns the two node names."""
+    basin_param = np.asarray(basin_param, 'f4'); aa_basin_energy = np.asarray(aa_basin_energy, 'f4')
+    transition_energy = np.asarray(transition_energy, 'f4')
+    restype_order = [x.decode() if isinstance(x, bytes) else str(x) for x in restype_order]
+    if basin_param.ndim != 2 or basin_param.shape[1] != 6 or basin_param.shape[0] < 1:
+        raise ValueError('basin_param must have shape [n_state, 6], not %s' % (basin_param.shape,))
+    n_state = basin_param.shape[0]
+    if aa_basin_energy.ndim != 2 or aa_basin_energy.shape[1] != n_state:
+        raise ValueError('aa_basin_energy must have shape [n_restype, n_state = %d], not %s' % (n_state, aa_basin_energy.shape))
+    if transition_energy.shape != (n_state, n_state):
+        raise ValueError('transition_energy must have shape [%d, %d], not %s' % (n_state, n_state, transition_energy.shape))
+    if len(restype_order) != aa_basin_energy.shape[0]:
+        raise ValueError('restype_order names %d residue types for the %d rows of aa_basin_energy' % (len(restype_order), aa_basin_energy.shape[0]))
+    number = dict((x, i) for i, x in enumerate(restype_order))
+    suffix = '_' + name if name else ''
+    names = ['torus_dbn' + suffix, 'fixed_hmm' + suffix]
+    with h5lite.open_file(path, 'r+') as f:
+        inp = f.group('input'); pot = inp.group('potential')
+        if 'rama_coord' not in pot:
+            raise ValueError('%s has no rama_coord node' % path)
+        seq = [x.decode() if isinstance(x, bytes) else str(x) for x in inp.read('sequence')]
+        if len(seq) < 3:
+            raise ValueError('the chain has %d residues; the TorusDBN prior needs at least 3 (it leaves out both ends)' % len(seq))
+        for nm in names:
+            if nm in pot:
+                raise ValueError('%s already has a node %s' % (path, nm))
+        missing = sorted(set(s for s in seq[1:-1] if s not in number))
+        if missing:
+            raise ValueError('residue name %s is not in restype_order' % ', '.join(missing))
+        ids = np.arange(1, len(seq) - 1, dtype='i4')
+        g = pot.create_group(names[0]); _args(g, ['rama_coord'])
+        g.write('id', ids); g.write('restypes', np.array([number[s] for s in seq[1:-1]], 'i4'))
+        g.write('prior_offset_energies', aa_basin_energy); g.write('basin_param', basin_param)
+        g = pot.create_group(names[1]); _args(g, [names[0]])
+        g.write('index', np.arange(len(ids), dtype='i4')); g.write('transition_energy', transition_energy)
+    return names
+
+
 def _dihedral(x1, x2, x3, x4):
     b1, b2, b3 = x2 - x1, x3 - x2, x4 - x3
     b2b3 = np.cross(b2, b3)

@@ -1811,6 +1811,143 @@ struct ScaledSum : public PotentialNode, BatchedParamDeriv {
 };
 RegisterNodeType<Builtin<ScaledSum>, 1> scaled_sum_node("scaled_sum");
 
+// ---------------------------------------------------------------------------------------------------
+// TorusDBN backbone prior: hmm.cpp:218-358 (torus_dbn), :38-216 (fixed_hmm); kernels_hmm.hip.
+
+// torus_dbn: one row of n_state emission energies per entry of id.  get_param() = prior_offset_energies [n_restype][n_state] in file
+// order, a device table rewritten in place by set_param.  The backward pass adds into rama's sens directly: id must be distinct.
+struct TorusDBN : public CoordNode, BatchedParamDeriv {
+    CoordNode& rama; upk_torus_dbn_t P; int n_restype, n_state;
+    vector<float> prior; DevBuf<float> d_prior, d_matrix; DevBuf<int> d_id, d_restypes;
+    static int rows(hid_t_compat grp) {
+        const int n = (int)dset_size(1, H(grp), "id")[0];
+        if (n < 1) throw string("torus_dbn: id is empty (the node needs at least one residue)");
+        return n;
+    }
+    static int states(hid_t_compat grp) {
+        const int n = (int)dset_size(2, H(grp), "basin_param")[0];
+        if (n < 1) throw string("torus_dbn: basin_param has no rows (n_state >= 1)");
+        return n;
+    }
+    TorusDBN(DeviceCtx* c, hid_t_compat grp, CoordNode& rama_) : CoordNode(c, rows(grp), states(grp)), rama(rama_), n_state(elem_width) {
+        memset(&P, 0, sizeof(P));
+        check_elem_width_lower_bound(rama, 2);
+        n_restype = (int)dset_size(2, H(grp), "prior_offset_energies")[0];
+        if (n_restype < 1) throw string("torus_dbn: prior_offset_energies has no rows");
+        check_size(H(grp), "restypes", {(size_t)n_elem});
+        check_size(H(grp), "prior_offset_energies", {(size_t)n_restype, (size_t)n_state});
+        check_size(H(grp), "basin_param", {(size_t)n_state, 6});
+        const auto id = read<int>(H(grp), "id", 1), restypes = read<int>(H(grp), "restypes", 1);
+        require_injective(id, rama.n_elem, "torus_dbn id");
+        for (int t : restypes) if (t < 0 || t >= n_restype)
+            throw string("torus_dbn restypes: entry ") + to_string(t) + " is outside the " + to_string(n_restype) + " rows of prior_offset_energies";
+        prior = read<float>(H(grp), "prior_offset_energies", 2);
+        const auto bp = read<float>(H(grp), "basin_param", 2);      // [n_state][6]: log norm, kappa_phi, mu_phi, kappa_psi, mu_psi, kappa_cor
+        vector<float> m(7 * (size_t)n_state);                       // hmm.cpp:275-293, and the log normalisation as row 6
+        for (int s = 0; s < n_state; ++s) {
+            const float* b = &bp[6 * (size_t)s];
+            const float k[3] = {-b[1], -b[3], b[5]}, a[3] = {b[2], b[4], b[2] - b[4]};
+            for (int i = 0; i < 3; ++i) { m[(2 * i) * (size_t)n_state + s] = k[i] * cosf(a[i]); m[(2 * i + 1) * (size_t)n_state + s] = k[i] * sinf(a[i]); }
+            m[6 * (size_t)n_state + s] = b[0];
+        }
+        d_id.upload(id); d_restypes.upload(restypes); d_prior.upload(prior); d_matrix.upload(m);
+        P.id = d_id.p; P.restypes = d_restypes.p; P.prior = d_prior.p; P.cs_to_emission = d_matrix.p; P.n_restype = n_restype;
+    }
+    // (profiling: one family per kernel; bytes = the emission rows written or read once)
+    double row_bytes() const { return 4. * ctx->n_system * (double)n_elem * n_state; }
+    void compute_value(ComputeMode) override {
+        if (ctx->profile) ctx->begin("torus_dbn_fwd:" + name);
+        upk_check(upk_torus_dbn_fwd(&ctx->L, &P, rama.coord(), coord()), "torus_dbn_fwd");
+        if (ctx->profile) ctx->end("torus_dbn_fwd:" + name, row_bytes());
+    }
+    void propagate_deriv() override {
+        if (ctx->profile) ctx->begin("torus_dbn_bwd:" + name);
+        upk_check(upk_torus_dbn_bwd(&ctx->L, &P, rama.coord(), coord()), "torus_dbn_bwd");
+        if (ctx->profile) ctx->end("torus_dbn_bwd:" + name, row_bytes());
+    }
+    vector<float> get_param() const override { return prior; }
+    void set_param(const vector<float>& p) override {
+        if (p.size() != prior.size()) throw string("Invalid dimensions for prior energy table");
+        prior = p;
+        hip_check(hipStreamSynchronize(ctx->stream), "hipStreamSynchronize");
+        hip_check(hipMemcpy(d_prior.p, p.data(), p.size() * sizeof(float), hipMemcpyHostToDevice), "H2D");
+    }
+    vector<float> get_param_deriv(int system) override {
+        return param_deriv_table(ctx, prior.size(), [&](float* t) {
+            upk_check(upk_torus_dbn_param_deriv(&ctx->L, &P, coord(), system, t), "torus_dbn param_deriv"); });
+    }
+    size_t param_deriv_size() const override { return prior.size(); }
+    void param_deriv_all(float* dev) override { upk_check(upk_torus_dbn_param_deriv_all(&ctx->L, &P, coord(), dev), "torus_dbn param_deriv_all"); }
+};
+RegisterNodeType<Builtin<TorusDBN>, 1> torus_dbn_node("torus_dbn");
+
+// fixed_hmm: potential = -log Z of the chain over the rows index[r] of its argument, posterior marginals into the argument's sens at
+// index[r] (the reference writes them to row r, which is the same thing for the index = arange its configurations carry; here index
+// must be distinct).  get_param() = transition_energy, row-major.  T = exp(offset - transition_energy) and the offset (the Boltzmann
+// average of the energies, hmm.cpp:63-69) are device values, rewritten in place by set_param.  The forward beliefs of the last pass
+// stay in a scratch buffer; the expected transition counts are computed from them when asked.
+struct FixedHMM : public PotentialNode, BatchedParamDeriv {
+    CoordNode& input; upk_fixed_hmm_t Hm; int n_residue, n_state;
+    vector<float> transition_energy; DevBuf<float> d_T, d_offset, fwd, w; DevBuf<int> d_index;
+    FixedHMM(DeviceCtx* c, hid_t_compat grp, CoordNode& input_) : PotentialNode(c), input(input_) {
+        memset(&Hm, 0, sizeof(Hm));
+        n_residue = (int)dset_size(1, H(grp), "index")[0];
+        const auto dims = dset_size(2, H(grp), "transition_energy");
+        n_state = (int)dims[0];
+        if (n_residue < 1) throw string("fixed_hmm: index is empty (the chain needs at least one residue)");
+        if (dims[0] != dims[1]) throw string("fixed_hmm: transition_energy is ") + to_string(dims[0]) + " x " + to_string(dims[1]) + ", not square";
+        if (n_state < 1 || n_state > upk_fixed_hmm_max_state())
+            throw string("fixed_hmm: ") + to_string(n_state) + " states exceed the device limit (1 <= n_state <= " + to_string(upk_fixed_hmm_max_state()) + ")";
+        if (input.elem_width != n_state)
+            throw string("fixed_hmm: transition_energy has ") + to_string(n_state) + " states but the argument has elem_width " + to_string(input.elem_width);
+        const auto index = read<int>(H(grp), "index", 1);
+        require_injective(index, input.n_elem, "fixed_hmm index");
+        transition_energy = read<float>(H(grp), "transition_energy", 2);
+        d_index.upload(index); d_T.alloc(transition_energy.size()); d_offset.alloc(1);
+        fwd.alloc((size_t)ctx->n_system * n_residue * input.stride);
+        Hm.T = d_T.p; Hm.offset = d_offset.p; Hm.index = d_index.p; Hm.n_residue = n_residue; Hm.n_state = n_state; Hm.row_stride = input.stride;
+        Hm.fwd = fwd.p;
+        upload_transition_matrix();
+    }
+    void upload_transition_matrix() {      // hmm.cpp:63-69, in double
+        double e_min = transition_energy[0];
+        for (float e : transition_energy) e_min = min(e_min, (double)e);
+        double num = 0., den = 0.;
+        for (float e : transition_energy) { const double wgt = exp(e_min - e); num += e * wgt; den += wgt; }
+        const float offset = (float)(num / den);
+        vector<float> T(transition_energy.size());
+        for (size_t i = 0; i < T.size(); ++i) T[i] = (float)exp((double)offset - (double)transition_energy[i]);
+        hip_check(hipStreamSynchronize(ctx->stream), "hipStreamSynchronize");
+        hip_check(hipMemcpy(d_T.p, T.data(), T.size() * sizeof(float), hipMemcpyHostToDevice), "H2D");
+        hip_check(hipMemcpy(d_offset.p, &offset, sizeof(float), hipMemcpyHostToDevice), "H2D");
+    }
+    void compute_value(ComputeMode mode) override {
+        if (ctx->profile) ctx->begin("fixed_hmm:" + name);
+        upk_check(upk_fixed_hmm(&ctx->L, &Hm, input.coord(), mode == PotentialAndDerivMode ? potential_dev.p : nullptr), "fixed_hmm");
+        // energies read twice, beliefs written and read, marginals added (read + write)
+        if (ctx->profile) ctx->end("fixed_hmm:" + name, 4. * ctx->n_system * (double)n_residue * n_state * 6.);
+    }
+    vector<float> get_param() const override { return transition_energy; }
+    void set_param(const vector<float>& p) override {
+        if (p.size() != transition_energy.size())
+            throw string("fixed_hmm expects ") + to_string(transition_energy.size()) + " transition energies (n_state x n_state) but got " + to_string(p.size());
+        transition_energy = p;
+        upload_transition_matrix();
+    }
+    void need_edge_scratch() { if (!w.p) { w.alloc(fwd.n); Hm.w = w.p; } }
+    vector<float> get_param_deriv(int system) override {
+        need_edge_scratch();
+        return param_deriv_table(ctx, transition_energy.size(), [&](float* t) {
+            upk_check(upk_fixed_hmm_param_deriv(&ctx->L, &Hm, input.coord(), system, t), "fixed_hmm param_deriv"); });
+    }
+    size_t param_deriv_size() const override { return transition_energy.size(); }
+    void param_deriv_all(float* dev) override {
+        need_edge_scratch();
+        upk_check(upk_fixed_hmm_param_deriv_all(&ctx->L, &Hm, input.coord(), dev), "fixed_hmm param_deriv_all");
+    }
+};
+RegisterNodeType<Builtin<FixedHMM>, 1> fixed_hmm_node("fixed_hmm");
+
 // What cv_restraint, cv_steer and cv_metadynamics share: a CV definition in the datasets of /input/collective_variables, read and checked on
 // the host by the constructor; the node's type then checks the rest of its group and calls install(), so that nothing touches the
 // device or pos' scatter plan before every host-side check has passed.  v_c is the very number upside_hip_cv_compute reports.
