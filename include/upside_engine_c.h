@@ -345,13 +345,41 @@ int upside_hip_mbar(long long n_sample, int n_state, int d, const float* values,
  *   out: G[M * M] = W^T W (may be NULL: only colsum is computed, a cheap pass), colsum[M] = the column sums of W, D[n_sample] (may be
  *   NULL).  Float64 throughout, no atomics, one summation order: two calls return the same bits, on any machine state -- the slab of
  *   W that is formed at a time depends on M alone (at most 512 MB; W itself is never held).  G is bitwise symmetric.
- * Limits: M <= 8192; the covariance built from G is the asymptotic one and assumes uncorrelated samples (subsample first).
+ * Limits: M <= 8192; the covariance built from G is the asymptotic one and assumes uncorrelated samples
+ * (upside_hip_series_inefficiency below gives the equilibration origin and the stride to subsample a recorded series with).
  * Returns 0, or 1 with upside_hip_last_error set.  Refused before anything is launched or copied: everything upside_hip_mbar refuses
  * about samples, states, counts and periods; n_extra < 0; n_state + n_extra > 8192; colsum or f NULL; log_extra NULL with n_extra > 0;
  * an f that is not finite; a log_extra entry that is NaN or +inf. */
 int upside_hip_mbar_gram(long long n_sample, int n_state, int d, const float* values, const double* energy, const double* beta,
                          const float* rows, const long long* n_k, const double* periods, const double* f, int n_extra,
                          const double* log_extra, double* G, double* colsum, double* D);
+
+/* Statistical inefficiency of recorded series at a set of origins (csrc/kernels_series.hip): what equilibration detection (Chodera
+ * 2016) and subsampling to uncorrelated samples (Chodera et al. 2007) are built on, and what the covariance from upside_hip_mbar_gram
+ * needs of its samples.  No engine is needed; every array is a HOST array; the call runs on a stream of its own on the current
+ * device and returns when it is done.  For series k and origin t0 = origin[j], with Tt = length[k] - t0 and the tail
+ * A_n = a[k * stride + t0 + n]:
+ *   mu = mean(A),  s2 = mean((A - mu)^2)
+ *   C(t) = sum_{n=0}^{Tt-1-t} (A_n - mu)(A_{n+t} - mu) / ((Tt - t) s2)            t = 1, 2, ...
+ *   g = max(1, 1 + 2 sum_{t=1}^{t_stop-1} C(t) (1 - t / Tt))
+ *   t_stop = the first t with (C(t) <= 0 and t > mintime), or t = max_lag + 1, or t = Tt - 1, whichever comes first
+ * -- pymbar's statistical_inefficiency(fast=False): every lag is visited.  The number of effectively uncorrelated samples of the
+ * tail is Tt / g.
+ *   out, each [n_series][n_origin]: g, stop_lag = t_stop, and (either may be NULL) mean = mu and variance = s2.
+ *   A tail with Tt < UPK_SERIES_MIN_TAIL = 16 (also an origin at or past the series' end) has no estimate: g = 0, stop_lag = -1
+ *   (mean and variance are those of what there is, 0 for nothing).  A tail with s2 == 0 returns g = 1, stop_lag = 0.  Neither is an
+ *   error and neither writes a NaN.
+ * The mean is taken off before any product is formed (first the series' first value, then the mean of the rest: a series at 1e6
+ * with unit scatter loses nothing and a constant series is exactly 0).  Float64 throughout, no atomics, one summation order: two
+ * calls return the same bits, and a series' result depends neither on n_series nor on its place among the series.  All origins of
+ * a series share one pass over the lagged products (v_mfma_f64_16x16x4_f64 tiles), so the cost is n_series x length x lags.
+ * Returns 0, or 1 with upside_hip_last_error set.  Refused before anything is launched or copied: n_series < 1; n_origin < 1;
+ * mintime < 1; max_lag < 1; a, length, origin, g or stop_lag NULL; n_series x stride not below 2^40; an origin that is negative or
+ * not above the one before it; a length below 1 or above stride; an entry of a series that is not finite.  Without a HIP device the
+ * call fails like every other (no CPU path).  It reads no environment switch. */
+int upside_hip_series_inefficiency(int n_series, long long stride, const long long* length, const double* a, int n_origin,
+                                   const long long* origin, int mintime, long long max_lag, double* g, long long* stop_lag, double* mean,
+                                   double* variance);
 
 /* Per-kernel timing hooks used by bench.py.  With profiling enabled every interaction-graph / BP kernel
  * launch is bracketed by HIP events on the engine's stream.  upside_hip_profile_dump writes one text line per

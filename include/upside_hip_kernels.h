@@ -674,6 +674,31 @@ typedef struct {
 } upk_mbar_gram_problem_t;
 int upk_mbar_gram_solve(const upk_mbar_gram_problem_t* P, char* message /* host */, int message_len);
 
+/* ---- statistical inefficiency of recorded series (upside_hip_series_inefficiency), csrc/kernels_series.hip ----------------------------
+ * upk_series_solve is the HOST side of upside_hip_series_inefficiency (include/upside_engine_c.h states the definition and the
+ * refusals): every pointer is a host pointer; the checks come before any device call; 0, or 1 with the reason in message.  The
+ * series are centred once on the device, the lagged products of all origins come from one pass of v_mfma_f64_16x16x4_f64 tiles over
+ * pieces of at most UPK_SERIES_PIECE samples, in blocks of UPK_SERIES_LAG_BLOCK lags, one launch per block over the series that are
+ * not finished.  fp64, no atomics, one summation order.  A tail shorter than UPK_SERIES_MIN_TAIL has no estimate (g = 0,
+ * stop_lag = -1).  stats (may be NULL) receives [0] the device time in ms between HIP events around the kernels (copies of the series
+ * excluded), [1] the wall time in ms of the whole call after its checks, [2] the lag blocks launched, [3] the sum over them of the
+ * unfinished series, [4] the v_mfma_f64_16x16x4_f64 instructions issued per wave summed over waves (2048 flop each). */
+#define UPK_SERIES_MIN_TAIL 16
+#define UPK_SERIES_LAG_BLOCK 128
+#define UPK_SERIES_PIECE 2048
+typedef struct {
+    int n_series; long long stride;
+    const long long* length;                                      /* host [n_series] */
+    const double* a;                                              /* host, series k at a[k * stride .. k * stride + length[k]) */
+    int n_origin; const long long* origin;                        /* host [n_origin], ascending */
+    int mintime; long long max_lag;
+    double* g; long long* stop_lag; double *mean, *variance;      /* host out [n_series][n_origin]; mean, variance may be NULL */
+    double* stats;                                                /* host out [5] or NULL */
+} upk_series_problem_t;
+int upk_series_solve(const upk_series_problem_t* P, char* message /* host */, int message_len);
+int upk_series_lag_block(void);     /* UPK_SERIES_LAG_BLOCK and UPK_SERIES_PIECE of the library that was built */
+int upk_series_piece(void);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,14 +1,17 @@
 """MBAR over the output files of an umbrella ladder run by `upside_hip`, on the GPU.
 
-    python tools/umbrella_mbar.py --temperature 0.85 [--node cv_restraint] [--bins 40] [--tol 1e-8] [--solver newton] [--uncertainty] w00.up ...
+    python tools/umbrella_mbar.py --temperature 0.85 [--node cv_restraint] [--bins 40] [--tol 1e-8] [--solver newton] [--uncertainty] [--decorrelate] w00.up ...
 
 Every file is one window: its `cv_restraint` node (`--node`) holds the window's centre, spring constant and flat width, and its
 /output/cv holds the CV series the run recorded at the frames (the CVs of /input/collective_variables; samples follow the window,
 as /output does).  The node's CVs are found among the recorded ones by name; a CV of the node that was not recorded is an error that
 names it.  Prints the free energy f_k of every window (in kT, f_0 = 0) and the unbiased free-energy profile along the node's first
 CV (in energy units, lowest bin 0; `inf` where no sample fell).  `--uncertainty` adds the asymptotic standard deviation of
-f_k - f_0 and a dF column to the profile (relative to the lowest bin; the frames are taken as uncorrelated, so `--skip`/subsample to
-the correlation time first); `--solver newton` converges a poorly overlapping ladder in a few steps."""
+f_k - f_0 and a dF column to the profile (relative to the lowest bin; the frames are taken as uncorrelated, so give `--decorrelate`
+for frames written more often than the correlation time; the covariance is the asymptotic one); `--solver newton` converges a
+poorly overlapping ladder in a few steps.  `--decorrelate` drops the start of every window up to the detected equilibration origin
+t0 and keeps every ceil(g)-th frame of the rest, g the statistical inefficiency of the window's own reduced bias
+(timeseries.detect_equilibration on the GPU); it prints one line per window (t0, g, frames kept) before the free energies."""
 import argparse
 import os
 import sys
@@ -41,6 +44,23 @@ def read_window(h5lite, config, path, node):
     return series.reshape(series.shape[0], -1), recorded, names, row, periods
 
 
+def decorrelate(pkg, values, rows, periods, kT):
+    """the kept frames of every window; prints one line per window"""
+    T = max(len(v) for v in values)
+    bias = np.zeros((len(values), T))
+    for k, v in enumerate(values):
+        bias[k, :len(v)] = pkg.mbar.own_state_reduced_bias(v, 1. / kT, rows[k][None, :], periods, np.zeros(len(v), 'i8'))
+    lengths = np.array([len(v) for v in values], 'i8')
+    t0, g, n_eff = pkg.timeseries.detect_equilibration(bias, lengths=lengths)
+    print('# window  equilibrated from t0  statistical inefficiency g  frames kept of')
+    out = []
+    for k, v in enumerate(values):
+        keep = pkg.timeseries.subsample_indices(len(v), t0[k], g[k])
+        print('#%4d  %8d  %12.4f  %7d  %7d' % (k, t0[k], g[k], len(keep), len(v)))
+        out.append(v[keep])
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('files', nargs='+')
@@ -52,6 +72,7 @@ def main():
     ap.add_argument('--max-iter', type=int, default=10000)
     ap.add_argument('--solver', choices=('self-consistent', 'newton'), default='self-consistent')
     ap.add_argument('--uncertainty', action='store_true', help='print the standard deviation of f_k - f_0 and a dF column of the profile')
+    ap.add_argument('--decorrelate', action='store_true', help='detect equilibration and subsample every window to uncorrelated frames first')
     args = ap.parse_args()
     pkg = load_package()
     values, rows, n_k, names0, periods0 = [], [], [], None, None
@@ -67,6 +88,9 @@ def main():
         v = series[args.skip:, [recorded.index(nm) for nm in names]]
         values.append(v); rows.append(row); n_k.append(len(v))
     kT = args.temperature
+    if args.decorrelate:
+        values = decorrelate(pkg, values, rows, periods0, kT)
+        n_k = [len(v) for v in values]
     v = np.concatenate(values)
     problem = (v, None, 1. / kT, np.stack(rows), np.array(n_k, 'i8'))
     r = pkg.mbar.mbar(*problem, periods0, args.tol, args.max_iter, target=(1. / kT, None), solver=args.solver)

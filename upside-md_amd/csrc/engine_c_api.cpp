@@ -73,6 +73,19 @@ extern "C" int upside_hip_mbar_gram(long long n_sample, int n_state, int d, cons
     return 0;
     API_CATCH(1)
 }
+// statistical inefficiency of recorded series: the checks and the staging are upk_series_solve (kernels_series.hip)
+extern "C" int upside_hip_series_inefficiency(int n_series, long long stride, const long long* length, const double* a, int n_origin,
+                                              const long long* origin, int mintime, long long max_lag, double* g, long long* stop_lag,
+                                              double* mean, double* variance) {
+    API_TRY
+    upk_series_problem_t P{};
+    P.n_series = n_series; P.stride = stride; P.length = length; P.a = a; P.n_origin = n_origin; P.origin = origin; P.mintime = mintime;
+    P.max_lag = max_lag; P.g = g; P.stop_lag = stop_lag; P.mean = mean; P.variance = variance;
+    char msg[256];
+    if (upk_series_solve(&P, msg, (int)sizeof(msg))) throw string(msg);
+    return 0;
+    API_CATCH(1)
+}
 
 // ---- construction ----------------------------------------------------------------------------------
 extern "C" int upside_hip_set_device(int device) {

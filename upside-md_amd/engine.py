@@ -495,7 +495,7 @@ class Ensemble(object):
         return out
 
     def umbrella_mbar(self, node_name, kT, tol=1e-8, max_iter=10000, f0=None, target=None, series=None, solver='self-consistent',
-                      n_sc=10, uncertainty=False):
+                      n_sc=10, uncertainty=False, decorrelate=False):
         """MBAR over the umbrella ladder of the cv_restraint node `node_name` from the recorded CV series (mbar.mbar on the device):
         system s is window s with its own row [center | spring_const | flat_width] (get_param of system s) and beta = 1 / kT for all
         (one temperature: the unbiased potential cancels and is not needed).  series: (n_stored, n_system, n_cv) as read_cvs gives it,
@@ -505,7 +505,12 @@ class Ensemble(object):
         mbar.mbar with values (N, d), rows (n_system, 3 d), periods (d,), n_k and names added; with a target, log_w feeds
         config.mbar_profile.  solver, n_sc: as mbar.mbar ('newton' for a ladder that converges slowly).  uncertainty=True adds sigma
         (n_system, n_system), the asymptotic standard deviation of f_i - f_j (mbar.free_energy_uncertainty: the samples are taken as
-        uncorrelated, so record or pass a series subsampled to its correlation time)."""
+        uncorrelated, so pass decorrelate=True for a series recorded more often than its correlation time; the covariance remains the
+        asymptotic one).  decorrelate=True: per window, the series of its own-state reduced bias (mbar.own_state_reduced_bias) goes
+        through timeseries.detect_equilibration on the device, the samples before the detected origin t0 are dropped and every
+        ceil(g)-th of the rest is kept (timeseries.subsample_indices); MBAR and the uncertainty then run on the kept samples, window
+        after window, with their unequal counts n_k, and t0, g, n_eff (each (n_system,)) and kept (the kept sample indices per
+        window) are added to the result.  decorrelate=False changes nothing."""
         from . import config, mbar as _mbar
         if not (np.ndim(kT) == 0 and np.isfinite(kT) and kT > 0):
             raise ValueError('umbrella_mbar: kT must be one finite positive number (one temperature for every window)')
@@ -533,6 +538,17 @@ class Ensemble(object):
         values = np.ascontiguousarray(series[:, :, cols].reshape(-1, d))
         n_k = np.full(self.n_system, series.shape[0], 'i8')
         beta = 1. / float(kT)
+        extra = {}
+        if decorrelate:
+            from . import timeseries as _ts
+            per_window = np.ascontiguousarray(series[:, :, cols].transpose(1, 0, 2))      # (n_system, n_stored, d)
+            state = np.repeat(np.arange(self.n_system), series.shape[0])
+            bias = _mbar.own_state_reduced_bias(per_window.reshape(-1, d), beta, rows, periods, state).reshape(self.n_system, -1)
+            t0, g, n_eff = _ts.detect_equilibration(bias, library=self.lib)
+            kept = [_ts.subsample_indices(series.shape[0], t0[s], g[s]) for s in range(self.n_system)]
+            values = np.ascontiguousarray(np.concatenate([per_window[s][kept[s]] for s in range(self.n_system)]))
+            n_k = np.array([len(k) for k in kept], 'i8')
+            extra = dict(t0=t0, g=g, n_eff=n_eff, kept=kept)
         if isinstance(target, str):
             if target != 'unbiased':
                 raise ValueError("umbrella_mbar: target must be None, 'unbiased' or a row")
@@ -542,7 +558,7 @@ class Ensemble(object):
         out = _mbar.mbar(values, None, beta, rows, n_k, periods, tol, max_iter, f0=f0, target=tgt, library=self.lib, solver=solver, n_sc=n_sc)
         if uncertainty:
             out['sigma'] = _mbar.free_energy_uncertainty(values, None, beta, rows, n_k, out['f'], periods, library=self.lib)
-        out.update(values=values, rows=rows, periods=periods, n_k=n_k, names=names)
+        out.update(values=values, rows=rows, periods=periods, n_k=n_k, names=names, **extra)
         return out
 
     # -- cv_metadynamics: the hills of a node (they live on the device; deposition happens inside run_rounds / run_steps) -----

@@ -3,7 +3,8 @@ csrc/kernels_mbar.hip, csrc/kernels_mbar_gram.hip): free energies of umbrella wi
 ladders from recorded energies, by self-consistent iteration or with Newton steps; their asymptotic uncertainties, and averages and
 profiles in a target state with error bars, from the Gram matrix of the weight matrix (Shirts & Chodera 2008, eq. D8/D9).
 Limits of the uncertainties: at most 8192 columns (states + target + observables or bins); the covariance is the asymptotic one; the
-samples are taken as uncorrelated, so subsample a correlated series first."""
+samples are taken as uncorrelated: timeseries.py finds the equilibration origin and the statistical inefficiency of a recorded series
+on the device, and Ensemble.umbrella_mbar(decorrelate=True) applies them per window (own_state_reduced_bias is the observable)."""
 import ctypes as ct
 import numpy as np
 
@@ -59,6 +60,33 @@ def _problem(values, energy, beta, rows, n_k, periods):
     if len(per) != d:
         raise ValueError('mbar: %d periods for %d CVs' % (len(per), d))
     return v, e, b, r, n_k, per
+
+
+def own_state_reduced_bias(values, beta, rows, periods, state_of_sample):
+    """(N,) float64 numpy: the reduced bias of every sample in the state it was drawn from,
+        beta_k sum_c 1/2 spring_const_kc max(0, |wrap_c(values[n][c] - center_kc)| - flat_width_kc)^2,   k = state_of_sample[n],
+    the u_k(n) of upside_hip_mbar without the energy term, CVs added in ascending order.  This is the observable whose correlation
+    matters for a window: timeseries.detect_equilibration on it gives the window's t0 and g.  values (N, d) or (N,), beta (K,) or a
+    scalar, rows (K, 3 d) = [center | spring_const | flat_width], periods (d,) or None (none periodic), state_of_sample (N,) ints."""
+    v = np.asarray(values, 'f8')
+    if v.ndim == 1:
+        v = v[:, None]
+    N, d = v.shape
+    r = np.asarray(rows, 'f8').reshape(-1, 3 * d)
+    K = len(r)
+    k = np.asarray(state_of_sample).reshape(-1).astype('i8')
+    if len(k) != N or (len(k) and (k.min() < 0 or k.max() >= K)):
+        raise ValueError('mbar.own_state_reduced_bias: state_of_sample must hold %d entries in 0 .. %d' % (N, K - 1))
+    b = np.broadcast_to(np.asarray(beta, 'f8'), (K,))
+    per = np.zeros(d) if periods is None else np.asarray(periods, 'f8').reshape(-1)
+    total = np.zeros(N)
+    for c in range(d):
+        x = v[:, c] - r[k, c]
+        if per[c] > 0:
+            x = x - per[c] * np.rint(x / per[c])
+        u = np.maximum(0., np.abs(x) - r[k, 2 * d + c])
+        total = total + 0.5 * r[k, d + c] * u * u
+    return b[k] * total
 
 
 def mbar(values, energy, beta, rows, n_k, periods=None, tol=1e-8, max_iter=10000, f0=None, target=None, want_denominators=True,
