@@ -345,14 +345,51 @@ int upside_hip_mbar(long long n_sample, int n_state, int d, const float* values,
  *   out: G[M * M] = W^T W (may be NULL: only colsum is computed, a cheap pass), colsum[M] = the column sums of W, D[n_sample] (may be
  *   NULL).  Float64 throughout, no atomics, one summation order: two calls return the same bits, on any machine state -- the slab of
  *   W that is formed at a time depends on M alone (at most 512 MB; W itself is never held).  G is bitwise symmetric.
- * Limits: M <= 8192; the covariance built from G is the asymptotic one and assumes uncorrelated samples
- * (upside_hip_series_inefficiency below gives the equilibration origin and the stride to subsample a recorded series with).
+ * Limits: M <= 8192; the covariance built from G is a large-sample estimate (upside_hip_mbar_bootstrap below gives bootstrap replicates
+ * where few samples are kept) and assumes uncorrelated samples (upside_hip_series_inefficiency below gives the equilibration origin
+ * and the stride to subsample a recorded series with).
  * Returns 0, or 1 with upside_hip_last_error set.  Refused before anything is launched or copied: everything upside_hip_mbar refuses
  * about samples, states, counts and periods; n_extra < 0; n_state + n_extra > 8192; colsum or f NULL; log_extra NULL with n_extra > 0;
  * an f that is not finite; a log_extra entry that is NaN or +inf. */
 int upside_hip_mbar_gram(long long n_sample, int n_state, int d, const float* values, const double* energy, const double* beta,
                          const float* rows, const long long* n_k, const double* periods, const double* f, int n_extra,
                          const double* log_extra, double* G, double* colsum, double* D);
+
+/* Bootstrap replicates of an MBAR problem, solved together in one batch on the device (csrc/kernels_mbar_boot.hip): what bootstrap
+ * error bars of free energies, averages and profiles are formed from where the asymptotic covariance of upside_hip_mbar_gram is not
+ * trusted (few samples per state after decorrelation, poorly overlapping neighbours).  The samples, the states, periods and u_k(n)
+ * are those of upside_hip_mbar.  New inputs:
+ *   state_of_sample[n]: the state that sample n was drawn from.
+ *   counts[b][n]: an unsigned 16-bit count for replicate b = 0 .. n_replicate - 1 and sample n, with
+ *     sum_{n : state_of_sample[n] = k} counts[b][n] = n_k[k] for every b and k -- the stratified bootstrap: each state keeps its
+ *     sample count.
+ * Per replicate, one iteration from f_b is
+ *   D_b(n)   = logsumexp_{l : n_k[l] > 0} (ln n_k[l] + f_{b,l} - u_l(n))
+ *   f'_{b,k} = -logsumexp_{n : c_b(n) > 0} (ln c_b(n) - u_k(n) - D_b(n)),   then f'_b -= f'_{b,0}
+ * Every replicate starts from f0 (the full-sample solution; NULL = 0) and stops when max_k |f' - f| < tol or after max_iter iterations
+ * (tol = 0: exactly max_iter).  All replicates iterate together; one that has stopped leaves the grid; the host synchronises once per
+ * iteration for the whole batch; the samples are copied once.
+ *   columns (n_column >= 0): log_numerator[j][n] carries a target state, an observable or a profile bin WITHOUT D (D differs per
+ *     replicate), -inf = weight 0; at the returned f_b
+ *       column_boot[b][j] = -logsumexp_{n : c_b(n) > 0} (ln c_b(n) + log_numerator[j][n] - D_b(n)),
+ *     +inf for a column with no contributing sample in replicate b (that replicate only).
+ *   out: f_boot[n_replicate][n_state]; column_boot[n_replicate][n_column]; n_iter[n_replicate] and last_delta[n_replicate] (either may
+ *     be NULL).
+ * Float64 throughout; every logsumexp takes its exact maximum first; no atomics; every sum has one order.  The bits of replicate b
+ * depend neither on n_replicate, nor on which other replicates are in the batch, nor on when they converge, nor on how the batch is
+ * cut into chunks (the denominators of a chunk fill at most 512 MB: 512 MB / (8 n_sample) replicates are solved at a time).
+ * Bootstrapping correlated samples underestimates the errors as the asymptotic estimate does: subsample first
+ * (upside_hip_series_inefficiency).
+ * Returns 0, or 1 with upside_hip_last_error set.  Refused before anything is launched or copied: everything upside_hip_mbar refuses
+ * about samples, states, counts n_k, periods, tol, max_iter and f0; f_boot NULL; n_replicate < 1; counts or state_of_sample NULL; a
+ * state index outside 0 .. n_state - 1 or naming a state with n_k = 0; origins that do not add up to n_k; a replicate whose counts of
+ * some state do not add up to n_k (the message names the replicate and the state); n_column < 0; n_column > 0 without log_numerator
+ * and column_boot; a log_numerator entry that is NaN or +inf; n_sample above 2^26 (not one replicate's denominators fit 512 MB).
+ * Without a HIP device the call fails like every other (no CPU path).  It reads no environment switch. */
+int upside_hip_mbar_bootstrap(long long n_sample, int n_state, int d, const float* values, const double* energy, const double* beta,
+                              const float* rows, const long long* n_k, const double* periods, const int* state_of_sample,
+                              int n_replicate, const unsigned short* counts, double tol, int max_iter, const double* f0, int n_column,
+                              const double* log_numerator, double* f_boot, double* column_boot, int* n_iter, double* last_delta);
 
 /* Statistical inefficiency of recorded series at a set of origins (csrc/kernels_series.hip): what equilibration detection (Chodera
  * 2016) and subsampling to uncorrelated samples (Chodera et al. 2007) are built on, and what the covariance from upside_hip_mbar_gram

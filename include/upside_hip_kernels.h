@@ -674,6 +674,55 @@ typedef struct {
 } upk_mbar_gram_problem_t;
 int upk_mbar_gram_solve(const upk_mbar_gram_problem_t* P, char* message /* host */, int message_len);
 
+/* ---- the MBAR bootstrap (upside_hip_mbar_bootstrap), csrc/kernels_mbar_boot.hip --------------------------------------------------------
+ * Replicates of one MBAR problem (S, X as above), replicate b weighting sample i by the unsigned 16-bit count counts[b * n + i], solved
+ * together; include/upside_engine_c.h states the definitions.  The replicates are the second axis of every grid: active[slot] is the
+ * replicate that slot = blockIdx.y serves (n_active of them, at most UPK_MBAR_BOOT_MAX_CHUNK), so a converged replicate leaves the
+ * grid and nothing is moved.  a, f: [replicate][n_state]; denom, f_new, delta: [slot]...; every pointer but S and X is a device
+ * pointer.  fp64, exact maxima, no atomics, one order per sum, and no workgroup reads what another replicate's workgroups wrote: the bits of a
+ * replicate depend neither on n_active nor on the other replicates.  The launchers return the launch's hipError_t or 941x for
+ * arguments they cannot run.
+ *   _log_counts:   log_count[c] = ln c for c = 0 .. 65535 (-inf at 0): the table the two passes below read.
+ *   _denominator:  denom[slot * n + i] = logsumexp over the states with a[b][l] > -inf of a[b][l] - u_l(i), b = active[slot].
+ *   _free_energy:  f_new[slot * n_state + k] = -logsumexp_{i : c_b(i) > 0} (ln c_b(i) - u_k(i) - denom[slot * n + i]); one workgroup per
+ *                  UPK_MBAR_FE_TILE states of one replicate, lane t takes samples t, t + 256, ... ascending.
+ *   _update:       for b = active[slot]: f[b] = f_new[slot] - f_new[slot][0], a[b] = ln_n + f[b] (ln_n[k] = ln N_k, -inf for N_k = 0),
+ *                  delta[slot] = max_k |f[b][k] - its value before| (a NaN is kept).
+ *   _columns:      column[b * n_column + j] = -logsumexp_{i : c_b(i) > 0} (ln c_b(i) + log_numerator[j * n + i] - denom[slot * n + i]),
+ *                  -inf entries skipped, +inf where nothing contributes.
+ * upk_mbar_boot_chunk: the replicates whose denominators fit workspace_bytes, workspace_bytes / (8 n_sample), at most
+ * UPK_MBAR_BOOT_MAX_CHUNK; 0: not even one.
+ * upk_mbar_boot_solve is the HOST side of upside_hip_mbar_bootstrap (which states the refusals): host pointers, the checks before any
+ * device call, one copy of the samples, chunks of upk_mbar_boot_chunk(n_sample, workspace_bytes) replicates each run to convergence
+ * with one synchronisation per iteration; workspace_bytes = 0 means UPK_MBAR_GRAM_MAX_WORKSPACE, more than that is refused.  0, or 1
+ * with the reason in message. */
+#define UPK_MBAR_BOOT_MAX_CHUNK 32768
+int upk_mbar_boot_log_counts(void* stream, double* log_count /* [65536] */);
+int upk_mbar_boot_denominator(void* stream, const upk_mbar_states_t* S, const upk_mbar_samples_t* X, const double* a, const int* active,
+                              int n_active, double* denom);
+int upk_mbar_boot_free_energy(void* stream, const upk_mbar_states_t* S, const upk_mbar_samples_t* X, const unsigned short* counts,
+                              const double* log_count, const int* active, int n_active, const double* denom, double* f_new);
+int upk_mbar_boot_update(void* stream, int n_state, const double* ln_n, const int* active, int n_active, const double* f_new, double* f,
+                         double* a, double* delta);
+int upk_mbar_boot_columns(void* stream, long long n_sample, const unsigned short* counts, const double* log_count, const int* active,
+                          int n_active, const double* denom, int n_column, const double* log_numerator, double* column);
+long long upk_mbar_boot_chunk(long long n_sample, size_t workspace_bytes);
+typedef struct {
+    long long n_sample; int n_state, d;
+    const float* values; const double* energy;                    /* host, as in upk_mbar_problem_t */
+    const double* beta; const float* rows; const long long* n_k;
+    const double* periods;
+    const int* state_of_sample;                                   /* host [n_sample] */
+    int n_replicate; const unsigned short* counts;                /* host [n_replicate][n_sample] */
+    double tol; int max_iter;
+    const double* f0;                                             /* host [n_state] or NULL = 0 */
+    int n_column; const double* log_numerator;                    /* host [n_column][n_sample]; -inf allowed, NaN and +inf refused */
+    size_t workspace_bytes;                                       /* of the denominators; 0 = UPK_MBAR_GRAM_MAX_WORKSPACE */
+    double *f_boot, *column_boot;                                 /* host out [n_replicate][n_state], [n_replicate][n_column] */
+    int* n_iter; double* last_delta;                              /* host out [n_replicate], either may be NULL */
+} upk_mbar_boot_problem_t;
+int upk_mbar_boot_solve(const upk_mbar_boot_problem_t* P, char* message /* host */, int message_len);
+
 /* ---- statistical inefficiency of recorded series (upside_hip_series_inefficiency), csrc/kernels_series.hip ----------------------------
  * upk_series_solve is the HOST side of upside_hip_series_inefficiency (include/upside_engine_c.h states the definition and the
  * refusals): every pointer is a host pointer; the checks come before any device call; 0, or 1 with the reason in message.  The

@@ -1,6 +1,6 @@
 """MBAR over the output files of an umbrella ladder run by `upside_hip`, on the GPU.
 
-    python tools/umbrella_mbar.py --temperature 0.85 [--node cv_restraint] [--bins 40] [--tol 1e-8] [--solver newton] [--uncertainty] [--decorrelate] w00.up ...
+    python tools/umbrella_mbar.py --temperature 0.85 [--node cv_restraint] [--bins 40] [--tol 1e-8] [--solver newton] [--uncertainty] [--decorrelate] [--bootstrap B [--seed S]] w00.up ...
 
 Every file is one window: its `cv_restraint` node (`--node`) holds the window's centre, spring constant and flat width, and its
 /output/cv holds the CV series the run recorded at the frames (the CVs of /input/collective_variables; samples follow the window,
@@ -8,8 +8,11 @@ as /output does).  The node's CVs are found among the recorded ones by name; a C
 names it.  Prints the free energy f_k of every window (in kT, f_0 = 0) and the unbiased free-energy profile along the node's first
 CV (in energy units, lowest bin 0; `inf` where no sample fell).  `--uncertainty` adds the asymptotic standard deviation of
 f_k - f_0 and a dF column to the profile (relative to the lowest bin; the frames are taken as uncorrelated, so give `--decorrelate`
-for frames written more often than the correlation time; the covariance is the asymptotic one); `--solver newton` converges a
-poorly overlapping ladder in a few steps.  `--decorrelate` drops the start of every window up to the detected equilibration origin
+for frames written more often than the correlation time; it is a large-sample estimate); `--bootstrap B` prints the BOOTSTRAP standard
+deviation of f_k - f_0 and of the profile from B stratified resamples (every window keeps its frame count; `--seed` seeds the draw),
+all solved in one batch on the GPU -- beside the asymptotic one with `--uncertainty`, in its place without; bootstrapping correlated
+frames underestimates the errors, so `--decorrelate` goes with it; `--solver newton` converges a poorly overlapping ladder in a few
+steps.  `--decorrelate` drops the start of every window up to the detected equilibration origin
 t0 and keeps every ceil(g)-th frame of the rest, g the statistical inefficiency of the window's own reduced bias
 (timeseries.detect_equilibration on the GPU); it prints one line per window (t0, g, frames kept) before the free energies."""
 import argparse
@@ -73,6 +76,8 @@ def main():
     ap.add_argument('--solver', choices=('self-consistent', 'newton'), default='self-consistent')
     ap.add_argument('--uncertainty', action='store_true', help='print the standard deviation of f_k - f_0 and a dF column of the profile')
     ap.add_argument('--decorrelate', action='store_true', help='detect equilibration and subsample every window to uncorrelated frames first')
+    ap.add_argument('--bootstrap', type=int, default=0, metavar='B', help='print bootstrap standard deviations from B stratified resamples')
+    ap.add_argument('--seed', type=int, default=0, help='the seed of the bootstrap resamples')
     args = ap.parse_args()
     pkg = load_package()
     values, rows, n_k, names0, periods0 = [], [], [], None, None
@@ -97,9 +102,20 @@ def main():
     print('# %d windows, %d samples, CVs %s; %d iterations%s, last max |df| = %.3e' %
           (len(rows), len(v), names0, r['n_iter'], ' and %d Newton steps' % r['n_newton'] if 'n_newton' in r else '', r['last_delta']))
     sigma = pkg.mbar.free_energy_uncertainty(*problem, r['f'], periods0) if args.uncertainty else None
-    print('# window  centre(%s)  samples  f_k / kT%s' % (names0[0], '  sigma(f_k - f_0)' if args.uncertainty else ''))
+    sigma_boot, counts = None, None
+    if args.bootstrap > 0:      # the windows are concatenated, so the samples are grouped by window: the default origins
+        import warnings
+        boot = pkg.mbar.bootstrap(*problem, r['f'], n_bootstrap=args.bootstrap, seed=args.seed, periods=periods0, tol=args.tol, max_iter=args.max_iter)
+        counts = boot['counts']
+        with warnings.catch_warnings():
+            warnings.simplefilter('ignore', RuntimeWarning)
+            sigma_boot = pkg.mbar.bootstrap_sigma(boot)
+        print('# bootstrap: %d replicates (seed %d), %d converged, %d .. %d iterations' %
+              (args.bootstrap, args.seed, int(boot['converged'].sum()), boot['n_iter'].min(), boot['n_iter'].max()))
+    print('# window  centre(%s)  samples  f_k / kT%s%s' % (names0[0], '  sigma(f_k - f_0)' if args.uncertainty else '', '  bootstrap sigma(f_k - f_0)' if args.bootstrap > 0 else ''))
     for k, (row, n) in enumerate(zip(rows, n_k)):
-        print('%4d  %12.6g  %7d  %14.8f%s' % (k, row[0], n, r['f'][k], '  %12.6f' % sigma[k, 0] if args.uncertainty else ''))
+        print('%4d  %12.6g  %7d  %14.8f%s%s' % (k, row[0], n, r['f'][k], '  %12.6f' % sigma[k, 0] if args.uncertainty else '',
+                                               '  %12.6f' % sigma_boot[k, 0] if args.bootstrap > 0 else ''))
     x = v[:, 0].astype('f8')
     if periods0[0] > 0:
         edges = np.linspace(-0.5 * periods0[0], 0.5 * periods0[0], args.bins + 1)
@@ -110,10 +126,15 @@ def main():
         prof, dF = pkg.mbar.profile(*problem, r['f'], edges, kT, period=periods0[0], target=(1. / kT, None), periods=periods0, cv=0)
     else:
         prof = pkg.config.mbar_profile(x, r['log_w'], edges, kT, period=periods0[0])
+    dF_boot = None
+    if args.bootstrap > 0:
+        _, dF_boot = pkg.mbar.profile_bootstrap(*problem, r['f'], edges, kT, period=periods0[0], target=(1. / kT, None), periods=periods0, cv=0, counts=counts,
+                                                tol=args.tol, max_iter=args.max_iter)
     prof = prof - prof[np.isfinite(prof)].min()
-    print('# unbiased profile along %s: bin centre, F%s' % (names0[0], ', dF' if args.uncertainty else ''))
+    print('# unbiased profile along %s: bin centre, F%s%s' % (names0[0], ', dF' if args.uncertainty else '', ', bootstrap dF' if args.bootstrap > 0 else ''))
     for b in range(args.bins):
-        print('%12.6g  %12.6f%s' % (0.5 * (edges[b] + edges[b + 1]), prof[b], '  %12.6f' % dF[b] if args.uncertainty else ''))
+        print('%12.6g  %12.6f%s%s' % (0.5 * (edges[b] + edges[b + 1]), prof[b], '  %12.6f' % dF[b] if args.uncertainty else '',
+                                     '  %12.6f' % dF_boot[b] if args.bootstrap > 0 else ''))
 
 
 if __name__ == '__main__':

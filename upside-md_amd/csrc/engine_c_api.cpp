@@ -73,6 +73,22 @@ extern "C" int upside_hip_mbar_gram(long long n_sample, int n_state, int d, cons
     return 0;
     API_CATCH(1)
 }
+// bootstrap replicates of MBAR in one batch: the checks, the staging and the iteration are upk_mbar_boot_solve (kernels_mbar_boot.hip)
+extern "C" int upside_hip_mbar_bootstrap(long long n_sample, int n_state, int d, const float* values, const double* energy, const double* beta,
+                                         const float* rows, const long long* n_k, const double* periods, const int* state_of_sample,
+                                         int n_replicate, const unsigned short* counts, double tol, int max_iter, const double* f0, int n_column,
+                                         const double* log_numerator, double* f_boot, double* column_boot, int* n_iter, double* last_delta) {
+    API_TRY
+    upk_mbar_boot_problem_t P{};
+    P.n_sample = n_sample; P.n_state = n_state; P.d = d; P.values = values; P.energy = energy; P.beta = beta; P.rows = rows; P.n_k = n_k;
+    P.periods = periods; P.state_of_sample = state_of_sample; P.n_replicate = n_replicate; P.counts = counts; P.tol = tol; P.max_iter = max_iter;
+    P.f0 = f0; P.n_column = n_column; P.log_numerator = log_numerator; P.f_boot = f_boot; P.column_boot = column_boot; P.n_iter = n_iter;
+    P.last_delta = last_delta;
+    char msg[256];
+    if (upk_mbar_boot_solve(&P, msg, (int)sizeof(msg))) throw string(msg);
+    return 0;
+    API_CATCH(1)
+}
 // statistical inefficiency of recorded series: the checks and the staging are upk_series_solve (kernels_series.hip)
 extern "C" int upside_hip_series_inefficiency(int n_series, long long stride, const long long* length, const double* a, int n_origin,
                                               const long long* origin, int mintime, long long max_lag, double* g, long long* stop_lag,

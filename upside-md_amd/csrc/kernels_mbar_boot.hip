@@ -1,0 +1,385 @@
+// gfx950 kernels and host driver of the MBAR bootstrap (upside_hip_mbar_bootstrap): B replicates of one MBAR problem, replicate b
+// weighting sample n by an unsigned 16-bit count c_b(n) (a stratified resample: per state of origin the counts add up to N_k), solved
+// together.  Per replicate, one self-consistent iteration from f_b is
+//     D_b(n)   = logsumexp_{l : N_l > 0} (ln N_l + f_{b,l} - u_l(n))                      k_mbar_boot_denominator
+//     f'_{b,k} = -logsumexp_{n : c_b(n) > 0} (ln c_b(n) - u_k(n) - D_b(n)),  every k      k_mbar_boot_free_energy
+//     f'_b     = f'_b - f'_{b,0},  delta_b = max_k |f'_{b,k} - f_{b,k}|                    k_mbar_boot_update
+// with u_k(n) of kernels_mbar.hip (mbar_energy of mbar_device.h).  The arithmetic is that file's: fp64, every logsumexp takes its exact
+// maximum first, no atomics, one order per sum.  The replicates share the samples and the states and nothing else, so they are the
+// second axis of every grid:
+//   - an array active[] maps blockIdx.y ("slot") to a replicate of the chunk; a replicate that has converged leaves the array, nothing
+//     is moved, and its f and a = ln N + f stay as its last iteration left them;
+//   - k_mbar_boot_denominator is the pass of k_mbar_denominator with a[b][.] staged per replicate; it writes D[slot][n];
+//   - k_mbar_boot_free_energy is the pass of k_mbar_free_energy: a workgroup owns UPK_MBAR_FE_TILE states of ONE replicate, lane t takes
+//     samples t, t + 256, ... ascending, reads c_b(n) (consecutive uint16 of consecutive lanes) and skips c = 0; ln c comes from a table
+//     of 65536 doubles that k_mbar_boot_log_counts fills once per call (an fp64 logarithm per sample and pass would cost a quarter of
+//     the pass).  The workgroup's maximum first, then the sum, block_sum of cv_device.h.  A tile of replicates per workgroup was not
+//     taken: k_mbar_free_energy is VGPR-limited from d = 4 on (profiles/mbar_rate.txt) and the exponentials are not shared;
+//   - k_mbar_boot_update subtracts f'_0, writes f, a and delta[slot]: the host reads one array of deltas per iteration, its one
+//     synchronisation for the whole batch;
+//   - k_mbar_boot_columns: column_boot[b][j] = -logsumexp_{n : c_b(n) > 0} (ln c_b(n) + log_numerator[j][n] - D_b(n)) at the returned
+//     f_b, the same reduction; -inf entries are skipped, a column without a contributing sample is +inf.
+// No block of any kernel reads what another replicate wrote, every lane's walk is a function of (n_sample, n_state) alone, so the bits
+// of a replicate depend neither on B, nor on the other replicates, nor on when they converge, nor on the chunking.
+// The workspace D[slot][n] bounds the replicates solved together: upk_mbar_boot_chunk(n_sample, workspace_bytes) of them, each chunk
+// run to convergence before the next.  upk_mbar_boot_solve is the host side: every refusal returns before any device call.
+#include "mbar_device.h"
+#include <cstring>
+
+using namespace up;
+using namespace up::mbar;
+
+#define BOOT_MAX_CHUNK UPK_MBAR_BOOT_MAX_CHUNK
+#define BOOT_COUNTS 65536      // the values of a count
+
+namespace {
+
+typedef unsigned short count_t;
+
+__global__ void __launch_bounds__(MBAR_BLOCK) k_mbar_boot_log_counts(double* __restrict__ log_count) {
+    const int c = blockIdx.x * MBAR_BLOCK + threadIdx.x;
+    if (c < BOOT_COUNTS) log_count[c] = c ? log((double)c) : -INFINITY;
+}
+
+template <int D>
+__global__ void __launch_bounds__(MBAR_BLOCK) k_mbar_boot_denominator(upk_mbar_states_t S, upk_mbar_samples_t X, const double* __restrict__ a_all,
+                                                                       const int* __restrict__ active, double* __restrict__ denom_all) {
+    constexpr int W = mbar_state_doubles<D>();
+    __shared__ double tile[MBAR_TILE * W];
+    const int tid = threadIdx.x;
+    const double* __restrict__ a = a_all + (size_t)active[blockIdx.y] * S.n_state;
+    double* __restrict__ denom = denom_all + (size_t)blockIdx.y * X.n;
+    const long long n_raw = (long long)blockIdx.x * MBAR_BLOCK + tid;
+    const long long n = n_raw < X.n ? n_raw : X.n - 1;      // (a lane past the end repeats the last sample and stores nothing)
+    double v[D ? D : 1], E;
+    mbar_load_sample<D>(X, n, v, E);
+    double m = -INFINITY, sum = 0.;
+    for (int pass = 0; pass < 2; ++pass)
+        for (int k0 = 0; k0 < S.n_state; k0 += MBAR_TILE) {
+            const int nt = min(MBAR_TILE, S.n_state - k0);
+            __syncthreads();      // (the previous tile has been read)
+            for (int i = tid; i < nt * W; i += MBAR_BLOCK) { const int l = i / W, j = i - l * W; mbar_stage_state<D>(S, k0 + l, a[k0 + l], tile + l * W, j); }
+            __syncthreads();
+            for (int l = 0; l < nt; ++l) {
+                const double* __restrict__ st = tile + l * W;
+                if (st[0] == -INFINITY) continue;      // N_l = 0
+                const double x = st[0] - st[1] * mbar_energy<D>(v, E, st, S);
+                if (pass == 0) m = fmax(m, x); else sum += exp(x - m);
+            }
+        }
+    if (n_raw < X.n) denom[n] = m + log(sum);
+}
+
+// the largest of v[j] over the workgroup, for every j; every lane receives it
+template <int K>
+__device__ __forceinline__ void boot_block_max(double (&v)[K], double (*part)[MBAR_FE]) {
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+#pragma unroll
+    for (int k = 0; k < K; ++k) {
+        double w = v[k];
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) w = fmax(w, __shfl_xor(w, o, 64));
+        if (lane == 0) part[wave][k] = w;
+    }
+    __syncthreads();
+#pragma unroll
+    for (int k = 0; k < K; ++k) {
+        double t = part[0][k];
+#pragma unroll
+        for (int w = 1; w < CV_WAVES; ++w) t = fmax(t, part[w][k]);
+        v[k] = t;
+    }
+}
+
+template <int D>
+__global__ void __launch_bounds__(MBAR_BLOCK) k_mbar_boot_free_energy(upk_mbar_states_t S, upk_mbar_samples_t X, const count_t* __restrict__ counts_all,
+                                                                       const double* __restrict__ log_count, const int* __restrict__ active,
+                                                                       const double* __restrict__ denom_all, double* __restrict__ f_new) {
+    constexpr int W = mbar_state_doubles<D>();
+    __shared__ double st[MBAR_FE][W];
+    __shared__ double part[CV_WAVES][CV_MAX_SUMS];
+    __shared__ double partm[CV_WAVES][MBAR_FE];
+    const int tid = threadIdx.x, k0 = blockIdx.x * MBAR_FE;
+    const count_t* __restrict__ counts = counts_all + (size_t)active[blockIdx.y] * X.n;
+    const double* __restrict__ denom = denom_all + (size_t)blockIdx.y * X.n;
+    if (tid < MBAR_FE * W) { const int l = tid / W, j = tid - l * W; mbar_stage_state<D>(S, min(k0 + l, S.n_state - 1), 0., st[l], j); }
+    __syncthreads();
+    double m[MBAR_FE], s[MBAR_FE];
+#pragma unroll
+    for (int l = 0; l < MBAR_FE; ++l) { m[l] = -INFINITY; s[l] = 0.; }
+    for (long long n = tid; n < X.n; n += MBAR_BLOCK) {
+        const int c = counts[n];
+        if (!c) continue;
+        double v[D ? D : 1], E;
+        mbar_load_sample<D>(X, n, v, E);
+        const double dn = denom[n], lc = log_count[c];
+#pragma unroll
+        for (int l = 0; l < MBAR_FE; ++l) m[l] = fmax(m[l], lc + (-(st[l][1] * mbar_energy<D>(v, E, st[l], S)) - dn));
+    }
+    boot_block_max<MBAR_FE>(m, partm);
+    for (long long n = tid; n < X.n; n += MBAR_BLOCK) {
+        const int c = counts[n];
+        if (!c) continue;
+        double v[D ? D : 1], E;
+        mbar_load_sample<D>(X, n, v, E);
+        const double dn = denom[n], lc = log_count[c];
+#pragma unroll
+        for (int l = 0; l < MBAR_FE; ++l) s[l] += exp(lc + (-(st[l][1] * mbar_energy<D>(v, E, st[l], S)) - dn) - m[l]);
+    }
+    block_sum<MBAR_FE>(s, part);
+    if (tid == 0) {
+#pragma unroll
+        for (int l = 0; l < MBAR_FE; ++l) if (k0 + l < S.n_state) f_new[(size_t)blockIdx.y * S.n_state + k0 + l] = -(m[l] + log(s[l]));
+    }
+}
+
+// one workgroup per active replicate: f = f' - f'_0, a = ln N + f, delta[slot] = max_k |f'_k - f_k| (a NaN is kept)
+__global__ void __launch_bounds__(MBAR_BLOCK) k_mbar_boot_update(int n_state, const double* __restrict__ ln_n, const int* __restrict__ active,
+                                                                  const double* __restrict__ f_new, double* __restrict__ f_all, double* __restrict__ a_all,
+                                                                  double* __restrict__ delta) {
+    __shared__ double part[MBAR_BLOCK];
+    __shared__ int bad[MBAR_BLOCK];
+    const int tid = threadIdx.x;
+    const double* __restrict__ fn = f_new + (size_t)blockIdx.x * n_state;
+    double* __restrict__ f = f_all + (size_t)active[blockIdx.x] * n_state;
+    double* __restrict__ a = a_all + (size_t)active[blockIdx.x] * n_state;
+    const double f0 = fn[0];
+    double mx = 0.; int nan_seen = 0;
+    for (int k = tid; k < n_state; k += MBAR_BLOCK) {
+        const double x = fn[k] - f0, dk = fabs(x - f[k]);
+        if (dk != dk) nan_seen = 1; else mx = fmax(mx, dk);
+        f[k] = x;
+        a[k] = ln_n[k] + x;      // (ln N = -inf where N = 0)
+    }
+    part[tid] = mx; bad[tid] = nan_seen;
+    __syncthreads();
+    if (tid == 0) {
+        for (int i = 1; i < MBAR_BLOCK; ++i) { mx = fmax(mx, part[i]); nan_seen |= bad[i]; }
+        delta[blockIdx.x] = nan_seen ? NAN : mx;
+    }
+}
+
+// grid (column, slot): slot = blockIdx.y is replicate active[slot], with its denominators in D[slot]
+__global__ void __launch_bounds__(MBAR_BLOCK) k_mbar_boot_columns(long long n_sample, const count_t* __restrict__ counts_all, const double* __restrict__ log_count,
+                                                                   const int* __restrict__ active, const double* __restrict__ denom_all, int n_column,
+                                                                   const double* __restrict__ log_numerator, double* __restrict__ column) {
+    __shared__ double part[CV_WAVES][CV_MAX_SUMS];
+    __shared__ double partm[CV_WAVES][MBAR_FE];
+    const int tid = threadIdx.x, j = blockIdx.x, b = active[blockIdx.y];
+    const count_t* __restrict__ counts = counts_all + (size_t)b * n_sample;
+    const double* __restrict__ denom = denom_all + (size_t)blockIdx.y * n_sample;
+    const double* __restrict__ ln = log_numerator + (size_t)j * n_sample;
+    double m[1] = {-INFINITY}, s[1] = {0.};
+    for (long long n = tid; n < n_sample; n += MBAR_BLOCK) {
+        const int c = counts[n];
+        const double x = ln[n];
+        if (!c || x == -INFINITY) continue;
+        m[0] = fmax(m[0], log_count[c] + (x - denom[n]));
+    }
+    boot_block_max<1>(m, partm);
+    if (m[0] != -INFINITY)      // (uniform: every lane holds the workgroup's maximum)
+        for (long long n = tid; n < n_sample; n += MBAR_BLOCK) {
+            const int c = counts[n];
+            const double x = ln[n];
+            if (!c || x == -INFINITY) continue;
+            s[0] += exp(log_count[c] + (x - denom[n]) - m[0]);
+        }
+    block_sum<1>(s, part);
+    if (tid == 0) column[(size_t)b * n_column + j] = m[0] == -INFINITY ? INFINITY : -(m[0] + log(s[0]));
+}
+
+inline bool boot_args_ok(const int* active, int n_active) { return active && n_active >= 1 && n_active <= BOOT_MAX_CHUNK; }
+
+}  // namespace
+
+extern "C" long long upk_mbar_boot_chunk(long long n_sample, size_t workspace_bytes) {
+    if (n_sample < 1) return 0;
+    const unsigned long long fit = (unsigned long long)workspace_bytes / sizeof(double) / (unsigned long long)n_sample;
+    return (long long)(fit < BOOT_MAX_CHUNK ? fit : BOOT_MAX_CHUNK);
+}
+extern "C" int upk_mbar_boot_log_counts(void* stream, double* log_count) {
+    if (!log_count) return 9410;
+    hipLaunchKernelGGL(k_mbar_boot_log_counts, dim3(BOOT_COUNTS / MBAR_BLOCK), dim3(MBAR_BLOCK), 0, (hipStream_t)stream, log_count);
+    return launch_status();
+}
+extern "C" int upk_mbar_boot_denominator(void* stream, const upk_mbar_states_t* S, const upk_mbar_samples_t* X, const double* a, const int* active,
+                                         int n_active, double* denom) {
+    if (!launch_args_ok(S, X) || !boot_args_ok(active, n_active) || !a || !denom) return 9411;
+    MBAR_DISPATCH(k_mbar_boot_denominator, dim3(sample_blocks(X->n), (unsigned)n_active), *S, *X, a, active, denom)
+    return launch_status();
+}
+extern "C" int upk_mbar_boot_free_energy(void* stream, const upk_mbar_states_t* S, const upk_mbar_samples_t* X, const unsigned short* counts,
+                                         const double* log_count, const int* active, int n_active, const double* denom, double* f_new) {
+    if (!launch_args_ok(S, X) || !boot_args_ok(active, n_active) || !counts || !log_count || !denom || !f_new) return 9412;
+    MBAR_DISPATCH(k_mbar_boot_free_energy, dim3((unsigned)((S->n_state + MBAR_FE - 1) / MBAR_FE), (unsigned)n_active), *S, *X, counts, log_count, active,
+                  denom, f_new)
+    return launch_status();
+}
+extern "C" int upk_mbar_boot_update(void* stream, int n_state, const double* ln_n, const int* active, int n_active, const double* f_new, double* f,
+                                    double* a, double* delta) {
+    if (n_state < 1 || !boot_args_ok(active, n_active) || !ln_n || !f_new || !f || !a || !delta) return 9413;
+    hipLaunchKernelGGL(k_mbar_boot_update, dim3((unsigned)n_active), dim3(MBAR_BLOCK), 0, (hipStream_t)stream, n_state, ln_n, active, f_new, f, a, delta);
+    return launch_status();
+}
+extern "C" int upk_mbar_boot_columns(void* stream, long long n_sample, const unsigned short* counts, const double* log_count, const int* active,
+                                     int n_active, const double* denom, int n_column, const double* log_numerator, double* column) {
+    if (n_sample < 1 || !boot_args_ok(active, n_active) || !counts || !log_count || !denom || n_column < 1 || !log_numerator || !column) return 9414;
+    hipLaunchKernelGGL(k_mbar_boot_columns, dim3((unsigned)n_column, (unsigned)n_active), dim3(MBAR_BLOCK), 0, (hipStream_t)stream, n_sample, counts,
+                       log_count, active, denom, n_column, log_numerator, column);
+    return launch_status();
+}
+
+// ---- host side -----------------------------------------------------------------------------------------------------------------------
+namespace {
+
+struct PinnedBuffer {
+    void* p = nullptr;
+    ~PinnedBuffer() { if (p) (void)hipHostFree(p); }
+    void alloc(size_t bytes, const char* what) { hip_ok(hipHostMalloc(&p, bytes ? bytes : 8, hipHostMallocDefault), what); }
+    template <class T> T* as() const { return (T*)p; }
+};
+
+// every refusal of upside_hip_mbar_bootstrap; nothing here touches the device
+void boot_check(const upk_mbar_boot_problem_t& P) {
+    // the samples, the states, tol, max_iter and f0: the refusals of upside_hip_mbar, one statement of them
+    upk_mbar_problem_t Q{};
+    Q.n_sample = P.n_sample; Q.n_state = P.n_state; Q.d = P.d; Q.values = P.values; Q.energy = P.energy; Q.beta = P.beta; Q.rows = P.rows;
+    Q.n_k = P.n_k; Q.periods = P.periods; Q.tol = P.tol; Q.max_iter = P.max_iter; Q.f0 = P.f0; Q.f = P.f_boot;      // (only tested against NULL)
+    if (!P.f_boot) MBAR_REFUSE("mbar_bootstrap: f_boot must be given");
+    mbar_check(Q);
+    if (P.n_replicate < 1) MBAR_REFUSE("mbar_bootstrap: n_replicate = %d, at least one replicate is needed", P.n_replicate);
+    if (!P.counts || !P.state_of_sample) MBAR_REFUSE("mbar_bootstrap: counts and state_of_sample must be given");
+    if (P.n_column < 0) MBAR_REFUSE("mbar_bootstrap: n_column = %d is negative", P.n_column);
+    if (P.n_column > 0 && (!P.log_numerator || !P.column_boot)) MBAR_REFUSE("mbar_bootstrap: log_numerator and column_boot must be given when n_column > 0");
+    const size_t N = (size_t)P.n_sample; const int K = P.n_state;
+    std::vector<long long> have((size_t)K, 0);
+    for (size_t n = 0; n < N; ++n) {
+        const int k = P.state_of_sample[n];
+        if (k < 0 || k >= K) MBAR_REFUSE("mbar_bootstrap: state_of_sample[%zu] = %d is outside 0 .. %d", n, k, K - 1);
+        if (P.n_k[k] == 0) MBAR_REFUSE("mbar_bootstrap: state_of_sample[%zu] = %d names a state without samples (n_k[%d] = 0)", n, k, k);
+        ++have[(size_t)k];
+    }
+    for (int k = 0; k < K; ++k)
+        if (have[(size_t)k] != P.n_k[k])
+            MBAR_REFUSE("mbar_bootstrap: state_of_sample names state %d for %lld samples, n_k[%d] is %lld", k, have[(size_t)k], k, P.n_k[k]);
+    for (int b = 0; b < P.n_replicate; ++b) {
+        const unsigned short* c = P.counts + (size_t)b * N;
+        std::fill(have.begin(), have.end(), 0ll);
+        for (size_t n = 0; n < N; ++n) have[(size_t)P.state_of_sample[n]] += c[n];
+        for (int k = 0; k < K; ++k)
+            if (have[(size_t)k] != P.n_k[k])
+                MBAR_REFUSE("mbar_bootstrap: replicate %d: the counts of state %d add up to %lld, n_k[%d] is %lld", b, k, have[(size_t)k], k, P.n_k[k]);
+    }
+    for (size_t j = 0; j < (size_t)P.n_column; ++j)
+        for (size_t n = 0; n < N; ++n) {
+            const double x = P.log_numerator[j * N + n];
+            if (std::isnan(x) || x == INFINITY)
+                MBAR_REFUSE("mbar_bootstrap: log_numerator: column %zu, sample %zu is %s (-inf is weight 0)", j, n, std::isnan(x) ? "not a number" : "+inf");
+        }
+    const size_t work = P.workspace_bytes ? P.workspace_bytes : (size_t)UPK_MBAR_GRAM_MAX_WORKSPACE;
+    if (work > UPK_MBAR_GRAM_MAX_WORKSPACE) MBAR_REFUSE("mbar_bootstrap: a workspace of %zu bytes, at most %llu are taken", work, UPK_MBAR_GRAM_MAX_WORKSPACE);
+    if (upk_mbar_boot_chunk(P.n_sample, work) < 1)
+        MBAR_REFUSE("mbar_bootstrap: the denominators of one replicate (%lld samples x 8 bytes) do not fit the workspace of %zu bytes", P.n_sample, work);
+}
+
+void boot_run(const upk_mbar_boot_problem_t& P) {
+    boot_check(P);
+    int n_dev = 0;
+    if (hipGetDeviceCount(&n_dev) != hipSuccess || n_dev < 1) MBAR_REFUSE("mbar_bootstrap: no HIP device (this library has no CPU path)");
+    const int K = P.n_state, d = P.d, B = P.n_replicate, J = P.n_column;
+    const size_t N = (size_t)P.n_sample;
+    const int chunk = (int)std::min<long long>(B, upk_mbar_boot_chunk(P.n_sample, P.workspace_bytes ? P.workspace_bytes : (size_t)UPK_MBAR_GRAM_MAX_WORKSPACE));
+    Stream st; hip_ok(hipStreamCreate(&st.s), "hipStreamCreate");
+    DeviceBuffer values, energy, beta, rows, ln_n, log_count, lognum, counts, a, f, f_new, denom, active, delta, column;
+    PinnedBuffer active_h, delta_h;
+    auto upload = [&](DeviceBuffer& buf, const void* src, size_t bytes, const char* what) {
+        buf.alloc(bytes, what); hip_ok(hipMemcpyAsync(buf.p, src, bytes, hipMemcpyHostToDevice, st.s), what);
+    };
+    // the samples, the states and the columns go to the device once
+    if (d) upload(values, P.values, N * d * sizeof(float), "copy of values");
+    if (P.energy) upload(energy, P.energy, N * sizeof(double), "copy of energy");
+    upload(beta, P.beta, K * sizeof(double), "copy of beta");
+    if (d) upload(rows, P.rows, (size_t)K * 3 * d * sizeof(float), "copy of rows");
+    std::vector<double> ln_n_h(K), start((size_t)chunk * K), a0((size_t)chunk * K);
+    for (int k = 0; k < K; ++k) ln_n_h[k] = P.n_k[k] > 0 ? std::log((double)P.n_k[k]) : -INFINITY;
+    for (int b = 0; b < chunk; ++b)
+        for (int k = 0; k < K; ++k) {
+            const double f0 = P.f0 ? P.f0[k] : 0.;
+            start[(size_t)b * K + k] = f0; a0[(size_t)b * K + k] = P.n_k[k] > 0 ? ln_n_h[k] + f0 : -INFINITY;
+        }
+    upload(ln_n, ln_n_h.data(), K * sizeof(double), "copy of n_k");
+    if (J) upload(lognum, P.log_numerator, (size_t)J * N * sizeof(double), "copy of log_numerator");
+    log_count.alloc(BOOT_COUNTS * sizeof(double), "log-count table");
+    counts.alloc((size_t)chunk * N * sizeof(count_t), "counts"); denom.alloc((size_t)chunk * N * sizeof(double), "denominators");
+    a.alloc((size_t)chunk * K * sizeof(double), "a"); f.alloc((size_t)chunk * K * sizeof(double), "f"); f_new.alloc((size_t)chunk * K * sizeof(double), "f");
+    active.alloc((size_t)chunk * sizeof(int), "active"); delta.alloc((size_t)chunk * sizeof(double), "delta");
+    if (J) column.alloc((size_t)chunk * J * sizeof(double), "columns");
+    active_h.alloc((size_t)chunk * sizeof(int), "active"); delta_h.alloc((size_t)chunk * sizeof(double), "delta");
+    int* act = active_h.as<int>(); const double* dl = delta_h.as<double>();
+
+    upk_mbar_states_t S{}; S.d = d; S.n_state = K; S.beta = beta.as<double>(); S.rows = rows.as<float>();
+    for (int c = 0; c < d; ++c) S.period[c] = P.periods[c];
+    upk_mbar_samples_t X{}; X.n = P.n_sample; X.values = values.as<float>(); X.energy = energy.as<double>();
+    upk_ok(upk_mbar_boot_log_counts(st.s, log_count.as<double>()), "log-count table");
+
+    std::vector<int> iters((size_t)chunk); std::vector<double> last((size_t)chunk);
+    for (int b0 = 0; b0 < B; b0 += chunk) {
+        const int nb = std::min(chunk, B - b0);
+        hip_ok(hipMemcpyAsync(counts.p, P.counts + (size_t)b0 * N, (size_t)nb * N * sizeof(count_t), hipMemcpyHostToDevice, st.s), "copy of counts");
+        hip_ok(hipMemcpyAsync(f.p, start.data(), (size_t)nb * K * sizeof(double), hipMemcpyHostToDevice, st.s), "copy of f0");
+        hip_ok(hipMemcpyAsync(a.p, a0.data(), (size_t)nb * K * sizeof(double), hipMemcpyHostToDevice, st.s), "copy of f0");
+        int n_active = nb;
+        for (int i = 0; i < nb; ++i) { act[i] = i; iters[(size_t)i] = 0; last[(size_t)i] = INFINITY; }
+        bool list_changed = true;
+        for (int it = 1; n_active > 0; ++it) {
+            if (list_changed) hip_ok(hipMemcpyAsync(active.p, act, (size_t)n_active * sizeof(int), hipMemcpyHostToDevice, st.s), "copy of the active list");
+            upk_ok(upk_mbar_boot_denominator(st.s, &S, &X, a.as<double>(), active.as<int>(), n_active, denom.as<double>()), "denominator pass");
+            upk_ok(upk_mbar_boot_free_energy(st.s, &S, &X, counts.as<count_t>(), log_count.as<double>(), active.as<int>(), n_active, denom.as<double>(),
+                                             f_new.as<double>()), "free-energy pass");
+            upk_ok(upk_mbar_boot_update(st.s, K, ln_n.as<double>(), active.as<int>(), n_active, f_new.as<double>(), f.as<double>(), a.as<double>(),
+                                        delta.as<double>()), "update");
+            hip_ok(hipMemcpyAsync(delta_h.p, delta.p, (size_t)n_active * sizeof(double), hipMemcpyDeviceToHost, st.s), "copy of delta");
+            hip_ok(hipStreamSynchronize(st.s), "hipStreamSynchronize");      // the one synchronisation of the iteration
+            int kept = 0;
+            for (int i = 0; i < n_active; ++i) {
+                const int b = act[i];
+                iters[(size_t)b] = it; last[(size_t)b] = dl[i];
+                if (!(dl[i] < P.tol) && it < P.max_iter) act[kept++] = b;      // (ascending order is kept)
+            }
+            list_changed = kept != n_active;
+            n_active = kept;
+        }
+        if (J) {      // the denominators of the returned f of every replicate of the chunk, then the columns
+            for (int i = 0; i < nb; ++i) act[i] = i;
+            hip_ok(hipMemcpyAsync(active.p, act, (size_t)nb * sizeof(int), hipMemcpyHostToDevice, st.s), "copy of the active list");
+            upk_ok(upk_mbar_boot_denominator(st.s, &S, &X, a.as<double>(), active.as<int>(), nb, denom.as<double>()), "denominator pass");
+            upk_ok(upk_mbar_boot_columns(st.s, P.n_sample, counts.as<count_t>(), log_count.as<double>(), active.as<int>(), nb, denom.as<double>(), J,
+                                         lognum.as<double>(), column.as<double>()), "column pass");
+            hip_ok(hipMemcpyAsync(P.column_boot + (size_t)b0 * J, column.p, (size_t)nb * J * sizeof(double), hipMemcpyDeviceToHost, st.s), "copy of the columns");
+        }
+        hip_ok(hipMemcpyAsync(P.f_boot + (size_t)b0 * K, f.p, (size_t)nb * K * sizeof(double), hipMemcpyDeviceToHost, st.s), "copy of f");
+        hip_ok(hipStreamSynchronize(st.s), "hipStreamSynchronize");      // (the next chunk overwrites counts, f and a)
+        for (int i = 0; i < nb; ++i) {
+            if (P.n_iter) P.n_iter[b0 + i] = iters[(size_t)i];
+            if (P.last_delta) P.last_delta[b0 + i] = last[(size_t)i];
+        }
+    }
+}
+
+}  // namespace
+
+extern "C" int upk_mbar_boot_solve(const upk_mbar_boot_problem_t* P, char* message, int message_len) {
+    if (message && message_len > 0) message[0] = 0;
+    try {
+        if (!P) MBAR_REFUSE("mbar_bootstrap: no problem given");
+        boot_run(*P);
+        return 0;
+    } catch (const MbarRefusal& r) {
+        // the checks and helpers shared with upside_hip_mbar say "mbar: ..."; the message names the entry point that refused
+        const bool shared = !strncmp(r.text, "mbar: ", 6);
+        if (message && message_len > 0) snprintf(message, (size_t)message_len, "%s%s", shared ? "mbar_bootstrap: " : "", r.text + (shared ? 6 : 0));
+    } catch (const std::exception& e) {
+        if (message && message_len > 0) snprintf(message, (size_t)message_len, "mbar_bootstrap: %s", e.what());
+    }
+    return 1;
+}

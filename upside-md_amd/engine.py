@@ -495,7 +495,7 @@ class Ensemble(object):
         return out
 
     def umbrella_mbar(self, node_name, kT, tol=1e-8, max_iter=10000, f0=None, target=None, series=None, solver='self-consistent',
-                      n_sc=10, uncertainty=False, decorrelate=False):
+                      n_sc=10, uncertainty=False, decorrelate=False, n_bootstrap=0, bootstrap_seed=0):
         """MBAR over the umbrella ladder of the cv_restraint node `node_name` from the recorded CV series (mbar.mbar on the device):
         system s is window s with its own row [center | spring_const | flat_width] (get_param of system s) and beta = 1 / kT for all
         (one temperature: the unbiased potential cancels and is not needed).  series: (n_stored, n_system, n_cv) as read_cvs gives it,
@@ -505,15 +505,24 @@ class Ensemble(object):
         mbar.mbar with values (N, d), rows (n_system, 3 d), periods (d,), n_k and names added; with a target, log_w feeds
         config.mbar_profile.  solver, n_sc: as mbar.mbar ('newton' for a ladder that converges slowly).  uncertainty=True adds sigma
         (n_system, n_system), the asymptotic standard deviation of f_i - f_j (mbar.free_energy_uncertainty: the samples are taken as
-        uncorrelated, so pass decorrelate=True for a series recorded more often than its correlation time; the covariance remains the
-        asymptotic one).  decorrelate=True: per window, the series of its own-state reduced bias (mbar.own_state_reduced_bias) goes
+        uncorrelated, so pass decorrelate=True for a series recorded more often than its correlation time; it is a large-sample
+        estimate, and n_bootstrap gives bootstrap error bars where few samples are kept or neighbours overlap poorly).
+        decorrelate=True: per window, the series of its own-state reduced bias (mbar.own_state_reduced_bias) goes
         through timeseries.detect_equilibration on the device, the samples before the detected origin t0 are dropped and every
         ceil(g)-th of the rest is kept (timeseries.subsample_indices); MBAR and the uncertainty then run on the kept samples, window
         after window, with their unequal counts n_k, and t0, g, n_eff (each (n_system,)) and kept (the kept sample indices per
-        window) are added to the result.  decorrelate=False changes nothing."""
+        window) are added to the result.  decorrelate=False changes nothing.  n_bootstrap > 0: that many stratified bootstrap
+        replicates (mbar.bootstrap_counts with bootstrap_seed; every window keeps its sample count) are solved in one device batch
+        from the returned f with the same tol and max_iter (mbar.bootstrap), and f_boot (n_bootstrap, n_system), sigma_boot
+        (n_system, n_system) = mbar.bootstrap_sigma over the converged replicates, n_boot_converged and boot_counts (n_bootstrap, N)
+        are added; the state every sample was drawn from follows the layout of values: sample (i, s) of window s without
+        decorrelate, grouped by window with it.  Bootstrapping correlated samples underestimates the errors, so decorrelate=True
+        goes with it.  n_bootstrap=0 changes nothing."""
         from . import config, mbar as _mbar
         if not (np.ndim(kT) == 0 and np.isfinite(kT) and kT > 0):
             raise ValueError('umbrella_mbar: kT must be one finite positive number (one temperature for every window)')
+        if int(n_bootstrap) < 0:
+            raise ValueError('umbrella_mbar: n_bootstrap must not be negative')
         with h5lite.open_file(self.config_file_path) as t:
             pot = t.group('input').group('potential')
             if node_name not in pot:
@@ -558,6 +567,15 @@ class Ensemble(object):
         out = _mbar.mbar(values, None, beta, rows, n_k, periods, tol, max_iter, f0=f0, target=tgt, library=self.lib, solver=solver, n_sc=n_sc)
         if uncertainty:
             out['sigma'] = _mbar.free_energy_uncertainty(values, None, beta, rows, n_k, out['f'], periods, library=self.lib)
+        if int(n_bootstrap) > 0:
+            import warnings
+            origin = np.repeat(np.arange(self.n_system), n_k) if decorrelate else np.tile(np.arange(self.n_system), series.shape[0])
+            boot = _mbar.bootstrap(values, None, beta, rows, n_k, out['f'], origin, int(n_bootstrap), bootstrap_seed, periods=periods, tol=tol,
+                                   max_iter=max_iter, library=self.lib)
+            with warnings.catch_warnings():      # (the number of unconverged replicates is returned below)
+                warnings.simplefilter('ignore', RuntimeWarning)
+                sigma_boot = _mbar.bootstrap_sigma(boot)
+            extra.update(f_boot=boot['f_boot'], sigma_boot=sigma_boot, n_boot_converged=int(boot['converged'].sum()), boot_counts=boot['counts'])
         out.update(values=values, rows=rows, periods=periods, n_k=n_k, names=names, **extra)
         return out
 

@@ -2,9 +2,12 @@
 csrc/kernels_mbar.hip, csrc/kernels_mbar_gram.hip): free energies of umbrella windows from the recorded CV series and of temperature
 ladders from recorded energies, by self-consistent iteration or with Newton steps; their asymptotic uncertainties, and averages and
 profiles in a target state with error bars, from the Gram matrix of the weight matrix (Shirts & Chodera 2008, eq. D8/D9).
-Limits of the uncertainties: at most 8192 columns (states + target + observables or bins); the covariance is the asymptotic one; the
-samples are taken as uncorrelated: timeseries.py finds the equilibration origin and the statistical inefficiency of a recorded series
-on the device, and Ensemble.umbrella_mbar(decorrelate=True) applies them per window (own_state_reduced_bias is the observable)."""
+Limits of the uncertainties: at most 8192 columns (states + target + observables or bins); the covariance from the Gram matrix is a
+large-sample estimate -- where a window keeps few samples or neighbours overlap poorly, bootstrap(), bootstrap_sigma() and
+profile_bootstrap() below give bootstrap error bars instead, all replicates solved in one device batch (upside_hip_mbar_bootstrap,
+csrc/kernels_mbar_boot.hip); the samples are taken as uncorrelated by both, and bootstrapping correlated samples underestimates the
+errors just as the asymptotic estimate does: timeseries.py finds the equilibration origin and the statistical inefficiency of a recorded
+series on the device, and Ensemble.umbrella_mbar(decorrelate=True) applies them per window (own_state_reduced_bias is the observable)."""
 import ctypes as ct
 import numpy as np
 
@@ -14,6 +17,7 @@ FE_TILE = 4              # UPK_MBAR_FE_TILE: states per workgroup of the free-en
 GRAM_TILE = 64           # UPK_MBAR_GRAM_TILE: the Gram pass computes G in tiles of 64 x 64
 GRAM_MAX_COLUMNS = 8192  # UPK_MBAR_GRAM_MAX_COLUMNS
 NULL_RCOND = 1e-10       # eigenvalues of I - Sigma V^T N V Sigma below this (relative) are its null space in covariance()
+BOOT_MAX_COUNT = 65535   # a bootstrap count is an unsigned 16-bit number
 
 
 def _bind(c):
@@ -24,6 +28,12 @@ def _bind(c):
     c.upside_hip_mbar.restype = i32
     c.upside_hip_mbar_gram.argtypes = [i64, i32, i32, vp, vp, vp, vp, vp, vp, vp, i32, vp, vp, vp, vp]
     c.upside_hip_mbar_gram.restype = i32
+    c.upside_hip_mbar_bootstrap.argtypes = [i64, i32, i32, vp, vp, vp, vp, vp, vp, vp, i32, vp, f64, i32, vp, i32, vp, vp, vp, vp, vp]
+    c.upside_hip_mbar_bootstrap.restype = i32
+    c.upk_mbar_boot_solve.argtypes = [vp, ct.c_char_p, i32]
+    c.upk_mbar_boot_solve.restype = i32
+    c.upk_mbar_boot_chunk.argtypes = [i64, ct.c_size_t]
+    c.upk_mbar_boot_chunk.restype = i64
     c.upside_hip_last_error.restype = ct.c_char_p
     c._mbar_bound = True
 
@@ -294,6 +304,18 @@ def expectation(values, energy, beta, rows, n_k, f, observables, target, periods
     return mean_p + shift, np.sqrt(np.maximum(var, 0.))
 
 
+def _bin_index(x, edges, period):
+    """(N,) the bin of every x among edges, -1 outside: the bins of numpy.histogram (the last one is closed), x wrapped into
+    [edges[0], edges[0] + period) first where period > 0"""
+    e = np.asarray(edges, 'f8').reshape(-1)
+    if period > 0:
+        x = e[0] + np.mod(x - e[0], float(period))
+    b = np.searchsorted(e, x, 'right') - 1
+    b[x == e[-1]] = len(e) - 2
+    b[(x < e[0]) | (x > e[-1])] = -1
+    return b
+
+
 def profile(values, energy, beta, rows, n_k, f, edges, kT, period=0, target=None, periods=None, cv=0, library=None):
     """(F (n_bin,), dF (n_bin,)): the free-energy profile of the target state along one CV with its asymptotic standard deviation.
     cv: the column of values to bin, or an (N,) array of its own.  F is config.mbar_profile of the target's weights.  One column is
@@ -304,12 +326,7 @@ def profile(values, energy, beta, rows, n_k, f, edges, kT, period=0, target=None
     x = np.asarray(values)[:, cv] if np.ndim(cv) == 0 else np.asarray(cv)
     x = np.asarray(x, 'f8').reshape(-1)
     F = config.mbar_profile(x, log_w, edges, kT, period)
-    e = np.asarray(edges, 'f8').reshape(-1)
-    if period > 0:
-        x = e[0] + np.mod(x - e[0], float(period))
-    b = np.searchsorted(e, x, 'right') - 1      # the bins of numpy.histogram: the last one is closed
-    b[x == e[-1]] = len(e) - 2
-    b[(x < e[0]) | (x > e[-1])] = -1
+    b = _bin_index(x, edges, period)
     full = np.flatnonzero(np.isfinite(F))
     dF = np.full(len(F), np.nan)
     if not len(full):
@@ -323,4 +340,216 @@ def profile(values, energy, beta, rows, n_k, f, edges, kT, period=0, target=None
     idx = K + np.arange(len(full))
     r = idx[np.argmin(F[full])]
     dF[full] = float(kT) * np.sqrt(np.maximum(theta[idx, idx] + theta[r, r] - 2. * theta[idx, r], 0.))
+    return F, dF
+
+
+# ---- the bootstrap: replicates of the problem with integer sample weights, solved in one device batch ---------------------------------
+class _BootProblem(ct.Structure):
+    """upk_mbar_boot_problem_t of include/upside_hip_kernels.h"""
+    _fields_ = [('n_sample', ct.c_longlong), ('n_state', ct.c_int), ('d', ct.c_int), ('values', ct.c_void_p), ('energy', ct.c_void_p),
+                ('beta', ct.c_void_p), ('rows', ct.c_void_p), ('n_k', ct.c_void_p), ('periods', ct.c_void_p), ('state_of_sample', ct.c_void_p),
+                ('n_replicate', ct.c_int), ('counts', ct.c_void_p), ('tol', ct.c_double), ('max_iter', ct.c_int), ('f0', ct.c_void_p),
+                ('n_column', ct.c_int), ('log_numerator', ct.c_void_p), ('workspace_bytes', ct.c_size_t), ('f_boot', ct.c_void_p),
+                ('column_boot', ct.c_void_p), ('n_iter', ct.c_void_p), ('last_delta', ct.c_void_p)]
+
+
+def _origins(n_k, state_of_sample):
+    """(state_of_sample (N,) i4, grouped): the default is the samples grouped by state, np.repeat(arange(K), n_k)"""
+    n_k = np.asarray(n_k).reshape(-1).astype('i8')
+    if state_of_sample is None:
+        return np.repeat(np.arange(len(n_k), dtype='i4'), n_k), True
+    sos = np.asarray(state_of_sample).reshape(-1)
+    if sos.dtype.kind not in 'iu':
+        raise ValueError('mbar: state_of_sample must hold integers')
+    return np.ascontiguousarray(sos, 'i4'), False
+
+
+def bootstrap_counts(n_k, n_bootstrap, seed=0, state_of_sample=None):
+    """(B, N) uint16: the sample counts of B = n_bootstrap stratified bootstrap replicates -- per state k, in ascending order of k,
+    numpy.random.default_rng(seed).multinomial(n_k[k], uniform over the state's n_k[k] samples, size=B), so every replicate keeps
+    every state's sample count.  state_of_sample (N,): the state each sample was drawn from, default np.repeat(arange(K), n_k)
+    (the samples grouped by state); the draw of a state goes to its samples in their order.  Raises ValueError where a count would
+    exceed 65535 or state_of_sample does not name n_k[k] samples for state k."""
+    n_k = np.asarray(n_k).reshape(-1).astype('i8')
+    B = int(n_bootstrap)
+    if B < 1:
+        raise ValueError('mbar.bootstrap_counts: n_bootstrap = %d, at least one replicate is needed' % B)
+    if (n_k < 0).any():
+        raise ValueError('mbar.bootstrap_counts: a negative n_k')
+    sos, grouped = _origins(n_k, state_of_sample)
+    N, K = int(n_k.sum()), len(n_k)
+    if len(sos) != N or (N and (sos.min() < 0 or sos.max() >= K)) or not np.array_equal(np.bincount(sos, minlength=K), n_k):
+        raise ValueError('mbar.bootstrap_counts: state_of_sample must name n_k[k] samples for every state k')
+    order = None if grouped else np.argsort(sos, kind='stable')
+    start = np.concatenate(([0], np.cumsum(n_k)))
+    rng = np.random.default_rng(seed)
+    counts = np.zeros((B, N), 'u2')
+    for k in range(K):
+        m = int(n_k[k])
+        if not m:
+            continue
+        draw = rng.multinomial(m, np.full(m, 1. / m), size=B)
+        if draw.max() > BOOT_MAX_COUNT:
+            raise ValueError('mbar.bootstrap_counts: a count of %d in state %d exceeds %d' % (draw.max(), k, BOOT_MAX_COUNT))
+        if grouped:
+            counts[:, start[k]:start[k + 1]] = draw
+        else:
+            counts[:, order[start[k]:start[k + 1]]] = draw
+    return counts
+
+
+def bootstrap(values, energy, beta, rows, n_k, f, state_of_sample=None, n_bootstrap=200, seed=0, counts=None, periods=None, tol=1e-8,
+              max_iter=10000, log_numerators=None, library=None, workspace_bytes=None):
+    """bootstrap replicates of the problem (the arguments of mbar()), all solved in ONE batch on the device (upside_hip_mbar_bootstrap):
+    replicate b weights sample n by counts[b, n] and iterates from f (the full-sample solution; None = 0) until its max |f' - f| < tol
+    or max_iter; a replicate that has converged leaves the grid, the host synchronises once per iteration for all, the samples are
+    copied once.
+      state_of_sample  (N,) the state every sample was drawn from; None: the samples are grouped by state, np.repeat(arange(K), n_k)
+      counts           (B, N) uint16, per replicate and state adding up to n_k; None: bootstrap_counts(n_k, n_bootstrap, seed, ...)
+      log_numerators   None or (J, N): columns carrying a target state, an observable or a profile bin WITHOUT the denominators (they
+                       differ per replicate), -inf = weight 0; columns[b, j] = -logsumexp_n (ln c_b(n) + log_numerators[j, n] - D_b(n))
+                       at the returned f_b, +inf where no sample of the replicate contributes
+      workspace_bytes  None, or the bytes the denominators of the replicates solved together may fill (at most the default, 512 MB):
+                       the results do not depend on it, bit for bit
+    Returns dict(f_boot (B, K), n_iter (B,), last_delta (B,), converged (B,) = last_delta < tol, counts (B, N)) and columns (B, J)
+    when columns were asked for.  The samples are taken as uncorrelated: bootstrapping correlated samples underestimates the errors,
+    so subsample first (Ensemble.umbrella_mbar(decorrelate=True), timeseries.py).  Every refusal of the entry point raises
+    RuntimeError with its message."""
+    from .engine import default_library
+    lib = library if library is not None else default_library()
+    c = lib.calc
+    _bind(c)
+    v, e, b, r, n_k, per = _problem(values, energy, beta, rows, n_k, periods)
+    (N, d), K = v.shape, len(n_k)
+    sos, _ = _origins(n_k, state_of_sample)
+    if len(sos) != N:
+        raise ValueError('mbar.bootstrap: state_of_sample holds %d entries for %d samples' % (len(sos), N))
+    if counts is None:
+        counts = bootstrap_counts(n_k, n_bootstrap, seed, state_of_sample)
+    cnt = np.asarray(counts)
+    if cnt.ndim == 1:
+        cnt = cnt[None, :]
+    if cnt.ndim != 2 or cnt.shape[1] != N:
+        raise ValueError('mbar.bootstrap: counts must be (B, %d samples), got %r' % (N, cnt.shape))
+    if cnt.dtype != np.uint16:
+        if cnt.dtype.kind not in 'iu' or (cnt.size and (cnt.min() < 0 or cnt.max() > BOOT_MAX_COUNT)):
+            raise ValueError('mbar.bootstrap: counts must be integers in 0 .. %d' % BOOT_MAX_COUNT)
+    cnt = np.ascontiguousarray(cnt, 'u2')
+    B = cnt.shape[0]
+    start = None
+    if f is not None:
+        start = np.ascontiguousarray(np.asarray(f, 'f8').reshape(-1))
+        if len(start) != K:
+            raise ValueError('mbar.bootstrap: f holds %d entries for %d states' % (len(start), K))
+    ln, J = None, 0
+    if log_numerators is not None:
+        ln = np.ascontiguousarray(np.asarray(log_numerators, 'f8'))
+        if ln.ndim == 1:
+            ln = ln[None, :]
+        if ln.ndim != 2 or ln.shape[1] != N:
+            raise ValueError('mbar.bootstrap: log_numerators must be (J, %d samples), got %r' % (N, ln.shape))
+        J = ln.shape[0]
+    f_boot = np.zeros((B, K), 'f8'); cols = np.zeros((B, J), 'f8')
+    n_iter = np.zeros(B, 'i4'); delta = np.zeros(B, 'f8')
+    if workspace_bytes is None:
+        rc = c.upside_hip_mbar_bootstrap(N, K, d, _ptr(v) if d else None, _ptr(e), _ptr(b), _ptr(r) if d else None, _ptr(n_k), _ptr(per) if d else None,
+                                         _ptr(sos), B, _ptr(cnt) if B else None, float(tol), int(max_iter), _ptr(start), J, _ptr(ln) if J else None,
+                                         _ptr(f_boot), _ptr(cols) if J else None, _ptr(n_iter), _ptr(delta))
+        msg = c.upside_hip_last_error().decode() if rc else ''
+    else:      # the same host side with a workspace of the caller's size (upk_mbar_boot_solve): the chunking is all that differs
+        p = _BootProblem(N, K, d, _ptr(v) if d else None, _ptr(e), _ptr(b), _ptr(r) if d else None, _ptr(n_k), _ptr(per) if d else None, _ptr(sos), B,
+                         _ptr(cnt) if B else None, float(tol), int(max_iter), _ptr(start), J, _ptr(ln) if J else None, int(workspace_bytes),
+                         _ptr(f_boot), _ptr(cols) if J else None, _ptr(n_iter), _ptr(delta))
+        buf = ct.create_string_buffer(256)
+        rc = c.upk_mbar_boot_solve(ct.byref(p), buf, 256)
+        msg = buf.value.decode()
+    if rc:
+        raise RuntimeError('mbar.bootstrap failed: %s' % msg)
+    out = dict(f_boot=f_boot, n_iter=n_iter, last_delta=delta, converged=delta < tol, counts=cnt)
+    if log_numerators is not None:
+        out['columns'] = cols
+    return out
+
+
+def boot_chunk(n_sample, workspace_bytes, library=None):
+    """the replicates solved together with a workspace of that many bytes (upk_mbar_boot_chunk); 0: not even one fits"""
+    from .engine import default_library
+    c = (library if library is not None else default_library()).calc
+    _bind(c)
+    return int(c.upk_mbar_boot_chunk(int(n_sample), int(workspace_bytes)))
+
+
+def bootstrap_sigma(f_boot, converged=None):
+    """sigma (K, K): the standard deviation (ddof = 1) over the converged replicates of f_i - f_j.  f_boot: (B, K), or the dict
+    bootstrap() returned (its 'converged' is then used); converged: (B,) bools, None = all.  Unconverged replicates are left out and
+    their number is reported by a RuntimeWarning; with fewer than two converged replicates every entry is nan."""
+    if isinstance(f_boot, dict):
+        if converged is None:
+            converged = f_boot['converged']
+        f_boot = f_boot['f_boot']
+    fb = np.asarray(f_boot, 'f8')
+    if fb.ndim != 2:
+        raise ValueError('mbar.bootstrap_sigma: f_boot must be (B, K)')
+    if converged is not None:
+        ok = np.asarray(converged, bool).reshape(-1)
+        if len(ok) != len(fb):
+            raise ValueError('mbar.bootstrap_sigma: %d flags for %d replicates' % (len(ok), len(fb)))
+        if not ok.all():
+            import warnings
+            warnings.warn('mbar.bootstrap_sigma: %d of %d replicates did not converge and are left out' % (int((~ok).sum()), len(ok)), RuntimeWarning)
+        fb = fb[ok]
+    K = fb.shape[1]
+    if len(fb) < 2:
+        return np.full((K, K), np.nan)
+    sigma = (fb[:, :, None] - fb[:, None, :]).std(axis=0, ddof=1)
+    sigma[np.arange(K), np.arange(K)] = 0.
+    return 0.5 * (sigma + sigma.T)
+
+
+def _target_reduced_energy(values, energy, target, periods):
+    """(N,) u_t(n) of the target (beta_t, row_t or None) in float64 on the host"""
+    beta_t, row_t = target
+    v = np.asarray(values, 'f8')
+    if v.ndim == 1:
+        v = v[:, None]
+    u = np.zeros(len(v))
+    if row_t is not None and v.shape[1]:
+        u = own_state_reduced_bias(v, float(beta_t), np.asarray(row_t, 'f8').reshape(1, -1), periods, np.zeros(len(v), 'i8'))
+    if energy is not None:
+        u = u + float(beta_t) * np.asarray(energy, 'f8').reshape(-1)
+    return u
+
+
+def profile_bootstrap(values, energy, beta, rows, n_k, f, edges, kT, period=0, target=None, periods=None, cv=0, state_of_sample=None,
+                      n_bootstrap=200, seed=0, counts=None, tol=1e-8, max_iter=10000, library=None):
+    """(F (n_bin,), dF_boot (n_bin,)): the free-energy profile of the target state along one CV, as profile() gives it from the full
+    sample, with the BOOTSTRAP standard deviation (ddof = 1) over the converged replicates of kT (F_bin - F_r) relative to the full
+    sample's lowest bin r (dF_boot[r] = 0).  One column per bin that holds samples, -u_target(n) inside the bin and -inf outside, goes
+    through bootstrap() (whose arguments state_of_sample, n_bootstrap, seed, counts, tol, max_iter are); F_bin / kT of a replicate is
+    its column up to a constant that cancels in the difference.  dF_boot is nan for a bin that is empty in the full sample; replicates
+    in which the bin or r received no sample (+inf) are left out of that bin's deviation."""
+    from . import config
+    if target is None:
+        raise ValueError('mbar: a target (beta_t, row_t or None) is needed')
+    f1, log_w = _target_weights(values, energy, beta, rows, n_k, f, periods, target, library)
+    x = np.asarray(values)[:, cv] if np.ndim(cv) == 0 else np.asarray(cv)
+    x = np.asarray(x, 'f8').reshape(-1)
+    F = config.mbar_profile(x, log_w, edges, kT, period)
+    b = _bin_index(x, edges, period)
+    full = np.flatnonzero(np.isfinite(F))
+    dF = np.full(len(F), np.nan)
+    if not len(full):
+        return F, dF
+    ut = _target_reduced_energy(values, energy, target, periods)
+    cols = np.full((len(full), len(x)), -np.inf)
+    for i, bin_ in enumerate(full):
+        inside = b == bin_
+        cols[i, inside] = -ut[inside]
+    r = bootstrap(values, energy, beta, rows, n_k, f1, state_of_sample, n_bootstrap, seed, counts, periods, tol, max_iter, cols, library)
+    g = float(kT) * r['columns'][r['converged']]
+    ref = int(np.argmin(F[full]))
+    for i, bin_ in enumerate(full):
+        both = np.isfinite(g[:, i]) & np.isfinite(g[:, ref])
+        diff = g[both, i] - g[both, ref]
+        dF[bin_] = diff.std(ddof=1) if len(diff) > 1 else np.nan
     return F, dF
