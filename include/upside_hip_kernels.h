@@ -592,6 +592,8 @@ int upk_cv_metad(const upk_launch_t* L, upk_coord_t pos, const upk_cv_t* C, cons
 int upk_cv_metad_deposit(const upk_launch_t* L, upk_coord_t pos, const upk_cv_t* C, const upk_cv_metad_t* M);
 
 /* ---- MBAR over umbrella and temperature ladders (upside_hip_mbar), csrc/kernels_mbar.hip ---------------------------------------------
+ * (The bodies of _denominator and _free_energy, the staging of the states and the host side's refusals and staging are stated once,
+ * in csrc/mbar_device.h, for this section, the Gram pass and the bootstrap below.)
  * n_state states over n samples.  The reduced energy of sample n in state k is
  *   u_k(n) = beta[k] * (energy[n] + sum_c 1/2 k_kc max(0, |wrap_c(values[n][c] - center_kc)| - w_kc)^2),
  *   wrap_c(x) = x - period[c] * rint(x / period[c]) where period[c] > 0 (0: the plain difference),

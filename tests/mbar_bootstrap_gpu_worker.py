@@ -61,6 +61,8 @@ def fixed(work, d):
             assert rd <= 2 * BOUND * max(1., float(np.abs(want['f_boot']).max())), ('last_delta', N, K, d, rd)
             plain = mbar(tol=0., max_iter=20, want_denominators=False, **case)['f']
             worst_plain = max(worst_plain, ratio(got['f_boot'][0], plain))
+            # ln 1 = 0 is added to every term and the walks are one body: the all-ones replicate is mbar.mbar bit for bit
+            assert got['f_boot'][0].tobytes() == plain.tobytes(), ('the all-ones replicate differs from mbar.mbar in its bits', N, K, d)
             n_case += 1
     print('d = %d: %d cases, N in %s, K in %s, 5 replicates (all ones, three seeded draws, one degenerate), 20 iterations from f = 0' % (d, n_case, MC.FIXED_N, MC.FIXED_K))
     print('f_boot: largest |gpu - f64| / (1e-9 max(1, |f64|)) = %.3e at (N, K, d) = %s; largest |gpu - f64| = %.3e' % (worst, at, worst_abs))

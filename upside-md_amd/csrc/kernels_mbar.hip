@@ -18,7 +18,8 @@
 //     samples t, t + 256, ... ascending; the workgroup's maximum first, then the sum, combined by block_sum of cv_device.h (the
 //     butterfly of every CV kernel, unchanged).  States past the last are clamped to it and not stored.
 //   - k_mbar_log_weights: ln w_n = -u_t(n) - D_n + f_t of a target state, one lane per sample.
-// The kernels are instantiated for d = 0 .. UPK_MBAR_MAX_DIM so that a sample's values are registers.
+// The kernels are instantiated for d = 0 .. UPK_MBAR_MAX_DIM so that a sample's values are registers.  The first two are
+// mbar_denominator_body and mbar_free_energy_body of mbar_device.h, which the bootstrap's kernels (kernels_mbar_boot.hip) call as well.
 // upk_mbar_solve is the host side: argument checks (every refusal returns before any device call), one copy of the samples to the
 // device, the iteration, the outputs.
 #include "mbar_device.h"
@@ -31,84 +32,13 @@ namespace {
 template <int D>
 __global__ void __launch_bounds__(MBAR_BLOCK) k_mbar_denominator(upk_mbar_states_t S, upk_mbar_samples_t X, const double* __restrict__ a,
                                                                   double* __restrict__ denom) {
-    constexpr int W = mbar_state_doubles<D>();
-    __shared__ double tile[MBAR_TILE * W];
-    const int tid = threadIdx.x;
-    const long long n_raw = (long long)blockIdx.x * MBAR_BLOCK + tid;
-    const long long n = n_raw < X.n ? n_raw : X.n - 1;      // (a lane past the end repeats the last sample and stores nothing)
-    double v[D ? D : 1], E;
-    mbar_load_sample<D>(X, n, v, E);
-    double m = -INFINITY, sum = 0.;
-    for (int pass = 0; pass < 2; ++pass)
-        for (int k0 = 0; k0 < S.n_state; k0 += MBAR_TILE) {
-            const int nt = min(MBAR_TILE, S.n_state - k0);
-            __syncthreads();      // (the previous tile has been read)
-            for (int i = tid; i < nt * W; i += MBAR_BLOCK) { const int l = i / W, j = i - l * W; mbar_stage_state<D>(S, k0 + l, a[k0 + l], tile + l * W, j); }
-            __syncthreads();
-            for (int l = 0; l < nt; ++l) {
-                const double* __restrict__ st = tile + l * W;
-                if (st[0] == -INFINITY) continue;      // N_l = 0
-                const double x = st[0] - st[1] * mbar_energy<D>(v, E, st, S);
-                if (pass == 0) m = fmax(m, x); else sum += exp(x - m);
-            }
-        }
-    if (n_raw < X.n) denom[n] = m + log(sum);
-}
-
-// the largest of v[j] over the workgroup, for every j; every lane receives it
-template <int K>
-__device__ __forceinline__ void mbar_block_max(double (&v)[K], double (*part)[MBAR_FE]) {
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-#pragma unroll
-    for (int k = 0; k < K; ++k) {
-        double w = v[k];
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) w = fmax(w, __shfl_xor(w, o, 64));
-        if (lane == 0) part[wave][k] = w;
-    }
-    __syncthreads();
-#pragma unroll
-    for (int k = 0; k < K; ++k) {
-        double t = part[0][k];
-#pragma unroll
-        for (int w = 1; w < CV_WAVES; ++w) t = fmax(t, part[w][k]);
-        v[k] = t;
-    }
+    mbar_denominator_body<D>(S, X, a, denom);
 }
 
 template <int D>
 __global__ void __launch_bounds__(MBAR_BLOCK) k_mbar_free_energy(upk_mbar_states_t S, upk_mbar_samples_t X, const double* __restrict__ denom,
                                                                   double* __restrict__ f) {
-    constexpr int W = mbar_state_doubles<D>();
-    __shared__ double st[MBAR_FE][W];
-    __shared__ double part[CV_WAVES][CV_MAX_SUMS];
-    __shared__ double partm[CV_WAVES][MBAR_FE];
-    const int tid = threadIdx.x, k0 = blockIdx.x * MBAR_FE;
-    if (tid < MBAR_FE * W) { const int l = tid / W, j = tid - l * W; mbar_stage_state<D>(S, min(k0 + l, S.n_state - 1), 0., st[l], j); }
-    __syncthreads();
-    double m[MBAR_FE], s[MBAR_FE];
-#pragma unroll
-    for (int l = 0; l < MBAR_FE; ++l) { m[l] = -INFINITY; s[l] = 0.; }
-    for (long long n = tid; n < X.n; n += MBAR_BLOCK) {
-        double v[D ? D : 1], E;
-        mbar_load_sample<D>(X, n, v, E);
-        const double dn = denom[n];
-#pragma unroll
-        for (int l = 0; l < MBAR_FE; ++l) m[l] = fmax(m[l], -(st[l][1] * mbar_energy<D>(v, E, st[l], S)) - dn);
-    }
-    mbar_block_max<MBAR_FE>(m, partm);
-    for (long long n = tid; n < X.n; n += MBAR_BLOCK) {
-        double v[D ? D : 1], E;
-        mbar_load_sample<D>(X, n, v, E);
-        const double dn = denom[n];
-#pragma unroll
-        for (int l = 0; l < MBAR_FE; ++l) s[l] += exp(-(st[l][1] * mbar_energy<D>(v, E, st[l], S)) - dn - m[l]);
-    }
-    block_sum<MBAR_FE>(s, part);
-    if (tid == 0) {
-#pragma unroll
-        for (int l = 0; l < MBAR_FE; ++l) if (k0 + l < S.n_state) f[k0 + l] = -(m[l] + log(s[l]));
-    }
+    mbar_free_energy_body<D, false>(S, X, nullptr, nullptr, denom, f);
 }
 
 template <int D>
@@ -125,8 +55,6 @@ __global__ void __launch_bounds__(MBAR_BLOCK) k_mbar_log_weights(upk_mbar_states
     mbar_load_sample<D>(X, n, v, E);
     log_w[n] = -(st[1] * mbar_energy<D>(v, E, st, S)) - denom[n] + f_target[0];
 }
-
-static_assert(MBAR_FE * mbar_state_doubles<UPK_MBAR_MAX_DIM>() <= MBAR_BLOCK, "one lane stages one double of the free-energy tile");
 
 }  // namespace
 
@@ -152,28 +80,18 @@ namespace {
 
 void mbar_run(const upk_mbar_problem_t& P) {
     mbar_check(P);
-    int n_dev = 0;
-    if (hipGetDeviceCount(&n_dev) != hipSuccess || n_dev < 1) MBAR_REFUSE("mbar: no HIP device (this library has no CPU path)");
+    StagedProblem staged(P);      // the samples and the states go to the device once
+    const upk_mbar_states_t& S = staged.S; const upk_mbar_samples_t& X = staged.X; Stream& st = staged.st;
     const int K = P.n_state, d = P.d;
     const size_t N = (size_t)P.n_sample;
-    Stream st; hip_ok(hipStreamCreate(&st.s), "hipStreamCreate");
-    DeviceBuffer values, energy, beta, rows, a, f_dev, denom, tbeta, trow, tf, lw;
-    // the samples and the states go to the device once
-    if (d) { values.alloc(N * d * sizeof(float), "samples"); hip_ok(hipMemcpyAsync(values.p, P.values, N * d * sizeof(float), hipMemcpyHostToDevice, st.s), "copy of values"); }
-    if (P.energy) { energy.alloc(N * sizeof(double), "energies"); hip_ok(hipMemcpyAsync(energy.p, P.energy, N * sizeof(double), hipMemcpyHostToDevice, st.s), "copy of energy"); }
-    beta.alloc(K * sizeof(double), "beta"); hip_ok(hipMemcpyAsync(beta.p, P.beta, K * sizeof(double), hipMemcpyHostToDevice, st.s), "copy of beta");
-    if (d) { rows.alloc((size_t)K * 3 * d * sizeof(float), "rows"); hip_ok(hipMemcpyAsync(rows.p, P.rows, (size_t)K * 3 * d * sizeof(float), hipMemcpyHostToDevice, st.s), "copy of rows"); }
+    DeviceBuffer a, f_dev, denom, tbeta, trow, tf, lw;
     a.alloc(K * sizeof(double), "a"); f_dev.alloc(K * sizeof(double), "f"); denom.alloc(N * sizeof(double), "denominators");
 
-    upk_mbar_states_t S{}; S.d = d; S.n_state = K; S.beta = beta.as<double>(); S.rows = rows.as<float>();
-    for (int c = 0; c < d; ++c) S.period[c] = P.periods[c];
-    upk_mbar_samples_t X{}; X.n = P.n_sample; X.values = values.as<float>(); X.energy = energy.as<double>();
-
-    std::vector<double> f(K, 0.), fn(K), av(K), ln_n(K);
+    std::vector<double> f(K, 0.), fn(K), av(K);
+    const std::vector<double> ln_n = log_sample_counts(P.n_k, K);
     if (P.f0) for (int k = 0; k < K; ++k) f[k] = P.f0[k];
-    for (int k = 0; k < K; ++k) ln_n[k] = P.n_k[k] > 0 ? std::log((double)P.n_k[k]) : -INFINITY;
     auto denominators = [&]() {
-        for (int k = 0; k < K; ++k) av[k] = P.n_k[k] > 0 ? ln_n[k] + f[k] : -INFINITY;
+        log_counts_plus_f(ln_n, f.data(), av.data());
         hip_ok(hipMemcpyAsync(a.p, av.data(), K * sizeof(double), hipMemcpyHostToDevice, st.s), "copy of f");
         hip_ok(hipStreamSynchronize(st.s), "hipStreamSynchronize");      // (av is pageable and rewritten by the next iteration)
         upk_ok(upk_mbar_denominator(st.s, &S, &X, a.as<double>(), denom.as<double>()), "denominator pass");
@@ -215,17 +133,10 @@ void mbar_run(const upk_mbar_problem_t& P) {
 }  // namespace
 
 extern "C" int upk_mbar_solve(const upk_mbar_problem_t* P, char* message, int message_len) {
-    if (message && message_len > 0) message[0] = 0;
-    try {
+    return guarded_entry("mbar", message, message_len, [&] {
         if (!P) MBAR_REFUSE("mbar: no problem given");
         mbar_run(*P);
-        return 0;
-    } catch (const MbarRefusal& r) {
-        if (message && message_len > 0) snprintf(message, (size_t)message_len, "%s", r.text);
-    } catch (const std::exception& e) {
-        if (message && message_len > 0) snprintf(message, (size_t)message_len, "mbar: %s", e.what());
-    }
-    return 1;
+    });
 }
 extern "C" int upk_mbar_state_tile(void) { return MBAR_TILE; }
 extern "C" int upk_mbar_fe_tile(void) { return MBAR_FE; }

@@ -9,8 +9,9 @@
 // second axis of every grid:
 //   - an array active[] maps blockIdx.y ("slot") to a replicate of the chunk; a replicate that has converged leaves the array, nothing
 //     is moved, and its f and a = ln N + f stay as its last iteration left them;
-//   - k_mbar_boot_denominator is the pass of k_mbar_denominator with a[b][.] staged per replicate; it writes D[slot][n];
-//   - k_mbar_boot_free_energy is the pass of k_mbar_free_energy: a workgroup owns UPK_MBAR_FE_TILE states of ONE replicate, lane t takes
+//   - k_mbar_boot_denominator is the pass of k_mbar_denominator (mbar_denominator_body of mbar_device.h) with a[b][.] staged per
+//     replicate; it writes D[slot][n];
+//   - k_mbar_boot_free_energy is the pass of k_mbar_free_energy (mbar_free_energy_body, with counts): a workgroup owns UPK_MBAR_FE_TILE states of ONE replicate, lane t takes
 //     samples t, t + 256, ... ascending, reads c_b(n) (consecutive uint16 of consecutive lanes) and skips c = 0; ln c comes from a table
 //     of 65536 doubles that k_mbar_boot_log_counts fills once per call (an fp64 logarithm per sample and pass would cost a quarter of
 //     the pass).  The workgroup's maximum first, then the sum, block_sum of cv_device.h.  A tile of replicates per workgroup was not
@@ -24,7 +25,6 @@
 // The workspace D[slot][n] bounds the replicates solved together: upk_mbar_boot_chunk(n_sample, workspace_bytes) of them, each chunk
 // run to convergence before the next.  upk_mbar_boot_solve is the host side: every refusal returns before any device call.
 #include "mbar_device.h"
-#include <cstring>
 
 using namespace up;
 using namespace up::mbar;
@@ -44,93 +44,15 @@ __global__ void __launch_bounds__(MBAR_BLOCK) k_mbar_boot_log_counts(double* __r
 template <int D>
 __global__ void __launch_bounds__(MBAR_BLOCK) k_mbar_boot_denominator(upk_mbar_states_t S, upk_mbar_samples_t X, const double* __restrict__ a_all,
                                                                        const int* __restrict__ active, double* __restrict__ denom_all) {
-    constexpr int W = mbar_state_doubles<D>();
-    __shared__ double tile[MBAR_TILE * W];
-    const int tid = threadIdx.x;
-    const double* __restrict__ a = a_all + (size_t)active[blockIdx.y] * S.n_state;
-    double* __restrict__ denom = denom_all + (size_t)blockIdx.y * X.n;
-    const long long n_raw = (long long)blockIdx.x * MBAR_BLOCK + tid;
-    const long long n = n_raw < X.n ? n_raw : X.n - 1;      // (a lane past the end repeats the last sample and stores nothing)
-    double v[D ? D : 1], E;
-    mbar_load_sample<D>(X, n, v, E);
-    double m = -INFINITY, sum = 0.;
-    for (int pass = 0; pass < 2; ++pass)
-        for (int k0 = 0; k0 < S.n_state; k0 += MBAR_TILE) {
-            const int nt = min(MBAR_TILE, S.n_state - k0);
-            __syncthreads();      // (the previous tile has been read)
-            for (int i = tid; i < nt * W; i += MBAR_BLOCK) { const int l = i / W, j = i - l * W; mbar_stage_state<D>(S, k0 + l, a[k0 + l], tile + l * W, j); }
-            __syncthreads();
-            for (int l = 0; l < nt; ++l) {
-                const double* __restrict__ st = tile + l * W;
-                if (st[0] == -INFINITY) continue;      // N_l = 0
-                const double x = st[0] - st[1] * mbar_energy<D>(v, E, st, S);
-                if (pass == 0) m = fmax(m, x); else sum += exp(x - m);
-            }
-        }
-    if (n_raw < X.n) denom[n] = m + log(sum);
-}
-
-// the largest of v[j] over the workgroup, for every j; every lane receives it
-template <int K>
-__device__ __forceinline__ void boot_block_max(double (&v)[K], double (*part)[MBAR_FE]) {
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-#pragma unroll
-    for (int k = 0; k < K; ++k) {
-        double w = v[k];
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) w = fmax(w, __shfl_xor(w, o, 64));
-        if (lane == 0) part[wave][k] = w;
-    }
-    __syncthreads();
-#pragma unroll
-    for (int k = 0; k < K; ++k) {
-        double t = part[0][k];
-#pragma unroll
-        for (int w = 1; w < CV_WAVES; ++w) t = fmax(t, part[w][k]);
-        v[k] = t;
-    }
+    mbar_denominator_body<D>(S, X, a_all + (size_t)active[blockIdx.y] * S.n_state, denom_all + (size_t)blockIdx.y * X.n);
 }
 
 template <int D>
 __global__ void __launch_bounds__(MBAR_BLOCK) k_mbar_boot_free_energy(upk_mbar_states_t S, upk_mbar_samples_t X, const count_t* __restrict__ counts_all,
                                                                        const double* __restrict__ log_count, const int* __restrict__ active,
                                                                        const double* __restrict__ denom_all, double* __restrict__ f_new) {
-    constexpr int W = mbar_state_doubles<D>();
-    __shared__ double st[MBAR_FE][W];
-    __shared__ double part[CV_WAVES][CV_MAX_SUMS];
-    __shared__ double partm[CV_WAVES][MBAR_FE];
-    const int tid = threadIdx.x, k0 = blockIdx.x * MBAR_FE;
-    const count_t* __restrict__ counts = counts_all + (size_t)active[blockIdx.y] * X.n;
-    const double* __restrict__ denom = denom_all + (size_t)blockIdx.y * X.n;
-    if (tid < MBAR_FE * W) { const int l = tid / W, j = tid - l * W; mbar_stage_state<D>(S, min(k0 + l, S.n_state - 1), 0., st[l], j); }
-    __syncthreads();
-    double m[MBAR_FE], s[MBAR_FE];
-#pragma unroll
-    for (int l = 0; l < MBAR_FE; ++l) { m[l] = -INFINITY; s[l] = 0.; }
-    for (long long n = tid; n < X.n; n += MBAR_BLOCK) {
-        const int c = counts[n];
-        if (!c) continue;
-        double v[D ? D : 1], E;
-        mbar_load_sample<D>(X, n, v, E);
-        const double dn = denom[n], lc = log_count[c];
-#pragma unroll
-        for (int l = 0; l < MBAR_FE; ++l) m[l] = fmax(m[l], lc + (-(st[l][1] * mbar_energy<D>(v, E, st[l], S)) - dn));
-    }
-    boot_block_max<MBAR_FE>(m, partm);
-    for (long long n = tid; n < X.n; n += MBAR_BLOCK) {
-        const int c = counts[n];
-        if (!c) continue;
-        double v[D ? D : 1], E;
-        mbar_load_sample<D>(X, n, v, E);
-        const double dn = denom[n], lc = log_count[c];
-#pragma unroll
-        for (int l = 0; l < MBAR_FE; ++l) s[l] += exp(lc + (-(st[l][1] * mbar_energy<D>(v, E, st[l], S)) - dn) - m[l]);
-    }
-    block_sum<MBAR_FE>(s, part);
-    if (tid == 0) {
-#pragma unroll
-        for (int l = 0; l < MBAR_FE; ++l) if (k0 + l < S.n_state) f_new[(size_t)blockIdx.y * S.n_state + k0 + l] = -(m[l] + log(s[l]));
-    }
+    mbar_free_energy_body<D, true>(S, X, counts_all + (size_t)active[blockIdx.y] * X.n, log_count, denom_all + (size_t)blockIdx.y * X.n,
+                                   f_new + (size_t)blockIdx.y * S.n_state);
 }
 
 // one workgroup per active replicate: f = f' - f'_0, a = ln N + f, delta[slot] = max_k |f'_k - f_k| (a NaN is kept)
@@ -176,7 +98,7 @@ __global__ void __launch_bounds__(MBAR_BLOCK) k_mbar_boot_columns(long long n_sa
         if (!c || x == -INFINITY) continue;
         m[0] = fmax(m[0], log_count[c] + (x - denom[n]));
     }
-    boot_block_max<1>(m, partm);
+    mbar_block_max<1>(m, partm);
     if (m[0] != -INFINITY)      // (uniform: every lane holds the workgroup's maximum)
         for (long long n = tid; n < n_sample; n += MBAR_BLOCK) {
             const int c = counts[n];
@@ -242,9 +164,8 @@ struct PinnedBuffer {
 // every refusal of upside_hip_mbar_bootstrap; nothing here touches the device
 void boot_check(const upk_mbar_boot_problem_t& P) {
     // the samples, the states, tol, max_iter and f0: the refusals of upside_hip_mbar, one statement of them
-    upk_mbar_problem_t Q{};
-    Q.n_sample = P.n_sample; Q.n_state = P.n_state; Q.d = P.d; Q.values = P.values; Q.energy = P.energy; Q.beta = P.beta; Q.rows = P.rows;
-    Q.n_k = P.n_k; Q.periods = P.periods; Q.tol = P.tol; Q.max_iter = P.max_iter; Q.f0 = P.f0; Q.f = P.f_boot;      // (only tested against NULL)
+    upk_mbar_problem_t Q = as_mbar_problem(P);
+    Q.tol = P.tol; Q.max_iter = P.max_iter; Q.f0 = P.f0; Q.f = P.f_boot;
     if (!P.f_boot) MBAR_REFUSE("mbar_bootstrap: f_boot must be given");
     mbar_check(Q);
     if (P.n_replicate < 1) MBAR_REFUSE("mbar_bootstrap: n_replicate = %d, at least one replicate is needed", P.n_replicate);
@@ -284,31 +205,21 @@ void boot_check(const upk_mbar_boot_problem_t& P) {
 
 void boot_run(const upk_mbar_boot_problem_t& P) {
     boot_check(P);
-    int n_dev = 0;
-    if (hipGetDeviceCount(&n_dev) != hipSuccess || n_dev < 1) MBAR_REFUSE("mbar_bootstrap: no HIP device (this library has no CPU path)");
-    const int K = P.n_state, d = P.d, B = P.n_replicate, J = P.n_column;
+    StagedProblem staged(P);      // the samples, the states and the columns go to the device once
+    const upk_mbar_states_t& S = staged.S; const upk_mbar_samples_t& X = staged.X; Stream& st = staged.st;
+    const int K = P.n_state, B = P.n_replicate, J = P.n_column;
     const size_t N = (size_t)P.n_sample;
     const int chunk = (int)std::min<long long>(B, upk_mbar_boot_chunk(P.n_sample, P.workspace_bytes ? P.workspace_bytes : (size_t)UPK_MBAR_GRAM_MAX_WORKSPACE));
-    Stream st; hip_ok(hipStreamCreate(&st.s), "hipStreamCreate");
-    DeviceBuffer values, energy, beta, rows, ln_n, log_count, lognum, counts, a, f, f_new, denom, active, delta, column;
+    DeviceBuffer ln_n, log_count, lognum, counts, a, f, f_new, denom, active, delta, column;
     PinnedBuffer active_h, delta_h;
-    auto upload = [&](DeviceBuffer& buf, const void* src, size_t bytes, const char* what) {
-        buf.alloc(bytes, what); hip_ok(hipMemcpyAsync(buf.p, src, bytes, hipMemcpyHostToDevice, st.s), what);
-    };
-    // the samples, the states and the columns go to the device once
-    if (d) upload(values, P.values, N * d * sizeof(float), "copy of values");
-    if (P.energy) upload(energy, P.energy, N * sizeof(double), "copy of energy");
-    upload(beta, P.beta, K * sizeof(double), "copy of beta");
-    if (d) upload(rows, P.rows, (size_t)K * 3 * d * sizeof(float), "copy of rows");
-    std::vector<double> ln_n_h(K), start((size_t)chunk * K), a0((size_t)chunk * K);
-    for (int k = 0; k < K; ++k) ln_n_h[k] = P.n_k[k] > 0 ? std::log((double)P.n_k[k]) : -INFINITY;
-    for (int b = 0; b < chunk; ++b)
-        for (int k = 0; k < K; ++k) {
-            const double f0 = P.f0 ? P.f0[k] : 0.;
-            start[(size_t)b * K + k] = f0; a0[(size_t)b * K + k] = P.n_k[k] > 0 ? ln_n_h[k] + f0 : -INFINITY;
-        }
-    upload(ln_n, ln_n_h.data(), K * sizeof(double), "copy of n_k");
-    if (J) upload(lognum, P.log_numerator, (size_t)J * N * sizeof(double), "copy of log_numerator");
+    const std::vector<double> ln_n_h = log_sample_counts(P.n_k, K);
+    std::vector<double> start((size_t)chunk * K, 0.), a0((size_t)chunk * K);
+    for (int b = 0; b < chunk; ++b) {
+        if (P.f0) std::copy(P.f0, P.f0 + K, start.begin() + (size_t)b * K);
+        log_counts_plus_f(ln_n_h, P.f0, a0.data() + (size_t)b * K);
+    }
+    ln_n.upload(st.s, ln_n_h.data(), K * sizeof(double), "copy of n_k");
+    if (J) lognum.upload(st.s, P.log_numerator, (size_t)J * N * sizeof(double), "copy of log_numerator");
     log_count.alloc(BOOT_COUNTS * sizeof(double), "log-count table");
     counts.alloc((size_t)chunk * N * sizeof(count_t), "counts"); denom.alloc((size_t)chunk * N * sizeof(double), "denominators");
     a.alloc((size_t)chunk * K * sizeof(double), "a"); f.alloc((size_t)chunk * K * sizeof(double), "f"); f_new.alloc((size_t)chunk * K * sizeof(double), "f");
@@ -317,9 +228,6 @@ void boot_run(const upk_mbar_boot_problem_t& P) {
     active_h.alloc((size_t)chunk * sizeof(int), "active"); delta_h.alloc((size_t)chunk * sizeof(double), "delta");
     int* act = active_h.as<int>(); const double* dl = delta_h.as<double>();
 
-    upk_mbar_states_t S{}; S.d = d; S.n_state = K; S.beta = beta.as<double>(); S.rows = rows.as<float>();
-    for (int c = 0; c < d; ++c) S.period[c] = P.periods[c];
-    upk_mbar_samples_t X{}; X.n = P.n_sample; X.values = values.as<float>(); X.energy = energy.as<double>();
     upk_ok(upk_mbar_boot_log_counts(st.s, log_count.as<double>()), "log-count table");
 
     std::vector<int> iters((size_t)chunk); std::vector<double> last((size_t)chunk);
@@ -369,17 +277,8 @@ void boot_run(const upk_mbar_boot_problem_t& P) {
 }  // namespace
 
 extern "C" int upk_mbar_boot_solve(const upk_mbar_boot_problem_t* P, char* message, int message_len) {
-    if (message && message_len > 0) message[0] = 0;
-    try {
+    return guarded_entry("mbar_bootstrap", message, message_len, [&] {
         if (!P) MBAR_REFUSE("mbar_bootstrap: no problem given");
         boot_run(*P);
-        return 0;
-    } catch (const MbarRefusal& r) {
-        // the checks and helpers shared with upside_hip_mbar say "mbar: ..."; the message names the entry point that refused
-        const bool shared = !strncmp(r.text, "mbar: ", 6);
-        if (message && message_len > 0) snprintf(message, (size_t)message_len, "%s%s", shared ? "mbar_bootstrap: " : "", r.text + (shared ? 6 : 0));
-    } catch (const std::exception& e) {
-        if (message && message_len > 0) snprintf(message, (size_t)message_len, "mbar_bootstrap: %s", e.what());
-    }
-    return 1;
+    });
 }

@@ -23,7 +23,6 @@
 //     samples t, t + 256, ... ascending, block_sum).  It needs no workspace and is the whole of a call with G == NULL.
 // upk_mbar_gram_solve is the host side of upside_hip_mbar_gram: every refusal returns before any device call.
 #include "mbar_device.h"
-#include <cstring>
 
 using namespace up;
 using namespace up::mbar;
@@ -68,10 +67,7 @@ __global__ void __launch_bounds__(MBAR_BLOCK) k_mbar_gram_slab(upk_mbar_states_t
     mbar_load_sample<D>(X, n, v, E);
     const double dn = denom[n];
     for (int k0 = 0; k0 < S.n_state; k0 += MBAR_TILE) {
-        const int nt = min(MBAR_TILE, S.n_state - k0);
-        __syncthreads();      // (the previous tile has been read)
-        for (int i = tid; i < nt * W; i += MBAR_BLOCK) { const int l = i / W, j = i - l * W; mbar_stage_state<D>(S, k0 + l, f[k0 + l], tile + l * W, j); }
-        __syncthreads();
+        const int nt = mbar_stage_tile<D>(S, k0, f, tile);
         if (r < rows_pad)
             for (int l = 0; l < nt; ++l) {
                 const double* __restrict__ st = tile + l * W;
@@ -177,7 +173,7 @@ __global__ void __launch_bounds__(MBAR_BLOCK) k_mbar_gram_colsum(upk_mbar_states
     __shared__ double st[MBAR_FE][W];
     __shared__ double part[CV_WAVES][CV_MAX_SUMS];
     const int tid = threadIdx.x, k0 = blockIdx.x * MBAR_FE;
-    if (tid < MBAR_FE * W) { const int l = tid / W, j = tid - l * W, k = min(k0 + l, S.n_state - 1); mbar_stage_state<D>(S, k, f[k], st[l], j); }
+    mbar_stage_fe<D, true>(S, k0, f, st);
     __syncthreads();
     double s[MBAR_FE];
 #pragma unroll
@@ -277,9 +273,8 @@ void gram_check(const upk_mbar_gram_problem_t& P) {
     if (!P.f) MBAR_REFUSE("mbar_gram: f must be given");
     if (P.n_extra > 0 && !P.log_extra) MBAR_REFUSE("mbar_gram: log_extra must be given when n_extra > 0");
     // the samples and the states: the refusals of upside_hip_mbar, one statement of them
-    upk_mbar_problem_t Q{};
-    Q.n_sample = P.n_sample; Q.n_state = P.n_state; Q.d = P.d; Q.values = P.values; Q.energy = P.energy; Q.beta = P.beta; Q.rows = P.rows;
-    Q.n_k = P.n_k; Q.periods = P.periods; Q.tol = 0.; Q.max_iter = 1; Q.f = const_cast<double*>(P.f);      // (only tested against NULL)
+    upk_mbar_problem_t Q = as_mbar_problem(P);
+    Q.tol = 0.; Q.max_iter = 1; Q.f = const_cast<double*>(P.f);
     mbar_check(Q);
     if (!all_finite(P.f, (size_t)P.n_state, &at)) MBAR_REFUSE("mbar_gram: f[%zu] is not finite", at);
     const size_t N = (size_t)P.n_sample;
@@ -292,31 +287,20 @@ void gram_check(const upk_mbar_gram_problem_t& P) {
 
 void gram_run(const upk_mbar_gram_problem_t& P) {
     gram_check(P);
-    int n_dev = 0;
-    if (hipGetDeviceCount(&n_dev) != hipSuccess || n_dev < 1) MBAR_REFUSE("mbar_gram: no HIP device (this library has no CPU path)");
-    const int K = P.n_state, d = P.d, M = K + P.n_extra;
+    StagedProblem staged(P);
+    const upk_mbar_states_t& S = staged.S; const upk_mbar_samples_t& X = staged.X; Stream& st = staged.st;
+    const int K = P.n_state, M = K + P.n_extra;
     const size_t N = (size_t)P.n_sample;
-    Stream st; hip_ok(hipStreamCreate(&st.s), "hipStreamCreate");
-    DeviceBuffer values, energy, beta, rows, a, f_dev, denom, extra, G, colsum, work;
-    auto upload = [&](DeviceBuffer& b, const void* src, size_t bytes, const char* what) {
-        b.alloc(bytes, what); hip_ok(hipMemcpyAsync(b.p, src, bytes, hipMemcpyHostToDevice, st.s), what);
-    };
-    if (d) upload(values, P.values, N * d * sizeof(float), "copy of values");
-    if (P.energy) upload(energy, P.energy, N * sizeof(double), "copy of energy");
-    upload(beta, P.beta, K * sizeof(double), "copy of beta");
-    if (d) upload(rows, P.rows, (size_t)K * 3 * d * sizeof(float), "copy of rows");
+    DeviceBuffer a, f_dev, denom, extra, G, colsum, work;
     std::vector<double> av(K);
-    for (int k = 0; k < K; ++k) av[k] = P.n_k[k] > 0 ? std::log((double)P.n_k[k]) + P.f[k] : -INFINITY;
-    upload(a, av.data(), K * sizeof(double), "copy of f");
-    upload(f_dev, P.f, K * sizeof(double), "copy of f");
-    if (P.n_extra) upload(extra, P.log_extra, (size_t)P.n_extra * N * sizeof(double), "copy of log_extra");
+    log_counts_plus_f(log_sample_counts(P.n_k, K), P.f, av.data());
+    a.upload(st.s, av.data(), K * sizeof(double), "copy of f");
+    f_dev.upload(st.s, P.f, K * sizeof(double), "copy of f");
+    if (P.n_extra) extra.upload(st.s, P.log_extra, (size_t)P.n_extra * N * sizeof(double), "copy of log_extra");
     denom.alloc(N * sizeof(double), "denominators"); colsum.alloc(M * sizeof(double), "colsum");
     const size_t work_bytes = P.G ? gram_public_workspace(M) : 0;
     if (P.G) { G.alloc((size_t)M * M * sizeof(double), "G"); work.alloc(work_bytes, "workspace"); }
 
-    upk_mbar_states_t S{}; S.d = d; S.n_state = K; S.beta = beta.as<double>(); S.rows = rows.as<float>();
-    for (int c = 0; c < d; ++c) S.period[c] = P.periods[c];
-    upk_mbar_samples_t X{}; X.n = P.n_sample; X.values = values.as<float>(); X.energy = energy.as<double>();
     upk_ok(upk_mbar_denominator(st.s, &S, &X, a.as<double>(), denom.as<double>()), "denominator pass");
     upk_ok(upk_mbar_gram(st.s, &S, &X, denom.as<double>(), f_dev.as<double>(), P.n_extra, extra.as<double>(), G.as<double>(), colsum.as<double>(),
                          work.p, work_bytes), "Gram pass");
@@ -329,17 +313,8 @@ void gram_run(const upk_mbar_gram_problem_t& P) {
 }  // namespace
 
 extern "C" int upk_mbar_gram_solve(const upk_mbar_gram_problem_t* P, char* message, int message_len) {
-    if (message && message_len > 0) message[0] = 0;
-    try {
+    return guarded_entry("mbar_gram", message, message_len, [&] {
         if (!P) MBAR_REFUSE("mbar_gram: no problem given");
         gram_run(*P);
-        return 0;
-    } catch (const MbarRefusal& r) {
-        // the checks and helpers shared with upside_hip_mbar say "mbar: ..."; the message names the entry point that refused
-        const bool shared = !strncmp(r.text, "mbar: ", 6);
-        if (message && message_len > 0) snprintf(message, (size_t)message_len, "%s%s", shared ? "mbar_gram: " : "", r.text + (shared ? 6 : 0));
-    } catch (const std::exception& e) {
-        if (message && message_len > 0) snprintf(message, (size_t)message_len, "mbar_gram: %s", e.what());
-    }
-    return 1;
+    });
 }

@@ -39,7 +39,6 @@
 // upk_series_solve is the host side: every refusal returns before any device call.
 #include "mbar_device.h"
 #include <chrono>
-#include <cstring>
 
 using namespace up;
 using namespace up::mbar;
@@ -277,8 +276,7 @@ struct Event {
 
 void series_run(const upk_series_problem_t& P) {
     series_check(P);
-    int n_dev = 0;
-    if (hipGetDeviceCount(&n_dev) != hipSuccess || n_dev < 1) MBAR_REFUSE("series: no HIP device (this library has no CPU path)");
+    require_device();
     const int K = P.n_series, J = P.n_origin;
     const size_t KJ = (size_t)K * J;
     const auto wall0 = std::chrono::steady_clock::now();
@@ -308,11 +306,8 @@ void series_run(const upk_series_problem_t& P) {
     Event ev0, ev1;
     hip_ok(hipEventCreate(&ev0.e), "hipEventCreate"); hip_ok(hipEventCreate(&ev1.e), "hipEventCreate");
     DeviceBuffer length, origin, d, shift, seg, delta, s2, gsum, head, last, stop, g, mean, variance, pstart, plen, poff, sfirst, Pb, Sb, active, list;
-    auto upload = [&](DeviceBuffer& b, const void* src, size_t bytes, const char* what) {
-        b.alloc(bytes, what); if (bytes) hip_ok(hipMemcpyAsync(b.p, src, bytes, hipMemcpyHostToDevice, st.s), what);
-    };
-    upload(length, P.length, K * sizeof(long long), "copy of length");
-    upload(origin, P.origin, J * sizeof(long long), "copy of origin");
+    length.upload(st.s, P.length, K * sizeof(long long), "copy of length");
+    origin.upload(st.s, P.origin, J * sizeof(long long), "copy of origin");
     d.alloc((size_t)K * P.stride * sizeof(double), "series");
     bool whole = true;
     for (int k = 0; k < K; ++k) whole = whole && P.length[k] == P.stride;
@@ -320,10 +315,10 @@ void series_run(const upk_series_problem_t& P) {
     else
         for (int k = 0; k < K; ++k)      // (what lies past a series' length is never read, on either side)
             hip_ok(hipMemcpyAsync(d.as<double>() + (size_t)k * P.stride, P.a + (size_t)k * P.stride, (size_t)P.length[k] * sizeof(double), hipMemcpyHostToDevice, st.s), "copy of the series");
-    upload(pstart, piece_start.data(), n_piece * sizeof(long long), "copy of the pieces");
-    upload(plen, piece_len.data(), n_piece * sizeof(int), "copy of the pieces");
-    upload(poff, piece_off.data(), (K + 1) * sizeof(long long), "copy of the pieces");
-    upload(sfirst, seg_first.data(), seg_first.size() * sizeof(int), "copy of the pieces");
+    pstart.upload(st.s, piece_start.data(), n_piece * sizeof(long long), "copy of the pieces");
+    plen.upload(st.s, piece_len.data(), n_piece * sizeof(int), "copy of the pieces");
+    poff.upload(st.s, piece_off.data(), (K + 1) * sizeof(long long), "copy of the pieces");
+    sfirst.upload(st.s, seg_first.data(), seg_first.size() * sizeof(int), "copy of the pieces");
     shift.alloc((size_t)K * 2 * sizeof(double), "workspace"); seg.alloc(KJ * 2 * sizeof(double), "workspace");
     for (DeviceBuffer* b : {&delta, &s2, &gsum, &head, &last, &g, &mean, &variance}) b->alloc(KJ * sizeof(double), "workspace");
     stop.alloc(KJ * sizeof(long long), "workspace");
@@ -382,19 +377,10 @@ void series_run(const upk_series_problem_t& P) {
 }  // namespace
 
 extern "C" int upk_series_solve(const upk_series_problem_t* P, char* message, int message_len) {
-    if (message && message_len > 0) message[0] = 0;
-    try {
+    return guarded_entry("series", message, message_len, [&] {
         if (!P) MBAR_REFUSE("series: no problem given");
         series_run(*P);
-        return 0;
-    } catch (const MbarRefusal& r) {
-        // the helpers shared with upside_hip_mbar say "mbar: ..."; the message names the entry point that refused
-        const bool shared = !strncmp(r.text, "mbar: ", 6);
-        if (message && message_len > 0) snprintf(message, (size_t)message_len, "%s%s", shared ? "series: " : "", r.text + (shared ? 6 : 0));
-    } catch (const std::exception& e) {
-        if (message && message_len > 0) snprintf(message, (size_t)message_len, "series: %s", e.what());
-    }
-    return 1;
+    });
 }
 extern "C" int upk_series_lag_block(void) { return SER_LAGS; }
 extern "C" int upk_series_piece(void) { return SER_PIECE; }
