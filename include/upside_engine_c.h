@@ -378,8 +378,8 @@ int upside_hip_mbar_gram(long long n_sample, int n_state, int d, const float* va
  * Float64 throughout; every logsumexp takes its exact maximum first; no atomics; every sum has one order.  The bits of replicate b
  * depend neither on n_replicate, nor on which other replicates are in the batch, nor on when they converge, nor on how the batch is
  * cut into chunks (the denominators of a chunk fill at most 512 MB: 512 MB / (8 n_sample) replicates are solved at a time).
- * Bootstrapping correlated samples underestimates the errors as the asymptotic estimate does: subsample first
- * (upside_hip_series_inefficiency).
+ * Bootstrapping correlated samples one by one underestimates the errors as the asymptotic estimate does: subsample first
+ * (upside_hip_series_inefficiency), or resample blocks (upside_hip_mbar_bootstrap_drawn below).
  * Returns 0, or 1 with upside_hip_last_error set.  Refused before anything is launched or copied: everything upside_hip_mbar refuses
  * about samples, states, counts n_k, periods, tol, max_iter and f0; f_boot NULL; n_replicate < 1; counts or state_of_sample NULL; a
  * state index outside 0 .. n_state - 1 or naming a state with n_k = 0; origins that do not add up to n_k; a replicate whose counts of
@@ -390,6 +390,40 @@ int upside_hip_mbar_bootstrap(long long n_sample, int n_state, int d, const floa
                               const float* rows, const long long* n_k, const double* periods, const int* state_of_sample,
                               int n_replicate, const unsigned short* counts, double tol, int max_iter, const double* f0, int n_column,
                               const double* log_numerator, double* f_boot, double* column_boot, int* n_iter, double* last_delta);
+
+/* The same batch with the counts DRAWN ON THE DEVICE, chunk by chunk, into the buffer the solve reads (k_mbar_boot_draw*): no host
+ * array of counts, no host pass over n_replicate x n_sample, no copy of counts.  The draw is the circular block bootstrap (Politis &
+ * Romano 1992) per state, stated so that it can be restated exactly anywhere.  For replicate b (global index from 0) and state k with
+ * m = n_k[k] > 0 samples and block length L = min(max(block[k], 1), m) (block NULL: L = 1, the plain stratified bootstrap):
+ *   n_block = ceil(m / L); block j has length L, the last one m - L (n_block - 1): the lengths add up to m.
+ *   Block j starts at s_j = floor(r_j m / 2^64) (the high 64 bits of the 128-bit product), r_j from Threefry4x32-20 with
+ *     counter (q lo32, q hi32, k, b), q = j >> 1, and key (seed lo32, seed hi32, 0x4d424152, 0):
+ *     r_j = X[0] | X[1] << 32 for even j, X[2] | X[3] << 32 for odd j.
+ *   Block j covers the positions (s_j + t) mod m, t = 0 .. length_j - 1, of the state's samples in their order of appearance
+ *     (state_of_sample), and the count of a sample is the number of blocks that cover it.  States with n_k = 0 are skipped.
+ * So per state the counts add up to n_k by construction, and a replicate's counts depend on (seed, b, k, n_k[k], block[k]) alone: not
+ * on n_replicate, the chunking, the other replicates or the layout.  Integer sums only: the bits are the definition's.  Blocks keep
+ * runs of consecutive samples together, so block > 1 asks for each state's samples in time order; block[k] of a few statistical
+ * inefficiencies (mbar.block_lengths of the Python layer: 5 g) keeps the error bars of correlated series honest without discarding
+ * samples.
+ *   upside_hip_mbar_bootstrap_drawn: the arguments of upside_hip_mbar_bootstrap with counts replaced by seed, block ([n_state] or
+ *     NULL) and counts_out ([n_replicate][n_sample] uint16 or NULL: the drawn counts, copied back only when asked for).  The
+ *     replicates are b = 0 .. n_replicate - 1.  Given the same counts, upside_hip_mbar_bootstrap returns the same bits.
+ *   upside_hip_mbar_bootstrap_counts: the draw alone, replicates first_replicate .. first_replicate + n_replicate - 1 into counts_out;
+ *     state_of_sample NULL: the samples are grouped by state.
+ * A count above 65535 cannot be stored: the device raises a flag and the call fails naming the replicate and the state (the expected
+ * coverage of a position is 1, so no legitimate input comes near).
+ * Return 0, or 1 with upside_hip_last_error set.  Refused before anything is launched or copied: everything upside_hip_mbar_bootstrap
+ * refuses apart from what concerns counts (_counts: about n_state, n_k, n_sample and state_of_sample); block[k] < 1; a first_replicate
+ * or n_replicate that is negative, or replicate indices that reach 2^32; counts_out NULL (_counts).  block[k] > n_k[k] is clipped: one
+ * block covers the whole series and every count is 1. */
+int upside_hip_mbar_bootstrap_drawn(long long n_sample, int n_state, int d, const float* values, const double* energy, const double* beta,
+                                    const float* rows, const long long* n_k, const double* periods, const int* state_of_sample,
+                                    int n_replicate, unsigned long long seed, const long long* block, unsigned short* counts_out, double tol,
+                                    int max_iter, const double* f0, int n_column, const double* log_numerator, double* f_boot,
+                                    double* column_boot, int* n_iter, double* last_delta);
+int upside_hip_mbar_bootstrap_counts(int n_state, const long long* n_k, long long n_sample, const int* state_of_sample, long long n_replicate,
+                                     long long first_replicate, unsigned long long seed, const long long* block, unsigned short* counts_out);
 
 /* Statistical inefficiency of recorded series at a set of origins (csrc/kernels_series.hip): what equilibration detection (Chodera
  * 2016) and subsampling to uncorrelated samples (Chodera et al. 2007) are built on, and what the covariance from upside_hip_mbar_gram

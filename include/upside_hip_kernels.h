@@ -725,6 +725,37 @@ typedef struct {
 } upk_mbar_boot_problem_t;
 int upk_mbar_boot_solve(const upk_mbar_boot_problem_t* P, char* message /* host */, int message_len);
 
+/* The counts drawn on the device (upside_hip_mbar_bootstrap_drawn and upside_hip_mbar_bootstrap_counts of include/upside_engine_c.h, which
+ * states the draw): the circular block bootstrap per state, from the counter-based Threefry4x32-20.
+ * upk_mbar_boot_draw fills counts[slot][n_sample] (uint16, device) for the n_replicate replicates first_replicate + slot.  The samples
+ * of state k are the positions start[k] .. start[k + 1] - 1 of the GROUPED order (start: device [n_state + 1], start[0] = 0,
+ * start[n_state] = n_sample); length[k] (device [n_state]) is the block length of state k, clipped to 1 .. n_k[k] by the caller;
+ * position p of the grouped order is sample order[p] (device [n_sample], the stable argsort of state_of_sample), or p where order is
+ * NULL.  A state of at most UPK_MBAR_BOOT_DRAW_TILE samples is counted by one workgroup in LDS (integer LDS atomics) and stored once;
+ * a larger one is counted by integer global atomics into scratch[slot][n_sample] (device int32, zeroed by the launcher), then narrowed
+ * to uint16 and stored.  largest_state = max_k n_k[k]: scratch may be NULL where it does not exceed the tile.  Integer sums have no
+ * order, so both paths give the bits of the definition.  A count above 65535 is stored as 65535 and
+ * *flag = min(*flag, (first_replicate + slot) << 32 | k); the caller sets *flag (device) to all ones before.  Every pointer is a device
+ * pointer.  Returns the launch's hipError_t or 9415 for arguments it cannot launch.
+ * upk_mbar_boot_solve_drawn is the HOST side of upside_hip_mbar_bootstrap_drawn: upk_mbar_boot_solve with P->counts == NULL and the
+ * counts of every chunk drawn in place by upk_mbar_boot_draw (no host array of counts unless D->counts_out is given, no pass over
+ * B x N on the host).  upk_mbar_boot_draw_solve is the host side of upside_hip_mbar_bootstrap_counts: the draw alone.  Both: 0, or 1
+ * with the reason in message; every refusal returns before any device call. */
+#define UPK_MBAR_BOOT_DRAW_TILE 8192
+#define UPK_MBAR_BOOT_DRAW_KEY 0x4d424152u   /* key word 2 of the draw's generator */
+int upk_mbar_boot_draw(void* stream, int n_state, long long n_sample, const int* start, const int* length, const int* order, int n_replicate,
+                       unsigned int first_replicate, unsigned long long seed, long long largest_state, int* scratch, unsigned short* counts,
+                       unsigned long long* flag);
+typedef struct {
+    unsigned long long seed;
+    const long long* block;              /* host [n_state] block lengths, each >= 1 (clipped to n_k); NULL = 1 everywhere */
+    long long first_replicate;           /* the global index of replicate 0 of the call */
+    unsigned short* counts_out;          /* host out [n_replicate][n_sample] or NULL */
+} upk_mbar_boot_draw_t;
+int upk_mbar_boot_solve_drawn(const upk_mbar_boot_problem_t* P, const upk_mbar_boot_draw_t* D, char* message /* host */, int message_len);
+int upk_mbar_boot_draw_solve(int n_state, const long long* n_k, long long n_sample, const int* state_of_sample /* or NULL: grouped */,
+                             long long n_replicate, const upk_mbar_boot_draw_t* D, char* message /* host */, int message_len);
+
 /* ---- statistical inefficiency of recorded series (upside_hip_series_inefficiency), csrc/kernels_series.hip ----------------------------
  * upk_series_solve is the HOST side of upside_hip_series_inefficiency (include/upside_engine_c.h states the definition and the
  * refusals): every pointer is a host pointer; the checks come before any device call; 0, or 1 with the reason in message.  The

@@ -1,6 +1,6 @@
 """MBAR over the output files of an umbrella ladder run by `upside_hip`, on the GPU.
 
-    python tools/umbrella_mbar.py --temperature 0.85 [--node cv_restraint] [--bins 40] [--tol 1e-8] [--solver newton] [--uncertainty] [--decorrelate] [--bootstrap B [--seed S]] w00.up ...
+    python tools/umbrella_mbar.py --temperature 0.85 [--node cv_restraint] [--bins 40] [--tol 1e-8] [--solver newton] [--uncertainty] [--decorrelate] [--bootstrap B [--seed S] [--bootstrap-draw device [--bootstrap-block N|auto]]] w00.up ...
 
 Every file is one window: its `cv_restraint` node (`--node`) holds the window's centre, spring constant and flat width, and its
 /output/cv holds the CV series the run recorded at the frames (the CVs of /input/collective_variables; samples follow the window,
@@ -11,7 +11,11 @@ f_k - f_0 and a dF column to the profile (relative to the lowest bin; the frames
 for frames written more often than the correlation time; it is a large-sample estimate); `--bootstrap B` prints the BOOTSTRAP standard
 deviation of f_k - f_0 and of the profile from B stratified resamples (every window keeps its frame count; `--seed` seeds the draw),
 all solved in one batch on the GPU -- beside the asymptotic one with `--uncertainty`, in its place without; bootstrapping correlated
-frames underestimates the errors, so `--decorrelate` goes with it; `--solver newton` converges a poorly overlapping ladder in a few
+frames underestimates the errors, so `--decorrelate` goes with it -- or `--bootstrap-draw device --bootstrap-block auto`, which draws the
+counts on the GPU as a circular block bootstrap with blocks of 5 g frames per window (mbar.block_lengths; g the statistical
+inefficiency of the window's own reduced bias over all its frames) and keeps every frame; `--bootstrap-block N` sets the block length
+itself, `--bootstrap-draw device` alone is the plain stratified resample drawn on the GPU (another stream of random numbers than the
+default `host`); `--solver newton` converges a poorly overlapping ladder in a few
 steps.  `--decorrelate` drops the start of every window up to the detected equilibration origin
 t0 and keeps every ceil(g)-th frame of the rest, g the statistical inefficiency of the window's own reduced bias
 (timeseries.detect_equilibration on the GPU); it prints one line per window (t0, g, frames kept) before the free energies."""
@@ -47,13 +51,18 @@ def read_window(h5lite, config, path, node):
     return series.reshape(series.shape[0], -1), recorded, names, row, periods
 
 
-def decorrelate(pkg, values, rows, periods, kT):
-    """the kept frames of every window; prints one line per window"""
+def own_bias(pkg, values, rows, periods, kT):
+    """(bias (K, T) padded with zeros, lengths (K,)): every window's own reduced bias along its frames"""
     T = max(len(v) for v in values)
     bias = np.zeros((len(values), T))
     for k, v in enumerate(values):
         bias[k, :len(v)] = pkg.mbar.own_state_reduced_bias(v, 1. / kT, rows[k][None, :], periods, np.zeros(len(v), 'i8'))
-    lengths = np.array([len(v) for v in values], 'i8')
+    return bias, np.array([len(v) for v in values], 'i8')
+
+
+def decorrelate(pkg, values, rows, periods, kT):
+    """the kept frames of every window; prints one line per window"""
+    bias, lengths = own_bias(pkg, values, rows, periods, kT)
     t0, g, n_eff = pkg.timeseries.detect_equilibration(bias, lengths=lengths)
     print('# window  equilibrated from t0  statistical inefficiency g  frames kept of')
     out = []
@@ -78,7 +87,18 @@ def main():
     ap.add_argument('--decorrelate', action='store_true', help='detect equilibration and subsample every window to uncorrelated frames first')
     ap.add_argument('--bootstrap', type=int, default=0, metavar='B', help='print bootstrap standard deviations from B stratified resamples')
     ap.add_argument('--seed', type=int, default=0, help='the seed of the bootstrap resamples')
+    ap.add_argument('--bootstrap-draw', choices=('host', 'device'), default='host', help='where the bootstrap counts are drawn')
+    ap.add_argument('--bootstrap-block', default=None, metavar='N|auto', help='block length of the circular block bootstrap (with --bootstrap-draw device)')
     args = ap.parse_args()
+    if args.bootstrap_block is not None and args.bootstrap_draw != 'device':
+        raise SystemExit('--bootstrap-block needs --bootstrap-draw device')
+    if args.bootstrap_block == 'auto' and args.decorrelate:
+        raise SystemExit('--bootstrap-block auto with --decorrelate: the kept frames are already uncorrelated')
+    if args.bootstrap_block not in (None, 'auto'):
+        try:
+            args.bootstrap_block = int(args.bootstrap_block)
+        except ValueError:
+            raise SystemExit('--bootstrap-block takes a block length or auto, got %r' % args.bootstrap_block)
     pkg = load_package()
     values, rows, n_k, names0, periods0 = [], [], [], None, None
     for path in args.files:
@@ -105,8 +125,15 @@ def main():
     sigma_boot, counts = None, None
     if args.bootstrap > 0:      # the windows are concatenated, so the samples are grouped by window: the default origins
         import warnings
-        boot = pkg.mbar.bootstrap(*problem, r['f'], n_bootstrap=args.bootstrap, seed=args.seed, periods=periods0, tol=args.tol, max_iter=args.max_iter)
-        counts = boot['counts']
+        block = args.bootstrap_block
+        if block == 'auto':
+            bias, lengths = own_bias(pkg, values, rows, periods0, kT)
+            g = pkg.timeseries.statistical_inefficiency(bias, lengths=lengths)['g'][:, 0]
+            block = pkg.mbar.block_lengths(g)
+            print('# bootstrap blocks: statistical inefficiency g = %s, block lengths %s' % (np.round(g, 3).tolist(), block.tolist()))
+        drawn = dict(draw=args.bootstrap_draw, block=block)
+        boot = pkg.mbar.bootstrap(*problem, r['f'], n_bootstrap=args.bootstrap, seed=args.seed, periods=periods0, tol=args.tol, max_iter=args.max_iter, **drawn)
+        counts = boot.get('counts')      # (drawn on the device, the same seed gives the profile below the same counts)
         with warnings.catch_warnings():
             warnings.simplefilter('ignore', RuntimeWarning)
             sigma_boot = pkg.mbar.bootstrap_sigma(boot)
@@ -129,7 +156,7 @@ def main():
     dF_boot = None
     if args.bootstrap > 0:
         _, dF_boot = pkg.mbar.profile_bootstrap(*problem, r['f'], edges, kT, period=periods0[0], target=(1. / kT, None), periods=periods0, cv=0, counts=counts,
-                                                tol=args.tol, max_iter=args.max_iter)
+                                                n_bootstrap=args.bootstrap, seed=args.seed, tol=args.tol, max_iter=args.max_iter, **drawn)
     prof = prof - prof[np.isfinite(prof)].min()
     print('# unbiased profile along %s: bin centre, F%s%s' % (names0[0], ', dF' if args.uncertainty else '', ', bootstrap dF' if args.bootstrap > 0 else ''))
     for b in range(args.bins):

@@ -89,6 +89,36 @@ extern "C" int upside_hip_mbar_bootstrap(long long n_sample, int n_state, int d,
     return 0;
     API_CATCH(1)
 }
+// the same batch with the counts drawn on the device (upk_mbar_boot_solve_drawn), and the draw alone (upk_mbar_boot_draw_solve)
+extern "C" int upside_hip_mbar_bootstrap_drawn(long long n_sample, int n_state, int d, const float* values, const double* energy, const double* beta,
+                                               const float* rows, const long long* n_k, const double* periods, const int* state_of_sample,
+                                               int n_replicate, unsigned long long seed, const long long* block, unsigned short* counts_out, double tol,
+                                               int max_iter, const double* f0, int n_column, const double* log_numerator, double* f_boot,
+                                               double* column_boot, int* n_iter, double* last_delta) {
+    API_TRY
+    upk_mbar_boot_problem_t P{};
+    P.n_sample = n_sample; P.n_state = n_state; P.d = d; P.values = values; P.energy = energy; P.beta = beta; P.rows = rows; P.n_k = n_k;
+    P.periods = periods; P.state_of_sample = state_of_sample; P.n_replicate = n_replicate; P.tol = tol; P.max_iter = max_iter;
+    P.f0 = f0; P.n_column = n_column; P.log_numerator = log_numerator; P.f_boot = f_boot; P.column_boot = column_boot; P.n_iter = n_iter;
+    P.last_delta = last_delta;
+    upk_mbar_boot_draw_t D{};
+    D.seed = seed; D.block = block; D.counts_out = counts_out;
+    char msg[256];
+    if (upk_mbar_boot_solve_drawn(&P, &D, msg, (int)sizeof(msg))) throw string(msg);
+    return 0;
+    API_CATCH(1)
+}
+extern "C" int upside_hip_mbar_bootstrap_counts(int n_state, const long long* n_k, long long n_sample, const int* state_of_sample,
+                                                long long n_replicate, long long first_replicate, unsigned long long seed, const long long* block,
+                                                unsigned short* counts_out) {
+    API_TRY
+    upk_mbar_boot_draw_t D{};
+    D.seed = seed; D.block = block; D.first_replicate = first_replicate; D.counts_out = counts_out;
+    char msg[256];
+    if (upk_mbar_boot_draw_solve(n_state, n_k, n_sample, state_of_sample, n_replicate, &D, msg, (int)sizeof(msg))) throw string(msg);
+    return 0;
+    API_CATCH(1)
+}
 // statistical inefficiency of recorded series: the checks and the staging are upk_series_solve (kernels_series.hip)
 extern "C" int upside_hip_series_inefficiency(int n_series, long long stride, const long long* length, const double* a, int n_origin,
                                               const long long* origin, int mintime, long long max_lag, double* g, long long* stop_lag,

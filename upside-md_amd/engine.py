@@ -495,7 +495,8 @@ class Ensemble(object):
         return out
 
     def umbrella_mbar(self, node_name, kT, tol=1e-8, max_iter=10000, f0=None, target=None, series=None, solver='self-consistent',
-                      n_sc=10, uncertainty=False, decorrelate=False, n_bootstrap=0, bootstrap_seed=0):
+                      n_sc=10, uncertainty=False, decorrelate=False, n_bootstrap=0, bootstrap_seed=0, bootstrap_draw='host',
+                      bootstrap_block=None, bootstrap_block_factor=5):
         """MBAR over the umbrella ladder of the cv_restraint node `node_name` from the recorded CV series (mbar.mbar on the device):
         system s is window s with its own row [center | spring_const | flat_width] (get_param of system s) and beta = 1 / kT for all
         (one temperature: the unbiased potential cancels and is not needed).  series: (n_stored, n_system, n_cv) as read_cvs gives it,
@@ -517,12 +518,29 @@ class Ensemble(object):
         (n_system, n_system) = mbar.bootstrap_sigma over the converged replicates, n_boot_converged and boot_counts (n_bootstrap, N)
         are added; the state every sample was drawn from follows the layout of values: sample (i, s) of window s without
         decorrelate, grouped by window with it.  Bootstrapping correlated samples underestimates the errors, so decorrelate=True
-        goes with it.  n_bootstrap=0 changes nothing."""
+        goes with it -- or blocks: bootstrap_draw='device' draws the counts on the device (mbar.bootstrap(draw='device'), another
+        stream of random numbers, no host array of counts), and bootstrap_block gives it the block lengths of the circular block
+        bootstrap, which keeps every sample of a correlated series: an int, an (n_system,) array, or 'auto' =
+        mbar.block_lengths(g, bootstrap_block_factor) with g the statistical inefficiency at origin 0
+        (timeseries.statistical_inefficiency) of each window's own reduced bias, the series decorrelate forms.  'auto' with
+        decorrelate=True raises ValueError (the kept samples are already uncorrelated), and so does a bootstrap_block with
+        bootstrap_draw='host'.  With bootstrap_draw='device' the result holds boot_block (n_system,) (None without blocks) and
+        boot_g ((n_system,) with 'auto', else None) and no boot_counts.  n_bootstrap=0 changes nothing, and a call without the
+        bootstrap_draw and bootstrap_block options returns what it returned before them."""
         from . import config, mbar as _mbar
         if not (np.ndim(kT) == 0 and np.isfinite(kT) and kT > 0):
             raise ValueError('umbrella_mbar: kT must be one finite positive number (one temperature for every window)')
         if int(n_bootstrap) < 0:
             raise ValueError('umbrella_mbar: n_bootstrap must not be negative')
+        if bootstrap_draw not in ('host', 'device'):
+            raise ValueError("umbrella_mbar: bootstrap_draw must be 'host' or 'device', got %r" % (bootstrap_draw,))
+        if bootstrap_block is not None and bootstrap_draw != 'device':
+            raise ValueError("umbrella_mbar: bootstrap_block needs bootstrap_draw='device'")
+        auto_block = isinstance(bootstrap_block, str)
+        if auto_block and bootstrap_block != 'auto':
+            raise ValueError("umbrella_mbar: bootstrap_block must be an int, an (n_system,) array or 'auto'")
+        if auto_block and decorrelate:
+            raise ValueError("umbrella_mbar: bootstrap_block='auto' with decorrelate=True: the kept samples are already uncorrelated")
         with h5lite.open_file(self.config_file_path) as t:
             pot = t.group('input').group('potential')
             if node_name not in pot:
@@ -570,12 +588,24 @@ class Ensemble(object):
         if int(n_bootstrap) > 0:
             import warnings
             origin = np.repeat(np.arange(self.n_system), n_k) if decorrelate else np.tile(np.arange(self.n_system), series.shape[0])
+            boot_g, block = None, bootstrap_block
+            if auto_block:
+                from . import timeseries as _ts
+                per_window = np.ascontiguousarray(series[:, :, cols].transpose(1, 0, 2))      # (n_system, n_stored, d)
+                state = np.repeat(np.arange(self.n_system), series.shape[0])
+                bias = _mbar.own_state_reduced_bias(per_window.reshape(-1, d), beta, rows, periods, state).reshape(self.n_system, -1)
+                boot_g = np.asarray(_ts.statistical_inefficiency(bias, library=self.lib)['g'], 'f8').reshape(-1)
+                block = _mbar.block_lengths(boot_g, bootstrap_block_factor)
             boot = _mbar.bootstrap(values, None, beta, rows, n_k, out['f'], origin, int(n_bootstrap), bootstrap_seed, periods=periods, tol=tol,
-                                   max_iter=max_iter, library=self.lib)
+                                   max_iter=max_iter, library=self.lib, draw=bootstrap_draw, block=block)
             with warnings.catch_warnings():      # (the number of unconverged replicates is returned below)
                 warnings.simplefilter('ignore', RuntimeWarning)
                 sigma_boot = _mbar.bootstrap_sigma(boot)
-            extra.update(f_boot=boot['f_boot'], sigma_boot=sigma_boot, n_boot_converged=int(boot['converged'].sum()), boot_counts=boot['counts'])
+            extra.update(f_boot=boot['f_boot'], sigma_boot=sigma_boot, n_boot_converged=int(boot['converged'].sum()))
+            if bootstrap_draw == 'device':
+                extra.update(boot_block=boot['block'], boot_g=boot_g)
+            else:
+                extra.update(boot_counts=boot['counts'])
         out.update(values=values, rows=rows, periods=periods, n_k=n_k, names=names, **extra)
         return out
 

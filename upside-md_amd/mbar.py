@@ -7,7 +7,10 @@ large-sample estimate -- where a window keeps few samples or neighbours overlap 
 profile_bootstrap() below give bootstrap error bars instead, all replicates solved in one device batch (upside_hip_mbar_bootstrap,
 csrc/kernels_mbar_boot.hip); the samples are taken as uncorrelated by both, and bootstrapping correlated samples underestimates the
 errors just as the asymptotic estimate does: timeseries.py finds the equilibration origin and the statistical inefficiency of a recorded
-series on the device, and Ensemble.umbrella_mbar(decorrelate=True) applies them per window (own_state_reduced_bias is the observable)."""
+series on the device, and Ensemble.umbrella_mbar(decorrelate=True) applies them per window (own_state_reduced_bias is the observable).
+bootstrap(draw='device') draws the counts on the device instead of the host (upside_hip_mbar_bootstrap_drawn; bootstrap_counts_device
+is the draw alone), as a circular block bootstrap where block lengths are given: blocks of block_lengths(g) samples keep every sample
+of a correlated series and its error bars honest."""
 import ctypes as ct
 import numpy as np
 
@@ -18,6 +21,7 @@ GRAM_TILE = 64           # UPK_MBAR_GRAM_TILE: the Gram pass computes G in tiles
 GRAM_MAX_COLUMNS = 8192  # UPK_MBAR_GRAM_MAX_COLUMNS
 NULL_RCOND = 1e-10       # eigenvalues of I - Sigma V^T N V Sigma below this (relative) are its null space in covariance()
 BOOT_MAX_COUNT = 65535   # a bootstrap count is an unsigned 16-bit number
+BOOT_DRAW_TILE = 8192    # UPK_MBAR_BOOT_DRAW_TILE: a state of at most this many samples is counted in LDS by the device draw
 
 
 def _bind(c):
@@ -32,6 +36,13 @@ def _bind(c):
     c.upside_hip_mbar_bootstrap.restype = i32
     c.upk_mbar_boot_solve.argtypes = [vp, ct.c_char_p, i32]
     c.upk_mbar_boot_solve.restype = i32
+    u64 = ct.c_ulonglong
+    c.upside_hip_mbar_bootstrap_drawn.argtypes = [i64, i32, i32, vp, vp, vp, vp, vp, vp, vp, i32, u64, vp, vp, f64, i32, vp, i32, vp, vp, vp, vp, vp]
+    c.upside_hip_mbar_bootstrap_drawn.restype = i32
+    c.upside_hip_mbar_bootstrap_counts.argtypes = [i32, vp, i64, vp, i64, i64, u64, vp, vp]
+    c.upside_hip_mbar_bootstrap_counts.restype = i32
+    c.upk_mbar_boot_solve_drawn.argtypes = [vp, vp, ct.c_char_p, i32]
+    c.upk_mbar_boot_solve_drawn.restype = i32
     c.upk_mbar_boot_chunk.argtypes = [i64, ct.c_size_t]
     c.upk_mbar_boot_chunk.restype = i64
     c.upside_hip_last_error.restype = ct.c_char_p
@@ -353,6 +364,11 @@ class _BootProblem(ct.Structure):
                 ('column_boot', ct.c_void_p), ('n_iter', ct.c_void_p), ('last_delta', ct.c_void_p)]
 
 
+class _BootDraw(ct.Structure):
+    """upk_mbar_boot_draw_t of include/upside_hip_kernels.h"""
+    _fields_ = [('seed', ct.c_ulonglong), ('block', ct.c_void_p), ('first_replicate', ct.c_longlong), ('counts_out', ct.c_void_p)]
+
+
 def _origins(n_k, state_of_sample):
     """(state_of_sample (N,) i4, grouped): the default is the samples grouped by state, np.repeat(arange(K), n_k)"""
     n_k = np.asarray(n_k).reshape(-1).astype('i8')
@@ -398,8 +414,73 @@ def bootstrap_counts(n_k, n_bootstrap, seed=0, state_of_sample=None):
     return counts
 
 
+def _seed64(seed, who):
+    seed = int(seed)
+    if not 0 <= seed < 1 << 64:
+        raise ValueError('%s: the seed must be an unsigned 64-bit number' % who)
+    return seed
+
+
+def _block_array(block, K, who):
+    """None, or (K,) i8 block lengths from an int or a (K,) array (their range is the entry point's to refuse)"""
+    if block is None:
+        return None
+    b = np.asarray(block)
+    if b.dtype.kind not in 'iu':
+        raise ValueError('%s: block must hold integers' % who)
+    if b.ndim == 0:
+        b = np.full(K, int(b))
+    if b.shape != (K,):
+        raise ValueError('%s: block must be one integer or (%d states,), got %r' % (who, K, b.shape))
+    return np.ascontiguousarray(b, 'i8')
+
+
+def block_lengths(g, factor=5):
+    """(K,) i8 block lengths for the circular block bootstrap of series with statistical inefficiencies g: ceil(factor g), and at
+    least 1 where g < 1 (no estimate).  Why a factor, and why 5: a block bootstrap with blocks of L samples sees the correlations
+    inside a block and none across block borders.  For exponentially decaying correlations rho_t = phi^t, g = (1 + phi) / (1 - phi),
+    the variance of a mean it reports is the Bartlett-weighted sum var / n (1 + 2 sum_{t<L} (1 - t / L) phi^t) =
+    var / n (g - 2 phi / ((1 - phi)^2 L) + O(phi^L / L)), and 2 phi / (1 - phi)^2 = (g^2 - 1) / 2: it is low by (g^2 - 1) / (2 g L)
+    relative, about g / (2 L).  At L = ceil(g) the variance is about half of what it should be (sigma 30 % low); at L = factor g it
+    is low by 1 / (2 factor), so factor 5 leaves the variance 10 % and the standard deviation about 5 % low -- the sampling noise of
+    the standard deviation over 200 replicates, 1 / sqrt(2 x 200).  (AR(1) with phi = 0.8, n = 4096, g = 9: L = 9 gives 0.057, L = 40
+    gives 0.076, L = 1 gives 0.026 against the analytic 0.077.)  A larger factor buys little and leaves fewer blocks, n / L, to draw."""
+    g = np.atleast_1d(np.asarray(g, 'f8'))
+    if not (float(factor) > 0):
+        raise ValueError('mbar.block_lengths: the factor must be positive')
+    with np.errstate(invalid='ignore'):
+        L = np.ceil(float(factor) * np.where(np.isfinite(g) & (g >= 1.), g, 0.))
+    return np.maximum(L, 1.).astype('i8')
+
+
+def bootstrap_counts_device(n_k, n_bootstrap, seed=0, state_of_sample=None, block=None, first=0, library=None):
+    """(B, N) uint16: the counts of replicates first .. first + n_bootstrap - 1 of the DEVICE draw (upside_hip_mbar_bootstrap_counts;
+    include/upside_engine_c.h states it and tests/mbar_boot_draw_reference.py restates it in numpy): per state the circular block
+    bootstrap with block length min(max(block[k], 1), n_k[k]) -- block None or 1 is the plain stratified bootstrap -- from the
+    counter-based Threefry4x32-20, so a replicate's counts depend on (seed, its index, k, n_k[k], block[k]) alone.  seed: an
+    unsigned 64-bit number.  block: None, one integer or (K,).  state_of_sample as bootstrap_counts takes it; block > 1 needs each
+    state's samples in time order.  These are the counts bootstrap(draw='device') solves with and returns with want_counts=True.
+    Every refusal of the entry point raises RuntimeError with its message."""
+    from .engine import default_library
+    c = (library if library is not None else default_library()).calc
+    _bind(c)
+    who = 'mbar.bootstrap_counts_device'
+    n_k = np.ascontiguousarray(np.asarray(n_k).reshape(-1), 'i8')
+    K, N, B = len(n_k), int(n_k.sum()), int(n_bootstrap)
+    sos = None
+    if state_of_sample is not None:
+        sos, _ = _origins(n_k, state_of_sample)
+        if len(sos) != N:
+            raise ValueError('%s: state_of_sample holds %d entries for %d samples' % (who, len(sos), N))
+    blk = _block_array(block, K, who)
+    counts = np.zeros((max(B, 0), N), 'u2')
+    if c.upside_hip_mbar_bootstrap_counts(K, _ptr(n_k), N, _ptr(sos), B, int(first), _seed64(seed, who), _ptr(blk), _ptr(counts)):
+        raise RuntimeError('%s failed: %s' % (who, c.upside_hip_last_error().decode()))
+    return counts
+
+
 def bootstrap(values, energy, beta, rows, n_k, f, state_of_sample=None, n_bootstrap=200, seed=0, counts=None, periods=None, tol=1e-8,
-              max_iter=10000, log_numerators=None, library=None, workspace_bytes=None):
+              max_iter=10000, log_numerators=None, library=None, workspace_bytes=None, draw='host', block=None, want_counts=None):
     """bootstrap replicates of the problem (the arguments of mbar()), all solved in ONE batch on the device (upside_hip_mbar_bootstrap):
     replicate b weights sample n by counts[b, n] and iterates from f (the full-sample solution; None = 0) until its max |f' - f| < tol
     or max_iter; a replicate that has converged leaves the grid, the host synchronises once per iteration for all, the samples are
@@ -411,10 +492,25 @@ def bootstrap(values, energy, beta, rows, n_k, f, state_of_sample=None, n_bootst
                        at the returned f_b, +inf where no sample of the replicate contributes
       workspace_bytes  None, or the bytes the denominators of the replicates solved together may fill (at most the default, 512 MB):
                        the results do not depend on it, bit for bit
+      draw             'host' (the default): the counts are given or come from bootstrap_counts.  'device': they are drawn on the
+                       device, chunk by chunk, into the buffer the solve reads (upside_hip_mbar_bootstrap_drawn; the draw is
+                       bootstrap_counts_device's, replicates 0 .. n_bootstrap - 1 of `seed`, an unsigned 64-bit number): no host
+                       array of counts, no host pass over them, no copy.  Another stream of random numbers than 'host'.
+      block            with draw='device': None, one integer or (K,) block lengths of the circular block bootstrap, for correlated
+                       series kept whole (block_lengths(g)); each state's samples must be in time order
+      want_counts      with draw='device': True copies the drawn counts back; given the same counts, draw='host' returns the same bits
     Returns dict(f_boot (B, K), n_iter (B,), last_delta (B,), converged (B,) = last_delta < tol, counts (B, N)) and columns (B, J)
-    when columns were asked for.  The samples are taken as uncorrelated: bootstrapping correlated samples underestimates the errors,
-    so subsample first (Ensemble.umbrella_mbar(decorrelate=True), timeseries.py).  Every refusal of the entry point raises
-    RuntimeError with its message."""
+    when columns were asked for; with draw='device', counts only with want_counts=True, and seed and block (K,) i8 (None: 1) are
+    added.  The samples are taken as uncorrelated unless blocks are drawn: bootstrapping correlated samples sample by sample
+    underestimates the errors, so subsample first (Ensemble.umbrella_mbar(decorrelate=True), timeseries.py) or draw blocks.  block
+    with draw='host', counts with draw='device', or a draw that is neither raise ValueError.  Every refusal of the entry point
+    raises RuntimeError with its message."""
+    if draw not in ('host', 'device'):
+        raise ValueError("mbar.bootstrap: draw must be 'host' or 'device', got %r" % (draw,))
+    if draw == 'host' and block is not None:
+        raise ValueError("mbar.bootstrap: block lengths are drawn on the device only, pass draw='device'")
+    if draw == 'device' and counts is not None:
+        raise ValueError("mbar.bootstrap: with draw='device' the counts are drawn, none may be given")
     from .engine import default_library
     lib = library if library is not None else default_library()
     c = lib.calc
@@ -424,18 +520,25 @@ def bootstrap(values, energy, beta, rows, n_k, f, state_of_sample=None, n_bootst
     sos, _ = _origins(n_k, state_of_sample)
     if len(sos) != N:
         raise ValueError('mbar.bootstrap: state_of_sample holds %d entries for %d samples' % (len(sos), N))
-    if counts is None:
-        counts = bootstrap_counts(n_k, n_bootstrap, seed, state_of_sample)
-    cnt = np.asarray(counts)
-    if cnt.ndim == 1:
-        cnt = cnt[None, :]
-    if cnt.ndim != 2 or cnt.shape[1] != N:
-        raise ValueError('mbar.bootstrap: counts must be (B, %d samples), got %r' % (N, cnt.shape))
-    if cnt.dtype != np.uint16:
-        if cnt.dtype.kind not in 'iu' or (cnt.size and (cnt.min() < 0 or cnt.max() > BOOT_MAX_COUNT)):
-            raise ValueError('mbar.bootstrap: counts must be integers in 0 .. %d' % BOOT_MAX_COUNT)
-    cnt = np.ascontiguousarray(cnt, 'u2')
-    B = cnt.shape[0]
+    device = draw == 'device'
+    if device:
+        B = int(n_bootstrap)
+        seed = _seed64(seed, 'mbar.bootstrap')
+        blk = _block_array(block, K, 'mbar.bootstrap')
+        cnt = np.zeros((max(B, 0), N), 'u2') if want_counts else None
+    else:
+        if counts is None:
+            counts = bootstrap_counts(n_k, n_bootstrap, seed, state_of_sample)
+        cnt = np.asarray(counts)
+        if cnt.ndim == 1:
+            cnt = cnt[None, :]
+        if cnt.ndim != 2 or cnt.shape[1] != N:
+            raise ValueError('mbar.bootstrap: counts must be (B, %d samples), got %r' % (N, cnt.shape))
+        if cnt.dtype != np.uint16:
+            if cnt.dtype.kind not in 'iu' or (cnt.size and (cnt.min() < 0 or cnt.max() > BOOT_MAX_COUNT)):
+                raise ValueError('mbar.bootstrap: counts must be integers in 0 .. %d' % BOOT_MAX_COUNT)
+        cnt = np.ascontiguousarray(cnt, 'u2')
+        B = cnt.shape[0]
     start = None
     if f is not None:
         start = np.ascontiguousarray(np.asarray(f, 'f8').reshape(-1))
@@ -449,8 +552,31 @@ def bootstrap(values, energy, beta, rows, n_k, f, state_of_sample=None, n_bootst
         if ln.ndim != 2 or ln.shape[1] != N:
             raise ValueError('mbar.bootstrap: log_numerators must be (J, %d samples), got %r' % (N, ln.shape))
         J = ln.shape[0]
-    f_boot = np.zeros((B, K), 'f8'); cols = np.zeros((B, J), 'f8')
-    n_iter = np.zeros(B, 'i4'); delta = np.zeros(B, 'f8')
+    f_boot = np.zeros((max(B, 0), K), 'f8'); cols = np.zeros((max(B, 0), J), 'f8')
+    n_iter = np.zeros(max(B, 0), 'i4'); delta = np.zeros(max(B, 0), 'f8')
+    if device:
+        cnt_out = _ptr(cnt) if cnt is not None and cnt.size else None
+        if workspace_bytes is None:
+            rc = c.upside_hip_mbar_bootstrap_drawn(N, K, d, _ptr(v) if d else None, _ptr(e), _ptr(b), _ptr(r) if d else None, _ptr(n_k),
+                                                   _ptr(per) if d else None, _ptr(sos), B, seed, _ptr(blk), cnt_out, float(tol), int(max_iter), _ptr(start),
+                                                   J, _ptr(ln) if J else None, _ptr(f_boot), _ptr(cols) if J else None, _ptr(n_iter), _ptr(delta))
+            msg = c.upside_hip_last_error().decode() if rc else ''
+        else:      # the same host side with a workspace of the caller's size (upk_mbar_boot_solve_drawn)
+            p = _BootProblem(N, K, d, _ptr(v) if d else None, _ptr(e), _ptr(b), _ptr(r) if d else None, _ptr(n_k), _ptr(per) if d else None, _ptr(sos), B,
+                             None, float(tol), int(max_iter), _ptr(start), J, _ptr(ln) if J else None, int(workspace_bytes),
+                             _ptr(f_boot), _ptr(cols) if J else None, _ptr(n_iter), _ptr(delta))
+            dr = _BootDraw(seed, _ptr(blk), 0, cnt_out)
+            buf = ct.create_string_buffer(256)
+            rc = c.upk_mbar_boot_solve_drawn(ct.byref(p), ct.byref(dr), buf, 256)
+            msg = buf.value.decode()
+        if rc:
+            raise RuntimeError('mbar.bootstrap failed: %s' % msg)
+        out = dict(f_boot=f_boot, n_iter=n_iter, last_delta=delta, converged=delta < tol, seed=seed, block=blk)
+        if want_counts:
+            out['counts'] = cnt
+        if log_numerators is not None:
+            out['columns'] = cols
+        return out
     if workspace_bytes is None:
         rc = c.upside_hip_mbar_bootstrap(N, K, d, _ptr(v) if d else None, _ptr(e), _ptr(b), _ptr(r) if d else None, _ptr(n_k), _ptr(per) if d else None,
                                          _ptr(sos), B, _ptr(cnt) if B else None, float(tol), int(max_iter), _ptr(start), J, _ptr(ln) if J else None,
@@ -521,11 +647,11 @@ def _target_reduced_energy(values, energy, target, periods):
 
 
 def profile_bootstrap(values, energy, beta, rows, n_k, f, edges, kT, period=0, target=None, periods=None, cv=0, state_of_sample=None,
-                      n_bootstrap=200, seed=0, counts=None, tol=1e-8, max_iter=10000, library=None):
+                      n_bootstrap=200, seed=0, counts=None, tol=1e-8, max_iter=10000, library=None, draw='host', block=None):
     """(F (n_bin,), dF_boot (n_bin,)): the free-energy profile of the target state along one CV, as profile() gives it from the full
     sample, with the BOOTSTRAP standard deviation (ddof = 1) over the converged replicates of kT (F_bin - F_r) relative to the full
     sample's lowest bin r (dF_boot[r] = 0).  One column per bin that holds samples, -u_target(n) inside the bin and -inf outside, goes
-    through bootstrap() (whose arguments state_of_sample, n_bootstrap, seed, counts, tol, max_iter are); F_bin / kT of a replicate is
+    through bootstrap() (whose arguments state_of_sample, n_bootstrap, seed, counts, tol, max_iter, draw, block are); F_bin / kT of a replicate is
     its column up to a constant that cancels in the difference.  dF_boot is nan for a bin that is empty in the full sample; replicates
     in which the bin or r received no sample (+inf) are left out of that bin's deviation."""
     from . import config
@@ -545,7 +671,8 @@ def profile_bootstrap(values, energy, beta, rows, n_k, f, edges, kT, period=0, t
     for i, bin_ in enumerate(full):
         inside = b == bin_
         cols[i, inside] = -ut[inside]
-    r = bootstrap(values, energy, beta, rows, n_k, f1, state_of_sample, n_bootstrap, seed, counts, periods, tol, max_iter, cols, library)
+    r = bootstrap(values, energy, beta, rows, n_k, f1, state_of_sample, n_bootstrap, seed, counts, periods, tol, max_iter, cols, library,
+                  draw=draw, block=block)
     g = float(kT) * r['columns'][r['converged']]
     ref = int(np.argmin(F[full]))
     for i, bin_ in enumerate(full):
