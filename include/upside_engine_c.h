@@ -452,6 +452,40 @@ int upside_hip_series_inefficiency(int n_series, long long stride, const long lo
                                    const long long* origin, int mintime, long long max_lag, double* g, long long* stop_lag, double* mean,
                                    double* variance);
 
+/* Analysis of metadynamics runs on the device (csrc/kernels_metad.hip): the bias of lists of hills at points and on product grids,
+ * and the log-sum-exps of the growing bias that the reweighting offset c(t) of Tiwary & Parrinello 2015 is made of.  No engine is
+ * needed; every array is a HOST array; a call runs on a stream of its own on the current device and returns when it is done.
+ * List l holds the hills hill_start[l] .. hill_start[l + 1] - 1 in deposit order: centres s_h (d float32) and weights w_h (float32),
+ * widened exactly to double; sigma[d] and periods[d] (0 = not periodic) are double and shared by all lists.  With
+ *   wrap_c(x) = x - periods[c] rint(x / periods[c])   where periods[c] > 0, else x
+ *   e_h(x)    = exp(-1/2 sum_c wrap_c(x_c - s_hc)^2 / sigma_c^2)         (only the nearest image of a hill in a periodic dimension)
+ *   V_m(x)    = sum_{h < m} w_h e_h(x)                                   the bias of the first m hills of the list
+ * upside_hip_metad_bias: point i of list l (point_start as hill_start) receives V[i] = V_{n_visible[i]}(points[i]) over the hills of
+ *   its own list (n_visible NULL: all of them); no hills give exactly 0.  A lane per point, hills staged through LDS, summed ascending;
+ *   a workgroup of 256 consecutive points walks only as far as its largest prefix, so frames in time order cost the triangle.
+ * upside_hip_metad_grid: the grid is the product of d axes (n_axis[c] values each, concatenated in axes), G = prod n_axis points in C
+ *   order, shared by all lists.  Per list, V_last[l][g] = V_m(g) at the last checkpoint m = checkpoints[l][n_checkpoint - 1] (may be
+ *   NULL) and lse[l][j][q] = ln sum_g exp(scales[q] V_{checkpoints[l][j]}(g)), every log-sum-exp with its exact maximum taken off.
+ *   d = 1, and grids with fewer than 8 rows or columns, are summed directly like the points above.  Otherwise the grid is a matrix
+ *   (rows: axis 0 for d = 2, axes 0 x 1 for d = 3 and 4; columns: the rest) and the hills between two checkpoints enter as V += A^T B,
+ *   A[h][row] and B[h][col] = w_h x the factors of the row and column dimensions, generated in panels of hills and folded with
+ *   v_mfma_f64_16x16x4_f64 tiles: H (rows + cols) exponentials, not H rows cols.
+ * Float64 throughout, no atomics, one summation order: two calls return the same bits, and a list's results depend neither on the
+ * other lists of the call, nor on its place among them, nor on how the lists are cut into chunks (a chunk's workspace stays below 1 GB).
+ * Return 0, or 1 with upside_hip_last_error set.  Refused before anything is launched or copied: d outside 1 .. 4; n_list < 1; a NULL
+ * among the required arrays (lse is required exactly when n_scale > 0); hill_start or point_start not starting at 0 or descending; a
+ * list above 2^24 hills; 2^31 or more points, or hills in total; a centre, weight, sigma, period, point, axis value or scale that is
+ * not finite; sigma <= 0; a negative period; an n_visible or a checkpoint below 0 or above its list's hill count; checkpoints that
+ * descend; n_checkpoint < 1; n_scale outside 0 .. 8; an n_axis < 1; G > 2^22.  Without a HIP device the calls fail like every other. */
+int upside_hip_metad_bias(int n_list, int d, const long long* hill_start /* n_list+1 */, const float* centers /* [hills][d] */,
+                          const float* weights, const double* sigma, const double* periods, const long long* point_start /* n_list+1 */,
+                          const double* points /* [points][d] */, const long long* n_visible /* per point, or NULL */, double* V /* per point */);
+int upside_hip_metad_grid(int n_list, int d, const long long* hill_start, const float* centers, const float* weights, const double* sigma,
+                          const double* periods, const int* n_axis /* d */, const double* axes /* concatenated, sum n_axis */,
+                          int n_checkpoint, const long long* checkpoints /* [n_list][n_checkpoint], ascending, repeats allowed */,
+                          int n_scale, const double* scales, double* V_last /* [n_list][G] or NULL */,
+                          double* lse /* [n_list][n_checkpoint][n_scale], NULL iff n_scale == 0 */);
+
 /* Per-kernel timing hooks used by bench.py.  With profiling enabled every interaction-graph / BP kernel
  * launch is bracketed by HIP events on the engine's stream.  upside_hip_profile_dump writes one text line per
  * kernel: "<kind>:<node> <total ms> <launches> <total algorithmic bytes> <total pair evaluations>" (bytes as defined in

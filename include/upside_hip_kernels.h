@@ -781,6 +781,46 @@ int upk_series_solve(const upk_series_problem_t* P, char* message /* host */, in
 int upk_series_lag_block(void);     /* UPK_SERIES_LAG_BLOCK and UPK_SERIES_PIECE of the library that was built */
 int upk_series_piece(void);
 
+/* ---- metadynamics analysis (upside_hip_metad_bias, upside_hip_metad_grid), csrc/kernels_metad.hip ---------------------------------------
+ * upk_metad_bias_solve and upk_metad_grid_solve are the HOST sides of the two entry points (include/upside_engine_c.h states the
+ * definitions and the refusals): every pointer is a host pointer; the checks come before any device call; 0, or 1 with the reason in
+ * message.  The grid solve takes two arguments the public entry point does not pass on: workspace_limit, the bytes a chunk of lists
+ * may use (0: UPK_METAD_WORKSPACE; a list that needs more is still run, alone), and path (0: by shape, 1: the direct sum, 2: the
+ * factorised sum whatever the shape, d >= 2).  Neither changes a bit of what a path returns.  stats (may be NULL) receives [0] the
+ * device time in ms between HIP events around the kernels (the copies in and the last copies out excluded; with several chunks of lists
+ * the V_last copies of the earlier ones lie between the events), [1] the wall time in ms of the call after its checks,
+ * [2] the exponentials executed by the hill sums (the log-sum-exps not counted), [3] the v_mfma_f64_16x16x4_f64 instructions issued
+ * per wave summed over waves (2048 flop each), [4] the path taken (1 or 2), [5] the chunks of lists. */
+#define UPK_METAD_MAX_SCALES 8
+#define UPK_METAD_MAX_GRID (1 << 22)
+#define UPK_METAD_MAX_LIST (1 << 24)
+#define UPK_METAD_WORKSPACE ((size_t)1 << 30)
+#define UPK_METAD_MIN_FACTORISED 8
+typedef struct {
+    int n_list, d;
+    const long long* hill_start;                                  /* host [n_list + 1] */
+    const float *centers, *weights;                               /* host [hills][d], [hills] */
+    const double *sigma, *periods;                                /* host [d] */
+} upk_metad_hills_t;
+typedef struct {
+    upk_metad_hills_t H;
+    const long long* point_start; const double* points;           /* host [n_list + 1], [points][d] */
+    const long long* n_visible;                                   /* host [points] or NULL */
+    double* V;                                                    /* host out [points] */
+    double* stats;                                                /* host out [6] or NULL */
+} upk_metad_bias_problem_t;
+typedef struct {
+    upk_metad_hills_t H;
+    const int* n_axis; const double* axes;                        /* host [d], [sum n_axis] */
+    int n_checkpoint; const long long* checkpoints;               /* host [n_list][n_checkpoint] */
+    int n_scale; const double* scales;
+    double *V_last, *lse;                                         /* host out [n_list][G] or NULL, [n_list][n_checkpoint][n_scale] */
+    size_t workspace_limit; int path;
+    double* stats;                                                /* host out [6] or NULL */
+} upk_metad_grid_problem_t;
+int upk_metad_bias_solve(const upk_metad_bias_problem_t* P, char* message /* host */, int message_len);
+int upk_metad_grid_solve(const upk_metad_grid_problem_t* P, char* message /* host */, int message_len);
+
 #ifdef __cplusplus
 }
 #endif

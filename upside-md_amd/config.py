@@ -1196,6 +1196,22 @@ def _metad_node_shape(path, node):
         return len(g.read('kind')), int(np.asarray(g.get_attr('capacity')).ravel()[0])
 
 
+def metad_node_parameters(path, node):
+    """what the analysis of a run needs of its cv_metadynamics node (metad.py, Ensemble.metad_reweight): dict(names, periods (d,),
+    sigma (d,) and height as the node computes with them, (double)(float) of what the file holds, kdT, pace, capacity, shared)"""
+    with h5lite.open_file(path) as f:
+        pot = f.group('input').group('potential')
+        if node not in pot:
+            raise ValueError('metad_node_parameters: %s has no node %r' % (path, node))
+        g = pot.group(node)
+        attr = dict((k, np.asarray(g.get_attr(k)).ravel()[0]) for k in ('height', 'kdT', 'pace', 'capacity', 'shared'))
+        out = dict(names=[x.decode() for x in g.read('names').ravel()], periods=cv_periods(dict(kind=g.read('kind'))),
+                   sigma=np.asarray(g.read('sigma'), 'f4').astype('f8').reshape(-1), height=float(np.float32(attr['height'])), kdT=float(attr['kdT']),
+                   pace=int(attr['pace']), capacity=int(attr['capacity']), shared=bool(int(attr['shared'])))
+        del g, pot
+    return out
+
+
 def set_metadynamics_hills(path, node, centers, weights):
     """the hills a run of `upside_hip` starts from: /input/metadynamics/<node>/{hill_center (n, d), hill_weight (n)} of the
     configuration (outside /input/potential: files are grouped into engines without regard to it).  To continue a run, pass what
@@ -1215,7 +1231,8 @@ def metadynamics_free_energy(centers, weights, sigma, grid_points, kT=None, kdT=
     """the free-energy estimate of a metadynamics run at grid_points (m, d) (or (m,) for d = 1), float64, up to a constant:
     -V for plain metadynamics (kdT = 0), -(kT + kdT) / kdT V for well-tempered (kT: the run's temperature in energy units).
     periods (d,), as cv_periods gives them: in a dimension with a period > 0 the difference to a hill is taken by its nearest image,
-    as the node does; None: no dimension is periodic"""
+    as the node does; None: no dimension is periodic.  The sum is formed on the host as one (points, hills, d) array: for large
+    inputs metad.free_energy_grid gives the same estimate on a product grid from the device."""
     sigma = np.asarray(sigma, 'f8').reshape(-1)
     d = len(sigma)
     w = np.asarray(weights, 'f8').reshape(-1)

@@ -132,6 +132,31 @@ extern "C" int upside_hip_series_inefficiency(int n_series, long long stride, co
     return 0;
     API_CATCH(1)
 }
+// metadynamics analysis: the checks and the staging are upk_metad_bias_solve and upk_metad_grid_solve (kernels_metad.hip)
+extern "C" int upside_hip_metad_bias(int n_list, int d, const long long* hill_start, const float* centers, const float* weights, const double* sigma,
+                                     const double* periods, const long long* point_start, const double* points, const long long* n_visible, double* V) {
+    API_TRY
+    upk_metad_bias_problem_t P{};
+    P.H.n_list = n_list; P.H.d = d; P.H.hill_start = hill_start; P.H.centers = centers; P.H.weights = weights; P.H.sigma = sigma; P.H.periods = periods;
+    P.point_start = point_start; P.points = points; P.n_visible = n_visible; P.V = V;
+    char msg[256];
+    if (upk_metad_bias_solve(&P, msg, (int)sizeof(msg))) throw string(msg);
+    return 0;
+    API_CATCH(1)
+}
+extern "C" int upside_hip_metad_grid(int n_list, int d, const long long* hill_start, const float* centers, const float* weights, const double* sigma,
+                                     const double* periods, const int* n_axis, const double* axes, int n_checkpoint, const long long* checkpoints,
+                                     int n_scale, const double* scales, double* V_last, double* lse) {
+    API_TRY
+    upk_metad_grid_problem_t P{};
+    P.H.n_list = n_list; P.H.d = d; P.H.hill_start = hill_start; P.H.centers = centers; P.H.weights = weights; P.H.sigma = sigma; P.H.periods = periods;
+    P.n_axis = n_axis; P.axes = axes; P.n_checkpoint = n_checkpoint; P.checkpoints = checkpoints; P.n_scale = n_scale; P.scales = scales;
+    P.V_last = V_last; P.lse = lse;
+    char msg[256];
+    if (upk_metad_grid_solve(&P, msg, (int)sizeof(msg))) throw string(msg);
+    return 0;
+    API_CATCH(1)
+}
 
 // ---- construction ----------------------------------------------------------------------------------
 extern "C" int upside_hip_set_device(int device) {

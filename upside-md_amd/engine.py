@@ -647,6 +647,57 @@ class Ensemble(object):
         self._check(self.calc.upside_hip_metad_values(self.engine, _b(node_name), out.ctypes.data), 'metad_values')
         return out
 
+    def metad_reweight(self, node_name, kT, axes=None, series=None, every=1, first_round=0, max_checkpoints=4096):
+        """the reweighting of the recorded frames of a metadynamics run (metad.frame_log_weights on the device; Tiwary & Parrinello
+        2015): the hills come from metad_hills, pace, kdT, sigma and shared from the node's group in config_file_path, the frames
+        from series ((n_stored, n_system, n_cv) as read_cvs gives it, default read_cvs(reset=False)).  The node's CVs are found among
+        the recorded ones BY NAME; a CV of the node that is not recorded raises ValueError naming it.  Frame i was recorded at
+        completed round first_round + (i + 1) * every, counted from the start of the deposits (record_cvs(every) called before the
+        first round gives first_round = 0).  axes: the d grid axes c(t) is integrated over, default metad.default_axes over all the
+        hills.  Returns the dict of metad.frame_log_weights per system (a list of n_system dicts; each system has its own list of
+        hills and its own weights, all of them from one bias call and one grid call), or, for a shared list, ONE dict over the
+        pooled frames in the order of series.reshape(-1, d) (frame-major, n_walker = n_system); `axes` is added to every dict."""
+        from . import config, metad as _metad
+        p = config.metad_node_parameters(self.config_file_path, node_name)
+        recorded = list(getattr(self, 'cv_names', []))
+        cols = []
+        for nm in p['names']:
+            if nm not in recorded:
+                raise ValueError('metad_reweight: the collective variable %r of node %r is not among the recorded ones %r' % (nm, node_name, recorded))
+            cols.append(recorded.index(nm))
+        d = len(cols)
+        if int(every) < 1 or int(first_round) < 0:
+            raise ValueError('metad_reweight: every >= 1 and first_round >= 0')
+        if series is None:
+            series = self.read_cvs(reset=False)
+        series = np.asarray(series, 'f4')
+        if series.ndim != 3 or series.shape[1] != self.n_system or series.shape[2] != len(recorded) or not series.shape[0]:
+            raise ValueError('metad_reweight: the series must be (n_stored >= 1, %d systems, %d CVs), got %r' % (self.n_system, len(recorded), series.shape))
+        n = series.shape[0]
+        rounds = int(first_round) + (np.arange(n, dtype='i8') + 1) * int(every)
+        S = self.n_system
+        if p['shared']:
+            c, w, _ = self.metad_hills(node_name, 0)
+            if not len(w):
+                raise ValueError('metad_reweight: node %r holds no hills yet' % node_name)
+            axes = _metad.default_axes(c, p['sigma'], p['periods']) if axes is None else axes
+            out = _metad.frame_log_weights(c, w, p['sigma'], series[:, :, cols].reshape(-1, d), np.repeat(rounds, S), p['pace'], kT, p['kdT'], axes,
+                                           n_walker=S, periods=p['periods'], max_checkpoints=max_checkpoints, library=self.lib)
+            out['axes'] = axes
+            return out
+        lists = [self.metad_hills(node_name, s)[:2] for s in range(S)]
+        c = np.concatenate([l[0] for l in lists]); w = np.concatenate([l[1] for l in lists])
+        if not len(w):
+            raise ValueError('metad_reweight: node %r holds no hills yet' % node_name)
+        hs = np.concatenate(([0], np.cumsum([len(l[1]) for l in lists]))).astype('i8')
+        axes = _metad.default_axes(c, p['sigma'], p['periods']) if axes is None else axes
+        frames = np.ascontiguousarray(series[:, :, cols].transpose(1, 0, 2)).reshape(-1, d)      # (system-major: the frames of a list together)
+        out = _metad.frame_log_weights_lists(c, w, p['sigma'], frames, np.tile(rounds, S), p['pace'], kT, p['kdT'], axes, hs, n * np.arange(S + 1),
+                                             periods=p['periods'], max_checkpoints=max_checkpoints, library=self.lib)
+        for o in out:
+            o['axes'] = axes
+        return out
+
     # -- cv_steer: clocks, work and centres of a node (they live on the device and advance inside run_rounds / run_steps) ---------
     def _steer_n_cv(self, node_name):
         n = np.zeros(1, 'i4')
