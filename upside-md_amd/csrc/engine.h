@@ -206,3 +206,23 @@ void check_swap_set(int n_system, int n_pair, const int* pairs);
 DerivEngine* initialize_engine_from_hdf5(int n_atom, int n_system, hid_t_compat potential_group, bool quiet = false,
                                          const std::function<void(DerivEngine&)>& before_finalize = nullptr);
 
+// What nodes.cpp tells the C-ABI and upside_main about the nodes of an engine, by node name
+int engine_pairlist(DerivEngine& e, const std::string& node_name, int sys, std::vector<std::pair<int, int>>& out);
+int engine_rotamer_iterations(DerivEngine& e, std::vector<int>& iters);
+int engine_cv_restraint_values(DerivEngine& e, const std::string& node_name, std::vector<float>* out);
+std::vector<std::string> engine_metad_nodes(DerivEngine& e);      // the names of the engine's cv_metadynamics nodes
+void engine_metad_info(DerivEngine& e, const std::string& node_name, int* d, int* capacity, int* n_list);
+void engine_metad_read(DerivEngine& e, const std::string& node_name, int list, float* centers, float* weights, int* n_hill, long long* n_attempt);
+void engine_metad_write(DerivEngine& e, const std::string& node_name, int list, const float* centers, const float* weights, int n_hill);
+std::vector<float> engine_metad_values(DerivEngine& e, const std::string& node_name);
+std::vector<std::string> engine_steer_nodes(DerivEngine& e);      // the names of the engine's cv_steer nodes
+int engine_steer_n_cv(DerivEngine& e, const std::string& node_name);
+void engine_steer_read(DerivEngine& e, const std::string& node_name, long long* clock, double* work, double* center);
+void engine_steer_write(DerivEngine& e, const std::string& node_name, const long long* clock, const double* work);
+std::vector<float> engine_steer_values(DerivEngine& e, const std::string& node_name);
+int engine_rebuild_flags(DerivEngine& e, const std::string& node_name, std::vector<int>& flags);
+int engine_igraph_stats(DerivEngine& e, const std::string& node_name, double* out);
+double engine_bp_bytes(DerivEngine& e);
+double engine_bp_min_bytes(DerivEngine& e);
+double engine_igraph_bytes(DerivEngine& e);
+

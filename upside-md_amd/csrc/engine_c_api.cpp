@@ -15,22 +15,6 @@
 
 using namespace std;
 
-int engine_pairlist(DerivEngine& e, const string& node_name, int sys, vector<pair<int, int>>& out);
-int engine_rotamer_iterations(DerivEngine& e, vector<int>& iters);
-int engine_cv_restraint_values(DerivEngine& e, const string& node_name, vector<float>* out);
-void engine_metad_info(DerivEngine& e, const string& node_name, int* d, int* capacity, int* n_list);
-void engine_metad_read(DerivEngine& e, const string& node_name, int list, float* centers, float* weights, int* n_hill, long long* n_attempt);
-void engine_metad_write(DerivEngine& e, const string& node_name, int list, const float* centers, const float* weights, int n_hill);
-vector<float> engine_metad_values(DerivEngine& e, const string& node_name);
-int engine_steer_n_cv(DerivEngine& e, const string& node_name);
-void engine_steer_read(DerivEngine& e, const string& node_name, long long* clock, double* work, double* center);
-void engine_steer_write(DerivEngine& e, const string& node_name, const long long* clock, const double* work);
-vector<float> engine_steer_values(DerivEngine& e, const string& node_name);
-int engine_rebuild_flags(DerivEngine& e, const string& node_name, vector<int>& flags);
-int engine_igraph_stats(DerivEngine& e, const string& node_name, double* out);
-double engine_bp_bytes(DerivEngine& e);
-double engine_bp_min_bytes(DerivEngine& e);
-double engine_igraph_bytes(DerivEngine& e);
 int upside_main_impl(int argc, const char* const* argv, int verbose);
 
 static thread_local string g_last_error;
@@ -165,9 +149,7 @@ extern "C" DerivEngine* upside_hip_construct(int n_atom, const char* potential_f
     API_TRY
     if (n_system < 1) throw string("n_system must be positive");
     H5Eset_auto2(H5E_DEFAULT, NULL, NULL);
-    hid_t f = H5Fopen(potential_file, H5F_ACC_RDONLY, H5P_DEFAULT);
-    if (f < 0) throw string("unable to open ") + potential_file;
-    h5u::Handle config(f, H5Fclose);
+    auto config = h5u::open_config(potential_file);
     auto potential_group = h5u::open_group(config, "/input/potential");
     return initialize_engine_from_hdf5(n_atom, n_system, (hid_t_compat)(hid_t)potential_group, quiet);
     API_CATCH(nullptr)
@@ -194,15 +176,6 @@ h5u::DigestSkip node_value_skip(const PerSystemValueSpec* sp) {
         return obj == "." && listed(sp->attributes, attr);
     };
 }
-hid_t open_config(const string& p) {
-    hid_t f = H5Fopen(p.c_str(), H5F_ACC_RDONLY, H5P_DEFAULT);
-    if (f < 0) throw string("unable to open ") + p;
-    return f;
-}
-struct ConfigFile {
-    h5u::Handle file;
-    explicit ConfigFile(const string& p) : file(open_config(p), H5Fclose) {}
-};
 }  // namespace
 
 extern "C" int upside_hip_group_configurations(int n_file, const char* const* files, int* group_of) {
@@ -213,8 +186,8 @@ extern "C" int upside_hip_group_configurations(int n_file, const char* const* fi
     const h5u::DigestSkip skip = potential_value_skip();
     vector<unsigned long long> keys;
     for (int i = 0; i < n_file; ++i) {
-        ConfigFile cf(files[i]);
-        auto pg = h5u::open_group(cf.file, "/input/potential");
+        auto cf = h5u::open_config(files[i]);
+        auto pg = h5u::open_group(cf, "/input/potential");
         const unsigned long long k = h5u::group_digest(pg, batch ? &skip : nullptr);
         size_t g = 0;
         while (g < keys.size() && keys[g] != k) ++g;
@@ -229,9 +202,8 @@ extern "C" DerivEngine* upside_hip_construct_files(int n_atom, int n_file, const
     API_TRY
     if (n_file < 1 || !files) throw string("n_file must be positive");
     H5Eset_auto2(H5E_DEFAULT, NULL, NULL);
-    vector<unique_ptr<ConfigFile>> cf;
-    vector<h5u::Handle> pg;
-    for (int i = 0; i < n_file; ++i) { cf.emplace_back(new ConfigFile(files[i])); pg.push_back(h5u::open_group(cf.back()->file, "/input/potential")); }
+    vector<h5u::Handle> cf, pg;
+    for (int i = 0; i < n_file; ++i) { cf.push_back(h5u::open_config(files[i])); pg.push_back(h5u::open_group(cf.back(), "/input/potential")); }
     // what each system loads on top of system 0's engine: (system, node) of every node group that is not byte-identical
     vector<pair<int, string>> to_load;
     const auto names0 = h5u::node_names_in_group(pg[0]);
@@ -639,9 +611,7 @@ vector<string> read_string_dataset(hid_t loc, const string& name) {      // fixe
 extern "C" int upside_hip_cv_load(DerivEngine* e, const char* config_file) {
     API_TRY
     H5Eset_auto2(H5E_DEFAULT, NULL, NULL);
-    hid_t f = H5Fopen(config_file, H5F_ACC_RDONLY, H5P_DEFAULT);
-    if (f < 0) throw string("unable to open ") + config_file;
-    h5u::Handle config(f, H5Fclose);
+    auto config = h5u::open_config(config_file);
     auto input = h5u::open_group(config, "/input");
     if (!h5u::exists(input, "collective_variables")) return 0;
     auto g = h5u::open_group(input, "collective_variables");
@@ -737,9 +707,7 @@ extern "C" int upside_hip_steer_values(DerivEngine* e, const char* node_name, fl
 extern "C" int upside_hip_load_mc(DerivEngine* e, const char* config_file) {
     API_TRY
     H5Eset_auto2(H5E_DEFAULT, NULL, NULL);
-    hid_t f = H5Fopen(config_file, H5F_ACC_RDONLY, H5P_DEFAULT);
-    if (f < 0) throw string("unable to open ") + config_file;
-    h5u::Handle config(f, H5Fclose);
+    auto config = h5u::open_config(config_file);
     auto input = h5u::open_group(config, "/input");
     int n = 0;
     e->invalidate_graph();

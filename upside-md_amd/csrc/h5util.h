@@ -21,6 +21,11 @@ struct Handle {   // RAII for hid_t
     operator hid_t() const { return id; }
 };
 
+inline Handle open_config(const std::string& path) {   // a configuration file, read-only
+    hid_t f = H5Fopen(path.c_str(), H5F_ACC_RDONLY, H5P_DEFAULT);
+    if (f < 0) throw std::string("unable to open ") + path;
+    return Handle(f, H5Fclose);
+}
 inline Handle open_group(hid_t loc, const std::string& name) {
     hid_t g = H5Gopen2(loc, name.c_str(), H5P_DEFAULT);
     if (g < 0) throw std::string("unable to open group '") + name + "'";
