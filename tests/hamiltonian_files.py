@@ -24,6 +24,48 @@ def scale_hbond(path, factor):
         g.set_attr('protein_hbond_energy', np.float64(factor * float(np.asarray(g.get_attr('protein_hbond_energy')).ravel()[0])))
 
 
+def rewrite_in_place(path, node, name, fn):
+    """dataset `name` of node `node` := fn(old values), written IN PLACE: type, shape and every attribute of the dataset stay what
+    they were (rewrite() re-creates the dataset and carries only time_* over, which loses e.g. coeff's spline_offset / spline_inv_dx)"""
+    h5 = P.pkg.h5lite
+    with h5.open_file(path, 'r+') as t:
+        g = t.group('input/potential/' + node)
+        old = np.asarray(g.read(name))
+        new = np.ascontiguousarray(np.asarray(fn(old.copy())).astype(old.dtype))
+        assert new.shape == old.shape
+        L = h5.lib()
+        d = L.H5Dopen2(g.hid, name.encode(), 0)
+        if d < 0:
+            raise IOError('cannot open %s/%s of %s' % (node, name, path))
+        try:
+            if L.H5Dwrite(d, h5._native(new.dtype), 0, 0, 0, new.ctypes.data) < 0:
+                raise IOError('cannot write %s/%s of %s' % (node, name, path))
+        finally:
+            L.H5Dclose(d)
+        del g
+
+
+def scale_dataset(path, node, name, k):
+    """dataset `name` of node `node` *= k; every attribute of the dataset is kept"""
+    rewrite_in_place(path, node, name, lambda v: v * k)
+
+
+def scale_coupling(path, k):
+    """the environment coupling's energy scale (every spline coefficient of nonlinear_coupling_environment)"""
+    scale_dataset(path, 'nonlinear_coupling_environment', 'coeff', k)
+
+
+def scale_coverage(path, k, n_radial):
+    """the energy scale of the side-chain / backbone hydrogen-bond coverage: the two radial pieces (the last n_radial = 2 n_knot
+    coefficients of every row of interaction_param) of both coverage graphs times k.  The angular pieces in front of them are weights,
+    not energies, and stay; a pair's value and its whole gradient are then exactly k times what they were."""
+    def radial(v):
+        v[..., -n_radial:] *= k
+        return v
+    for node in ('hbond_coverage', 'hbond_coverage_hydrophobe'):
+        rewrite_in_place(path, node, 'interaction_param', radial)
+
+
 def copy_fixture(name, dst):
     shutil.copyfile(P.fixture(name), str(dst))
     return str(dst)

@@ -249,7 +249,11 @@ __device__ __forceinline__ int exchange_accept(float lb, uint32_t seed, uint64_t
 
 // fixed-point image of a float (|v| < 2^31): v * 2^32 as a 64-bit two's-complement integer, exact down to 2^-31.  Integer adds commute, so
 // sums accumulated through LDS atomics in any order are the EXACT sum of the contributions (and bit-reproducible); LDS integer
-// atomics run at full rate on gfx950, float ones at 3 cycles per lane (tools/ubench/lds_atomics.hip)
+// atomics run at full rate on gfx950, float ones at 3 cycles per lane (tools/ubench/lds_atomics.hip).
+// Range: -2^31 <= v < 2^31, and the same for every partial sum of an accumulator.  Nothing is checked: (int)h is v_cvt_i32_f32, which
+// saturates -- a contribution of 2^31 or more is added as 2^31 - 2^-32 (the high word stops at 2^31 - 1, it does not wrap), one
+// below -2^31 as -2^31, a NaN as 0 -- and a sum past 2^31 wraps.  The force field would have to be 1e7 times as steep as the shipped one
+// (DESIGN.md section 3.3).  Restated for the host, with these edges, in tests/fixed_point_host.cpp.
 __device__ __forceinline__ unsigned long long to_fixed32(float v) {
     const float h = rintf(v);                                     // nearest integer; v - h is exact (|v| < 0.5: h = 0; else h within a factor 2 of v)
     const int hi = (int)h, half = (int)((v - h) * 2147483648.f);  // |v - h| <= 0.5: the product is exact, |half| <= 2^30 (resolution 2^-31)

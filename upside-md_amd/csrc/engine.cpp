@@ -914,7 +914,11 @@ void DerivEngine::check_device_errors() {
                          "co-resident; something else occupied the device): the forces of this step are not valid.  Set UPSIDE_HIP_BP_CLUSTER=1 "
                          "to use the one-workgroup solve");
         if (f[0] == 8)   // kernels_rotamer.hip: RotGradOp2::flush
-            throw string("side-chain gradient: a bead's gradient is not finite (NaN or overflow in the pair pass): the forces of this step are not valid");
+            throw string("side-chain gradient: a bead's gradient, or a pair's contribution to it, is not finite or beyond what the fixed-point "
+                         "accumulators of the pair pass hold (2^24 per pair, 2^40 per bead): the forces of this step are not valid");
+        if (f[0] == 10)  // kernels_pair.hip: CovBackwardOp2 (pair2_device.h: lds_add_fixed22_pairs)
+            throw string("hbond_coverage gradient: a pair's contribution to a gradient is not finite or is 2^24 or more, beyond what the "
+                         "fixed-point accumulators of the coverage pair pass hold: the forces of this step are not valid");
         if (f[0] == 9)   // kernels_rotamer.hip: k_rotamer_bp, layout of the message inbox
             throw string("belief propagation: 3-float message rows were laid out for a solve that does not hold its inbox in LDS (internal error): "
                          "the forces of this step are not valid");

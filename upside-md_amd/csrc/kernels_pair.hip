@@ -432,15 +432,8 @@ struct CovBackwardOp2 {
         const v2 pss = ps * bc2(P2_FIX_SCALE);              // (fixed-point scale folded into the sensitivity: two values per instruction)
 #pragma unroll
         for (int c = 0; c < DO; ++c) od[c] = pss * dv[c];
-        const int n_o = RS == 1 ? G.n2 : G.n1;          // accumulators as DO planes [component][element]
-        if (liveA) {
-#pragma unroll
-            for (int c = 0; c < DO; ++c) lds_add_fixed22_scaled(oacc + c * n_o + jA, od[c].x);
-        }
-        if (liveB) {
-#pragma unroll
-            for (int c = 0; c < DO; ++c) lds_add_fixed22_scaled(oacc + c * n_o + jB, od[c].y);
-        }
+        // accumulators as DO planes [component][element]; a contribution the 32-bit conversion cannot hold takes the wide path (pair2_device.h)
+        lds_add_fixed22_pairs<DO>(oacc, RS == 1 ? G.n2 : G.n1, jA, jB, liveA, liveB, od, G.error_flag, 10);
     }
     __device__ __forceinline__ void flush(int row) {
         float t[DR];

@@ -506,16 +506,9 @@ struct RotGradOp2 {
             od[c] = pss * dd[c]; od[3 + c] = pss * g2[c];
             acc[c] = fma2(-ps, dd[c], acc[c]); acc[3 + c] = fma2(ps, g1[c], acc[3 + c]);
         }
-        // accumulators as six planes [component][bead]: the consecutive partners of a row group fall into distinct banks
-        const int n1 = R.G.n1;
-        if (liveA) {
-#pragma unroll
-            for (int c = 0; c < 6; ++c) lds_add_fixed22_scaled(L.acc + c * n1 + mA.j, od[c].x);
-        }
-        if (liveB) {
-#pragma unroll
-            for (int c = 0; c < 6; ++c) lds_add_fixed22_scaled(L.acc + c * n1 + mB.j, od[c].y);
-        }
+        // accumulators as six planes [component][bead]: the consecutive partners of a row group fall into distinct banks; a contribution the
+        // 32-bit conversion cannot hold takes the wide path (pair2_device.h)
+        lds_add_fixed22_pairs<6>(L.acc, R.G.n1, mA.j, mB.j, liveA, liveB, od, R.G.error_flag, 8);
     }
     __device__ __forceinline__ void flush(int row) {
         float t[6];
@@ -524,7 +517,7 @@ struct RotGradOp2 {
         if ((threadIdx.x & (P2_LANES - 1)) != 0) return;
 #pragma unroll
         for (int c = 0; c < 6; ++c) {
-            if (!(fabsf(t[c]) < 1e30f)) *R.G.error_flag = 8;     // NaN / overflow would vanish in the integer conversion: report the step
+            if (!(fabsf(t[c]) < P2_FIX_TOTAL_MAX)) *R.G.error_flag = 8;     // NaN / overflow would vanish in the integer conversion: report the step
             lds_add_fixed22_wide(L.acc + c * R.G.n1 + row, t[c]);
         }
     }

@@ -14,10 +14,16 @@
 // SENTINEL element (a far-away, finite dummy row staged behind the real ones) with sensitivity zero: every body is
 // branch-free and the discarded halves contribute an exact +0.
 //
-// Gradient accumulators: 64-bit integer LDS atomics as before (order-independent, bit-reproducible), but a contribution is
-// converted as floor(v * 2^22 + 0.5) -- a packed multiply shared by two values, v_cvt_rpi_i32_f32 and a sign extension instead of the 8
-// instructions of the 2^32 split (igraph_device.h: to_fixed32): resolution
-// 2.4e-7, below the rounding of the fp32 sums it replaces; |v| >= 512 saturates (v_cvt_i32_f32), sums cannot overflow.
+// Gradient accumulators: 64-bit integer LDS atomics as before (order-independent, bit-reproducible), in counts of 2^-22.
+//   Resolution: a contribution is converted as floor(v * 2^22 + 0.5) -- a packed multiply shared by two values, v_cvt_rpi_i32_f32 and a sign
+//     extension instead of the 8 instructions of the 2^32 split (device_math.h: to_fixed32) -- so it is off by at most 2^-23 = 1.2e-7, and
+//     a sum of n contributions by at most n 2^-23: below the rounding of the fp32 sums it replaces.
+//   Range: the 32-bit conversion holds |v| < 512 and SATURATES beyond (600 would be added as 512, a NaN as 0, with no sign of either).
+//     So the two partners of a lane and trip are checked together (lds_add_fixed22_pairs: the sum of their squares, a handful of packed
+//     FMAs); a trip whose contributions' squares sum to 256^2 or more converts through the 64-bit wide path instead, which is exact
+//     up to |v| < 2^24 (1.7e7).  Beyond that, and for a contribution that is not finite, the pass sets the engine's error flag and the call
+//     fails (engine.cpp: check_device_errors): with at most 2^16 partners per element below 2^24 each and an own total below 2^40
+//     the 64-bit sums cannot wrap.  The shipped force field stays below 50 even on clashing structures.
 #pragma once
 #include "igraph_device.h"
 
@@ -30,26 +36,58 @@ __device__ __forceinline__ v2 fma2(v2 a, v2 b, v2 c) { return __builtin_elementw
 
 #define P2_FIX_BITS 22
 #define P2_FIX_SCALE ((float)(1 << P2_FIX_BITS))
-// vs = value * 2^22 (the callers scale two values per v_pk_mul_f32): v_cvt_rpi_i32_f32 = floor(vs + 0.5), saturating; v_ashrrev 31
+// vs = value * 2^22 (the callers scale two values per v_pk_mul_f32): v_cvt_rpi_i32_f32 = floor(vs + 0.5), saturating at |vs| >= 2^31; v_ashrrev 31
 __device__ __forceinline__ unsigned long long to_fixed22_scaled(float vs) {
     int q;
     asm("v_cvt_rpi_i32_f32 %0, %1" : "=v"(q) : "v"(vs));
     return (unsigned long long)(long long)q;
 }
-__device__ __forceinline__ unsigned long long to_fixed22(float v) { return to_fixed22_scaled(v * P2_FIX_SCALE); }
-__device__ __forceinline__ void lds_add_fixed22_scaled(unsigned long long* p, float vs) {
-    __hip_atomic_fetch_add(p, to_fixed22_scaled(vs), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+#define P2_FIX_NARROW 1073741824.f           // 2^30: scaled contributions below it take the 32-bit conversion (|v| < 256)
+#define P2_FIX_WIDE   70368744177664.f       // 2^46: ... below it the 64-bit one (|v| < 2^24); at or beyond it, or not finite: the error flag
+// the wide path of one contribution: the same rounding below 2^30, exact integers from there on (a float of 2^23 or more has no fraction)
+__device__ __forceinline__ void lds_add_fixed22_wide_scaled(unsigned long long* p, float vs, int* error_flag, int error_code) {
+    const float a = fabsf(vs);
+    if (!(a < P2_FIX_WIDE)) { *error_flag = error_code; return; }       // (also NaN and infinity: never a clean zero)
+    const unsigned long long q = a < P2_FIX_NARROW ? to_fixed22_scaled(vs) : (unsigned long long)__float2ll_rn(vs);
+    __hip_atomic_fetch_add(p, q, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
 }
-// a ROW's own total (one conversion per row and component, not per pair): the full 64-bit range instead of the saturating
-// 32-bit conversion above -- a badly clashing start structure can push a row total past 512
+// The partner-side contributions of the two pairs a lane evaluated in one trip: od[c] = (contribution to component c) * 2^22 of partner
+// jA (.x) and jB (.y), accumulators as D planes [component][element] of `stride` elements.  One check for all 2 D values: the sum of their
+// squares is below 2^60 only if every |od| is below 2^30 (and none is NaN or infinite: both survive the sum), which is all but never
+// false; then the 32-bit conversions.  Otherwise every value of the trip goes through the wide path.  A dead half carries exact zeros.
+template <int D>
+__device__ __forceinline__ void lds_add_fixed22_pairs(unsigned long long* acc, int stride, int jA, int jB, bool liveA, bool liveB, const v2* od,
+                                                      int* error_flag, int error_code) {
+    v2 sq = od[0] * od[0];
+#pragma unroll
+    for (int c = 1; c < D; ++c) sq = __builtin_elementwise_fma(od[c], od[c], sq);
+    if (__builtin_expect(sq.x + sq.y < P2_FIX_NARROW * P2_FIX_NARROW, 1)) {
+        if (liveA) {
+#pragma unroll
+            for (int c = 0; c < D; ++c) __hip_atomic_fetch_add(acc + c * stride + jA, to_fixed22_scaled(od[c].x), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+        }
+        if (liveB) {
+#pragma unroll
+            for (int c = 0; c < D; ++c) __hip_atomic_fetch_add(acc + c * stride + jB, to_fixed22_scaled(od[c].y), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+        }
+    } else {
+        if (liveA) {
+#pragma unroll
+            for (int c = 0; c < D; ++c) lds_add_fixed22_wide_scaled(acc + c * stride + jA, od[c].x, error_flag, error_code);
+        }
+        if (liveB) {
+#pragma unroll
+            for (int c = 0; c < D; ++c) lds_add_fixed22_wide_scaled(acc + c * stride + jB, od[c].y, error_flag, error_code);
+        }
+    }
+}
+// a ROW's own total (one conversion per row and component, not per pair): always the 64-bit conversion; the caller checks |v| < 2^40
+#define P2_FIX_TOTAL_MAX 1099511627776.f     // 2^40
 __device__ __forceinline__ unsigned long long to_fixed22_wide(float v) { return (unsigned long long)__float2ll_rn(v * P2_FIX_SCALE); }
 __device__ __forceinline__ void lds_add_fixed22_wide(unsigned long long* p, float v) {
     __hip_atomic_fetch_add(p, to_fixed22_wide(v), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
 }
 __device__ __forceinline__ float from_fixed22(unsigned long long a) { return (float)((double)(long long)a * (1.0 / (double)(1 << P2_FIX_BITS))); }
-__device__ __forceinline__ void lds_add_fixed22(unsigned long long* p, float v) {
-    __hip_atomic_fetch_add(p, to_fixed22(v), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-}
 
 // Staged elements of the packed passes: TWO 16-byte planes per side -- [0, 4 n') the words 0..3 of every row (position, first
 // direction component), [4 n', 8 n') the words 4..7 (rest of the direction, the two metadata words), n' = n + 1 rows: the last
