@@ -269,6 +269,10 @@ int upk_igraph_inrange(const upk_launch_t* L, const upk_igraph_t* G, unsigned ch
 #endif
 #define UPK_FLAG_GRID(S) ((S) < 16 ? (S) : ((S) / UPK_FLAG_DIV > 16 ? (S) / UPK_FLAG_DIV : 16))
 #define UPK_FLAG_LIST(G) ((G).flagged + (size_t)(G).parity * (G).flag_stride)
+/* (of upk_rotamer_t below) k_rotamer_bp_layout folds the edges to 1-state partners into the node probabilities, and the solve takes them over, under this
+   condition and for the systems it laid out (word n_node + 7 of the record == 0).  Probability form only: the fold multiplies by the
+   matrix rows as stored, and in energy form they hold E until the solve's own exp pass, which runs behind the layout launch. */
+#define UPK_ROTAMER_PREFOLD(R) ((R).bp_layout && !(R).node_prob_in_solve && (R).p_prob)
 
 typedef struct {
     upk_igraph_t G;                      /* symmetric bead graph */

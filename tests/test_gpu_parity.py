@@ -653,8 +653,11 @@ ALT_PATHS = [
     {'UPSIDE_HIP_ROT_POLY': '0'},            # side-chain energy pass on the spline-coefficient table (tables too large for the polynomial form)
     {'UPSIDE_HIP_BP_CLUSTER': '1', 'UPSIDE_HIP_BP_ENERGY_TABLE': '1'},  # one-workgroup BP taking exp(-E) of the pair matrices itself
     {'UPSIDE_HIP_BP_CLUSTER': '1', 'UPSIDE_HIP_BP_COMPACT': '0'},       # one-workgroup BP of 1024 lanes streaming every pair matrix over the cached inbox layout
-    {'UPSIDE_HIP_BP_CLUSTER': '1', 'UPSIDE_HIP_BP_LAYOUT': '1'},        # one-workgroup BP with the inbox layout and the fold as a launch of their own (the choice from 512 systems on)
-    {'UPSIDE_HIP_BP_CLUSTER': '1', 'UPSIDE_HIP_BP_LAYOUT': '2'},        # ... whose scratch is too small for the system: every solve lays its inbox out itself after all
+    # one-workgroup BP with the inbox layout and the fold of the 1-state partners as a launch of their own (the choice from 512 systems on).  The fold
+    # runs there only with the node probabilities from a kernel of their own, which 1 to 3 systems do not select by themselves: hence the second switch
+    {'UPSIDE_HIP_BP_CLUSTER': '1', 'UPSIDE_HIP_BP_LAYOUT': '1', 'UPSIDE_HIP_NODE_PROB_IN_SOLVE': '0'},
+    # ... whose scratch is too small for the system: every solve lays its inbox out and folds itself after all
+    {'UPSIDE_HIP_BP_CLUSTER': '1', 'UPSIDE_HIP_BP_LAYOUT': '2', 'UPSIDE_HIP_NODE_PROB_IN_SOLVE': '0'},
     {'UPSIDE_HIP_BP_CLUSTER': '1', 'UPSIDE_HIP_BP_LDS_MSG_KB': '0'},    # one-workgroup BP, every message in global memory
     {'UPSIDE_HIP_BP_CLUSTER': '1', 'UPSIDE_HIP_BP_LDS_MSG_KB': '8'},    # LDS boundary inside the rows to 3-state nodes
     {'UPSIDE_HIP_BP_CLUSTER': '1', 'UPSIDE_HIP_BP_LDS_MSG_KB': '60'},   # LDS boundary inside the rows to 6-state nodes
@@ -707,9 +710,11 @@ def test_large_batch_solver_on_every_fixture():
     """what a LARGE batch runs is chosen by batch size (one-workgroup belief propagation, list upkeep on one side stream per graph, every
     kernel a launch of its own, no graph replay); forced here for the small parity cases -- every fixture incl. the degenerate
     sequences (empty slot classes), named values, truncated solves -- by re-running those tests in a child pytest: once with the
-    pinned-matrix solve over the dense inbox, once with the streaming solve over the cached inbox layout (the two compiled solves)"""
+    pinned-matrix solve over the dense inbox, once with the streaming solve over the cached inbox layout (the two compiled solves), and once
+    with the layout and the fold of the 1-state partners as a launch in front of the pinned-matrix solve (from 512 systems on: the fold runs
+    there only with the node probabilities from a kernel of their own, which these small cases select through the second switch)"""
     import subprocess
-    for extra in ({}, {'UPSIDE_HIP_BP_COMPACT': '0'}, {'UPSIDE_HIP_BP_LAYOUT': '1'}):
+    for extra in ({}, {'UPSIDE_HIP_BP_COMPACT': '0'}, {'UPSIDE_HIP_BP_LAYOUT': '1', 'UPSIDE_HIP_NODE_PROB_IN_SOLVE': '0'}):
         env = dict(os.environ, UPSIDE_HIP_BP_CLUSTER='1', UPSIDE_HIP_BATCH='0', UPSIDE_HIP_GRAPH='0', **extra)
         out = subprocess.run([sys.executable, '-m', 'pytest', os.path.abspath(__file__), '-q', '-x', '-m', 'gpu', '-p', 'no:cacheprovider',
                               '-k', 'force_pass or degenerate or named_values or truncated or golden'], env=env,

@@ -12,6 +12,7 @@ usage: python tools/make_fixtures.py [name ...]
        python tools/make_fixtures.py --restraints                    (proteinG56_restraints: every optional node)
        python tools/make_fixtures.py --edge-cases                    (edge_*: degenerate sequences)
        python tools/make_fixtures.py --parameters                    (tests/golden/parameters: what write_config reads)
+       python tools/make_fixtures.py --multibead                     (multibead_proteinG56.golden.npz: two beads per state, tests/rotamer_multibead.py)
 """
 import os
 import subprocess
@@ -337,7 +338,32 @@ def make_parameters():
     np.save(os.path.join(out, 'rama_reference.npy'), cfg.load_rama_reference(os.path.join(PARAM, 'common', 'rama_reference.pkl')))
 
 
+def make_multibead():
+    """golden vectors of the reference on protein G with the synthetic several-beads-per-state side-chain library of
+    tests/rotamer_multibead.py (the library and the configuration are made at test time; only the vectors are committed)"""
+    import tempfile
+    sys.path.insert(0, os.path.join(ROOT, 'tests'))
+    import rotamer_multibead as M
+    with tempfile.TemporaryDirectory() as d:
+        path, info, n_type = M.write_configuration(d)
+        up = pkg.Upside(path, library=pkg.UpsideLibrary(os.path.join(REF, 'libupside_7A.so')))
+        g = M.record(up, path, n_type)
+        up.close()
+        dump = os.path.join(d, 'pairs.txt')
+        subprocess.check_call([os.path.join(REF, 'pairlist_dump_7A'), path, dump])
+        lines = open(dump).read().split('\n')
+        n_edge = int(lines[0].split()[1])
+        arr = np.array([ln.split() for ln in lines[1:1 + n_edge]], dtype='f8').reshape(n_edge, 5)
+        g['pairlist/edges'] = arr[:, :4].astype('i4')
+    np.savez_compressed(M.GOLDEN, **g)
+    print('%s: beads %d, bead types %d, energy %.4f, rotamer edges %d, golden %.2f MB' % (M.NAME, info['n_bead'], n_type, g['energy'], n_edge,
+                                                                                   os.path.getsize(M.GOLDEN) / 1e6))
+
+
 if __name__ == '__main__':
+    if sys.argv[1:2] == ['--multibead']:
+        make_multibead()
+        sys.exit(0)
     if sys.argv[1:2] == ['--parameters']:
         make_parameters()
         sys.exit(0)

@@ -12,7 +12,21 @@ orc = P.oracle_library()
 O1 = {'7A': '/tmp/refO1_7A/libupside_O1.so', '10A': '/tmp/refO1_10A/libupside_O1.so'}
 FIX = [('trpcage20_7A', '7A'), ('proteinG56_7A', '7A'), ('syn300_7A', '7A'), ('syn150_10A', '10A'), ('syn300_10A', '10A'),
        ('proteinG56_restraints', '7A'), ('edge_gly5', '7A'), ('edge_pro6', '7A'), ('edge_awa3', '7A')]
+# `python tools/noise_floor.py multibead_proteinG56`: that configuration alone (made by tests/rotamer_multibead.py in a temporary directory),
+# merged into the committed table; the profile line goes to stdout only
+ONLY = sys.argv[1:]
+FIXTURE_PATH = {}
+if ONLY:
+    import tempfile, rotamer_multibead as M
+    assert ONLY == [M.NAME], ONLY
+    _tmp = tempfile.TemporaryDirectory()
+    FIXTURE_PATH[M.NAME] = M.write_configuration(_tmp.name)[0]
+    FIX = [(M.NAME, '7A')]
+    _fixture = P.fixture
+    P.fixture = lambda name: FIXTURE_PATH.get(name) or _fixture(name)
 table, lines = {}, []
+if ONLY:
+    table = json.load(open(os.path.join(ROOT, 'tests', 'golden', 'reference_noise_floor.json')))
 for name, variant in FIX:
     lib = P.pkg.UpsideLibrary(O1[variant])
     g = P.golden(name)
@@ -37,7 +51,14 @@ for name, variant in FIX:
         else:
             line += ' | oracle-vs-golden: deriv %.2e' % entry['oracle_deriv']
         line += ' | oracle-vs-refO1: deriv %.2e' % P.rel_rms(a['deriv'], o['deriv'])
+        if ONLY and tag == 'pos' and 'param_deriv/rotamer' in g:      # (the several-beads configuration: its side-chain parameter derivative is pinned on its own)
+            up.deriv(g[tag]); uo.deriv(g[tag])
+            shp = g['param_deriv/rotamer'].shape
+            entry['param_deriv'] = float(P.rel_rms(g['param_deriv/rotamer'], up.get_param_deriv(shp, 'rotamer')))
+            entry['oracle_param_deriv'] = float(P.rel_rms(g['param_deriv/rotamer'], uo.get_param_deriv(shp, 'rotamer')))
+            line += ' | rotamer param deriv refO1 %.2e oracle %.2e' % (entry['param_deriv'], entry['oracle_param_deriv'])
         table[name][tag] = entry
         lines.append(line); print(line)
-open(os.path.join(ROOT, 'profiles', 'r03_reference_noise_floor.txt'), 'w').write('\n'.join(lines) + '\n')
+if not ONLY:
+    open(os.path.join(ROOT, 'profiles', 'r03_reference_noise_floor.txt'), 'w').write('\n'.join(lines) + '\n')
 json.dump(table, open(os.path.join(ROOT, 'tests', 'golden', 'reference_noise_floor.json'), 'w'), indent=1, sort_keys=True)

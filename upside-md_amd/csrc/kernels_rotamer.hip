@@ -1455,8 +1455,9 @@ __global__ void __launch_bounds__(BPL_THREADS) k_rotamer_bp_layout(upk_rotamer_t
     for (int i = tid; i <= NN; i += nt) o[i] = bp_start[i];
     if (tid < 3) o[NN + 1 + tid] = n_act[tid];
     if (tid == 0) { o[NN + 4] = ly.inbox_floats; o[NN + 5] = ly.inbox_floats3; o[NN + 6] = ly.w3; }
-    // the fold of the solve's prologue (a chain of dependent loads per node: slot ids -> flags -> matrix rows)
-    if (!R.node_prob_in_solve) {
+    // the fold of the solve's prologue (a chain of dependent loads per node: slot ids -> flags -> matrix rows); in energy form the rows
+    // still hold E here, so the solve folds after its exp pass
+    if (UPK_ROTAMER_PREFOLD(R)) {
         const int* adj_cnt = R.adj_cnt + (size_t)s * NN;
         const int* adj_slot = R.adj_slot + (size_t)s * NN * R.adj_cap;
         float* fo = (float*)(o + NN + 8);
@@ -1594,7 +1595,7 @@ __global__ void __launch_bounds__(BLOCK) k_rotamer_bp(upk_rotamer_t R, int want_
     BP_STAMP(2);
     // fold edges to 1-state partners into the node probabilities (move_edge_prob_to_node2, rotamer.cpp:378-385)
     // (four partners per trip: slot ids, then flags, then the rows, each as one batch of loads; same product order)
-    const bool pre_folded = COMPACT && R.bp_layout && !R.node_prob_in_solve && R.bp_layout[(size_t)s * bp_layout_stride(NN) + NN + 7] == 0;      // (k_rotamer_bp_layout folded: its probabilities replace the ones loaded above)
+    const bool pre_folded = COMPACT && UPK_ROTAMER_PREFOLD(R) && R.bp_layout[(size_t)s * bp_layout_stride(NN) + NN + 7] == 0;      // (k_rotamer_bp_layout folded: its probabilities replace the ones loaded above)
     if (pre_folded) {
         const float* fo = (const float*)(R.bp_layout + (size_t)s * bp_layout_stride(NN) + NN + 8);
         for (int i = tid; i < NN * 6; i += nt) prob[(i / 6) * NS + i % 6] = fo[i];

@@ -1401,7 +1401,8 @@ struct RotamerSidechain : public PotentialNode, BatchedParamDeriv {
         // solves of a launch run in several rounds over the CUs (a solve owns a whole CU): UPSIDE_HIP_BP_LAYOUT=0/1 forces it off / on (tests)
         {
             const int want = env_int("UPSIDE_HIP_BP_LAYOUT", -1);
-            if (want >= 1 || (want < 0 && S >= 512)) { bp_layout.alloc((size_t)S * (UPK_BP_LAYOUT_PER_NODE * n_node + UPK_BP_LAYOUT_EXTRA)); R.bp_layout = bp_layout.p; }
+            // (every word -1 until k_rotamer_bp_layout writes a record: word n_node + 7 == 0 then means "laid out by that launch" and nothing else)
+            if (want >= 1 || (want < 0 && S >= 512)) { bp_layout.alloc((size_t)S * (UPK_BP_LAYOUT_PER_NODE * n_node + UPK_BP_LAYOUT_EXTRA)); bp_layout.fill_bytes(0xff); R.bp_layout = bp_layout.p; }
         }
         iters.alloc(S); n_bad.alloc(S); energy.alloc(S); bp_start.alloc((size_t)S * (n_node + 1)); slot_off.alloc((size_t)S * R.slot_cap * 2);
         class_start.alloc((size_t)S * 6); slot_active_last.alloc((size_t)S * R.slot_cap);
@@ -1680,6 +1681,16 @@ struct RotamerSidechain : public PotentialNode, BatchedParamDeriv {
                 }
             }
             return ev;
+        }
+        if (!strcmp(log_name, "solve_form")) {   // which forms the solve runs in (tests): p_prob, node_prob_in_solve, bp_layout allocated, bp_C, the pre-fold
+            // selected, then word n_node + 7 of every system's layout record (0: laid out by k_rotamer_bp_layout in the last solve, 1: handed back to its
+            // solve, -1: no record written)
+            if (!bp_C_chosen) throw string("solve_form: no force evaluation yet");
+            vector<float> r = {(float)R.p_prob, (float)R.node_prob_in_solve, R.bp_layout ? 1.f : 0.f, (float)R.bp_C, UPK_ROTAMER_PREFOLD(R) ? 1.f : 0.f};
+            const auto ly = bp_layout.download();
+            const size_t stride = (size_t)UPK_BP_LAYOUT_PER_NODE * n_node + UPK_BP_LAYOUT_EXTRA;
+            for (int s = 0; s < ctx->n_system; ++s) r.push_back(R.bp_layout ? (float)ly[s * stride + n_node + 7] : -1.f);
+            return r;
         }
         if (!strcmp(log_name, "bp_trace")) {   // diagnostics: phase clocks (10 ns units) of system 0's last solve
             if (!R.bp_trace) throw string("set UPSIDE_HIP_BP_TRACE=1 before constructing the engine");
