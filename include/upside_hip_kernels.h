@@ -221,9 +221,6 @@ int upk_pairlist_build(const upk_launch_t* L, const upk_igraph_t* G);
 /* ... of the sides in `sides` only (bit 1: side-1 rows, bit 2: side-2 rows): a graph whose pair passes all gather over the rows of
  * one side never reads the other side's lists on the MD path (they can be built later from the same cache_pos) */
 int upk_pairlist_build_sides(const upk_launch_t* L, const upk_igraph_t* G, int sides);
-/* 1 if upk_igraph_rows and upk_igraph_backward over the rows of `row_side` take the LDS-staged (hit-list) path for this graph,
- * 0 if they fall back to the list-walking kernels, which read the cached lists of BOTH sides */
-int upk_igraph_passes_staged(const upk_launch_t* L, const upk_igraph_t* G, int row_side);
 /* K2b: this step's in-range pairs of every system for the rows of `side` (hit lists above), from the cached lists and
  * cur_pos; then the rows of that side sorted by descending hit count (ord1 / ord2, and ord1u for symmetric graphs) */
 int upk_pairlist_refine(const upk_launch_t* L, const upk_igraph_t* G, int side);
@@ -344,10 +341,7 @@ int upk_rotamer_node_prob(const upk_launch_t* L, const upk_rotamer_t* R);
 int upk_rotamer_pair_energy(const upk_launch_t* L, const upk_rotamer_t* R);
 /* damped belief propagation + marginals (+ Bethe free energy): rotamer.cpp:1005-1061, 453-522, 283-302, 405-451, 854-866 */
 int upk_rotamer_bp(const upk_launch_t* L, const upk_rotamer_t* R, int want_energy);
-/* floats of exp(-E) pair matrices one workgroup of the cluster solve can keep in LDS (to choose bp_C) */
-int upk_rotamer_bp_cluster_capacity(const upk_rotamer_t* R);
-int upk_rotamer_bp_cluster_threads(void);
-int upk_device_cu_count(void);   /* and the number of slots of one class it can own (one per lane) */
+int upk_device_cu_count(void);   /* compute units of the current device: an input of the launch plan (csrc/launch_plan.h) */
 /* derivative push: pair marginal x pair gradient gathered per bead, node marginals to the 1-body parents
  * (rotamer.cpp:956-985, interaction_graph.h:525-555) */
 int upk_rotamer_grad(const upk_launch_t* L, const upk_rotamer_t* R);

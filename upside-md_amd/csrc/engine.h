@@ -11,7 +11,7 @@
 // the library plug in through include/upside_hip_plugin.h (device nodes, or HostPotentialNode / HostCoordNode whose maths
 // runs on the host behind an explicit synchronisation).
 #pragma once
-#include "env_switch.h"
+#include "launch_plan.h"
 #include "../../include/upside_hip_plugin.h"   // the public part of the contract: DerivComputation, CoordNode, PotentialNode, registry
 
 struct Pos : public CoordNode {   // deriv_engine.h:122-141

@@ -1,5 +1,6 @@
 // The one reader of the environment switches (UPSIDE_HIP_*: INTEGRATION.md section 6 lists them all).
-// A switch that is read once per process is written `static const int x = env_int(...);` at its point of use.
+// Switches that select a code path or size a capacity are read once, into PlanSwitches (launch_plan.h); a diagnostic switch is written
+// `static const int x = env_int(...);` at its point of use.
 #pragma once
 #include <cstdlib>
 

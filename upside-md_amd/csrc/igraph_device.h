@@ -23,7 +23,7 @@
 #include "../../include/upside_hip_kernels.h"
 #include <hip/amd_detail/amd_hip_unsafe_atomics.h>
 
-#include "env_switch.h"
+#include "launch_plan.h"
 
 // block coordinates of a kernel body: those of its own launch, or its range of a merged launch (kernels_batch.h)
 struct BX { int bx, gx, by, gy; };
@@ -297,9 +297,6 @@ __device__ __forceinline__ void load_row8(float* x, const float* p) {   // one 3
 }
 
 // ---- 8-lane groups ------------------------------------------------------------------------------------------
-#ifndef PG_LANES
-#define PG_LANES 8
-#endif
 #define PG_PER_WAVE (UP_WAVE / PG_LANES)
 // pair kernels run one 1024-lane workgroup per CU (LDS): 4 wavefronts per SIMD, so a lane may use 128 VGPRs -- tell the
 // register allocator, or it keeps to 64 in the hope of an occupancy the LDS footprint rules out
@@ -350,7 +347,6 @@ __device__ __forceinline__ void stage_ranges(int* lds_range, unsigned short* lds
         lds_ord[t] = ord[t];
     }
 }
-#define PG_WALK_LDS_WORDS(n_rows) ((n_rows) + ((n_rows) + 1) / 2)   // 32-bit words of LDS behind stage_ranges
 
 // Batches b = batch_first, batch_first + batch_step, ... of 8 consecutive rows of the sorted order `ord` (LDS), claimed by
 // the wavefronts of this workgroup through the LDS counter `counter` (zeroed and barrier-published by the caller).  Op provides
@@ -412,23 +408,10 @@ __device__ __forceinline__ void group_batch_loop(Op& op, int n_rows, const unsig
     }
 }
 
-// launch geometry of an LDS-staged pair pass: workgroups per system and lanes per workgroup.  A large batch runs one
-// 1024-lane workgroup (16 wavefronts = 128 rows in flight) per system; small batches spread a system over several smaller
-// workgroups (each stages the system again, so only as many as it takes to give every CU work).
-// lanes_per_row, rows_per_full_wg: PG_LANES and 128 for the 8-row batches of pair_walk, P2_LANES and 256 for the 16-row batches of pair2_walk.
-static inline void pair_geometry(int n_system, int n_rows, int lanes_per_row, int rows_per_full_wg, int& wgs_per_system, int& threads) {
-    static const int wgs_env = env_int("UPSIDE_HIP_IG_WGS", 256);
-    const int target = wgs_env < 1 ? 256 : wgs_env;
-    int bps = (target + n_system - 1) / n_system;
-    // every workgroup stages the whole system (table, elements, row order): at least one batch of rows per wavefront of a
-    // 1024-lane workgroup, i.e. 128 (256) rows each -- a single system is served by ~10 fat workgroups, not by 40 thin ones
-    const int max_bps = (n_rows + rows_per_full_wg - 1) / rows_per_full_wg;
-    if (bps > max_bps) bps = max_bps;
-    if (bps < 1) bps = 1;
-    const int rows_per_wg = (n_rows + bps - 1) / bps;
-    int t = ((rows_per_wg * lanes_per_row + 63) / 64) * 64;      // one batch per wavefront
-    threads = t < 256 ? 256 : (t > 1024 ? 1024 : t);
-    wgs_per_system = bps;
+// what the planner needs to know of a two-sided graph (launch_plan.h)
+static inline PairShape pair_shape(const upk_igraph_t* G) {
+    const bool cov = G->itype == UPK_IT_HBOND_COVERAGE;
+    return {cov, cov && G->param_poly, G->n1, G->n2, G->cap1, G->cap2, G->n_type1, G->n_type2, G->n_param, G->n_poly};
 }
 
 __device__ __forceinline__ float fast_rcp(float x) { return __builtin_amdgcn_rcpf(x); }   // v_rcp_f32, 1 ulp

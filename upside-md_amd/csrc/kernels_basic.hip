@@ -4,7 +4,7 @@
 // gathers deterministically (upk_gather_contrib) -- no float atomics anywhere in the force pass.
 #include "device_math.h"
 #include "../../include/upside_hip_kernels.h"
-#include "env_switch.h"
+#include "launch_plan.h"
 #include <cstdio>
 #include <cstring>
 #include <cstdlib>
@@ -1836,7 +1836,8 @@ __global__ void __launch_bounds__(T) k_fused_one(FusedOp op) {       // an op on
 
 namespace {
 struct FuseQueue {
-    int n_system = 1, threads = 1024;
+    int n_system = 1;
+    int lanes(bool heavy) const { return plan_fuse_lanes(plan_switches(), n_system, heavy); }   // workgroup size of a fused launch
     bool enabled = true;
     FusedOp* table_dev = nullptr; int cap = 4096;
     std::vector<FusedOp> table;                                   // host mirror of the registered ops
@@ -1854,21 +1855,9 @@ unsigned long long fuse_hash(const FusedOp& op) {
     for (size_t i = 0; i < sizeof(FusedOp); i += 8) { unsigned long long w; memcpy(&w, b + i, 8); h = (h ^ w) * 1099511628211ull; h ^= h >> 29; }
     return h;
 }
-// workgroup size of a fused launch: enough lanes for the per-element loops of a system (a few hundred to a few thousand items) in a
-// small batch, several systems resident per CU in a large one
-int fuse_threads(int n_system) {
-    static const int forced_env = env_int("UPSIDE_HIP_FUSE_THREADS", 0);
-    const int forced = (forced_env % 64 || forced_env > 1024) ? 0 : forced_env;
-    if (forced) return forced;
-    // (256-lane workgroups fill a CU eight at a time: worth it once there are systems for all of them -- 512 lanes against 256, k
-    //  system-steps/s: 300 residues x 256 149 / 142, x 1024 178 / 175, x 2048 equal, x 4096 186 / 187; 56 residues x 256 664 / 613,
-    //  x 512 893 / 846, x 2048 1069 / 1099)
-    return n_system >= 2048 ? 256 : (n_system >= 256 ? 512 : 1024);
-}
 template <bool LIST, typename... Args>
 void fuse_launch(bool heavy, int threads, int n_system, size_t lds, hipStream_t st, Args... args) {
     const dim3 g(n_system);
-    if (heavy && threads > 512) threads = 512;           // (the heavy instances are built for at most 512 lanes)
     const dim3 b(threads);
     if constexpr (LIST) {
         if (heavy) { if (threads <= 256) hipLaunchKernelGGL((k_fused_list<true, 256>), g, b, lds, st, args...); else hipLaunchKernelGGL((k_fused_list<true, 512>), g, b, lds, st, args...); }
@@ -1886,10 +1875,10 @@ static_assert(sizeof(FusedOp) == 16 + FUSE_PAYLOAD && sizeof(FusedOp) % 8 == 0, 
 
 extern "C" void* upk_fuse_create(int n_system) {
     FuseQueue* q = new FuseQueue;
-    q->n_system = n_system; q->threads = fuse_threads(n_system);
-    q->enabled = env_int("UPSIDE_HIP_FUSE", 1) != 0;
+    q->n_system = n_system;
+    q->enabled = plan_switches().FUSE != 0;
     q->pending.n = 0;
-    q->elide = env_int("UPSIDE_HIP_FUSE_BARRIERS", 0) == 0;
+    q->elide = plan_switches().FUSE_BARRIERS == 0;
     if (env_set("UPSIDE_HIP_FUSE_TRACE")) (void)hipMalloc((void**)&q->trace_dev, sizeof(long long) * (FUSE_MAX_PENDING + 1));
     if (hipMalloc((void**)&q->table_dev, (size_t)q->cap * sizeof(FusedOp)) != hipSuccess) { delete q; return nullptr; }
     q->table.reserve(256);
@@ -1921,8 +1910,9 @@ extern "C" int upk_fuse_flush(const upk_launch_t* L) {
     size_t lds = (size_t)q->pending_lds; if (lds < 64) lds = 64;      // (c_reduce_sum's partial sums)
     static const bool debug = env_set("UPSIDE_HIP_FUSE_DEBUG");
     if (debug) { fprintf(stderr, "fused launch (%s):", q->pending_heavy ? "heavy" : "light"); for (int k = 0; k < q->pending.n; ++k) fprintf(stderr, " %d%s", q->table[q->pending.id[k]].kind, (q->table[q->pending.id[k]].flags & 1) ? "" : "|"); fprintf(stderr, "\n"); }
-    { const int T = q->pending_heavy && q->threads > 512 ? 512 : q->threads; for (int k = 0; k < q->pending.n; ++k) q->pending.rot[k] %= T; }   // (the heavy instance runs 512 lanes)
-    fuse_launch<true>(q->pending_heavy, q->threads, q->n_system, lds, ST(L), (const FusedOp*)q->table_dev, q->pending, q->trace_dev);
+    const int T = q->lanes(q->pending_heavy);
+    for (int k = 0; k < q->pending.n; ++k) q->pending.rot[k] %= T;      // (the heavy instance runs at most 512 lanes)
+    fuse_launch<true>(q->pending_heavy, T, q->n_system, lds, ST(L), (const FusedOp*)q->table_dev, q->pending, q->trace_dev);
     if (q->trace_dev) {       // per-op times of wavefront 0 of system 0 (with barriers elided an op's time includes waiting for nothing: reach-to-reach)
         long long t[FUSE_MAX_PENDING + 1];
         if (hipStreamSynchronize(ST(L)) == hipSuccess && hipMemcpy(t, q->trace_dev, sizeof(long long) * (q->pending.n + 1), hipMemcpyDeviceToHost) == hipSuccess)
@@ -1968,7 +1958,7 @@ static int fuse_submit_raw(const upk_launch_t* L, int kind, const void* args, si
     }
     auto alone = [&]() {
         size_t lds = (size_t)lds_bytes; if (lds < 64) lds = 64;
-        fuse_launch<false>(kind == FOP_AFFINE_BWD, q ? q->threads : fuse_threads(L->n_system), L->n_system, lds, ST(L), op);
+        fuse_launch<false>(kind == FOP_AFFINE_BWD, plan_fuse_lanes(plan_switches(), q ? q->n_system : L->n_system, kind == FOP_AFFINE_BWD), L->n_system, lds, ST(L), op);
         return launch_status();
     };
     // (an op that launches now, not through the queue: what an open merged launch holds runs first)
@@ -1989,13 +1979,11 @@ static int fuse_submit_raw(const upk_launch_t* L, int kind, const void* args, si
         q->table.push_back(op); bucket.push_back(id);
     }
     if (kind == FOP_AFFINE_BWD) {
-        // a large batch, or a system whose other ops want all 1024 lanes, runs the register-hungry op in a launch of its own: the ops
-        // around it keep the light instance (its occupancy, its workgroup size)
-        if (q->n_system >= 256 || n > 64) { UPK_FLUSH(L); q->pending.rot[q->pending.n] = 0; q->pending.id[q->pending.n++] = (unsigned short)id; q->pending_heavy = true; return upk_fuse_flush(L); }
+        if (plan_heavy_op_alone(q->n_system, n)) { UPK_FLUSH(L); q->pending.rot[q->pending.n] = 0; q->pending.id[q->pending.n++] = (unsigned short)id; q->pending_heavy = true; return upk_fuse_flush(L); }
         q->pending_heavy = true;
     }
     {   // where this op's element loop starts: behind the lanes of the ops it may run beside (whole wavefronts; collective ops take them all)
-        const int T = q->pending_heavy && q->threads > 512 ? 512 : q->threads;
+        const int T = q->lanes(q->pending_heavy);
         const int lanes = n > 0 ? (n + 63) & ~63 : T;
         q->pending.rot[q->pending.n] = (unsigned short)(q->next_rot % T);
         q->next_rot = (q->next_rot + (lanes < T ? lanes : T)) % T;

@@ -191,33 +191,20 @@ __device__ __forceinline__ void d_pairlist_check(const upk_igraph_t& G, const BX
     }
 }
 __global__ void k_pairlist_check(upk_igraph_t G)  { d_pairlist_check(G, BX_REAL, nullptr); }
-// Workgroup size of the list-upkeep kernels (rebuild test, list build) when they are launched on their own.  A batch that fills the
-// device runs them on side streams next to the pair passes of the main stream, whose 1024-lane workgroups hold ~100 registers per lane
-// and 55-106 KB of LDS: what a CU has left beside one of those is 4 wavefront slots and ~96 registers per SIMD -- room for workgroups of
-// 256 lanes at <= 40 registers, none for one of 1024.  With 256 lanes the vector-bound list build and the memory-bound rebuild test run
-// BESIDE the LDS-bound pair passes instead of taking turns with them at workgroup granularity (4096 systems: 214.8 -> 218.2 k system-steps/s,
-// three alternating runs; the build alone +0.8 %; the slot-numbering kernel at 320 lanes as well: no further change; 1024 systems +0.9 %,
-// 512 x 150 residues +0.4 %, 256 systems -1.4 %: from two systems per CU on).  Smaller batches keep the large workgroups: there a
-// system's latency is what a step waits for.
-static inline int upkeep_block(int n_system, int large) { return n_system >= 2 * upk_device_cu_count() ? 256 : large; }
 extern "C" int upk_pairlist_check(const upk_launch_t* L, const upk_igraph_t* G) {
     if (batch_add(L, BK_CHECK, 1, L->n_system, 0, G, sizeof(*G))) return 0;
     UPK_FLUSH(L);
     // (latency bound -- every element is a chain load position -> load reference -> store packed copy: as many lanes as the
     //  system has elements, up to a full workgroup, so that a lane walks one or two elements instead of seven)
     const int n_tot = G->symmetric ? G->n1 : G->n1 + G->n2;
-    const int threads = upkeep_block(L->n_system, n_tot <= 256 ? 256 : (n_tot <= 512 ? 512 : 1024));
+    const int threads = plan_upkeep_block(L->n_system, upk_device_cu_count(), n_tot <= 256 ? 256 : (n_tot <= 512 ? 512 : 1024));
     hipLaunchKernelGGL(k_pairlist_check, dim3(1, L->n_system), dim3(threads), 0, ST(L), *G);
     return launch_status();
 }
 
 // K2: rebuild the row lists of the flagged systems from the refreshed reference positions.  A workgroup stages the
-// whole other side (16 bytes per element) in LDS and serves plb_rows() rows; one wavefront per row tests 64
+// whole other side (16 bytes per element) in LDS and serves plan_list_build_rows() rows; one wavefront per row tests 64
 // candidates at a time and compacts hits with a ballot + popcount prefix, so each row comes out in ascending order.
-// rows per workgroup: every workgroup stages the whole other side first, so more rows per workgroup amortise that copy
-// (128 rows: +0.4 % of the benchmark at 4096 systems; 256 leaves too few workgroups per system: -0.4 %), while a small
-// batch wants its few rebuilds spread over many workgroups (64 rows: +1 % at 1 and 64 systems)
-static inline int plb_rows(int n_system) { return n_system >= upk_device_cu_count() ? 128 : 64; }
 // IT: pair functor (compile time, so the id rule is straight-line code); the inner loop is written without
 // short-circuit tests: uniform branches and nested exec masks cost as much as the arithmetic here (measured: the
 // branchy form spent ~half of each 64-candidate trip in scalar control flow).  The staged copy is padded to a multiple
@@ -311,22 +298,21 @@ __global__ void __launch_bounds__(1024) k_pairlist_build(upk_igraph_t G, int blo
 }
 template <int IT>
 static void plb_launch(const upk_launch_t* L, const upk_igraph_t* G, dim3 grid, size_t lds, bool staged, int blocks1) {
-    const int rows = plb_rows(L->n_system);
-    if (staged) hipLaunchKernelGGL((k_pairlist_build<true, IT>), grid, dim3(upkeep_block(L->n_system, 1024)), lds, ST(L), *G, blocks1, rows);
+    const int rows = plan_list_build_rows(L->n_system, upk_device_cu_count());
+    if (staged) hipLaunchKernelGGL((k_pairlist_build<true, IT>), grid, dim3(plan_upkeep_block(L->n_system, upk_device_cu_count(), 1024)), lds, ST(L), *G, blocks1, rows);
     else hipLaunchKernelGGL((k_pairlist_build<false, IT>), grid, dim3(1024), 0, ST(L), *G, blocks1, rows);
 }
 extern "C" int upk_pairlist_build(const upk_launch_t* L, const upk_igraph_t* G) { return upk_pairlist_build_sides(L, G, 3); }
 extern "C" int upk_pairlist_build_sides(const upk_launch_t* L, const upk_igraph_t* G, int sides) {
     if (!list_words_match(G)) return 9010;
-    const int rows = plb_rows(L->n_system);
+    const int rows = plan_list_build_rows(L->n_system, upk_device_cu_count());
     const int blocks1 = (sides & 1) ? (G->n1 + rows - 1) / rows : 0;
     const int blocks2 = (G->symmetric || !(sides & 2)) ? 0 : (G->n2 + rows - 1) / rows;
     if (blocks1 + blocks2 == 0) return 0;
     const int n_max = G->n1 > G->n2 ? G->n1 : G->n2;
     const size_t lds = (size_t)((n_max + 63) & ~63) * 16;
     const dim3 grid(blocks1 + blocks2, UPK_FLAG_GRID(L->n_system));
-    static const bool force_unstaged = env_int("UPSIDE_HIP_PLB_UNSTAGED", 0) != 0;   // =1 exercises the path of systems whose elements do not fit LDS
-    const bool staged = lds <= 150 * 1024 && !force_unstaged;
+    const bool staged = plan_list_build_staged(plan_switches(), lds);   // (UPSIDE_HIP_PLB_UNSTAGED=1 exercises the path of systems whose elements do not fit LDS)
     if (staged) {       // merged launch (kernels_batch.h)
         const int bk = G->itype == UPK_IT_ROTAMER ? BK_BUILD_ROT : G->itype == UPK_IT_HBOND_COVERAGE ? BK_BUILD_COV : G->itype == UPK_IT_ENVIRONMENT ? BK_BUILD_ENV
                      : G->itype == UPK_IT_PROTEIN_HBOND ? BK_BUILD_HB : 0;
@@ -353,9 +339,6 @@ extern "C" int upk_pairlist_build_sides(const upk_launch_t* L, const upk_igraph_
 // the next PLR_DEPTH row pairs in flight.
 #ifndef PLR_BLOCK
 #define PLR_BLOCK 256
-#endif
-#ifndef PLR_ROWS
-#define PLR_ROWS 256
 #endif
 #ifndef PLR_DEPTH
 #define PLR_DEPTH 2
@@ -507,13 +490,8 @@ extern "C" int upk_pairlist_refine(const upk_launch_t* L, const upk_igraph_t* G,
     if (!list_words_match(G)) return 9010;
     if ((G->symmetric != 0) == (G->word16 != 0)) return 9011;   // the two list forms there are: the rotamer graph's (symmetric, 32-bit words) and everyone else's
     const size_t lds = (size_t)((n_other > 0 ? n_other : 0) + 1) * 16;
-    if (lds > 150 * 1024) return 9006;   // (callers fall back to the list-walking kernels long before this)
-    // every workgroup stages the other side again: few fat workgroups for a large batch, many small ones for a small one
-    int rows_per_wg = L->n_system >= upk_device_cu_count() ? PLR_ROWS : (L->n_system >= 16 ? 64 : 16);
-    {   // a side of a few hundred rows (environment graph: 300): smaller workgroups, or one of its two would walk 256 rows as 32
-        // dependent row pairs per wavefront while the other has 44 (0.30 -> 0.24 ms)
-        if (n_rows <= 512 && rows_per_wg > 128) rows_per_wg = 128;
-    }
+    if (lds > PLAN_LIST_LDS) return 9006;   // (callers fall back to the list-walking kernels long before this)
+    const int rows_per_wg = plan_refine_rows(L->n_system, upk_device_cu_count(), n_rows);
     {   // merged launch: 1024-lane workgroups, four times the wavefronts -- four times the rows, so that a wavefront keeps its run of row pairs
         const int rows_b = rows_per_wg * 4;
         if (batch_add(L, G->symmetric ? BK_REFINE_SYM : BK_REFINE, (n_rows + rows_b - 1) / rows_b, L->n_system, lds, G, sizeof(*G), nullptr, 0, side, rows_b)) return 0;
@@ -786,7 +764,7 @@ extern "C" int upk_igraph_param_deriv(const upk_launch_t* L, const upk_igraph_t*
 }
 
 // Parameter derivatives of ALL systems in one launch (upside_hip_get_param_deriv_all), into [n_system][n_type1][n_type2][n_param],
-// every entry written.  grid: x = slice of the table's type-pair rows (pd_table_slices), y = system; one workgroup adds the terms
+// every entry written.  grid: x = slice of the table's type-pair rows (plan_pd_table_slices), y = system; one workgroup adds the terms
 // of the pairs of its system whose row lies in its slice to a 64-bit fixed-point image of the slice in LDS (to_fixed32: integer
 // adds are exact and commute, so an entry depends neither on the order of arrival nor on the other systems of the batch -- no
 // float atomic decides a value) and stores it as fp32 with plain coalesced stores.  Pairs of other slices are skipped before
@@ -830,15 +808,6 @@ __global__ void __launch_bounds__(IG_BLOCK) k_igraph_param_deriv_all(upk_igraph_
     float* out = table + ((size_t)s * n_rows + r_lo) * G.n_param;
     for (int t = threadIdx.x; t < n_acc; t += blockDim.x) out[t] = from_fixed32(pd_acc[t]);
 }
-// rows of n_param entries per workgroup so that a slice's fixed-point image fits the LDS (the pair passes' 158 KiB); 0: one row
-// alone does not fit
-static int pd_table_slices(int n_rows, int n_param, int& n_slice) {
-    const size_t row_bytes = (size_t)(n_param > 0 ? n_param : 1) * sizeof(unsigned long long);
-    const int fit = (int)((size_t)158 * 1024 / row_bytes);
-    if (fit < 1 || n_rows < 1) { n_slice = 0; return 0; }
-    n_slice = (n_rows + fit - 1) / fit;
-    return (n_rows + n_slice - 1) / n_slice;      // balanced slices
-}
 extern "C" int upk_igraph_param_deriv_all(const upk_launch_t* L, const upk_igraph_t* G, int sens_mode, const float* sens1, const float* sens2,
                                           long sens_sys_stride, int sens_stride, float* table) {
     UPK_FLUSH(L);
@@ -848,9 +817,10 @@ extern "C" int upk_igraph_param_deriv_all(const upk_launch_t* L, const upk_igrap
         if (n) { const hipError_t e = hipMemsetAsync(table, 0, n * sizeof(float), ST(L)); if (e != hipSuccess) return (int)e; }
         return 0;
     }
-    int n_slice; const int rows = pd_table_slices(G->n_type1 * G->n_type2, G->n_param, n_slice);
-    if (!n_slice) return n ? 9103 : 0;
-    hipLaunchKernelGGL(k_igraph_param_deriv_all, dim3(n_slice, L->n_system), dim3(IG_BLOCK), (size_t)rows * G->n_param * sizeof(unsigned long long),
+    const TableSlices sl = plan_pd_table_slices(G->n_type1 * G->n_type2, G->n_param);
+    const int rows = sl.rows;
+    if (!sl.n_slice) return n ? 9103 : 0;
+    hipLaunchKernelGGL(k_igraph_param_deriv_all, dim3(sl.n_slice, L->n_system), dim3(IG_BLOCK), (size_t)rows * G->n_param * sizeof(unsigned long long),
                        ST(L), *G, rows, sens_mode, sens1, sens2, sens_sys_stride, sens_stride, table);
     return launch_status();
 }

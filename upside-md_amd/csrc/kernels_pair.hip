@@ -9,6 +9,7 @@
 #include "igraph_device.h"
 #include "pair2_device.h"
 #include <cstring>
+#include <type_traits>
 
 using namespace up;
 // list words of the graphs served here (every graph but the rotamer's, which has its own passes in kernels_rotamer.hip): igraph_device.h
@@ -509,16 +510,6 @@ __device__ __forceinline__ void d_pair_backward_finish(const upk_igraph_t& G, in
 }
 __global__ void k_pair_backward_finish(upk_igraph_t G, int other_side, double unit)  { d_pair_backward_finish(G, other_side, unit, BX_REAL, nullptr); }
 
-// LDS bytes of a staged pair pass; false when the system does not fit (callers fall back to the list-walking kernels)
-static bool pair_lds_bytes(const upk_igraph_t* G, bool poly, int& tab_floats, size_t& bytes) {
-    tab_floats = G->n_type1 * G->n_type2 * (poly ? G->n_poly : G->n_param);
-    if (poly && !(G->itype == UPK_IT_HBOND_COVERAGE && G->param_poly)) return false;
-    const int n_max = G->n1 > G->n2 ? G->n1 : G->n2;
-    bytes = ((size_t)((tab_floats + 3) & ~3) + (size_t)(G->n1 + G->n2) * 8 + PG_WALK_LDS_WORDS(n_max) + 4) * sizeof(float);
-    static const bool force_unstaged = env_int("UPSIDE_HIP_IG_UNSTAGED", 0) != 0;   // =1 exercises the path taken by systems too large for LDS staging
-    return bytes <= 158 * 1024 && !force_unstaged && n_max < 65536 && G->cap1 < 65536 && G->cap2 < 65536;
-}
-
 template <int IT, int SIDES, bool POLY>
 static void rows_launch(const upk_launch_t* L, const upk_igraph_t* G, int mode, dim3 grid, dim3 block, size_t lds, const PairArgs& A) {
     if (mode == 0) hipLaunchKernelGGL((k_pair_rows<IT, SIDES, 0, POLY>), grid, block, lds, ST(L), *G, A);
@@ -531,22 +522,12 @@ static void rows_launch_sides(const upk_launch_t* L, const upk_igraph_t* G, int 
     else if (side == 2) rows_launch<IT, 2, POLY>(L, G, mode, grid, block, lds, A);
     else rows_launch<IT, 3, POLY>(L, G, mode, grid, block, lds, A);
 }
-// the polynomial table when it fits LDS next to the elements (and extra bytes), else the spline coefficients, else nothing fits
-static int pair_table_choice(const upk_igraph_t* G, size_t extra, int& tab_floats, size_t& lds) {
-    static const bool no_poly = env_int("UPSIDE_HIP_IG_POLY", 1) == 0;   // =0: always the spline-coefficient table (A/B and the large-table path)
-    if (!no_poly && pair_lds_bytes(G, true, tab_floats, lds) && lds + extra <= 158 * 1024) return 2;
-    if (pair_lds_bytes(G, false, tab_floats, lds) && lds + extra <= 158 * 1024) return 1;
-    return 0;
-}
-
-extern "C" int upk_igraph_passes_staged(const upk_launch_t* L, const upk_igraph_t* G, int row_side) {
-    UPK_FLUSH(L);
-    (void)L;
-    if (row_side != 1 && row_side != 2) return 0;
-    const int n_other = row_side == 1 ? G->n2 : G->n1;
-    int tab_floats; size_t lds;
-    if (!pair_table_choice(G, 0, tab_floats, lds)) return 0;
-    return pair_table_choice(G, 8 + (size_t)n_other * 8 * sizeof(unsigned long long), tab_floats, lds) ? 1 : 0;   // (an upper bound of the accumulators)
+// f(side, poly) with both as compile-time constants: the instances of the packed coverage passes and of the coverage backward pass
+template <typename F>
+static void with_side_poly(int side, bool poly, F f) {
+    using S1 = std::integral_constant<int, 1>; using S2 = std::integral_constant<int, 2>;
+    if (side == 1) { if (poly) f(S1(), std::true_type()); else f(S1(), std::false_type()); }
+    else { if (poly) f(S2(), std::true_type()); else f(S2(), std::false_type()); }
 }
 
 extern "C" int upk_igraph_rows(const upk_launch_t* L, const upk_igraph_t* G, int side, int mode, float* out, long out_sys_stride,
@@ -560,9 +541,11 @@ extern "C" int upk_igraph_rows(const upk_launch_t* L, const upk_igraph_t* G, int
     A.own_grad = own_grad;
     A.sens_mode = sens_mode; A.sens1 = sens1; A.sens2 = sens2; A.sens_sys_stride = sens_sys_stride; A.sens_stride = sens_stride;
     A.atomic_sens = side == 3 && G->sens_overlap;
-    size_t lds;
-    const int table = pair_table_choice(G, 0, A.tab_floats, lds);
-    if (!table) {                                      // list-walking kernels, one side at a time
+    const PlanSwitches& sw = plan_switches();
+    const PairPass p = plan_pair_forward(sw, pair_shape(G), side, mode);
+    A.tab_floats = p.tab_floats;
+    const size_t lds = p.lds_bytes; const bool poly = p.table == PLAN_TABLE_POLY;
+    if (!p.table) {                                    // list-walking kernels, one side at a time
         UPK_FLUSH(L);
         int r = 0;
         for (int sd = 1; sd <= 2 && !r; ++sd) {
@@ -574,17 +557,15 @@ extern "C" int upk_igraph_rows(const upk_launch_t* L, const upk_igraph_t* G, int
         return r;
     }
     const int n_rows = side == 1 ? G->n1 : (side == 2 ? G->n2 : (G->n1 > G->n2 ? G->n1 : G->n2));
-    int bps, threads;
-    if (G->itype == UPK_IT_HBOND_COVERAGE && mode == 0 && side != 3 && pair2_enabled() && lds + 64 <= 158 * 1024) {   // packed pass
-        pair_geometry(L->n_system, n_rows, P2_LANES, 256, bps, threads);
-        if (side == 2 && batch_add(L, table == 2 ? BK_COV_ROWS2_POLY : BK_COV_ROWS2, bps, L->n_system, lds + 64, G, sizeof(*G), &A, sizeof(A))) return 0;
+    const PairGeometry g = plan_pair_geometry(sw, L->n_system, n_rows, p.packed);
+    const int bps = g.wgs_per_system; int threads = g.lanes;
+    if (p.packed) {
+        if (side == 2 && batch_add(L, poly ? BK_COV_ROWS2_POLY : BK_COV_ROWS2, bps, L->n_system, lds, G, sizeof(*G), &A, sizeof(A))) return 0;
         UPK_FLUSH(L);
-        const dim3 grid2(bps, L->n_system), block2(threads);
-        if (side == 1) { if (table == 2) hipLaunchKernelGGL((k_cov_rows2<1, true>), grid2, block2, lds + 64, ST(L), *G, A); else hipLaunchKernelGGL((k_cov_rows2<1, false>), grid2, block2, lds + 64, ST(L), *G, A); }
-        else { if (table == 2) hipLaunchKernelGGL((k_cov_rows2<2, true>), grid2, block2, lds + 64, ST(L), *G, A); else hipLaunchKernelGGL((k_cov_rows2<2, false>), grid2, block2, lds + 64, ST(L), *G, A); }
+        with_side_poly(side, poly, [&](auto rs, auto pl) {
+            hipLaunchKernelGGL((k_cov_rows2<decltype(rs)::value, decltype(pl)::value>), dim3(bps, L->n_system), dim3(threads), lds, ST(L), *G, A); });
         return launch_status();
     }
-    pair_geometry(L->n_system, n_rows, PG_LANES, 128, bps, threads);
     // (a few hundred rows of two or three pairs: the pass is the latency of staging the system, which several small workgroups
     //  per CU overlap: 1024 lanes 0.29 + 0.23 ms, 512: 0.25 + 0.18, 256: 0.23 + 0.17, 128: 0.29 + 0.20; the environment graph, 300 rows of ~40 pairs, is best left at 1024)
     if (G->itype == UPK_IT_PROTEIN_HBOND && bps == 1) {
@@ -599,7 +580,7 @@ extern "C" int upk_igraph_rows(const upk_launch_t* L, const upk_igraph_t* G, int
     const dim3 grid(bps, L->n_system), block(threads);
     switch (G->itype) {
         case UPK_IT_HBOND_COVERAGE:
-            if (table == 2) rows_launch_sides<UPK_IT_HBOND_COVERAGE, true>(L, G, side, mode, grid, block, lds, A);
+            if (poly) rows_launch_sides<UPK_IT_HBOND_COVERAGE, true>(L, G, side, mode, grid, block, lds, A);
             else rows_launch_sides<UPK_IT_HBOND_COVERAGE, false>(L, G, side, mode, grid, block, lds, A);
             break;
         case UPK_IT_ENVIRONMENT: rows_launch_sides<UPK_IT_ENVIRONMENT>(L, G, side, mode, grid, block, lds, A); break;
@@ -629,56 +610,32 @@ extern "C" int upk_igraph_backward(const upk_launch_t* L, const upk_igraph_t* G,
     const int d_other = G->itype == UPK_IT_HBOND_COVERAGE ? (row_side == 1 ? PairDims<UPK_IT_HBOND_COVERAGE>::d2 : PairDims<UPK_IT_HBOND_COVERAGE>::d1)
                       : G->itype == UPK_IT_ENVIRONMENT    ? (row_side == 1 ? PairDims<UPK_IT_ENVIRONMENT>::d2 : PairDims<UPK_IT_ENVIRONMENT>::d1)
                                                           : (row_side == 1 ? PairDims<UPK_IT_PROTEIN_HBOND>::d2 : PairDims<UPK_IT_PROTEIN_HBOND>::d1);
-    const size_t acc_bytes = 8 + (size_t)n_other * d_other * sizeof(unsigned long long);    // the other side's accumulators (BackwardOp::DO per element)
-    size_t lds;
-    const int table = pair_table_choice(G, acc_bytes, A.tab_floats, lds);
-    lds += acc_bytes;
-    if (!table) {      // list-walking kernels, one side at a time (they need no hit lists)
+    const PlanSwitches& sw = plan_switches();
+    const PairPass p = plan_pair_backward(sw, pair_shape(G), row_side, d_other);
+    A.tab_floats = p.tab_floats;
+    const size_t lds = p.lds_bytes; const bool poly = p.table == PLAN_TABLE_POLY;
+    if (!p.table) {      // list-walking kernels, one side at a time (they need no hit lists)
         UPK_FLUSH(L);
         int r = upk_igraph_grad(L, G, 1, sens_mode, sens1, sens2, sens_sys_stride, sens_stride);
         if (!r) r = upk_igraph_grad(L, G, 2, sens_mode, sens1, sens2, sens_sys_stride, sens_stride);
         return r;
     }
-    int bps, threads;
-    if (G->itype == UPK_IT_HBOND_COVERAGE && pair2_enabled()) {            // packed pass: + sentinel rows and the sites' sensitivities
-        const size_t extra = 64 + (size_t)G->n1 * sizeof(float);
-        size_t lds2; int tf;
-        const int table2 = pair_table_choice(G, acc_bytes + extra, tf, lds2);
-        if (table2) {
-            A.tab_floats = tf; lds2 += acc_bytes + extra;
-            pair_geometry(L->n_system, n_rows, P2_LANES, 256, bps, threads);
-            if (!G->gacc) bps = 1;
-            if (row_side == 2 && batch_add(L, table2 == 2 ? BK_COV_BWD2_POLY : BK_COV_BWD2, bps, L->n_system, lds2, G, sizeof(*G), &A, sizeof(A))) {
-                if (bps > 1 && !batch_add(L, BK_BWD_FINISH, (n_other * 8 + 1023) / 1024, L->n_system, 0, G, sizeof(*G), nullptr, 0, 3 - row_side, 0, 1.0 / (double)(1 << P2_FIX_BITS)))
-                    return finish_alone(L, G, n_other, 3 - row_side, 1.0 / (double)(1 << P2_FIX_BITS));
-                return 0;
-            }
-            UPK_FLUSH(L);
-            const dim3 grid2(bps, L->n_system), block2(threads);
-            if (row_side == 1) { if (table2 == 2) hipLaunchKernelGGL((k_cov_backward2<1, true>), grid2, block2, lds2, ST(L), *G, A); else hipLaunchKernelGGL((k_cov_backward2<1, false>), grid2, block2, lds2, ST(L), *G, A); }
-            else { if (table2 == 2) hipLaunchKernelGGL((k_cov_backward2<2, true>), grid2, block2, lds2, ST(L), *G, A); else hipLaunchKernelGGL((k_cov_backward2<2, false>), grid2, block2, lds2, ST(L), *G, A); }
-            if (bps > 1) hipLaunchKernelGGL(k_pair_backward_finish, dim3((n_other * 8 + 255) / 256, L->n_system), dim3(256), 0, ST(L), *G, 3 - row_side, 1.0 / (double)(1 << P2_FIX_BITS));
-            return launch_status();
-        }
-    }
-    pair_geometry(L->n_system, n_rows, PG_LANES, 128, bps, threads);
-    if (!G->gacc) bps = 1;
-    if (G->itype == UPK_IT_ENVIRONMENT && row_side == 1 && batch_add(L, BK_ENV_BWD, bps, L->n_system, lds, G, sizeof(*G), &A, sizeof(A))) {
-        if (bps > 1 && !batch_add(L, BK_BWD_FINISH, (n_other * 8 + 1023) / 1024, L->n_system, 0, G, sizeof(*G), nullptr, 0, 3 - row_side, 0, 1.0 / 4294967296.0))
-            return finish_alone(L, G, n_other, 3 - row_side, 1.0 / 4294967296.0);
+    const PairGeometry g = plan_pair_geometry(sw, L->n_system, n_rows, p.packed);
+    const int bps = G->gacc ? g.wgs_per_system : 1, threads = g.lanes;
+    const double unit = p.packed ? 1.0 / (double)(1 << P2_FIX_BITS) : 1.0 / 4294967296.0;   // value of one accumulator count
+    const int bk = p.packed ? (row_side == 2 ? (poly ? BK_COV_BWD2_POLY : BK_COV_BWD2) : 0) : ((G->itype == UPK_IT_ENVIRONMENT && row_side == 1) ? BK_ENV_BWD : 0);
+    if (bk && batch_add(L, bk, bps, L->n_system, lds, G, sizeof(*G), &A, sizeof(A))) {
+        if (bps > 1 && !batch_add(L, BK_BWD_FINISH, (n_other * 8 + 1023) / 1024, L->n_system, 0, G, sizeof(*G), nullptr, 0, 3 - row_side, 0, unit))
+            return finish_alone(L, G, n_other, 3 - row_side, unit);
         return 0;
     }
     UPK_FLUSH(L);
     const dim3 grid(bps, L->n_system), block(threads);
-    switch (G->itype) {
+    if (p.packed)
+        with_side_poly(row_side, poly, [&](auto rs, auto pl) { hipLaunchKernelGGL((k_cov_backward2<decltype(rs)::value, decltype(pl)::value>), grid, block, lds, ST(L), *G, A); });
+    else switch (G->itype) {
         case UPK_IT_HBOND_COVERAGE:
-            if (table == 2) {
-                if (row_side == 1) hipLaunchKernelGGL((k_pair_backward<UPK_IT_HBOND_COVERAGE, 1, true>), grid, block, lds, ST(L), *G, A);
-                else hipLaunchKernelGGL((k_pair_backward<UPK_IT_HBOND_COVERAGE, 2, true>), grid, block, lds, ST(L), *G, A);
-            } else {
-                if (row_side == 1) hipLaunchKernelGGL((k_pair_backward<UPK_IT_HBOND_COVERAGE, 1, false>), grid, block, lds, ST(L), *G, A);
-                else hipLaunchKernelGGL((k_pair_backward<UPK_IT_HBOND_COVERAGE, 2, false>), grid, block, lds, ST(L), *G, A);
-            }
+            with_side_poly(row_side, poly, [&](auto rs, auto pl) { hipLaunchKernelGGL((k_pair_backward<UPK_IT_HBOND_COVERAGE, decltype(rs)::value, decltype(pl)::value>), grid, block, lds, ST(L), *G, A); });
             break;
         case UPK_IT_ENVIRONMENT:
             if (row_side == 1) hipLaunchKernelGGL((k_pair_backward<UPK_IT_ENVIRONMENT, 1, false>), grid, block, lds, ST(L), *G, A);
@@ -690,7 +647,7 @@ extern "C" int upk_igraph_backward(const upk_launch_t* L, const upk_igraph_t* G,
             break;
         default: return 9008;
     }
-    if (bps > 1) hipLaunchKernelGGL(k_pair_backward_finish, dim3((n_other * 8 + 255) / 256, L->n_system), dim3(256), 0, ST(L), *G, 3 - row_side, 1.0 / 4294967296.0);
+    if (bps > 1) hipLaunchKernelGGL(k_pair_backward_finish, dim3((n_other * 8 + 255) / 256, L->n_system), dim3(256), 0, ST(L), *G, 3 - row_side, unit);
     return launch_status();
 }
 

@@ -17,11 +17,11 @@
 #include "../../include/upside_hip_kernels.h"
 #include "igraph_device.h"
 #include "pair2_device.h"
+#include "launch_plan.h"
 
 using namespace up;
 
 #define ST(L) ((hipStream_t)(L)->stream)
-#define BP_BLOCK 1024
 #ifndef UPK_LAUNCH_STATUS_DEFINED
 #define UPK_LAUNCH_STATUS_DEFINED
 static inline int launch_status() { return (int)hipGetLastError(); }
@@ -41,7 +41,7 @@ static inline int launch_status() { return (int)hipGetLastError(); }
 #define PIDX(R, sl, e) PIDX6((R).slot_cap, sl, (e) / 6, (e) % 6)
 
 // slot classes in storage order
-enum { CL33 = 0, CL36 = 1, CL66 = 2, CL11 = 3, CL1X = 4, N_CLASS = 5 };
+enum { CL33 = 0, CL36 = 1, CL66 = 2, CL11 = 3, CL1X = 4 };   // (N_CLASS of them: launch_plan.h)
 __device__ __forceinline__ int slot_class(int na, int nb) {   // na <= nb
     if (na == 1) return nb == 1 ? CL11 : CL1X;
     if (na == 3) return nb == 3 ? CL33 : CL36;
@@ -265,9 +265,7 @@ extern "C" int upk_rotamer_build_slots(const upk_launch_t* L, const upk_rotamer_
     // a small system's slot stamping (upk_rotamer_nbr_slots) rides behind the numbering in the same workgroup: one launch less on the upkeep chain
     if (R->G.n1 <= 512 && batch_add(L, BK_SLOTS_BOTH, 1, L->n_system < wgs ? L->n_system : wgs, lds, R, sizeof(*R))) { batch_of(L)->skip_nbr_slots = true; return 0; }
     // workgroups per system (see the kernel): several while the device has CUs to spare, one when systems fill it
-    static const int split_env = env_int("UPSIDE_HIP_SLOT_SPLIT", 0);    // (experiments / tests)
-    const int split = (split_env < 0 || split_env > 16) ? 0 : split_env;
-    const int K = split ? split : ((L->n_system <= 256 && R->n_node > 64) ? 4 : 1);
+    const int K = plan_slot_split(plan_switches(), L->n_system, R->n_node);
     if (batch_add(L, BK_BUILD_SLOTS, K, L->n_system < wgs ? L->n_system : wgs, lds, R, sizeof(*R))) return 0;
     UPK_FLUSH(L);
     hipLaunchKernelGGL(k_rotamer_build_slots, dim3(K, L->n_system < wgs ? L->n_system : wgs), dim3(BP_BLOCK), lds, ST(L), *R);
@@ -580,39 +578,18 @@ __global__ void __launch_bounds__(1024) PG_KERNEL_ATTR k_rotamer_grad2(upk_rotam
     }
 }
 
-static int rot_geometry(const upk_launch_t* L, const upk_rotamer_t* R, bool want_acc, int& tab_floats, size_t& lds_bytes, dim3& grid, dim3& block,
-                        bool poly = false, bool pair2 = false) {
-    const int nt = R->G.n_type1;
-    tab_floats = (nt * (nt + 1) / 2) * (poly ? R->n_poly : R->G.n_param);
-    const size_t fixed = ((size_t)((tab_floats + 3) & ~3) + PG_WALK_LDS_WORDS(R->G.n1) + 4) * sizeof(float);
-    static const bool force_unstaged = env_int("UPSIDE_HIP_ROT_UNSTAGED", 0) != 0;   // =1 exercises the large-system path
-    int staged = 1;
-    lds_bytes = fixed + (size_t)R->G.n1 * (want_acc ? 20 : 8) * sizeof(float) + (pair2 ? 32 : 0);
-    if (lds_bytes > 158 * 1024 || force_unstaged || R->bead_pack) { staged = 0; lds_bytes = fixed; }   // (a system whose gradient pass needs the packed copy uses it in both passes)
-    if (lds_bytes > 158 * 1024 || (!staged && !R->bead_pack)) return -1;
-    int bps, threads;
-    if (pair2) pair_geometry(L->n_system, R->G.n1, P2_LANES, 256, bps, threads);
-    else pair_geometry(L->n_system, R->G.n1, PG_LANES, 128, bps, threads);
-    grid = dim3(bps, L->n_system); block = dim3(threads);
-    return staged;
-}
+static RotShape rot_shape(const upk_rotamer_t* R) { return {R->G.n1, R->G.n_type1, R->G.n_param, R->n_poly, R->param_tri_poly != nullptr}; }
 extern "C" int upk_rotamer_pair_energy(const upk_launch_t* L, const upk_rotamer_t* R) {
     if (!list_words_match(&R->G)) return 9010;
     UPK_FLUSH(L);
-    int tab_floats; size_t lds; dim3 grid, block;
-    static const bool no_poly = env_int("UPSIDE_HIP_ROT_POLY", 1) == 0;   // =0 keeps the energy pass on the spline-coefficient table (A/B and the large-table path)
-    // (the packed two-partners-per-lane form of THIS pass was built in round 3 and removed in round 6: the pass is bound by its scattered
-    //  pair-matrix stores, and 16 rows x 4 partners per store instruction touch 1.7x the cache lines of 8 rows x 8 partners: 1.45 against 1.26 ms)
-    if (R->param_tri_poly && !no_poly && rot_geometry(L, R, false, tab_floats, lds, grid, block, true) == 1) {   // polynomial table + beads fit LDS
-        hipLaunchKernelGGL((k_rotamer_pair_energy<true, true>), grid, block, lds, ST(L), *R, tab_floats);
-        return launch_status();
-    }
-    const int staged = rot_geometry(L, R, false, tab_floats, lds, grid, block);
-    if (staged < 0) return 9005;   // interaction table larger than LDS
-    if (staged) hipLaunchKernelGGL((k_rotamer_pair_energy<true, false>), grid, block, lds, ST(L), *R, tab_floats);
+    const RotPass p = plan_rot_energy(plan_switches(), rot_shape(R), L->n_system, R->bead_pack != nullptr);
+    if (!p.fits) return 9005;   // interaction table larger than LDS
+    const dim3 grid(p.grid_x, L->n_system), block(p.lanes);
+    if (p.poly) hipLaunchKernelGGL((k_rotamer_pair_energy<true, true>), grid, block, p.lds_bytes, ST(L), *R, p.tab_floats);
+    else if (p.staged) hipLaunchKernelGGL((k_rotamer_pair_energy<true, false>), grid, block, p.lds_bytes, ST(L), *R, p.tab_floats);
     else {
         hipLaunchKernelGGL(k_rotamer_pack_beads, dim3((R->G.n1 * 8 + 255) / 256, L->n_system), dim3(256), 0, ST(L), *R);   // also serves upk_rotamer_grad
-        hipLaunchKernelGGL((k_rotamer_pair_energy<false, false>), grid, block, lds, ST(L), *R, tab_floats);
+        hipLaunchKernelGGL((k_rotamer_pair_energy<false, false>), grid, block, p.lds_bytes, ST(L), *R, p.tab_floats);
     }
     return launch_status();
 }
@@ -723,24 +700,15 @@ __global__ void k_rotamer_grad_finish(upk_rotamer_t R, double unit) {   // unit:
 extern "C" int upk_rotamer_grad(const upk_launch_t* L, const upk_rotamer_t* R) {
     if (!list_words_match(&R->G)) return 9010;
     UPK_FLUSH(L);
-    int tab_floats; size_t lds; dim3 grid, block;
-    const double unit32 = 1.0 / 4294967296.0, unit22 = 1.0 / (double)(1 << P2_FIX_BITS);
-    if (pair2_enabled()) {                     // packed passes: polynomial table if it fits beside the accumulators, else spline coefficients
-        for (int poly = 1; poly >= 0; --poly) {
-            if (poly && !R->param_tri_poly) continue;
-            if (rot_geometry(L, R, true, tab_floats, lds, grid, block, poly != 0, true) != 1) continue;
-            if (poly) hipLaunchKernelGGL(k_rotamer_grad2<true>, grid, block, lds, ST(L), *R, tab_floats);
-            else hipLaunchKernelGGL(k_rotamer_grad2<false>, grid, block, lds, ST(L), *R, tab_floats);
-            if (grid.x > 1) hipLaunchKernelGGL(k_rotamer_grad_finish, dim3((R->G.n1 * 6 + 255) / 256, L->n_system), dim3(256), 0, ST(L), *R, unit22);
-            return launch_status();
-        }
-    }
-    const int staged = rot_geometry(L, R, true, tab_floats, lds, grid, block);
-    if (staged < 0) return 9005;
-    if (staged) hipLaunchKernelGGL(k_rotamer_grad<true>, grid, block, lds, ST(L), *R, tab_floats);
-    else hipLaunchKernelGGL(k_rotamer_grad<false>, grid, block, lds, ST(L), *R, tab_floats);   // beads packed by upk_rotamer_pair_energy this step
-    if (!staged || grid.x > 1)
-        hipLaunchKernelGGL(k_rotamer_grad_finish, dim3((R->G.n1 * 6 + 255) / 256, L->n_system), dim3(256), 0, ST(L), *R, unit32);
+    const RotPass p = plan_rot_grad(plan_switches(), rot_shape(R), L->n_system, R->bead_pack != nullptr);
+    if (!p.fits) return 9005;
+    const dim3 grid(p.grid_x, L->n_system), block(p.lanes);
+    if (p.packed && p.poly) hipLaunchKernelGGL(k_rotamer_grad2<true>, grid, block, p.lds_bytes, ST(L), *R, p.tab_floats);
+    else if (p.packed) hipLaunchKernelGGL(k_rotamer_grad2<false>, grid, block, p.lds_bytes, ST(L), *R, p.tab_floats);
+    else if (p.staged) hipLaunchKernelGGL(k_rotamer_grad<true>, grid, block, p.lds_bytes, ST(L), *R, p.tab_floats);
+    else hipLaunchKernelGGL(k_rotamer_grad<false>, grid, block, p.lds_bytes, ST(L), *R, p.tab_floats);   // beads packed by upk_rotamer_pair_energy this step
+    if (!p.staged || p.grid_x > 1)   // the value of one accumulator count: 2^-22 in the packed pass, 2^-32 in the scalar one
+        hipLaunchKernelGGL(k_rotamer_grad_finish, dim3((R->G.n1 * 6 + 255) / 256, L->n_system), dim3(256), 0, ST(L), *R, p.packed ? 1.0 / (double)(1 << P2_FIX_BITS) : 1.0 / 4294967296.0);
     return launch_status();
 }
 
@@ -856,9 +824,10 @@ __global__ void __launch_bounds__(1024) k_rotamer_param_deriv_all(upk_rotamer_t 
 }
 extern "C" int upk_rotamer_param_deriv_all(const upk_launch_t* L, const upk_rotamer_t* R, float* table) {
     UPK_FLUSH(L);
-    int n_slice; const int rows = pd_table_slices(R->G.n_type1 * R->G.n_type2, R->G.n_param, n_slice);
-    if (!n_slice) return 9103;
-    hipLaunchKernelGGL(k_rotamer_param_deriv_all, dim3(n_slice, L->n_system), dim3(1024), (size_t)rows * R->G.n_param * sizeof(unsigned long long),
+    const TableSlices sl = plan_pd_table_slices(R->G.n_type1 * R->G.n_type2, R->G.n_param);
+    const int rows = sl.rows;
+    if (!sl.n_slice) return 9103;
+    hipLaunchKernelGGL(k_rotamer_param_deriv_all, dim3(sl.n_slice, L->n_system), dim3(1024), (size_t)rows * R->G.n_param * sizeof(unsigned long long),
                        ST(L), *R, rows, table);
     return launch_status();
 }
@@ -1222,10 +1191,6 @@ __device__ __forceinline__ void bp_rescale_pow2(float (&bb)[6], int n) {
 #ifndef BP_GROUP3
 #define BP_GROUP3 2
 #endif
-#ifndef BP_NODE_STRIDE
-#define BP_NODE_STRIDE 6      // (8 = one b128 + one b64 per node row: measured equal, and 6 leaves 7 KB more of the LDS to the inbox)
-#endif
-#define BP_NODE_ARRAYS 2      // node arrays of BP_NODE_STRIDE floats in the one-workgroup solve's LDS: probabilities, beliefs
 #ifndef BP_NODE_ROWS_512
 #define BP_NODE_ROWS_512 4
 #endif
@@ -1424,9 +1389,6 @@ __device__ __forceinline__ void bp_fold_node(const upk_rotamer_t& R, const BpCtx
 // scratch_words: LDS ints behind C.inbox_lds for the row masks and word bases (two per 32 cached rows + 1).  The launcher sizes it for a
 // quarter of the slot capacity (the capacity allows 96 residue pairs per node, a protein has ~30): a system with more rows than that sets
 // word n_node + 7 of its record and its solve lays the inbox out itself.
-#ifndef BPL_THREADS
-#define BPL_THREADS 512
-#endif
 __global__ void __launch_bounds__(BPL_THREADS) k_rotamer_bp_layout(upk_rotamer_t R, int lds_msg_floats, int* __restrict__ out, int scratch_words) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
     const int s = blockIdx.x, tid = threadIdx.x, nt = blockDim.x, NN = R.n_node;
@@ -2002,7 +1964,6 @@ __device__ __forceinline__ float bpc_marginal(const BpcSlot<NA, NB>& st, const f
 
 #define BPC_GROUP 16  // lanes cooperating on one node
 
-#define BPC_BLOCK 512   // 8 waves: 256 VGPRs per lane keep the three slot states + a 6x6 matrix out of scratch
 __global__ void __launch_bounds__(BPC_BLOCK) k_rotamer_bp_cluster(upk_rotamer_t R, int want_energy, int C, int sys0, int n_sys, int p_cap) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
     if ((int)blockIdx.x >= n_sys) return;
@@ -2256,72 +2217,30 @@ static int device_cu_count() {
     return n;
 }
 extern "C" int upk_device_cu_count() { return device_cu_count(); }
-extern "C" int upk_rotamer_bp_cluster_threads() { return BPC_BLOCK; }   // slots of one class a workgroup can own
-extern "C" int upk_rotamer_bp_cluster_capacity(const upk_rotamer_t* R) {   // floats of pair matrices one workgroup can hold
-    const int fixed = R->n_node * 14 + 48;
-    return (int)(156 * 1024 / sizeof(float)) - fixed;
-}
-// one-workgroup solve: BP_BLOCK lanes streaming every matrix, or BP_BLOCK / 2 lanes with the first trips of each class pinned in registers
-static void bp_launch(const upk_launch_t* L, const upk_rotamer_t* R, int want_energy, int only_fallback, size_t lds, int lds_msg_floats) {
-    // TWO compiled solves.  (i) 512 lanes x 256 registers, the dense per-solve inbox, one slot of every class pinned in registers per lane:
-    // every batch size (round 4 measured it against two pinned 6x6 slots, a 1024-lane streaming form and larger pinned sets across proteins
-    // and batch sizes; the losers are gone: `git log` has them).  (ii) 1024 lanes streaming every matrix over the CACHED inbox layout: the
-    // hand-over solve behind a cluster launch, systems whose layout scratch does not fit, UPSIDE_HIP_BP_COMPACT=0 (tests).
-    const dim3 grid(1, L->n_system);
-    static const bool compact = env_int("UPSIDE_HIP_BP_COMPACT", 1) != 0;  // =0: the cached inbox layout (tests)
-    // (the layout pass borrows the LDS inbox for an activity bit per cached row and a prefix per 32 rows: at most two rows per slot)
-    const size_t layout_scratch = (((size_t)2 * R->slot_cap + 64) / 32 * 2 + 2) * sizeof(int);
-    const bool dense = compact && R->slot_row && R->row_start && (size_t)lds_msg_floats * sizeof(float) >= layout_scratch;
-    if (!only_fallback && dense) {
-        upk_rotamer_t Rl = *R;
-        // the dense layout as a launch of its own in front of the solve (R->bp_layout allocated by the host node: from 512 systems on),
-        // when its scratch fits a quarter of a CU's LDS; else inside the solve
-        static const bool hand_back = env_int("UPSIDE_HIP_BP_LAYOUT", 0) == 2;      // (tests): no scratch at all, so that every system is handed back to its solve
-        const int scratch_words = hand_back ? 1 : (int)((((size_t)2 * (R->slot_cap / 4 + 32) + 64) / 32) * 2 + 2);
-        const size_t layout_lds = ((size_t)R->n_node * (BP_NODE_STRIDE + 1) + 64 + N_CLASS + 16) * sizeof(float) + (size_t)scratch_words * sizeof(int) + 64;
-        if (R->bp_layout && layout_lds <= 40 * 1024)
-            hipLaunchKernelGGL(k_rotamer_bp_layout, dim3(L->n_system), dim3(BPL_THREADS), layout_lds, ST(L), *R, lds_msg_floats, R->bp_layout, scratch_words);
-        else Rl.bp_layout = nullptr;
-        hipLaunchKernelGGL((k_rotamer_bp<BP_BLOCK / 2, 1, 1, 1, true>), grid, dim3(BP_BLOCK / 2), lds, ST(L), Rl, want_energy, only_fallback, lds_msg_floats);
-    } else
-        hipLaunchKernelGGL((k_rotamer_bp<BP_BLOCK, 0, 0, 0>), grid, dim3(BP_BLOCK), lds, ST(L), *R, want_energy, only_fallback, lds_msg_floats);
-}
+// the one-workgroup solve: dense (BP_BLOCK / 2 lanes, the first trips of each class pinned in registers) or streaming (BP_BLOCK lanes): plan_bp_solve
 extern "C" int upk_rotamer_bp(const upk_launch_t* L, const upk_rotamer_t* R, int want_energy) {
     UPK_FLUSH(L);
-    const size_t lds_base = ((size_t)R->n_node * (BP_NODE_ARRAYS * BP_NODE_STRIDE + 2) + 64 + 8) * sizeof(float);
-    if (lds_base > 155 * 1024) return 9004;
-    // LDS left over holds the messages to the 3-state nodes (at most all of the inbox: 16 floats per slot)
-    static const int lds_msg_kb = env_int("UPSIDE_HIP_BP_LDS_MSG_KB", 160);   // (experiments): 0 keeps every message in global memory
-    size_t msg_bytes = (size_t)lds_msg_kb * 1024;
-    // LDS of the one-workgroup solve, beliefs + inbox: all 160 KB of the CU (the kernel has no static LDS)
-    if (lds_base + msg_bytes > (size_t)160 * 1024) msg_bytes = lds_base >= (size_t)160 * 1024 ? 0 : (size_t)160 * 1024 - lds_base;
-    if (msg_bytes > (size_t)R->slot_cap * 64) msg_bytes = (size_t)R->slot_cap * 64;
-    msg_bytes &= ~(size_t)15;
-    const int lds_msg_floats = (int)(msg_bytes / sizeof(float));
-    const size_t lds = lds_base + msg_bytes;
-    const int C = R->bp_C;
-    if (C > 1) {
-        // clusters of C co-resident workgroups, one per CU: at most CUs / C systems per launch (multiples of 8 keep a
-        // cluster on one XCD under round-robin workgroup dispatch, so its exchange stays in that XCD's L2)
-        int chunk = device_cu_count() / C;
-        if (chunk >= 8) chunk &= ~7;
-        if (chunk >= 1) {
-            const int p_cap = upk_rotamer_bp_cluster_capacity(R);
-            for (int s0 = 0; s0 < L->n_system; s0 += chunk) {
-                const int n = L->n_system - s0 < chunk ? L->n_system - s0 : chunk;
-                // grid.x rounded up to a multiple of 8 (the surplus workgroups leave at once): workgroup b is dispatched to XCD b mod 8, so the C
-                // workgroups of a system -- linear ids s + c * grid.x -- then share an XCD and their exchange stays in its L2, also when fewer
-                // than 8 systems are solved (placement for speed only: the protocol is placement independent).  One 300-residue system, 6
-                // workgroups: solve 211 -> 200 us.  (Round 6, measured on that placement and not taken: plain stores + sc1 loads and no acquire
-                // fence, which is valid only while the cluster shares an L2: 180 us, 2 235 -> 2 287 steps/s -- 0.9 us per barrier; the rest of a
-                // 10 us sweep is the counter round trips and the phases' own dependent loads.)
-                const int gx = (n + 7) & ~7;
-                hipLaunchKernelGGL(k_rotamer_bp_cluster, dim3(gx, C), dim3(BPC_BLOCK), 156 * 1024, ST(L), *R, want_energy, C, s0, n, p_cap);
-            }
-            bp_launch(L, R, want_energy, 1, lds_base, 0);   // rare path: no LDS inbox, so that the (normally empty) launch does not wait for a whole CU's LDS
-            return launch_status();
+    const BpSolve p = plan_bp_solve(plan_switches(), R->n_node, R->slot_cap, R->slot_row && R->row_start, R->bp_layout != nullptr);
+    if (p.refused) return 9004;
+    const dim3 grid(1, L->n_system);
+    const int C = R->bp_C, chunk = plan_cluster_per_launch(device_cu_count(), C);
+    if (C > 1 && chunk >= 1) {
+        const int p_cap = plan_cluster_capacity(R->n_node);
+        for (int s0 = 0; s0 < L->n_system; s0 += chunk) {
+            const int n = L->n_system - s0 < chunk ? L->n_system - s0 : chunk;
+            hipLaunchKernelGGL(k_rotamer_bp_cluster, dim3(plan_cluster_grid_x(n), C), dim3(BPC_BLOCK), PLAN_BP_CLUSTER_LDS, ST(L), *R, want_energy, C, s0, n, p_cap);
         }
+        hipLaunchKernelGGL((k_rotamer_bp<BP_BLOCK, 0, 0, 0>), grid, dim3(BP_BLOCK), p.lds_base, ST(L), *R, want_energy, 1, 0);   // rare path: the systems handed over
+        return launch_status();
     }
-    bp_launch(L, R, want_energy, 0, lds, lds_msg_floats);
+    const size_t lds = p.lds_base + p.msg_bytes;
+    if (p.dense) {
+        upk_rotamer_t Rl = *R;
+        if (p.layout_launch)
+            hipLaunchKernelGGL(k_rotamer_bp_layout, dim3(L->n_system), dim3(BPL_THREADS), p.layout_lds, ST(L), *R, p.msg_floats, R->bp_layout, p.scratch_words);
+        else Rl.bp_layout = nullptr;
+        hipLaunchKernelGGL((k_rotamer_bp<BP_BLOCK / 2, 1, 1, 1, true>), grid, dim3(BP_BLOCK / 2), lds, ST(L), Rl, want_energy, 0, p.msg_floats);
+    } else
+        hipLaunchKernelGGL((k_rotamer_bp<BP_BLOCK, 0, 0, 0>), grid, dim3(BP_BLOCK), lds, ST(L), *R, want_energy, 0, p.msg_floats);
     return launch_status();
 }

@@ -440,10 +440,10 @@ struct BackbonePairs : public PotentialNode {
         alloc_terms(n_residue);
         fused_forward = fused_backward = true;
         memset(&cache, 0, sizeof(cache));
-        if (n_residue > 128 && env_int("UPSIDE_HIP_BACKBONE_LIST", 1)) {
+        if (const BackboneList bl = plan_backbone_list(plan_switches(), n_residue); bl.on) {
             // residue centres move by ~0.15 A per step: a 3 A skin is rebuilt every ~10 steps and keeps ~45 partners per row at 300 residues
             const size_t S = (size_t)ctx->n_system;
-            cache.cap = min(n_residue, env_int("UPSIDE_HIP_BACKBONE_LIST_CAP", 128)); cache.skin = env_float("UPSIDE_HIP_BACKBONE_SKIN", 3.f);
+            cache.cap = bl.cap; cache.skin = bl.skin;
             bb_list.alloc(S * n_residue * cache.cap); bb_cnt.alloc(S * n_residue);
             vector<float> far(S * n_residue * 4, 1e10f);
             bb_ref0.upload(far); bb_ref1.upload(far);
@@ -518,9 +518,13 @@ struct IGraphHost {
     // reference positions, by the few off-path readers (canonical pair list, parameter derivatives): ensure_all_sides().
     int md_sides = 3; bool other_side_stale = false;
     DevBuf<int> all_systems;           // flag list naming every system (ensure_all_sides)
+    PairShape pair_shape() const {     // what the planner needs to know of the graph (launch_plan.h)
+        const bool cov = G.itype == UPK_IT_HBOND_COVERAGE;
+        return {cov, cov && G.param_poly, G.n1, G.n2, G.cap1, G.cap2, G.n_type1, G.n_type2, G.n_param, G.n_poly};
+    }
     void use_sides(int sides) {        // called by the owning node once the graph is complete
         const int row_side = sides == 1 ? 1 : 2;
-        md_sides = (!G.symmetric && (sides == 1 || sides == 2) && upk_igraph_passes_staged(&ctx->L, &G, row_side)) ? sides : 3;
+        md_sides = (!G.symmetric && (sides == 1 || sides == 2) && plan_passes_staged(plan_switches(), pair_shape(), row_side)) ? sides : 3;
         // the hit lists of a side that no pass walks are never written: give the memory back (1.2-1.8 MB per system and graph)
         if (!(md_sides & 1)) { hit1.alloc(0); hcnt1.alloc(0); ord1.alloc(0); G.hit1 = nullptr; G.hcnt1 = nullptr; G.ord1 = nullptr; }
         if (!(md_sides & 2)) { hit2.alloc(0); hcnt2.alloc(0); ord2.alloc(0); G.hit2 = nullptr; G.hcnt2 = nullptr; G.ord2 = nullptr; }
@@ -560,26 +564,7 @@ struct IGraphHost {
         G.cache_cutoff = cutoff + skin_scale() * (1.0f + 0.2f * cutoff);
     }
 
-    // Width of the cached-list margin relative to the reference's 1 + 0.2*cutoff (interaction_graph.h:395): any margin
-    // gives the same in-range pairs, it only trades rebuild frequency against list length.  Here the residue-pair slots of
-    // the side-chain solve are cut from the cached list too, so a long list also makes every belief-propagation sweep
-    // longer.  Measured at 1024 x 300 residues, system-steps/s by scale: 1.8: 73 k, 1.4: 79 k, 1.0: 85.6 k, 0.8: 89.2 k,
-    // 0.6: 91.2 k, 0.45: 90.6 k (256 systems: 78.0 / 82.4 / 82.2 k at 1.0 / 0.6 / 0.45); with the straight-line list
-    // build 0.6: 92.3 k, 0.5: 93.8 k, 0.4: 93.4 k.
-    // (round 4: a batch of a few systems is a chain of launches, not work -- a longer list is cheap there and every rebuild lengthens the
-    //  chain: 1.5 x the reference's margin up to 16 systems; 56 residues, 1 / 8 systems: 4.97 k / 34.4 k against 4.88 k / 32.8 k system-steps/s
-    //  at 0.5, one 300-residue system 2.09 k against 1.99 k; 64 systems: 57 k against 62 k)
-    // (round 5: with 16-bit list words and the cheaper refine a longer list costs less: 4096 systems 215.4 k at 0.75 against 212.7 k at 0.5, four
-    //  alternating runs each on one box; 1024 and 256 systems no difference, 64 systems 0.5 still ahead by 0.6 %)
-    // (the side-chain graph keeps 0.5 there: its cached residue pairs are the solve's slots, and the slot matrices of pairs that are cached
-    //  but out of range lie between the active ones -- solve 4.98 -> 5.26 ms, pair energies 1.23 -> 1.35 ms at 0.75; with it at 0.5 and the
-    //  others at 0.75: 217.1 against 214.6 k on one box, 220.6 against 219.8 k on another)
-    float skin_scale() const {
-        static const float v = env_float("UPSIDE_HIP_SKIN_SCALE", 0.f);
-        if (v > 0.f) return v;
-        if (ctx->n_system <= 16) return 1.5f;
-        return (ctx->n_system <= 256 || G.itype == UPK_IT_ROTAMER) ? 0.5f : 0.75f;
-    }
+    float skin_scale() const { return plan_skin_scale(plan_switches(), ctx->n_system, G.itype == UPK_IT_ROTAMER); }   // width of the cached-list margin
     IGraphHost(DeviceCtx* c, hid_t grp, int itype, CoordNode* n1, CoordNode* n2) : ctx(c), node1(n1), node2(n2 ? n2 : n1) {
         memset(&G, 0, sizeof(G));
         G.itype = itype; G.symmetric = itype == UPK_IT_ROTAMER || itype == UPK_IT_RADIAL;
@@ -632,7 +617,7 @@ struct IGraphHost {
         require_injective(loc1, node1->n_elem, "interaction graph index1");
         require_injective(loc2, node2->n_elem, "interaction graph index2");
 
-        const int cap_max = env_int("UPSIDE_HIP_NBR_CAP", 512);
+        const int cap_max = plan_switches().NBR_CAP;
         G.cap1 = min(round_up(G.n2, 4), cap_max);
         G.cap2 = min(round_up(G.n1, 4), cap_max);
         const int S = c->n_system;
@@ -660,7 +645,7 @@ struct IGraphHost {
             if (G.symmetric) { /* (each pair once: the lists hold the partners above the row only) */ }
             else { hit2.alloc(list_ints((size_t)S * G.n2 * G.cap2 + 4)); hcnt2.alloc((size_t)S * G.n2); ord2.alloc((size_t)S * G.n2); }
         }
-        if (!G.symmetric && S < 256) { gacc.alloc((size_t)S * max(G.n1, G.n2) * 8); G.gacc = gacc.p; }   // (from 256 systems on a system has one workgroup)
+        if (plan_gacc(G.symmetric, S)) { gacc.alloc((size_t)S * max(G.n1, G.n2) * 8); G.gacc = gacc.p; }
         G.hit1 = hit1.p; G.hit2 = hit2.p; G.hcnt1 = hcnt1.p; G.hcnt2 = hcnt2.p; G.hlo1 = hlo1.p;
         G.ord1 = ord1.p; G.ord2 = ord2.p; G.ord1u = ord1u.p;
         G.cur_pos1 = cur_pos1.p; G.cur_pos2 = G.symmetric ? cur_pos1.p : cur_pos2.p;
@@ -1351,12 +1336,13 @@ struct RotamerSidechain : public PotentialNode, BatchedParamDeriv {
         n1 = n_elem_rot[1]; n3 = n_elem_rot[3]; n6 = n_elem_rot[6]; n_node = n1 + n3 + n6;
         // one lane per node in the slot numbering and the LDS bit matrix of residue pairs (kernels_rotamer.hip: 1024 x 1024 bits = 128 KB);
         // UPSIDE_HIP_MAX_ROTAMER_NODES lowers the limit so that the refusal can be tested with the shipped fixtures
-        const int max_node = min(1024, env_int("UPSIDE_HIP_MAX_ROTAMER_NODES", 1024));
+        const PlanSwitches& sw = plan_switches();
+        const int max_node = min(1024, sw.MAX_ROTAMER_NODES);
         if (n_node > max_node)
             throw string("rotamer: ") + to_string(n_node) + " side-chain nodes, but the device belief-propagation solve handles at most " + to_string(max_node) +
                   " (one system per workgroup: slot numbering and pair-matrix bookkeeping live in the 160 KB LDS of a CU)";
         const int start[7] = {0, 0, 0, n1, 0, 0, n1 + n3};
-        if (env_int("UPSIDE_HIP_ROT_SORT_BEADS", 1)) {      // beads in (node, rotamer state) order: see IGraphHost::permute_elements
+        if (sw.ROT_SORT_BEADS) {      // beads in (node, rotamer state) order: see IGraphHost::permute_elements
             vector<int> perm(ig.G.n1);
             for (int i = 0; i < ig.G.n1; ++i) perm[i] = i;
             auto key = [&](int i) {
@@ -1381,7 +1367,7 @@ struct RotamerSidechain : public PotentialNode, BatchedParamDeriv {
         nb_start[n_node * 6] = (int)nb_list.size();
         one_bead_per_state = true;           // then every pair-matrix entry has a single contributing bead pair
         for (auto& b : beads_of) if (b.size() > 1u) one_bead_per_state = false;
-        if (env_int("UPSIDE_HIP_ROTAMER_ATOMIC", 0)) one_bead_per_state = false;   // tests: the general accumulation path
+        if (sw.ROTAMER_ATOMIC) one_bead_per_state = false;   // tests: the general accumulation path
         const int S = c->n_system;
         d_node_nrot.upload(node_nrot); d_bead_node.upload(bead_node); d_bead_rot.upload(bead_rot); d_nb_start.upload(nb_start); d_nb_list.upload(nb_list);
         vector<int> bead_meta(n_bead);
@@ -1390,20 +1376,12 @@ struct RotamerSidechain : public PotentialNode, BatchedParamDeriv {
             bead_meta[i] = ig.type1[i] | (bead_rot[i] << 8) | (node_nrot[bead_node[i]] << 12);
         }
         d_bead_meta.upload(bead_meta);
-        const float slot_factor = env_float("UPSIDE_HIP_SLOT_FACTOR", 96.f);
-        long full = (long)n_node * (n_node - 1) / 2;
-        R.slot_cap = (int)max(1L, min(full, (long)(n_node * slot_factor)));
-        R.adj_cap = min(max(n_node, 1), env_int("UPSIDE_HIP_ADJ_CAP", 256));
+        R.slot_cap = plan_slot_cap(sw, n_node); R.adj_cap = plan_adj_cap(sw, n_node);
         n_slot.alloc(S); slot_a.alloc((size_t)S * R.slot_cap); slot_b.alloc((size_t)S * R.slot_cap); slot_active.alloc((size_t)S * R.slot_cap);
         slot_of.alloc((size_t)S * n_node * n_node); adj_cnt.alloc((size_t)S * n_node); adj_slot.alloc((size_t)S * n_node * R.adj_cap);
         bp_rec.alloc((size_t)S * R.slot_cap * 4);
-        // the dense inbox layout as a launch of its own in front of the one-workgroup solve (kernels_rotamer.hip: k_rotamer_bp_layout) once the
-        // solves of a launch run in several rounds over the CUs (a solve owns a whole CU): UPSIDE_HIP_BP_LAYOUT=0/1 forces it off / on (tests)
-        {
-            const int want = env_int("UPSIDE_HIP_BP_LAYOUT", -1);
-            // (every word -1 until k_rotamer_bp_layout writes a record: word n_node + 7 == 0 then means "laid out by that launch" and nothing else)
-            if (want >= 1 || (want < 0 && S >= 512)) { bp_layout.alloc((size_t)S * (UPK_BP_LAYOUT_PER_NODE * n_node + UPK_BP_LAYOUT_EXTRA)); bp_layout.fill_bytes(0xff); R.bp_layout = bp_layout.p; }
-        }
+        // (every word -1 until k_rotamer_bp_layout writes a record: word n_node + 7 == 0 then means "laid out by that launch" and nothing else)
+        if (plan_layout_record(sw, S)) { bp_layout.alloc((size_t)S * (UPK_BP_LAYOUT_PER_NODE * n_node + UPK_BP_LAYOUT_EXTRA)); bp_layout.fill_bytes(0xff); R.bp_layout = bp_layout.p; }
         iters.alloc(S); n_bad.alloc(S); energy.alloc(S); bp_start.alloc((size_t)S * (n_node + 1)); slot_off.alloc((size_t)S * R.slot_cap * 2);
         class_start.alloc((size_t)S * 6); slot_active_last.alloc((size_t)S * R.slot_cap);
         row_start.alloc((size_t)S * (n_node + 2)); slot_row.alloc((size_t)S * R.slot_cap * 2);
@@ -1456,10 +1434,9 @@ struct RotamerSidechain : public PotentialNode, BatchedParamDeriv {
         R.bp_bar = bp_bar.p; R.bp_fallback = bp_fallback.p; R.bp_nbx = bp_nbx.p; R.bp_dev = bp_dev.p; R.bp_en_part = bp_en_part.p;
         if (R.slot_cap >= UPK_ROT_SLOT_NONE) throw string("rotamer pair lists pack the residue-pair slot into 19 bits: lower UPSIDE_HIP_SLOT_FACTOR");
         R.bp_C = 1;
-        R.bead_pack = nullptr;   // packed global bead rows: only when table + beads exceed the LDS budget of the pair kernels
+        R.bead_pack = nullptr;
         grad_acc.alloc((size_t)ctx->n_system * ig.G.n1 * 6); R.grad_acc = grad_acc.p;
-        if (((size_t)(ig.G.n_type1 * (ig.G.n_type1 + 1) / 2) * ig.G.n_param + (size_t)ig.G.n1 * 22 + 8) * sizeof(float) > 158 * 1024 ||   // triangle table + beads + accumulators + row order
-            env_int("UPSIDE_HIP_ROT_UNSTAGED", 0)) {
+        if (plan_bead_pack(plan_switches(), {ig.G.n1, ig.G.n_type1, ig.G.n_param, R.n_poly, true})) {
             bead_pack.alloc((size_t)ctx->n_system * ig.G.n1 * 8); R.bead_pack = bead_pack.p;
         }
         R.bp_trace = nullptr;
@@ -1476,54 +1453,26 @@ struct RotamerSidechain : public PotentialNode, BatchedParamDeriv {
         upk_check(upk_rotamer_nbr_slots(&ctx->L, &R), "rotamer_nbr_slots");
         ig.refine(ig.G);
     }
-    // workgroups per system of the belief-propagation solve: enough that the exp(-E) matrices of the multi-state
-    // residue pairs fit their LDS (15% slack for the fluctuation of the pair count; systems that outgrow it fall
-    // back to the one-workgroup kernel on the device).  Decided once, from the first pair list.
+    // workgroups per system of the belief-propagation solve (plan_cluster_size).  Decided once, from the first pair list.
+    MatrixForm form = {};
     void choose_bp_cluster() {
         bp_C_chosen = true;
         ctx->flush();
-        const int want = env_int("UPSIDE_HIP_BP_CLUSTER", -1);   // 1 disables, >1 forces
-        if (want == 1) { R.bp_C = 1; set_matrix_form(); return; }
-        hip_check(hipStreamSynchronize(ctx->stream), "sync");
-        auto cs = class_start.download();
+        const PlanSwitches& sw = plan_switches();
         long need = 0, widest = 0;
-        for (int s = 0; s < ctx->n_system; ++s) {
-            const int* c = &cs[(size_t)s * 6];
-            need = max(need, 9L * (c[1] - c[0]) + 18L * (c[2] - c[1]) + 36L * (c[3] - c[2]));
-            widest = max(widest, (long)max(c[1] - c[0], max(c[2] - c[1], c[3] - c[2])));
+        if (sw.BP_CLUSTER != 1) {
+            hip_check(hipStreamSynchronize(ctx->stream), "sync");
+            auto cs = class_start.download();
+            for (int s = 0; s < ctx->n_system; ++s) {
+                const int* c = &cs[(size_t)s * 6];
+                need = max(need, 9L * (c[1] - c[0]) + 18L * (c[2] - c[1]) + 36L * (c[3] - c[2]));
+                widest = max(widest, (long)max(c[1] - c[0], max(c[2] - c[1], c[3] - c[2])));
+            }
+            R.bp_test_abort = sw.BP_CLUSTER_TEST_ABORT;
         }
-        const int cap = upk_rotamer_bp_cluster_capacity(&R), lanes = upk_rotamer_bp_cluster_threads();
-        int C = cap > 0 ? (int)((need * 115 / 100 + cap - 1) / cap) : 1;
-        C = max(C, (int)((widest * 115 / 100 + lanes - 1) / lanes));   // one slot per class per lane
-        if (want > 1) C = want;
-        if (C > 16 || n_node - R.n_node1 < C) C = 1;             // too large for a co-resident cluster: one-workgroup solve
-        // The cluster solve trades HBM/L2 traffic for two device-scope barriers per sweep.  Re-measured after the
-        // one-workgroup kernel got its batched loads and the short list margin (BP ms, cluster vs one workgroup):
-        //   300 residues / 10 A (C = 8):  1 system 0.19 vs 0.31, 8: 0.23 vs 0.35, 32: 0.35 vs 0.43, 48 (two launches):
-        //                                 0.63 vs 0.47, 64: 0.56 vs 0.48
-        //   300 residues / 7 A, 150 residues / 10 A (C = 3..4): 0.22 vs 0.19 at 1 system, 0.31 vs 0.24 at 32
-        //   56 and 20 residues (C = 1): the one-workgroup solve by construction
-        // so the cluster is used when the pair matrices need many workgroups (C >= 6) and the batch fits 4/5 of one
-        // launch (CUs / C systems); everything else takes the one-workgroup solve.  (A second cluster form that kept the
-        // matrices in global memory won nowhere after these measurements and is gone: `git log` has it.)
-        const int n_cu = upk_device_cu_count();
-        int per_launch = C > 1 ? n_cu / C : 0;
-        if (per_launch >= 8) per_launch &= ~7;
-        // (round 2, after the one-workgroup solve got its look-ahead loads: 32 systems 0.37 vs 0.38 ms, 40: 0.41 vs 0.39, 48 (two launches):
-        //  0.61 vs 0.39 -- the cluster up to 4/5 of one launch)
-        const int resident_limit = C >= 6 ? per_launch * 4 / 5 : 0;
-        if (want <= 1 && ctx->n_system > resident_limit) C = 1;
-        R.bp_C = C < 1 ? 1 : C;
-        R.bp_test_abort = env_int("UPSIDE_HIP_BP_CLUSTER_TEST_ABORT", 0);
-        set_matrix_form();
-    }
-    // One-workgroup solve with single-writer matrices: the pair-energy kernel writes exp(-E) itself and the matrices rest at 1
-    // (= no interaction) between evaluations, which removes the solve's exp pass over every active matrix.  The cluster
-    // solves and the accumulating (several beads per state) path keep energies resting at 0.
-    void set_matrix_form() {
-        // (a small batch is a chain of launches: the 1-body pass rides in the prologue of the one-workgroup solve)
-        R.node_prob_in_solve = ((ctx->n_system <= 16 || ctx->L.batch) && env_int("UPSIDE_HIP_NODE_PROB_IN_SOLVE", 1)) ? 1 : 0;   // (a launch less where launches are what a step waits for; the cluster solve does the same for its own nodes)
-        R.p_prob = (R.bp_C <= 1 && one_bead_per_state && !env_int("UPSIDE_HIP_BP_ENERGY_TABLE", 0)) ? 1 : 0;
+        R.bp_C = plan_cluster_size(sw, need, widest, n_node, R.n_node1, ctx->n_system, upk_device_cu_count());
+        form = plan_matrix_form(sw, ctx->n_system, ctx->L.batch != nullptr, R.bp_C, one_bead_per_state, R.bp_layout != nullptr);
+        R.node_prob_in_solve = form.node_prob_in_solve; R.p_prob = form.p_prob;
         rest_matrices();
     }
     void rest_matrices() {
@@ -1686,7 +1635,7 @@ struct RotamerSidechain : public PotentialNode, BatchedParamDeriv {
             // selected, then word n_node + 7 of every system's layout record (0: laid out by k_rotamer_bp_layout in the last solve, 1: handed back to its
             // solve, -1: no record written)
             if (!bp_C_chosen) throw string("solve_form: no force evaluation yet");
-            vector<float> r = {(float)R.p_prob, (float)R.node_prob_in_solve, R.bp_layout ? 1.f : 0.f, (float)R.bp_C, UPK_ROTAMER_PREFOLD(R) ? 1.f : 0.f};
+            vector<float> r = {(float)R.p_prob, (float)R.node_prob_in_solve, R.bp_layout ? 1.f : 0.f, (float)R.bp_C, (float)form.prefold};
             const auto ly = bp_layout.download();
             const size_t stride = (size_t)UPK_BP_LAYOUT_PER_NODE * n_node + UPK_BP_LAYOUT_EXTRA;
             for (int s = 0; s < ctx->n_system; ++s) r.push_back(R.bp_layout ? (float)ly[s * stride + n_node + 7] : -1.f);

@@ -284,10 +284,6 @@ __device__ __forceinline__ v2 quadspline_pair2(const QuadShape& Q, const float* 
 }
 
 // ---- 4-lane groups, two hit-list words per lane and trip ---------------------------------------------------------------
-#ifndef P2_LANES
-#define P2_LANES 4      // (measured at 4096 systems: 8 lanes within 0.5 %, 16 lanes -4.5 %: the LDS bank conflicts of the partner gathers --
-                        //  two thirds of the LDS-active cycles -- are not what bounds the passes)
-#endif
 #define P2_ROWS (UP_WAVE / P2_LANES)
 #ifndef P2_CHUNK
 #define P2_CHUNK 2      // trips whose list words are loaded together, one chunk ahead (a trip = 8 words of a row)
@@ -346,11 +342,6 @@ __device__ __forceinline__ void group2_batch_loop(Op& op, int n_rows, const unsi
         if (cur.valid) op.flush(cur.row);
         cur = nxt; have = have_next;
     }
-}
-
-static inline bool pair2_enabled() {   // UPSIDE_HIP_PAIR2=0: the scalar passes (one partner per lane) -- A/B and tests
-    static const bool on = env_int("UPSIDE_HIP_PAIR2", 1) != 0;
-    return on;
 }
 
 }  // namespace up
