@@ -241,9 +241,18 @@ const char* upside_hip_last_error(void);
  *     CV order; NULL where no CV is of that kind.  A dihedral's selection is its 4 atoms, a dihedral_similarity's is interleaved
  *     quadruples.  Further refusals: a dihedral without exactly 4 atoms, a dihedral_similarity list that is no multiple of 4, a
  *     quadruple with a repeated atom, dihedral_ref NULL or not finite where a dihedral_similarity exists.
+ *   _cv_define3: the same with the arrays of the path kinds, 8 path_s (progress along a path of K reference frames, in [1, K]) and
+ *     9 path_z (distance from the path, Angstrom^2) -- codes 6 and 7 are not in use: path_n_frame (n_cv; K of a path CV, 0 for the other
+ *     kinds), path_lambda (n_cv; Angstrom^-2, read for path CVs only) and path_ref_pos (rows of 3: the K * n rows of each path CV, frame
+ *     after frame, in CV order; n is the length of the CV's selection).  All three NULL where no CV is of a path kind.  Further
+ *     refusals: K < 2 or K > 64 (UPK_CV_PATH_MAX_FRAMES), a path selection under 3 atoms, path_lambda not finite or not positive, frames
+ *     not finite, any of the three arrays NULL where a path kind exists (so a kind 8 or 9 through _cv_define or _cv_define2).  A path_s
+ *     and a path_z over the same frames each compute their own K alignments.
  *   _cv_load: the same from the group /input/collective_variables of a configuration (datasets kind, atom_start, atoms, ref_pos (n,3),
  *     contact_r0, contact_beta, contact_lambda, the optional dihedral_ref -- absent means empty; its length must be the number of
- *     dihedral_similarity quadruples -- and the fixed-length string vector names; config.add_collective_variables writes it).
+ *     dihedral_similarity quadruples --, the optional path_n_frame (n_cv) i32, path_lambda (n_cv) f32 and path_ref_pos (rows, 3) f32 --
+ *     all three or none; the rows must be the sum of K * n over the path CVs -- and the fixed-length string vector names;
+ *     config.add_collective_variables writes it).
  *     Returns the number of CVs, 0 without the group, -1 on error (the convention of upside_hip_load_mc).
  *   _cv_count: the number of CVs defined.
  *   _cv_compute: out is host (n_system, n_cv), at the current device positions; no force pass, pair lists untouched.
@@ -262,6 +271,10 @@ int upside_hip_cv_define(DerivEngine* engine, int n_cv, const int* kind, const i
 int upside_hip_cv_define2(DerivEngine* engine, int n_cv, const int* kind, const int* atom_start /* n_cv+1 */, const int* atoms,
                           const float* ref_pos, const float* contact_r0, const float* contact_beta /* n_cv */,
                           const float* contact_lambda /* n_cv */, const float* dihedral_ref);
+int upside_hip_cv_define3(DerivEngine* engine, int n_cv, const int* kind, const int* atom_start /* n_cv+1 */, const int* atoms,
+                          const float* ref_pos, const float* contact_r0, const float* contact_beta /* n_cv */,
+                          const float* contact_lambda /* n_cv */, const float* dihedral_ref, const int* path_n_frame /* n_cv */,
+                          const float* path_lambda /* n_cv */, const float* path_ref_pos);
 int upside_hip_cv_load(DerivEngine* engine, const char* config_file);
 int upside_hip_cv_count(DerivEngine* engine);
 int upside_hip_cv_compute(DerivEngine* engine, float* out /* host (n_system, n_cv) */);

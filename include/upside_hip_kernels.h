@@ -516,18 +516,32 @@ int upk_fixed_hmm_param_deriv_all(const upk_launch_t* L, const upk_fixed_hmm_t* 
  *                    2 pi: the biases below take differences of its values by the nearest image, wrap(d) = d - 2 pi rint(d / 2 pi)
  *   UPK_CV_DIHEDRAL_SIMILARITY  the list is interleaved quadruples; mean over quadruples of 1/2 (1 + cos(phi_i - phi0_i)), in [0, 1],
  *                    phi0_i = dihedral_ref[aux_start[c] + quadruple] (radians).  Not periodic
+ *   UPK_CV_PATH_S, UPK_CV_PATH_Z  path CVs over K = path_n_frame[c] frames of the list's n >= 3 atoms (2 <= K <= UPK_CV_PATH_MAX_FRAMES): the
+ *                    frames are ref rows aux_start[c] + k n + atom (frame-major, each CENTRED by the host, fp64) and
+ *                    path_g[path_frame_start[c] + k] the sum of frame k's squared norms.  With d_k the minimum mean squared deviation
+ *                    over proper rigid motions to frame k (Angstrom^2, the square of an rmsd), d_min = min_k d_k and
+ *                    w_k = exp(-path_lambda[c] (d_k - d_min)):  path_s = sum_k k w_k / sum_k w_k in [1, K] (k = 1..K),
+ *                    path_z = d_min - ln(sum_k w_k) / path_lambda[c] in Angstrom^2.  Not periodic.  The K alignments of one CV run side
+ *                    by side (csrc/cv_path_device.h); a path_s and a path_z of the same path each align on their own.  Codes 6 and 7
+ *                    are not in use
  * One workgroup per system, every sum in fp64 and in one fixed order, no atomics: a system's row is bit-identical run to run and
- * whatever else shares its batch.  The lists are not staged anywhere, so the only limits are UPK_CV_MAX CVs per definition and
- * UPK_CV_MAX_LIST entries per list (what the launch checks and the 32-bit indices hold). */
-enum { UPK_CV_RG = 0, UPK_CV_RMSD = 1, UPK_CV_CONTACTS = 2, UPK_CV_DISTANCE = 3, UPK_CV_DIHEDRAL = 4, UPK_CV_DIHEDRAL_SIMILARITY = 5 };
+ * whatever else shares its batch.  The lists are not staged anywhere, so the only limits are UPK_CV_MAX CVs per definition,
+ * UPK_CV_MAX_LIST entries per list (what the launch checks and the 32-bit indices hold) and UPK_CV_PATH_MAX_FRAMES frames per path CV
+ * (their alignments are kept in LDS). */
+enum { UPK_CV_RG = 0, UPK_CV_RMSD = 1, UPK_CV_CONTACTS = 2, UPK_CV_DISTANCE = 3, UPK_CV_DIHEDRAL = 4, UPK_CV_DIHEDRAL_SIMILARITY = 5,
+       UPK_CV_PATH_S = 8, UPK_CV_PATH_Z = 9 };
 #define UPK_CV_MAX 64
 #define UPK_CV_MAX_LIST (1 << 24)   /* entries of one CV's list */
+#define UPK_CV_PATH_MAX_FRAMES 64    /* frames of one path CV: one lane of a wavefront solves each frame's alignment */
 typedef struct {
     int n_cv;
     const int *kind, *atom_start, *atoms, *aux_start;   /* [n_cv], [n_cv+1], [atom_start[n_cv]], [n_cv] */
     const double *ref, *ref_g;                          /* [n_ref_atom][3], [n_cv] */
     const float *r0, *beta, *lambda;                    /* [n_contact_pair], [n_cv], [n_cv] */
     const float* dihedral_ref;                          /* [n_similarity_quadruple] */
+    const int *path_n_frame, *path_frame_start;         /* [n_cv] (0 for the other kinds), [n_cv] */
+    const double* path_g;                               /* [n_path_frame] */
+    const float* path_lambda;                           /* [n_cv], Angstrom^-2 */
 } upk_cv_t;
 /* out [S][n_cv] at the current positions */
 int upk_cv_compute(const upk_launch_t* L, upk_coord_t pos, const upk_cv_t* C, float* out);

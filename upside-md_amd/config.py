@@ -690,6 +690,12 @@ CV_KINDS = ('rg', 'rmsd', 'contacts', 'distance', 'dihedral', 'dihedral_similari
 CV_MAX = 64                                            # UPK_CV_MAX of include/upside_hip_kernels.h
 # the period of each kind, 0 = not periodic: cv_restraint and cv_metadynamics take the differences of a periodic CV by the nearest image
 CV_PERIOD = dict((k, 2. * np.pi if k == 'dihedral' else 0.) for k in CV_KINDS)
+# the path kinds (upside_hip_cv_define3): progress s along and distance z from K reference frames.  Their codes are 8 and 9 -- 6 and 7
+# are not in use --, neither is periodic
+CV_PATH_KINDS = ('path_s', 'path_z')
+CV_PATH_MAX_FRAMES = 64                                # UPK_CV_PATH_MAX_FRAMES
+CV_KIND_CODE = dict([(k, i) for i, k in enumerate(CV_KINDS)] + [('path_s', 8), ('path_z', 9)])      # name -> code
+CV_KIND_NAME = dict((i, k) for k, i in CV_KIND_CODE.items())                                          # code -> name
 
 
 def native_contacts(pos, atoms, cutoff=8.0, min_seq_sep=4):
@@ -719,28 +725,49 @@ def pack_collective_variables(specs, n_atom):
          {'kind': 'distance', 'pair': (a,b)}
          {'kind': 'dihedral', 'atoms': (a,b,c,d)}                       the torsion in radians, in (-pi, pi]; periodic (CV_PERIOD)
          {'kind': 'dihedral_similarity', 'quads': (m,4), 'ref': (m,) or scalar}     mean of 1/2 (1 + cos(phi_i - ref_i)), in [0, 1]
+         {'kind': 'path_s' | 'path_z', 'atoms': (n,), 'frames': (K,n,3), 'lambda': l}     progress along / distance from the path of
+                  K frames (2 <= K <= 64, n >= 3) of the SAME atoms, l > 0 in A^-2 (path_lambda(frames) gives the usual choice):
+                  path_s in [1, K], path_z in A^2 (path_specs returns both)
     'name' defaults to the kind, numbered when it repeats.  Raises ValueError naming the spec and what is wrong with it."""
     if len(specs) > CV_MAX:
         raise ValueError('%d collective variables exceed the limit of %d' % (len(specs), CV_MAX))
     kind, atom_start, atoms, ref, r0, beta, lam, names, dref = [], [0], [], [], [], [], [], [], []
+    path_k, path_lam, path_ref = [], [], []
     for c, sp in enumerate(specs):
         who = 'collective variable %d' % c
         if not isinstance(sp, dict) or 'kind' not in sp:
             raise ValueError(who + ": a dict with a 'kind' is expected")
         k = sp['kind']
-        if k not in CV_KINDS:
-            raise ValueError(who + ': unknown kind %r (one of %s)' % (k, ', '.join(CV_KINDS)))
+        if k not in CV_KIND_CODE:
+            raise ValueError(who + ': unknown kind %r (one of %s)' % (k, ', '.join(CV_KINDS + CV_PATH_KINDS)))
         who += ' (%s)' % k
         allowed = {'rg': ('atoms',), 'rmsd': ('atoms', 'ref'), 'contacts': ('pairs', 'r0', 'beta', 'lambda'), 'distance': ('pair',),
-                   'dihedral': ('atoms',), 'dihedral_similarity': ('quads', 'ref')}[k]
+                   'dihedral': ('atoms',), 'dihedral_similarity': ('quads', 'ref'), 'path_s': ('atoms', 'frames', 'lambda'),
+                   'path_z': ('atoms', 'frames', 'lambda')}[k]
         extra = sorted(set(sp) - set(allowed) - set(('kind', 'name')))
         if extra:
             raise ValueError(who + ': unexpected key %r' % extra[0])
-        missing = [a for a in allowed if a not in sp and a not in ('beta', 'lambda')]
+        missing = [a for a in allowed if a not in sp and (a != 'beta' and a != 'lambda' or k in CV_PATH_KINDS)]
         if missing:
             raise ValueError(who + ': %r is missing' % missing[0])
         b, l = 0., 0.
-        if k in ('rg', 'rmsd'):
+        pk, pl = 0, 0.
+        if k in CV_PATH_KINDS:
+            a = np.asarray(sp['atoms']).reshape(-1)
+            fr = np.asarray(sp['frames'], 'f8')
+            if fr.ndim != 3 or fr.shape[1:] != (len(a), 3):
+                raise ValueError(who + ': frames must be (K, %d, 3), one row per atom of the selection in every frame' % len(a))
+            if not 2 <= len(fr) <= CV_PATH_MAX_FRAMES:
+                raise ValueError(who + ': %d frames; a path needs 2 to %d' % (len(fr), CV_PATH_MAX_FRAMES))
+            if len(a) < 3:
+                raise ValueError(who + ': a path selection needs at least 3 atoms')
+            if not np.isfinite(fr).all():
+                raise ValueError(who + ': frames are not finite')
+            if np.ndim(sp['lambda']) != 0 or not np.isfinite(np.float32(sp['lambda'])) or not np.float32(sp['lambda']) > 0:
+                raise ValueError(who + ': lambda must be one positive, finite number')
+            pk, pl = len(fr), float(sp['lambda'])
+            path_ref.append(fr.reshape(-1, 3))
+        elif k in ('rg', 'rmsd'):
             a = np.asarray(sp['atoms']).reshape(-1)
             if k == 'rmsd':
                 rf = np.asarray(sp['ref'], 'f8')
@@ -796,8 +823,9 @@ def pack_collective_variables(specs, n_atom):
             for i, q in enumerate(a.reshape(-1, 4)):
                 if len(set(q.tolist())) != 4:
                     raise ValueError(who + ': quadruple %d repeats an atom' % i)
-        kind.append(CV_KINDS.index(k)); atoms.append(a.astype('i4')); atom_start.append(atom_start[-1] + len(a))
+        kind.append(CV_KIND_CODE[k]); atoms.append(a.astype('i4')); atom_start.append(atom_start[-1] + len(a))
         beta.append(b); lam.append(l)
+        path_k.append(pk); path_lam.append(pl)
         names.append(str(sp.get('name', k)))
     given = list(names)
     for c, nm in enumerate(given):      # a repeated default name gets its position
@@ -806,27 +834,109 @@ def pack_collective_variables(specs, n_atom):
     if len(set(names)) != len(names):
         raise ValueError('collective variables: names must be distinct')
     cat = lambda v, t, shape: (np.concatenate(v).astype(t) if v else np.zeros(shape, t))
-    return dict(kind=np.asarray(kind, 'i4'), atom_start=np.asarray(atom_start, 'i4'), atoms=cat(atoms, 'i4', (0,)),
-                ref_pos=cat(ref, 'f4', (0, 3)), contact_r0=cat(r0, 'f4', (0,)), contact_beta=np.asarray(beta, 'f4'),
-                contact_lambda=np.asarray(lam, 'f4'), names=np.asarray(names, 'S') if names else np.zeros((0,), 'S1'),
-                dihedral_ref=cat(dref, 'f4', (0,)))
+    out = dict(kind=np.asarray(kind, 'i4'), atom_start=np.asarray(atom_start, 'i4'), atoms=cat(atoms, 'i4', (0,)),
+               ref_pos=cat(ref, 'f4', (0, 3)), contact_r0=cat(r0, 'f4', (0,)), contact_beta=np.asarray(beta, 'f4'),
+               contact_lambda=np.asarray(lam, 'f4'), names=np.asarray(names, 'S') if names else np.zeros((0,), 'S1'),
+               dihedral_ref=cat(dref, 'f4', (0,)))
+    if path_ref:      # (the three path arrays only where a path kind exists: the other definitions pack as they always did)
+        out.update(path_n_frame=np.asarray(path_k, 'i4'), path_lambda=np.asarray(path_lam, 'f4'), path_ref_pos=cat(path_ref, 'f4', (0, 3)))
+    return out
+
+
+def unpack_collective_variables(p):
+    """the list of specs that pack_collective_variables turns into the packed dict p (its numbers as the float32 p holds)"""
+    kind = np.asarray(p['kind']).reshape(-1); start = np.asarray(p['atom_start']).reshape(-1)
+    names = [x.decode() if isinstance(x, bytes) else str(x) for x in np.asarray(p['names']).reshape(-1)] if 'names' in p else [None] * len(kind)
+    at = {'ref': 0, 'r0': 0, 'dref': 0, 'path': 0}
+    specs = []
+    for c, code in enumerate(kind):
+        k = CV_KIND_NAME[int(code)]
+        a = np.asarray(p['atoms'])[start[c]:start[c + 1]]
+        sp = {'kind': k}
+        if names[c] is not None:
+            sp['name'] = names[c]
+        if k in CV_PATH_KINDS:
+            K = int(p['path_n_frame'][c])
+            sp.update(atoms=a, frames=np.asarray(p['path_ref_pos'])[at['path']:at['path'] + K * len(a)].reshape(K, len(a), 3), **{'lambda': float(p['path_lambda'][c])})
+            at['path'] += K * len(a)
+        elif k in ('rg', 'dihedral'):
+            sp['atoms'] = a
+        elif k == 'rmsd':
+            sp.update(atoms=a, ref=np.asarray(p['ref_pos'])[at['ref']:at['ref'] + len(a)]); at['ref'] += len(a)
+        elif k == 'contacts':
+            m = len(a) // 2
+            sp.update(pairs=a.reshape(-1, 2), r0=np.asarray(p['contact_r0'])[at['r0']:at['r0'] + m], beta=float(p['contact_beta'][c]),
+                      **{'lambda': float(p['contact_lambda'][c])}); at['r0'] += m
+        elif k == 'dihedral_similarity':
+            m = len(a) // 4
+            sp.update(quads=a.reshape(-1, 4), ref=np.asarray(p['dihedral_ref'])[at['dref']:at['dref'] + m]); at['dref'] += m
+        else:
+            sp['pair'] = a
+        specs.append(sp)
+    return specs
+
+
+CV_PATH_DATASETS = ('path_n_frame', 'path_lambda', 'path_ref_pos')
+
+
+def _superpose(b, a):
+    """b (n,3) moved by the proper rigid motion that minimises its squared deviation from a (n,3); returns (b moved, the minimum MSD)"""
+    a = np.asarray(a, 'f8'); b = np.asarray(b, 'f8')
+    ca, cb = a.mean(0), b.mean(0)
+    u, sv, vt = np.linalg.svd((b - cb).T @ (a - ca))
+    d = np.sign(np.linalg.det(u @ vt))
+    rot = u @ np.diag([1., 1., d]) @ vt
+    moved = (b - cb) @ rot + ca
+    return moved, float(((moved - a) ** 2).sum() / len(a))
+
+
+def path_lambda(frames):
+    """2.3 / (mean over adjacent frames of their MSD after optimal superposition, A^2): with it a structure on frame k gives its
+    neighbours a weight of exp(-2.3) = 0.1 (the PLUMED convention for PATHMSD)"""
+    frames = np.asarray(frames, 'f8')
+    if frames.ndim != 3 or frames.shape[2] != 3 or len(frames) < 2 or frames.shape[1] < 3:
+        raise ValueError('path_lambda: frames must be (K >= 2, n >= 3, 3)')
+    msd = np.mean([_superpose(frames[k + 1], frames[k])[1] for k in range(len(frames) - 1)])
+    if not msd > 1e-14 * ((frames - frames.mean(1, keepdims=True)) ** 2).sum(2).mean():      # (nothing but the rounding of the superposition)
+        raise ValueError('path_lambda: adjacent frames coincide')
+    return 2.3 / msd
+
+
+def interpolate_path(a, b, K):
+    """K frames (K,n,3) from a to b: b is superposed on a, then the frames are the linear interpolation a + t (b' - a), t = 0 .. 1"""
+    a = np.asarray(a, 'f8')
+    if a.ndim != 2 or a.shape[1] != 3 or np.shape(b) != a.shape or len(a) < 3:
+        raise ValueError('interpolate_path: a and b must be (n >= 3, 3), of one shape')
+    if not 2 <= int(K) <= CV_PATH_MAX_FRAMES:
+        raise ValueError('interpolate_path: K must be 2 to %d' % CV_PATH_MAX_FRAMES)
+    moved = _superpose(b, a)[0]
+    return a[None] + np.linspace(0., 1., int(K))[:, None, None] * (moved - a)[None]
+
+
+def path_specs(name, atoms, frames, lam=None):
+    """[path_s spec, path_z spec] named name + '_s' and name + '_z' over the same frames (K,n,3) of `atoms`; lam defaults to
+    path_lambda(frames).  Each of the two CVs aligns the K frames on its own."""
+    lam = path_lambda(frames) if lam is None else float(lam)
+    return [{'name': '%s_%s' % (name, k[-1]), 'kind': k, 'atoms': np.asarray(atoms), 'frames': np.asarray(frames, 'f8'), 'lambda': lam} for k in CV_PATH_KINDS]
 
 
 CV_DATASETS = ('kind', 'atom_start', 'atoms', 'ref_pos', 'contact_r0', 'contact_beta', 'contact_lambda', 'names')
 
 
 def _cv_datasets(p):
-    """the datasets of a CV definition's group: dihedral_ref only where a dihedral_similarity needs it, so that a definition of the
-    other kinds is written exactly as it always was"""
-    return CV_DATASETS + (('dihedral_ref',) if (np.asarray(p['kind']) == CV_KINDS.index('dihedral_similarity')).any() else ())
+    """the datasets of a CV definition's group: dihedral_ref only where a dihedral_similarity needs it and the three path datasets only
+    where a path kind does, so that a definition of the other kinds is written exactly as it always was"""
+    kind = np.asarray(p['kind'])
+    return (CV_DATASETS + (('dihedral_ref',) if (kind == CV_KINDS.index('dihedral_similarity')).any() else ()) +
+            (CV_PATH_DATASETS if np.isin(kind, [CV_KIND_CODE[k] for k in CV_PATH_KINDS]).any() else ()))
 
 
 def cv_periods(packed_or_specs):
     """one period per CV (0 = not periodic) from the packed dict of pack_collective_variables or a list of specs: what
     metadynamics_free_energy(periods=...) takes"""
     if isinstance(packed_or_specs, dict):
-        return np.array([CV_PERIOD[CV_KINDS[int(k)]] for k in np.asarray(packed_or_specs['kind']).reshape(-1)], 'f8')
-    return np.array([CV_PERIOD[sp['kind']] for sp in packed_or_specs], 'f8')
+        return np.array([CV_PERIOD.get(CV_KIND_NAME[int(k)], 0.) for k in np.asarray(packed_or_specs['kind']).reshape(-1)], 'f8')
+    return np.array([CV_PERIOD.get(sp['kind'], 0.) for sp in packed_or_specs], 'f8')
 
 
 def backbone_dihedrals(path):

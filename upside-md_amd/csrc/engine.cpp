@@ -732,8 +732,9 @@ void DerivEngine::param_deriv_accumulate(int node, const float* weights) {
 
 // ---- collective variables (upside_hip_cv_define / _compute / _record / _read) -----------------------------------------------------
 CvHostDefinition cv_check_definition(int n_atom, int n_cv, const int* kind, const int* atom_start, const int* atoms, const float* ref_pos,
-                                     const float* contact_r0, const float* contact_beta, const float* contact_lambda, const float* dihedral_ref) {
-    static const char* kind_name[] = {"rg", "rmsd", "contacts", "distance", "dihedral", "dihedral_similarity"};
+                                     const float* contact_r0, const float* contact_beta, const float* contact_lambda, const float* dihedral_ref,
+                                     const int* path_n_frame, const float* path_lambda, const float* path_ref_pos) {
+    static const char* kind_name[] = {"rg", "rmsd", "contacts", "distance", "dihedral", "dihedral_similarity", "", "", "path_s", "path_z"};
     if (n_cv < 0) throw string("collective variables: n_cv is negative");
     if (n_cv > UPK_CV_MAX) throw string("collective variables: ") + to_string(n_cv) + " CVs exceed the kernel's limit of " + to_string(UPK_CV_MAX) + " (UPK_CV_MAX)";
     if (n_cv && (!kind || !atom_start || !atoms)) throw string("collective variables: kind, atom_start and atoms must be given");
@@ -742,14 +743,16 @@ CvHostDefinition cv_check_definition(int n_atom, int n_cv, const int* kind, cons
     vector<double>&h_ref = def.ref, &h_ref_g = def.ref_g;
     vector<float>&h_r0 = def.r0, &h_beta = def.beta, &h_lambda = def.lambda, &h_dref = def.dihedral_ref;
     h_aux.assign((size_t)n_cv, 0); h_ref_g.assign((size_t)n_cv, 0.); h_beta.assign((size_t)n_cv, 0.f); h_lambda.assign((size_t)n_cv, 0.f);
+    def.path_n_frame.assign((size_t)n_cv, 0); def.path_frame_start.assign((size_t)n_cv, 0); def.path_lambda.assign((size_t)n_cv, 0.f);
     if (n_cv) {
         h_kind.assign(kind, kind + n_cv); h_start.assign(atom_start, atom_start + n_cv + 1);
         if (h_start[0] != 0) throw string("collective variables: atom_start[0] must be 0");
-        size_t n_ref = 0, n_pair = 0, n_quad = 0;
+        size_t n_ref = 0, n_pair = 0, n_quad = 0, n_path_row = 0, n_path_frame = 0;
         for (int c = 0; c < n_cv; ++c) {
             const string who = "collective variable " + to_string(c);
-            if (h_kind[c] < 0 || h_kind[c] > UPK_CV_DIHEDRAL_SIMILARITY)
-                throw who + ": unknown kind " + to_string(h_kind[c]) + " (0 rg, 1 rmsd, 2 contacts, 3 distance, 4 dihedral, 5 dihedral_similarity)";
+            const bool is_path = h_kind[c] == UPK_CV_PATH_S || h_kind[c] == UPK_CV_PATH_Z;
+            if (h_kind[c] < 0 || (h_kind[c] > UPK_CV_DIHEDRAL_SIMILARITY && !is_path))
+                throw who + ": unknown kind " + to_string(h_kind[c]) + " (0 rg, 1 rmsd, 2 contacts, 3 distance, 4 dihedral, 5 dihedral_similarity, 8 path_s, 9 path_z)";
             const string whok = who + " (" + kind_name[h_kind[c]] + ")";
             const long n = (long)h_start[c + 1] - h_start[c];
             if (n < 0) throw whok + ": atom_start must not decrease";
@@ -783,12 +786,39 @@ CvHostDefinition cv_check_definition(int n_atom, int n_cv, const int* kind, cons
                     for (long i = 0; i < n / 4; ++i) if (!std::isfinite(dihedral_ref[n_quad + i])) throw whok + ": dihedral_ref is not finite";
                     h_aux[c] = (int)n_quad; n_quad += (size_t)(n / 4);
                 }
+            } else if (is_path) {
+                if (!path_n_frame || !path_lambda || !path_ref_pos)
+                    throw whok + ": path_n_frame, path_lambda and path_ref_pos must be given (upside_hip_cv_define3)";
+                const int K = path_n_frame[c];
+                if (K < 2 || K > UPK_CV_PATH_MAX_FRAMES)
+                    throw whok + ": " + to_string(K) + " frames; a path needs 2 to " + to_string(UPK_CV_PATH_MAX_FRAMES) + " (UPK_CV_PATH_MAX_FRAMES)";
+                if (n < 3) throw whok + ": a path selection needs at least 3 atoms";
+                if (!std::isfinite(path_lambda[c]) || !(path_lambda[c] > 0.f)) throw whok + ": path_lambda must be positive and finite";
+                for (size_t i = 0; i < (size_t)K * n * 3; ++i)
+                    if (!std::isfinite(path_ref_pos[n_path_row * 3 + i])) throw whok + ": path_ref_pos is not finite";
+                h_aux[c] = (int)n_path_row;      // (rows of path_ref_pos for now: the rmsd references' rows are added below)
+                def.path_n_frame[c] = K; def.path_frame_start[c] = (int)n_path_frame; def.path_lambda[c] = path_lambda[c];
+                n_path_row += (size_t)K * n; n_path_frame += (size_t)K;
             }
         }
         h_atoms.assign(atoms, atoms + h_start[n_cv]);
         h_r0.assign(contact_r0, contact_r0 + (contact_r0 ? n_pair : 0));
         h_dref.assign(dihedral_ref, dihedral_ref + (dihedral_ref ? n_quad : 0));
-        h_ref.resize(n_ref * 3);
+        h_ref.resize((n_ref + n_path_row) * 3);
+        def.path_g.assign(n_path_frame, 0.);
+        for (int c = 0; c < n_cv; ++c) if (h_kind[c] == UPK_CV_PATH_S || h_kind[c] == UPK_CV_PATH_Z) {      // every frame centred in double, and its squared norm
+            const size_t n = (size_t)(h_start[c + 1] - h_start[c]), in = (size_t)h_aux[c] * 3;
+            h_aux[c] += (int)n_ref;
+            for (int k = 0; k < def.path_n_frame[c]; ++k) {
+                const float* f = path_ref_pos + in + (size_t)k * n * 3;
+                double* o = h_ref.data() + ((size_t)h_aux[c] + (size_t)k * n) * 3;
+                double cen[3] = {0., 0., 0.}, g = 0.;
+                for (size_t i = 0; i < n; ++i) for (int d = 0; d < 3; ++d) cen[d] += (double)f[3 * i + d];
+                for (int d = 0; d < 3; ++d) cen[d] /= (double)n;
+                for (size_t i = 0; i < n; ++i) for (int d = 0; d < 3; ++d) { const double v = (double)f[3 * i + d] - cen[d]; o[3 * i + d] = v; g += v * v; }
+                def.path_g[(size_t)def.path_frame_start[c] + k] = g;
+            }
+        }
         for (int c = 0; c < n_cv; ++c) if (h_kind[c] == UPK_CV_RMSD) {      // the reference centred in double, and its squared norm
             const size_t n = (size_t)(h_start[c + 1] - h_start[c]), o = (size_t)h_aux[c] * 3;
             double cen[3] = {0., 0., 0.};
@@ -817,11 +847,28 @@ CvHostDefinition cv_read_definition(hid_t_compat group, int n_atom, const string
     if (beta.size() != n_cv || lambda.size() != n_cv) throw where + ": contact_beta and contact_lambda must have n_cv entries";
     vector<float> dref;      // optional: a file without it has no dihedral_similarity
     if (h5u::exists(g, "dihedral_ref")) dref = h5u::read<float>(g, "dihedral_ref", 1);
+    vector<int> path_k; vector<float> path_lam, path_ref;      // optional, all three or none: a file without them has no path kind
+    const int n_path_set = (int)h5u::exists(g, "path_n_frame") + (int)h5u::exists(g, "path_lambda") + (int)h5u::exists(g, "path_ref_pos");
+    if (n_path_set != 0 && n_path_set != 3) throw where + ": path_n_frame, path_lambda and path_ref_pos come together";
+    if (n_path_set) {
+        path_k = h5u::read<int>(g, "path_n_frame", 1); path_lam = h5u::read<float>(g, "path_lambda", 1);
+        if (path_k.size() != n_cv || path_lam.size() != n_cv) throw where + ": path_n_frame and path_lambda must have n_cv entries";
+        vector<hsize_t> pd;
+        path_ref = h5u::read<float>(g, "path_ref_pos", 2, &pd);
+        if (pd[0] && pd[1] != 3) throw where + ": path_ref_pos must be (n, 3)";
+    }
     // the packed arrays must be as long as the kinds say (cv_check_definition reads them by those counts)
-    size_t n_ref = 0, n_pair = 0, n_quad = 0;
+    size_t n_ref = 0, n_pair = 0, n_quad = 0, n_path_row = 0;
     for (size_t c = 0; c < n_cv; ++c) {
         const long n = (long)atom_start[c + 1] - atom_start[c];
         if (n < 0) throw where + ": atom_start must not decrease";
+        if (kind[c] == UPK_CV_PATH_S || kind[c] == UPK_CV_PATH_Z) {
+            if (!n_path_set) throw where + ": collective variable " + to_string(c) + " is a path kind, but path_n_frame, path_lambda and path_ref_pos are absent";
+            if (path_k[c] < 2 || path_k[c] > UPK_CV_PATH_MAX_FRAMES)
+                throw where + ": collective variable " + to_string(c) + ": " + to_string(path_k[c]) + " frames; a path needs 2 to " +
+                      to_string(UPK_CV_PATH_MAX_FRAMES) + " (UPK_CV_PATH_MAX_FRAMES)";
+            n_path_row += (size_t)path_k[c] * (size_t)n;
+        }
         if (kind[c] == UPK_CV_RMSD) n_ref += (size_t)n; else if (kind[c] == UPK_CV_CONTACTS) n_pair += (size_t)(n / 2);
         else if (kind[c] == UPK_CV_DIHEDRAL_SIMILARITY) n_quad += (size_t)(n / 4);
     }
@@ -829,19 +876,25 @@ CvHostDefinition cv_read_definition(hid_t_compat group, int n_atom, const string
     if (r0.size() != n_pair) throw where + ": contact_r0 holds " + to_string(r0.size()) + " entries, the contacts lists " + to_string(n_pair) + " pairs";
     if (dref.size() != n_quad)
         throw where + ": dihedral_ref holds " + to_string(dref.size()) + " entries, the dihedral_similarity lists " + to_string(n_quad) + " quadruples";
+    if (path_ref.size() != n_path_row * 3)
+        throw where + ": path_ref_pos holds " + to_string(path_ref.size() / 3) + " rows, the frames of the path kinds " + to_string(n_path_row);
     return cv_check_definition(n_atom, (int)n_cv, kind.data(), atom_start.data(), atoms.data(), ref_pos.data(), r0.data(), beta.data(), lambda.data(),
-                               dref.data());
+                               dref.data(), n_path_set ? path_k.data() : nullptr, n_path_set ? path_lam.data() : nullptr, n_path_set ? path_ref.data() : nullptr);
 }
 void CvDeviceDefinition::upload(const CvHostDefinition& d) {
     kind.upload(d.kind); atom_start.upload(d.atom_start); atoms.upload(d.atoms); aux_start.upload(d.aux_start);
     ref.upload(d.ref); ref_g.upload(d.ref_g); r0.upload(d.r0); beta.upload(d.beta); lambda.upload(d.lambda); dihedral_ref.upload(d.dihedral_ref);
     C.n_cv = d.n_cv; C.kind = kind.p; C.atom_start = atom_start.p; C.atoms = atoms.p; C.aux_start = aux_start.p;
     C.ref = ref.p; C.ref_g = ref_g.p; C.r0 = r0.p; C.beta = beta.p; C.lambda = lambda.p; C.dihedral_ref = dihedral_ref.p;
+    path_n_frame.upload(d.path_n_frame); path_frame_start.upload(d.path_frame_start); path_g.upload(d.path_g); path_lambda.upload(d.path_lambda);
+    C.path_n_frame = path_n_frame.p; C.path_frame_start = path_frame_start.p; C.path_g = path_g.p; C.path_lambda = path_lambda.p;
 }
 void DerivEngine::cv_define(int n_cv, const int* kind, const int* atom_start, const int* atoms, const float* ref_pos, const float* contact_r0,
-                            const float* contact_beta, const float* contact_lambda, const float* dihedral_ref) {
+                            const float* contact_beta, const float* contact_lambda, const float* dihedral_ref, const int* path_n_frame,
+                            const float* path_lambda, const float* path_ref_pos) {
     // everything is checked and built on the host before the first device array is touched: a refusal leaves the old definition in force
-    cv_install(cv_check_definition(pos->n_atom, n_cv, kind, atom_start, atoms, ref_pos, contact_r0, contact_beta, contact_lambda, dihedral_ref));
+    cv_install(cv_check_definition(pos->n_atom, n_cv, kind, atom_start, atoms, ref_pos, contact_r0, contact_beta, contact_lambda, dihedral_ref, path_n_frame,
+                                   path_lambda, path_ref_pos));
 }
 void DerivEngine::cv_install(const CvHostDefinition& def) {
     sync();

@@ -57,15 +57,18 @@ struct PerSystemValues {
 struct CvHostDefinition {
     int n_cv = 0;
     std::vector<int> kind, atom_start, atoms, aux_start; std::vector<double> ref, ref_g; std::vector<float> r0, beta, lambda, dihedral_ref;
+    std::vector<int> path_n_frame, path_frame_start; std::vector<double> path_g; std::vector<float> path_lambda;      // the path kinds (their centred frames follow the rmsd references in ref)
 };
 // throws a message naming the CV and what is wrong with it; touches no device memory
 CvHostDefinition cv_check_definition(int n_atom, int n_cv, const int* kind, const int* atom_start, const int* atoms, const float* ref_pos,
-                                     const float* contact_r0, const float* contact_beta, const float* contact_lambda, const float* dihedral_ref);
-// the same from a group with the datasets of /input/collective_variables (`where` names it in messages; `names` is not read; dihedral_ref may be absent)
+                                     const float* contact_r0, const float* contact_beta, const float* contact_lambda, const float* dihedral_ref,
+                                     const int* path_n_frame = nullptr, const float* path_lambda = nullptr, const float* path_ref_pos = nullptr);
+// the same from a group with the datasets of /input/collective_variables (`where` names it in messages; `names` is not read; dihedral_ref and the three path_* datasets may be absent)
 CvHostDefinition cv_read_definition(hid_t_compat group, int n_atom, const std::string& where);
 struct CvDeviceDefinition {
     upk_cv_t C{};
     DevBuf<int> kind, atom_start, atoms, aux_start; DevBuf<double> ref, ref_g; DevBuf<float> r0, beta, lambda, dihedral_ref;
+    DevBuf<int> path_n_frame, path_frame_start; DevBuf<double> path_g; DevBuf<float> path_lambda;
     void upload(const CvHostDefinition& d);
 };
 
@@ -192,7 +195,8 @@ struct DerivEngine {   // deriv_engine.h:145-237
         DevBuf<unsigned long long> rounds; DevBuf<int> n_attempt; DevBuf<float> samples;
     } cv;
     void cv_define(int n_cv, const int* kind, const int* atom_start, const int* atoms, const float* ref_pos, const float* contact_r0,
-                   const float* contact_beta, const float* contact_lambda, const float* dihedral_ref);      // throws, leaving the previous definition in force
+                   const float* contact_beta, const float* contact_lambda, const float* dihedral_ref, const int* path_n_frame = nullptr,
+                   const float* path_lambda = nullptr, const float* path_ref_pos = nullptr);      // throws, leaving the previous definition in force
     void cv_install(const CvHostDefinition& def);      // a checked definition
     void cv_compute(float* out_host);
     void cv_record(int every_n_round, int capacity);

@@ -590,7 +590,13 @@ extern "C" int upside_hip_cv_define(DerivEngine* e, int n_cv, const int* kind, c
 }
 extern "C" int upside_hip_cv_define2(DerivEngine* e, int n_cv, const int* kind, const int* atom_start, const int* atoms, const float* ref_pos,
                                      const float* contact_r0, const float* contact_beta, const float* contact_lambda, const float* dihedral_ref) {
-    API_TRY e->cv_define(n_cv, kind, atom_start, atoms, ref_pos, contact_r0, contact_beta, contact_lambda, dihedral_ref); return 0; API_CATCH(1)
+    return upside_hip_cv_define3(e, n_cv, kind, atom_start, atoms, ref_pos, contact_r0, contact_beta, contact_lambda, dihedral_ref, nullptr, nullptr, nullptr);
+}
+extern "C" int upside_hip_cv_define3(DerivEngine* e, int n_cv, const int* kind, const int* atom_start, const int* atoms, const float* ref_pos,
+                                     const float* contact_r0, const float* contact_beta, const float* contact_lambda, const float* dihedral_ref,
+                                     const int* path_n_frame, const float* path_lambda, const float* path_ref_pos) {
+    API_TRY e->cv_define(n_cv, kind, atom_start, atoms, ref_pos, contact_r0, contact_beta, contact_lambda, dihedral_ref, path_n_frame, path_lambda,
+                         path_ref_pos); return 0; API_CATCH(1)
 }
 namespace {
 vector<string> read_string_dataset(hid_t loc, const string& name) {      // fixed-length strings, one dimension

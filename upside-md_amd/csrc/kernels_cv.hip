@@ -7,8 +7,8 @@
 //
 // One workgroup of CV_BLOCK lanes owns one system (blockIdx.x) and walks the system's CVs one after the other; a CV is a handful of
 // sums over its atom list, read through the engine's position layout ([S][n_atom][stride]).  Nothing here is large: 300 CA atoms
-// are 3.6 KB, so the kernel is bound by its launch and by the one read of the positions, and occupancy is no concern (no
-// LDS beyond 4 x CV_MAX_SUMS doubles, 104 VGPRs).  What matters is that the numbers can be trusted:
+// are 3.6 KB, so the kernel is bound by its launch and by the one read of the positions, and occupancy is no concern (LDS: 4 x
+// CV_MAX_SUMS doubles and the frame rows of a path CV, 6 KB; no scratch).  What matters is that the numbers can be trusted:
 //   - every sum is accumulated in fp64: the RMSD is sqrt((Ga + Gb - 2 lambda) / n), which cancels to the last bits near the
 //     reference; fp32 sums would leave ~3e-4 x Rg where the answer is 0.
 //   - every sum has ONE order: lane t adds elements t, t + CV_BLOCK, ... ascending; the 64 lanes of a wavefront combine in a fixed
@@ -17,10 +17,14 @@
 //     the batch size, the system's place in the batch, or the way the launch was issued (eagerly or from a captured graph).
 //   - the largest eigenvalue of Horn's 4x4 quaternion matrix comes from cyclic Jacobi rotations in fp64 (one lane; 4x4).
 // (The sums, the butterfly and the eigenvalue solver are in cv_device.h.)
+// The path kinds (path_s, path_z: K reference frames per CV) have their own device functions in cv_path_device.h: every kernel here
+// branches to them on the kind, uniformly over the workgroup, and lends them one LDS row of CV_PATH_ROW doubles per frame
+// (UPK_CV_PATH_MAX_FRAMES rows, 5.5 KB; k_cv_metad keeps one such block per CV, 22 KB at D = 4).
 // Recording (upk_cv_record) is the same kernel behind a sample decision taken on the device: each system's workgroup advances its
 // own round counter (equal entries, like the thermostat's n_invocations) and stores a row on every `every`-th round while the
 // buffer has room, so a captured MD graph replays it unchanged.
 #include "cv_device.h"
+#include "cv_path_device.h"
 
 using namespace up;
 
@@ -29,6 +33,7 @@ static inline int launch_status() { return (int)hipGetLastError(); }
 
 __global__ void __launch_bounds__(CV_BLOCK) k_collective_variables(upk_coord_t pos, upk_cv_t C, upk_cv_record_t R, float* __restrict__ out) {
     __shared__ double part[CV_WAVES][CV_MAX_SUMS];
+    __shared__ double path[UPK_CV_PATH_MAX_FRAMES][CV_PATH_ROW];
     const int s = blockIdx.x, tid = threadIdx.x;
     float* row;
     if (R.rounds) {       // recording: this system's own counters decide (uniform over the workgroup)
@@ -45,7 +50,7 @@ __global__ void __launch_bounds__(CV_BLOCK) k_collective_variables(upk_coord_t p
 
     for (int c = 0; c < C.n_cv; ++c) {
         double cen[3], rot[9];
-        const double value = cv_evaluate<false>(x, stride, C, c, part, cen, rot);
+        const double value = cv_is_path(C.kind[c]) ? cv_path_evaluate<false>(x, stride, C, c, part, cen, path) : cv_evaluate<false>(x, stride, C, c, part, cen, rot);
         if (tid == 0) row[c] = (float)value;
     }
 }
@@ -82,6 +87,7 @@ __global__ void __launch_bounds__(CV_BLOCK) k_cv_restraint(upk_coord_t pos, upk_
                                                            float* __restrict__ pot_terms) {
     __shared__ double part[CV_WAVES][CV_MAX_SUMS];
     __shared__ double bc[2][11];      // v, dE/dv, R; by CV parity (a lane may still read CV c's while lane 0 writes CV c+1's)
+    __shared__ double path[UPK_CV_PATH_MAX_FRAMES][CV_PATH_ROW];      // a path CV's frames (its R_k stay here)
     const int s = blockIdx.x, tid = threadIdx.x;
     const float* __restrict__ x = pos.out + (size_t)s * pos.n_elem * pos.stride;
     const int stride = pos.stride;
@@ -90,8 +96,9 @@ __global__ void __launch_bounds__(CV_BLOCK) k_cv_restraint(upk_coord_t pos, upk_
 
     for (int c = 0; c < C.n_cv; ++c) {
         double cen[3], rot[9];
-        const double value = cv_evaluate<true>(x, stride, C, c, part, cen, rot);
         const int kind = C.kind[c];
+        const bool is_path = cv_is_path(kind);
+        const double value = is_path ? cv_path_evaluate<true>(x, stride, C, c, part, cen, path) : cv_evaluate<true>(x, stride, C, c, part, cen, rot);
         double* b = bc[c & 1];
         if (tid == 0) {
             double d = value - (double)row[c];
@@ -107,7 +114,8 @@ __global__ void __launch_bounds__(CV_BLOCK) k_cv_restraint(upk_coord_t pos, upk_
             if (pot_terms) pot_terms[(size_t)s * C.n_cv + c] = (float)(0.5 * k * u * u);
         }
         __syncthreads();
-        cv_write_gradient(x, stride, C, c, b[0], b[1], cen, b + 2, out);
+        if (is_path) cv_path_write_gradient(x, stride, C, c, b[0], b[1], cen, path, out);
+        else cv_write_gradient(x, stride, C, c, b[0], b[1], cen, b + 2, out);
     }
 }
 
@@ -132,6 +140,7 @@ __global__ void __launch_bounds__(CV_BLOCK) k_cv_steer(upk_coord_t pos, upk_cv_t
                                                        float* __restrict__ values, float* __restrict__ pot_terms, double* __restrict__ centers) {
     __shared__ double part[CV_WAVES][CV_MAX_SUMS];
     __shared__ double bc[2][11];      // v, dE/dv, R; by CV parity (a lane may still read CV c's while lane 0 writes CV c+1's)
+    __shared__ double path[UPK_CV_PATH_MAX_FRAMES][CV_PATH_ROW];      // a path CV's frames (its R_k stay here)
     const int s = blockIdx.x, tid = threadIdx.x;
     const float* __restrict__ x = pos.out + (size_t)s * pos.n_elem * pos.stride;
     const int stride = pos.stride;
@@ -141,8 +150,9 @@ __global__ void __launch_bounds__(CV_BLOCK) k_cv_steer(upk_coord_t pos, upk_cv_t
 
     for (int c = 0; c < C.n_cv; ++c) {
         double cen[3], rot[9];
-        const double value = cv_evaluate<true>(x, stride, C, c, part, cen, rot);
         const int kind = C.kind[c];
+        const bool is_path = cv_is_path(kind);
+        const double value = is_path ? cv_path_evaluate<true>(x, stride, C, c, part, cen, path) : cv_evaluate<true>(x, stride, C, c, part, cen, rot);
         double* b = bc[c & 1];
         if (tid == 0) {
             const double centre = cv_steer_center((double)row[c], (double)row[C.n_cv + c], (double)row[2 * C.n_cv + c], t);
@@ -160,7 +170,8 @@ __global__ void __launch_bounds__(CV_BLOCK) k_cv_steer(upk_coord_t pos, upk_cv_t
             if (pot_terms) pot_terms[(size_t)s * C.n_cv + c] = (float)E;
         }
         __syncthreads();
-        cv_write_gradient(x, stride, C, c, b[0], b[1], cen, b + 2, out);
+        if (is_path) cv_path_write_gradient(x, stride, C, c, b[0], b[1], cen, path, out);
+        else cv_write_gradient(x, stride, C, c, b[0], b[1], cen, b + 2, out);
     }
 }
 
@@ -178,10 +189,11 @@ __global__ void __launch_bounds__(CV_BLOCK) k_cv_steer_advance(upk_coord_t pos, 
     const float* __restrict__ row = par + (size_t)s * par_stride;
     const unsigned long long t = tid == 0 ? clock[s] : 0ull;
     double dw = 0.;
+    __shared__ double path[UPK_CV_PATH_MAX_FRAMES][CV_PATH_ROW];
 
     for (int c = 0; c < C.n_cv; ++c) {
         double cen[3], rot[9];
-        const double value = cv_evaluate<false>(x, stride, C, c, part, cen, rot);
+        const double value = cv_is_path(C.kind[c]) ? cv_path_evaluate<false>(x, stride, C, c, part, cen, path) : cv_evaluate<false>(x, stride, C, c, part, cen, rot);
         if (tid == 0) {
             const double v = (double)(float)value;
             const double c0 = (double)row[c], rate = (double)row[C.n_cv + c], c_end = (double)row[2 * C.n_cv + c];
@@ -256,6 +268,7 @@ __global__ void __launch_bounds__(CV_BLOCK) k_cv_metad(upk_coord_t pos, upk_cv_t
                                                        float* __restrict__ values, float* __restrict__ pot_terms) {
     __shared__ double part[CV_WAVES][CV_MAX_SUMS];
     __shared__ double st[D][13];      // per CV: v, centroid, R
+    __shared__ double path[D][UPK_CV_PATH_MAX_FRAMES][CV_PATH_ROW];      // per path CV: d_k, R_k and w_k of its frames, kept from phase 1 to phase 3
     const int s = blockIdx.x, tid = threadIdx.x;
     const float* __restrict__ x = pos.out + (size_t)s * pos.n_elem * pos.stride;
     const int stride = pos.stride;
@@ -264,11 +277,12 @@ __global__ void __launch_bounds__(CV_BLOCK) k_cv_metad(upk_coord_t pos, upk_cv_t
 #pragma unroll 1
     for (int c = 0; c < D; ++c) {
         double cen[3], rot[9];
-        const double value = cv_evaluate<true>(x, stride, C, c, part, cen, rot);
+        const bool is_path = cv_is_path(C.kind[c]);
+        const double value = is_path ? cv_path_evaluate<true>(x, stride, C, c, part, cen, path[c]) : cv_evaluate<true>(x, stride, C, c, part, cen, rot);
         if (tid == 0) {
             const int kind = C.kind[c];
             st[c][0] = value;
-            if (kind == UPK_CV_RG || kind == UPK_CV_RMSD) { st[c][1] = cen[0]; st[c][2] = cen[1]; st[c][3] = cen[2]; }
+            if (kind == UPK_CV_RG || kind == UPK_CV_RMSD || is_path) { st[c][1] = cen[0]; st[c][2] = cen[1]; st[c][3] = cen[2]; }
             if (kind == UPK_CV_RMSD) {
 #pragma unroll
                 for (int i = 0; i < 9; ++i) st[c][4 + i] = rot[i];
@@ -289,7 +303,8 @@ __global__ void __launch_bounds__(CV_BLOCK) k_cv_metad(upk_coord_t pos, upk_cv_t
 #pragma unroll 1
     for (int c = 0; c < D; ++c) {
         const double cen[3] = {st[c][1], st[c][2], st[c][3]};
-        cv_write_gradient(x, stride, C, c, v[c], acc[1 + c], cen, &st[c][4], out);
+        if (cv_is_path(C.kind[c])) cv_path_write_gradient(x, stride, C, c, v[c], acc[1 + c], cen, path[c], out);
+        else cv_write_gradient(x, stride, C, c, v[c], acc[1 + c], cen, &st[c][4], out);
     }
 }
 
@@ -302,6 +317,7 @@ template <int D>
 __global__ void __launch_bounds__(CV_BLOCK) k_cv_metad_deposit(upk_coord_t pos, upk_cv_t C, upk_cv_metad_t M) {
     __shared__ double part[CV_WAVES][CV_MAX_SUMS];
     __shared__ double st[D];
+    __shared__ double path[UPK_CV_PATH_MAX_FRAMES][CV_PATH_ROW];
     const int s = blockIdx.x, tid = threadIdx.x, n_system = (int)gridDim.x;
     const unsigned long long r = M.rounds[s] + 1ull;
     const int k = M.n_deposit[s], na = M.n_attempt[s];
@@ -315,7 +331,7 @@ __global__ void __launch_bounds__(CV_BLOCK) k_cv_metad_deposit(upk_coord_t pos, 
 #pragma unroll 1
     for (int c = 0; c < D; ++c) {
         double cen[3], rot[9];
-        const double value = cv_evaluate<false>(x, stride, C, c, part, cen, rot);
+        const double value = cv_is_path(C.kind[c]) ? cv_path_evaluate<false>(x, stride, C, c, part, cen, path) : cv_evaluate<false>(x, stride, C, c, part, cen, rot);
         if (tid == 0) st[c] = (double)(float)value;
     }
     __syncthreads();

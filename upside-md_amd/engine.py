@@ -283,6 +283,7 @@ class Ensemble(object):
         c.upside_hip_last_error.restype = ct.c_char_p
         c.upside_hip_cv_define.argtypes = [vp, i32, vp, vp, vp, vp, vp, vp, vp]
         c.upside_hip_cv_define2.argtypes = [vp, i32, vp, vp, vp, vp, vp, vp, vp, vp]
+        c.upside_hip_cv_define3.argtypes = [vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
         c.upside_hip_cv_load.argtypes = [vp, ct.c_char_p]
         c.upside_hip_cv_count.argtypes = [vp]
         c.upside_hip_cv_compute.argtypes = [vp, vp]
@@ -430,9 +431,10 @@ class Ensemble(object):
         arr = dict((k, np.ascontiguousarray(p[k], t)) for k, t in (('kind', 'i4'), ('atom_start', 'i4'), ('atoms', 'i4'), ('ref_pos', 'f4'),
                                                                      ('contact_r0', 'f4'), ('contact_beta', 'f4'), ('contact_lambda', 'f4')))
         dref = np.ascontiguousarray(p['dihedral_ref'], 'f4') if 'dihedral_ref' in p else None      # (a dict packed before the kind existed)
-        self._check(self.calc.upside_hip_cv_define2(self.engine, n_cv, *([arr[k].ctypes.data for k in
+        path = [np.ascontiguousarray(p[k], t) if k in p else None for k, t in (('path_n_frame', 'i4'), ('path_lambda', 'f4'), ('path_ref_pos', 'f4'))]
+        self._check(self.calc.upside_hip_cv_define3(self.engine, n_cv, *([arr[k].ctypes.data for k in
                     ('kind', 'atom_start', 'atoms', 'ref_pos', 'contact_r0', 'contact_beta', 'contact_lambda')] +
-                    [None if dref is None else dref.ctypes.data])), 'cv_define')
+                    [None if v is None else v.ctypes.data for v in [dref] + path])), 'cv_define')
         self.cv_names = [x.decode() if isinstance(x, bytes) else str(x) for x in p['names']]
         self._cv_periods = config.cv_periods(p)
 
