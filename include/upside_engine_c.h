@@ -210,7 +210,8 @@ int upside_hip_param_deriv_read(DerivEngine* engine, const char* node_name, int 
  *     numbered by first appearance; returns the number of groups, -1 on failure.  Files that are identical or differ only
  *     in the table's values share a group; UPSIDE_HIP_HAMILTONIAN_BATCH=0 groups by the whole /input/potential instead.
  *   _set_param_system / _get_param_system: set_param / get_param of one system (hbond_energy, cv_restraint, cv_steer).
- *     set_param keeps its meaning (every system); get_param returns system 0's values.
+ *     set_param keeps its meaning (every system); get_param returns system 0's values.  set_param first waits for the MD steps
+ *     still in flight on the engine's stream, and it ends the exchange attempt whose energies a _replica_swap_next would reuse.
  *   _hamiltonian_swap: one swap set (main.cpp:251-273) on the engine's stream: energy pass, the pairs trade coordinates,
  *     energy pass, Metropolis verdicts of upside_replica_decide_lboltz (each system's own temperature), refused pairs trade
  *     back.  draw0 >= 0: first draw of the set (0 for the first set of an attempt); draw0 < 0: continue from the draw the

@@ -349,7 +349,13 @@ extern "C" int evaluate_deriv(float* deriv, DerivEngine* e, const float* pos) {
 // ---- parameters and node inspection (engine_c_library.cpp:67-193) ---------------------------------------
 extern "C" int set_param(int n_param, const float* param, DerivEngine* e, const char* node_name) {
     API_TRY
+    if (!e || !node_name || (n_param && !param)) throw string("engine, node name or parameter array is NULL");
+    // run_steps returns with its steps still in flight on the engine's non-blocking stream, and the nodes upload their tables with
+    // blocking copies that do not order behind it: wait first, so that no step in flight reads a half-written table and no
+    // graph exec is destroyed while it runs
+    e->sync();
     e->invalidate_graph();   // cut-offs travel as kernel arguments
+    e->invalidate_attempt(); // the energies of an exchange attempt belong to the old parameters
     e->get(string(node_name)).computation->set_param(vector<float>(param, param + n_param)); return 0; API_CATCH(1) }
 extern "C" int get_param(int n_param, float* param, DerivEngine* e, const char* node_name) {
     API_TRY
