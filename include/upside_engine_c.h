@@ -500,7 +500,37 @@ int upside_hip_metad_grid(int n_list, int d, const long long* hill_start, const 
                           int n_scale, const double* scales, double* V_last /* [n_list][G] or NULL */,
                           double* lse /* [n_list][n_checkpoint][n_scale], NULL iff n_scale == 0 */);
 
-/* Per-kernel timing hooks used by bench.py.  With profiling enabled every interaction-graph / BP kernel
+/* Pairwise RMSD of frames after optimal superposition, on the device (csrc/kernels_rmsd.hip): the distance matrix of two frame sets,
+ * the nearest column frame of every row frame, and the number of column frames within a cutoff -- what clustering and the choice of
+ * path frames are made of.  No engine is needed; every array is a HOST array; a call runs on a stream of its own on the current
+ * device and returns when it is done.  Frame f holds n atoms x_f,i (float32, widened exactly).  In fp64,
+ *   c_f = (1/n) sum_i x_f,i      y_f,i = x_f,i - c_f      G_f = sum_i |y_f,i|^2
+ *   M_ab[c][d] = sum_i y_a,i[c] y_b,i[d]  (atoms ascending)      lambda_ab = the largest eigenvalue of Horn's 4 x 4 matrix of M_ab
+ *   d2_ab = max(0, G_a + G_b - 2 lambda_ab) / n                  d_ab = sqrt(d2_ab)
+ * (Horn 1987: the best PROPER rotation, no reflection, equal weights, every pair centred on its own).
+ * upside_hip_frames_create centres the frames on the device and returns a handle; it is the only copy of coordinates to the device.
+ * The three calls name frame sets by handle; ia / ib are int32 positions into the sets (repeats allowed) or NULL for all frames in
+ * order, and nA / nB must then equal the set's size.
+ *   upside_hip_rmsd_matrix:  out[p][q] = d of row position p and column position q, row-major (nA, nB).  With the same set and the
+ *     same (or no) index list on both sides only pairs p < q are computed, the rest is mirrored and the diagonal is exactly 0.
+ *   upside_hip_rmsd_nearest: index[p] = the column POSITION with the smallest d2 (the lowest on equal bits), dist[p] = that d.
+ *   upside_hip_rmsd_count:   count[p] = the number of column positions with d2 <= cutoff^2.
+ * The 3 x 3 matrices of 16 x 16 frame pairs are nine accumulators of v_mfma_f64_16x16x4_f64; a lane solves its pairs by cyclic
+ * Jacobi.  Float64 throughout, no atomics, one summation order: the bits of an entry depend on its two frames (row, column) alone,
+ * not on the rest of the call, the pair's place in a tile, or how a call is cut up.  Limits: distances below about
+ * 1e-6 sqrt((G_a + G_b) / n) are rounding noise (two copies of a frame come out near 1e-7 A, not 0, off the diagonal); a set holds
+ * 3 n_frame n_pad doubles on the device (n_pad = n_atom rounded up to 4); one device.
+ * Return 0, or 1 with upside_hip_last_error set.  Refused before any device call: a NULL handle, one that was freed, or a NULL output; n_atom < 3; n_frame < 1;
+ * n_atom x n_frame x 3 at or above 2^40; a coordinate that is not finite; different n_atom on the two sides; nA or nB < 1, or not the
+ * set's size without an index list; an index outside its set; a cutoff that is negative or not finite; nA x nB at or above 2^40 for
+ * the matrix.  A device allocation that fails is refused with its byte count.  Without a HIP device the calls fail like every other. */
+int upside_hip_frames_create(int n_atom, long long n_frame, const float* pos /* (n_frame, n_atom, 3) */, void** frames);
+void upside_hip_frames_free(void* frames);
+int upside_hip_rmsd_matrix(void* A, long long nA, const int* ia, void* B, long long nB, const int* ib, double* out /* (nA, nB) */);
+int upside_hip_rmsd_nearest(void* A, long long nA, const int* ia, void* B, long long nB, const int* ib, long long* index, double* dist);
+int upside_hip_rmsd_count(void* A, long long nA, const int* ia, void* B, long long nB, const int* ib, double cutoff, long long* count);
+
+/* Per-kernel timing hooks used by bench.py. With profiling enabled every interaction-graph / BP kernel
  * launch is bracketed by HIP events on the engine's stream.  upside_hip_profile_dump writes one text line per
  * kernel: "<kind>:<node> <total ms> <launches> <total algorithmic bytes> <total pair evaluations>" (bytes as defined in
  * DESIGN.md; pair evaluations = in-range pairs of system 0 x systems, per launch of a pair pass). */

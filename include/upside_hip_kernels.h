@@ -833,6 +833,43 @@ typedef struct {
 int upk_metad_bias_solve(const upk_metad_bias_problem_t* P, char* message /* host */, int message_len);
 int upk_metad_grid_solve(const upk_metad_grid_problem_t* P, char* message /* host */, int message_len);
 
+/* ---- pairwise RMSD of frames (upside_hip_frames_create, upside_hip_rmsd_matrix / _nearest / _count), csrc/kernels_rmsd.hip ----------------
+ * upk_rmsd_frames_create and upk_rmsd_solve are the HOST sides of the entry points (include/upside_engine_c.h states the definitions and
+ * the refusals): the checks come before any device call; 0, or 1 with the reason in message.  A frame set is a upk_rmsd_frames_t made
+ * by upk_rmsd_frames_create: the centred coordinates in fp64, component-major, y[(c * n_frame + f) * n_pad + i] with the atoms padded
+ * with zeros to n_pad (a multiple of the MFMA k-step of 4), and g[f] = sum_i |y_f,i|^2.  A workgroup (4 waves) owns UPK_RMSD_TILE_ROWS x
+ * UPK_RMSD_TILE_COLS frame pairs; a wave owns 16 rows x 32 columns as 2 x 9 accumulators of v_mfma_f64_16x16x4_f64 and each lane solves
+ * its eight pairs by cyclic Jacobi on Horn's matrix.  fp64, no atomics, one summation order.  stats (may be NULL) receives [0] the
+ * device time in ms between HIP events around the tile kernel (copies excluded), [1] the wall time in ms of the call after its checks,
+ * [2] the workgroups launched. */
+#define UPK_RMSD_MAGIC 0x75706b52
+#define UPK_RMSD_TILE_ROWS 64
+#define UPK_RMSD_TILE_COLS 32
+#define UPK_RMSD_MATRIX 0
+#define UPK_RMSD_NEAREST 1
+#define UPK_RMSD_COUNT 2
+typedef struct {
+    int magic, n_atom, n_pad;                                     /* UPK_RMSD_MAGIC while the set lives */
+    long long n_frame;
+    double *y, *g;                                                /* device */
+    double create_ms[2];                                          /* [0] the copies to the device, [1] the centring kernel (wall, synchronised) */
+} upk_rmsd_frames_t;
+typedef struct {
+    int mode;                                                     /* UPK_RMSD_MATRIX, _NEAREST or _COUNT */
+    const upk_rmsd_frames_t *A, *B;
+    long long nA, nB;
+    const int *ia, *ib;                                           /* host [nA], [nB] positions into the sets, or NULL: all frames in order */
+    double cutoff;                                                /* _COUNT */
+    double* out;                                                  /* _MATRIX: host out [nA][nB] */
+    long long* index; double* dist;                               /* _NEAREST: host out [nA] */
+    long long* count;                                             /* _COUNT: host out [nA] */
+    double* stats;                                                /* host out [3] or NULL */
+} upk_rmsd_problem_t;
+int upk_rmsd_frames_create(int n_atom, long long n_frame, const float* pos /* host (n_frame, n_atom, 3) */, upk_rmsd_frames_t** frames,
+                           char* message /* host */, int message_len);
+void upk_rmsd_frames_free(upk_rmsd_frames_t* frames);
+int upk_rmsd_solve(const upk_rmsd_problem_t* P, char* message /* host */, int message_len);
+
 #ifdef __cplusplus
 }
 #endif

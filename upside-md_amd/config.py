@@ -920,6 +920,16 @@ def path_specs(name, atoms, frames, lam=None):
     return [{'name': '%s_%s' % (name, k[-1]), 'kind': k, 'atoms': np.asarray(atoms), 'frames': np.asarray(frames, 'f8'), 'lambda': lam} for k in CV_PATH_KINDS]
 
 
+def path_neighbour_table(frames, library=None):
+    """the K x K RMSD matrix of a path's frames (K,n,3), on the device (cluster.rmsd_matrix): the standard check that consecutive
+    frames are equidistant -- the first off-diagonal about constant, the rest growing with |k - l| -- before a path_lambda is trusted"""
+    from . import cluster
+    frames = np.asarray(frames)
+    if frames.ndim != 3 or frames.shape[2] != 3 or len(frames) < 2 or frames.shape[1] < 3:
+        raise ValueError('path_neighbour_table: frames must be (K >= 2, n >= 3, 3)')
+    return cluster.rmsd_matrix(frames, library=library)
+
+
 CV_DATASETS = ('kind', 'atom_start', 'atoms', 'ref_pos', 'contact_r0', 'contact_beta', 'contact_lambda', 'names')
 
 

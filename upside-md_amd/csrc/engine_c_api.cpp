@@ -141,6 +141,38 @@ extern "C" int upside_hip_metad_grid(int n_list, int d, const long long* hill_st
     return 0;
     API_CATCH(1)
 }
+// pairwise RMSD of frames: the checks and the staging are upk_rmsd_frames_create and upk_rmsd_solve (kernels_rmsd.hip)
+extern "C" int upside_hip_frames_create(int n_atom, long long n_frame, const float* pos, void** frames) {
+    API_TRY
+    char msg[256];
+    if (upk_rmsd_frames_create(n_atom, n_frame, pos, (upk_rmsd_frames_t**)frames, msg, (int)sizeof(msg))) throw string(msg);
+    return 0;
+    API_CATCH(1)
+}
+extern "C" void upside_hip_frames_free(void* frames) { upk_rmsd_frames_free((upk_rmsd_frames_t*)frames); }
+static int rmsd_call(upk_rmsd_problem_t& P, void* A, long long nA, const int* ia, void* B, long long nB, const int* ib) {
+    API_TRY
+    P.A = (const upk_rmsd_frames_t*)A; P.nA = nA; P.ia = ia; P.B = (const upk_rmsd_frames_t*)B; P.nB = nB; P.ib = ib;
+    char msg[256];
+    if (upk_rmsd_solve(&P, msg, (int)sizeof(msg))) throw string(msg);
+    return 0;
+    API_CATCH(1)
+}
+extern "C" int upside_hip_rmsd_matrix(void* A, long long nA, const int* ia, void* B, long long nB, const int* ib, double* out) {
+    upk_rmsd_problem_t P{};
+    P.mode = UPK_RMSD_MATRIX; P.out = out;
+    return rmsd_call(P, A, nA, ia, B, nB, ib);
+}
+extern "C" int upside_hip_rmsd_nearest(void* A, long long nA, const int* ia, void* B, long long nB, const int* ib, long long* index, double* dist) {
+    upk_rmsd_problem_t P{};
+    P.mode = UPK_RMSD_NEAREST; P.index = index; P.dist = dist;
+    return rmsd_call(P, A, nA, ia, B, nB, ib);
+}
+extern "C" int upside_hip_rmsd_count(void* A, long long nA, const int* ia, void* B, long long nB, const int* ib, double cutoff, long long* count) {
+    upk_rmsd_problem_t P{};
+    P.mode = UPK_RMSD_COUNT; P.cutoff = cutoff; P.count = count;
+    return rmsd_call(P, A, nA, ia, B, nB, ib);
+}
 
 // ---- construction ----------------------------------------------------------------------------------
 extern "C" int upside_hip_set_device(int device) {
