@@ -176,6 +176,35 @@ int upside_hip_igraph_stats(DerivEngine* engine, const char* node_name, double* 
 /* Parity/diagnostic access: the in-range pair list of an interaction-graph node of system `sys` after the
  * last force pass, canonical order of interaction_graph.h:122-157.  Returns n_edge or -1. */
 int upside_hip_get_pairlist(DerivEngine* engine, const char* node_name, int sys, int max_edge, int* i1, int* i2);
+/* Diagnostic, read only: the lists the pair passes of the LAST force pass walked, for system `sys` and the rows of `side` (1 or 2)
+ * of an interaction-graph node (rotamer, hbond_coverage*, environment_coverage, protein_hbond, radial, hbond_sc_radial), copied
+ * as they lie on the device.  It launches nothing, builds no side on demand and changes no counter; it waits for the stream and
+ * copies that system's slices.  Sizes first, then fill: with ints == floats == NULL only info20 / cutoffs2 / sources are written.
+ * Returns 0; 1 on an error (no graph, bad system, bad side); 2 when the MD path does not keep that side; 3 when a buffer is too
+ * small (info20[14], info20[15] say what is needed); upside_hip_last_error() states the reason.
+ * info20: 0 n_rows, 1 n_other, 2 cap (words per row), 3 symmetric, 4 md_sides (bit mask of the sides kept), 5 graph type,
+ *   6 bits per list word on the device, 7 nbr_j_bits (0: a word is the partner's element index; else the index is the low
+ *   nbr_j_bits bits and the residue-pair slot lies above them), 8 n_slot of the system (rotamer; else -1), 9 has hit lists (the
+ *   radial graphs walk their cached lists), 10 has hlo, 11 has ord, 12 has ordu, 13 elements renumbered, 14 ints needed,
+ *   15 floats needed, 16 rows hold the partners above the row only, 17 refines so far, 18 the slot value "none", 19 the system's
+ *   rebuild flag.   cutoffs2: cutoff, cache_cutoff (fp32, as the kernels use them).
+ * sources: "<node of the rows>\n<node of the other side>", the coordinate nodes the positions were read from.
+ * ints, in this order (a section that info20 says is absent is left out): cnt[n_rows], hcnt[n_rows], hlo[n_rows], ord[n_rows],
+ *   ordu[n_rows], id of the rows, id of the other side, the caller's element number (orig_of) of the rows, of the other side,
+ *   element of the source node (index) of the rows, of the other side, cached words [n_rows][cap], hit words [n_rows][cap]
+ *   (words widened to 32 bits, otherwise unchanged).
+ * floats: cur_pos of the rows [n_rows][4], of the other side [n_other][4] (what the refine tested), cache_pos of the rows, of the
+ *   other side (4th word: the element id's bits), then the source nodes' own x, y, z of this system at the graph's elements:
+ *   rows [n_rows][3], other side [n_other][3]. */
+int upside_hip_get_walked_lists(DerivEngine* engine, const char* node_name, int sys, int side, int* info20, float* cutoffs2,
+                                char* sources, int sources_len, int n_int, int* ints, int n_float, float* floats);
+/* ... and the cached residue-pair list of a backbone_pairs node.  info2: n_residue, cap; cutoffs3: skin, dist_cutoff, and the node's
+ * potential of this system in the last force pass that asked for energies (written with the lists, and when 2 is returned).
+ * ints: cnt[n_residue], residue ids [n_residue], partners [n_residue][cap]; floats: [n_residue][4] the reference centres the NEXT
+ * force pass will test the displacements against, then [n_residue][3] the residues' current centres (the alignment node's own rows of
+ * this system).  Returns as above; 2 when the node keeps no list. */
+int upside_hip_get_backbone_list(DerivEngine* engine, const char* node_name, int sys, int* info2, float* cutoffs3, int n_int, int* ints,
+                                 int n_float, float* floats);
 
 /* number of BP sweeps of the last rotamer solve per system (rotamer.cpp:1038-1051) */
 int upside_hip_rotamer_iterations(DerivEngine* engine, int* iters);

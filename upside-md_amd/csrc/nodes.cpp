@@ -2275,10 +2275,194 @@ int engine_rebuild_flags(DerivEngine& e, const string& node_name, vector<int>& f
     else if (auto* h = dynamic_cast<HBondCoverage*>(c)) ig = &h->ig;
     else if (auto* en = dynamic_cast<EnvironmentCoverage*>(c)) ig = &en->ig;
     else if (auto* p = dynamic_cast<ProteinHBond*>(c)) ig = &p->ig;
+    else if (auto* rp = dynamic_cast<RadialPairs*>(c)) ig = &rp->ig;
     if (!ig) return -1;
     e.sync();
     flags = ig->rebuild_flag.download();
     return 0;
+}
+// Diagnostics (upside_hip_get_walked_lists / upside_hip_get_backbone_list, include/upside_engine_c.h, which gives the layout of info /
+// ints / floats): what the pair passes of the last force pass walked, one system and one side of one graph, copied as it lies on the
+// device.  Read only: it launches nothing, builds no side on demand and touches no counter; it waits for the stream and copies this
+// system's slices.  engine_walked_lists returns -1: the node has no graph, 2: the MD path does not keep that side (info holds the
+// sizes, nothing is copied), 0: filled (sizes only unless `fill`); engine_backbone_list -1: not a backbone_pairs, 2: the list is off.
+namespace {
+struct WalkedLists {
+    int info[20] = {0}; float cutoff = 0.f, cache_cutoff = 0.f;
+    string source_rows, source_other;      // the coordinate nodes upk_pairlist_check read the positions from
+    vector<int> ints; vector<float> floats;
+};
+struct BackboneListCopy {
+    int n_residue = 0, cap = 0; float skin = 0.f, dist_cutoff = 0.f, potential = 0.f;      // potential: the node's, of this system, in the last force pass that asked for energies
+    vector<int> cnt, id, list; vector<float> ref, centre;      // ref [n_residue][4]: the reference centres the NEXT pass reads; centre [n_residue][3]: the current ones
+};
+template <typename T> void d2h(T* dst, const T* src, size_t n) {
+    if (n) hip_check(hipMemcpy(dst, src, n * sizeof(T), hipMemcpyDeviceToHost), "D2H");
+}
+string name_of(DerivEngine& e, const DerivComputation* c) {
+    for (auto& n : e.nodes) if (n.computation.get() == c) return n.name;
+    return "";
+}
+}
+static int engine_walked_lists(DerivEngine& e, const string& node_name, int sys, int side, bool fill, WalkedLists& W) {
+    auto* c = e.get(node_name).computation.get();
+    IGraphHost* ig = nullptr;
+    const CoordNode* src1 = nullptr;
+    int* n_slot_dev = nullptr;
+    if (auto* r = dynamic_cast<RotamerSidechain*>(c)) { ig = &r->ig; n_slot_dev = r->n_slot.p; }
+    else if (auto* h = dynamic_cast<HBondCoverage*>(c)) { ig = &h->ig; src1 = h->site_positions; }
+    else if (auto* en = dynamic_cast<EnvironmentCoverage*>(c)) ig = &en->ig;
+    else if (auto* p = dynamic_cast<ProteinHBond*>(c)) ig = &p->ig;
+    else if (auto* rp = dynamic_cast<RadialPairs*>(c)) ig = &rp->ig;
+    if (!ig) return -1;
+    const upk_igraph_t& G = ig->G;
+    if (sys < 0 || sys >= e.ctx.n_system) throw string("invalid system");
+    if (side != 1 && side != 2) throw string("side must be 1 or 2");
+    if (G.symmetric && side == 2) throw string("a symmetric graph has one side only");
+    if (!src1) src1 = ig->node1;
+    const CoordNode* src2 = ig->node2;
+    const bool rows1 = side == 1;
+    const int n_rows = rows1 ? G.n1 : G.n2, n_other = rows1 ? G.n2 : G.n1, cap = rows1 ? G.cap1 : G.cap2;
+    const int* hit = rows1 ? G.hit1 : G.hit2; const int* hcnt = rows1 ? G.hcnt1 : G.hcnt2;
+    const unsigned short* ord = rows1 ? G.ord1 : G.ord2;
+    const bool has_hit = hit && hcnt, has_hlo = rows1 && G.symmetric && G.hlo1, has_ord = ord != nullptr, has_ordu = has_hlo && G.ord1u;
+    const size_t nr = (size_t)n_rows, no = (size_t)n_other, words = nr * cap;
+    W = WalkedLists();
+    W.cutoff = G.cutoff; W.cache_cutoff = G.cache_cutoff;
+    W.source_rows = name_of(e, rows1 ? src1 : src2); W.source_other = name_of(e, rows1 ? src2 : src1);
+    const size_t n_int = nr * (1 + has_hit + has_hlo + has_ord + has_ordu) + 3 * (nr + no) + words * (1 + has_hit);
+    const size_t n_float = 11 * (nr + no);      // cur_pos and cache_pos of both sides (4 floats each), the source rows (3)
+    int* I = W.info;
+    I[0] = n_rows; I[1] = n_other; I[2] = cap; I[3] = G.symmetric; I[4] = ig->md_sides; I[5] = G.itype; I[6] = G.word16 ? 16 : 32;
+    I[7] = G.nbr_j_bits; I[8] = -1; I[9] = has_hit; I[10] = has_hlo; I[11] = has_ord; I[12] = has_ordu; I[13] = !ig->orig_of.empty();
+    I[14] = (int)n_int; I[15] = (int)n_float; I[16] = G.itype == UPK_IT_ROTAMER; I[17] = (int)min(ig->n_refine, 1L << 30);
+    I[18] = UPK_ROT_SLOT_NONE; I[19] = -1;
+    if (!(ig->md_sides & side)) return 2;
+    if (!fill) return 0;
+    e.sync();
+    if (n_slot_dev) d2h(&I[8], n_slot_dev + sys, 1);
+    d2h(&I[19], G.rebuild_flag + sys, 1);
+    W.ints.assign(n_int, 0); W.floats.assign(n_float, 0.f);
+    int* out = W.ints.data();
+    float* f = W.floats.data();
+    auto room = [&](size_t n_i, size_t n_f) {      // (every section is checked against the sizes announced in info before it is written)
+        if ((size_t)(out - W.ints.data()) + n_i > n_int || (size_t)(f - W.floats.data()) + n_f > n_float) throw string("walked lists: section past the announced size"); };
+    auto take_int = [&](const int* base) { room(nr, 0); d2h(out, base + (size_t)sys * nr, nr); out += nr; };
+    auto take_u16 = [&](const unsigned short* base, size_t off, size_t n) {
+        room(n, 0); vector<unsigned short> t(n); d2h(t.data(), base + off, n);
+        for (size_t k = 0; k < n; ++k) out[k] = t[k];
+        out += n; };
+    auto take_words = [&](const int* base) {
+        if (G.word16) take_u16((const unsigned short*)base, (size_t)sys * words, words);
+        else { room(words, 0); d2h(out, base + (size_t)sys * words, words); out += words; } };
+    auto take_host = [&](const vector<int>& v, size_t n) { room(n, 0); if (v.size() < n) throw string("walked lists: short element array"); copy(v.begin(), v.begin() + n, out); out += n; };
+    take_int(rows1 ? G.cnt1 : G.cnt2);
+    if (has_hit) take_int(hcnt);
+    if (has_hlo) take_int(G.hlo1);
+    if (has_ord) take_u16(ord, (size_t)sys * nr, nr);
+    if (has_ordu) take_u16(G.ord1u, (size_t)sys * nr, nr);
+    const vector<int>& id_r = rows1 ? ig->id1 : ig->id2; const vector<int>& id_o = rows1 ? ig->id2 : ig->id1;
+    const vector<int>& loc_r = rows1 ? ig->loc1 : ig->loc2; const vector<int>& loc_o = rows1 ? ig->loc2 : ig->loc1;
+    take_host(id_r, nr); take_host(id_o, no);
+    room(nr + no, 0);
+    for (size_t k = 0; k < nr; ++k) out[k] = ig->orig_of.empty() ? (int)k : ig->orig_of[k];
+    out += nr;
+    for (size_t k = 0; k < no; ++k) out[k] = ig->orig_of.empty() ? (int)k : ig->orig_of[k];
+    out += no;
+    take_host(loc_r, nr); take_host(loc_o, no);
+    take_words(rows1 ? G.nbr1 : G.nbr2);
+    if (has_hit) take_words(hit);
+    room(0, 8 * (nr + no));
+    d2h(f, (rows1 ? G.cur_pos1 : G.cur_pos2) + (size_t)sys * nr * 4, nr * 4); f += nr * 4;
+    d2h(f, (rows1 ? G.cur_pos2 : G.cur_pos1) + (size_t)sys * no * 4, no * 4); f += no * 4;
+    d2h(f, (rows1 ? G.cache_pos1 : G.cache_pos2) + (size_t)sys * nr * 4, nr * 4); f += nr * 4;
+    d2h(f, (rows1 ? G.cache_pos2 : G.cache_pos1) + (size_t)sys * no * 4, no * 4); f += no * 4;
+    // the source nodes' own rows of this system (what get_output reads for system 0), at the graph's elements
+    auto take_source = [&](const CoordNode* node, const vector<int>& loc, size_t n) {
+        const size_t row = (size_t)node->n_elem * node->stride;
+        room(0, n * 3);
+        vector<float> t(row); d2h(t.data(), node->output.p + (size_t)sys * row, row);
+        for (size_t k = 0; k < n; ++k) for (int d = 0; d < 3; ++d) f[k * 3 + d] = t[(size_t)loc[k] * node->stride + d];
+        f += n * 3; };
+    take_source(rows1 ? src1 : src2, loc_r, nr);
+    take_source(rows1 ? src2 : src1, loc_o, no);
+    if (out != W.ints.data() + n_int || f != W.floats.data() + n_float) throw string("walked lists: the sections do not add up to the announced size");
+    return 0;
+}
+static int engine_backbone_list(DerivEngine& e, const string& node_name, int sys, bool fill, BackboneListCopy& B) {
+    auto* bp = dynamic_cast<BackbonePairs*>(e.get(node_name).computation.get());
+    if (!bp) return -1;
+    if (sys < 0 || sys >= e.ctx.n_system) throw string("invalid system");
+    B = BackboneListCopy();
+    const size_t n = (size_t)bp->n_residue;
+    B.n_residue = bp->n_residue; B.cap = bp->cache.cap; B.skin = bp->cache.skin; B.dist_cutoff = bp->dist_cutoff;
+    if (fill || !bp->cache.list) { e.sync(); d2h(&B.potential, bp->potential_dev.p + sys, 1); }
+    if (!bp->cache.list) return 2;
+    if (!fill) return 0;
+    B.cnt.resize(n); B.id.resize(n); B.list.resize(n * B.cap); B.ref.resize(n * 4);
+    d2h(B.cnt.data(), bp->cache.cnt + (size_t)sys * n, n);
+    d2h(B.id.data(), bp->id.p, n);
+    d2h(B.list.data(), bp->cache.list + (size_t)sys * n * B.cap, n * B.cap);
+    // a pass of parity p reads ref[p] and writes ref[1 - p]: the next pass reads what the last one (ctx.n_pass) wrote
+    const float* next = (e.ctx.n_pass & 1) ? bp->cache.ref0 : bp->cache.ref1;
+    d2h(B.ref.data(), next + (size_t)sys * n * 4, n * 4);
+    // the residues' current centres: the alignment node's own rows of this system (what get_output reads for system 0)
+    const CoordNode& al = bp->alignment;
+    const size_t row = (size_t)al.n_elem * al.stride;
+    vector<float> t(row); d2h(t.data(), al.output.p + (size_t)sys * row, row);
+    B.centre.resize(n * 3);
+    for (size_t k = 0; k < n; ++k) for (int d = 0; d < 3; ++d) B.centre[k * 3 + d] = t[(size_t)B.id[k] * al.stride + d];
+    return 0;
+}
+extern "C" void upside_hip_set_last_error(const char* msg);   // engine_c_api.cpp: prints "ERROR: ..." and keeps the message
+#define DIAG_CATCH } catch (const string& s) { upside_hip_set_last_error(s.c_str()); return 1; } catch (const std::exception& x) { upside_hip_set_last_error(x.what()); return 1; } \
+    catch (...) { upside_hip_set_last_error("unknown error"); return 1; }
+extern "C" int upside_hip_get_walked_lists(DerivEngine* e, const char* node_name, int sys, int side, int* info20, float* cutoffs2,
+                                           char* sources, int sources_len, int n_int, int* ints, int n_float, float* floats) {
+    try {
+    if (!e || !node_name || !info20 || !cutoffs2) throw string("upside_hip_get_walked_lists: null argument");
+    WalkedLists W;
+    const bool fill = ints || floats;
+    const int rc = engine_walked_lists(*e, node_name, sys, side, fill, W);
+    if (rc < 0) throw string("node has no interaction graph");
+    copy(W.info, W.info + 20, info20); cutoffs2[0] = W.cutoff; cutoffs2[1] = W.cache_cutoff;
+    if (sources && sources_len > 0) snprintf(sources, (size_t)sources_len, "%s\n%s", W.source_rows.c_str(), W.source_other.c_str());
+    if (rc == 2) {
+        upside_hip_set_last_error((string("the MD path of ") + node_name + " does not keep the lists of side " + to_string(side) + " (it is not built on demand)").c_str());
+        return 2;
+    }
+    if (!fill) return 0;
+    if (!ints || !floats || n_int < W.info[14] || n_float < W.info[15]) {
+        upside_hip_set_last_error(("buffer too small: the walked lists need " + to_string(W.info[14]) + " ints and " + to_string(W.info[15]) + " floats").c_str());
+        return 3;
+    }
+    copy(W.ints.begin(), W.ints.end(), ints); copy(W.floats.begin(), W.floats.end(), floats);
+    return 0;
+    DIAG_CATCH
+}
+extern "C" int upside_hip_get_backbone_list(DerivEngine* e, const char* node_name, int sys, int* info2, float* cutoffs3, int n_int, int* ints,
+                                            int n_float, float* floats) {
+    try {
+    if (!e || !node_name || !info2 || !cutoffs3) throw string("upside_hip_get_backbone_list: null argument");
+    BackboneListCopy B;
+    const bool fill = ints || floats;
+    const int rc = engine_backbone_list(*e, node_name, sys, fill, B);
+    if (rc < 0) throw string("node is not a backbone_pairs");
+    info2[0] = B.n_residue; info2[1] = B.cap; cutoffs3[0] = B.skin; cutoffs3[1] = B.dist_cutoff; cutoffs3[2] = B.potential;
+    if (rc == 2) {
+        upside_hip_set_last_error((string(node_name) + " keeps no cached residue-pair list (UPSIDE_HIP_BACKBONE_LIST=0, or too few residues)").c_str());
+        return 2;
+    }
+    if (!fill) return 0;
+    const int need_i = B.n_residue * (2 + B.cap), need_f = B.n_residue * 7;
+    if (!ints || !floats || n_int < need_i || n_float < need_f) {
+        upside_hip_set_last_error(("buffer too small: the backbone list needs " + to_string(need_i) + " ints and " + to_string(need_f) + " floats").c_str());
+        return 3;
+    }
+    int* o = copy(B.cnt.begin(), B.cnt.end(), ints); o = copy(B.id.begin(), B.id.end(), o); copy(B.list.begin(), B.list.end(), o);
+    copy(B.centre.begin(), B.centre.end(), copy(B.ref.begin(), B.ref.end(), floats));
+    return 0;
+    DIAG_CATCH
 }
 int engine_igraph_stats(DerivEngine& e, const string& node_name, double* out) {
     // diagnostics (tools/list_stats.py): sizes and per-system mean list lengths of a node's interaction graph

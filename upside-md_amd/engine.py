@@ -203,6 +203,49 @@ class Upside(object):
             pass
 
 
+def unpack_walked_lists(node_name, system, side, info, cutoffs, sources, ints, floats):
+    """the flat arrays of upside_hip_get_walked_lists (include/upside_engine_c.h) as a dict of named numpy arrays"""
+    n_rows, n_other, cap = int(info[0]), int(info[1]), int(info[2])
+    has_hit, has_hlo, has_ord, has_ordu = (bool(info[k]) for k in (9, 10, 11, 12))
+    bits = int(info[7])
+    src = (sources.split('\n') + ['', ''])[:2]
+    r = dict(node=node_name, system=int(system), side=int(side), n_rows=n_rows, n_other=n_other, cap=cap,
+             symmetric=bool(info[3]), md_sides=int(info[4]), itype=int(info[5]), word_bits=int(info[6]), nbr_j_bits=bits,
+             n_slot=int(info[8]), upper=bool(info[16]), n_refine=int(info[17]), slot_none=int(info[18]), rebuilt=int(info[19]),
+             cutoff=np.float32(cutoffs[0]), cache_cutoff=np.float32(cutoffs[1]), source_rows=src[0], source_other=src[1])
+    at = [0]
+
+    def take(a, n, shape=None):
+        v = a[at[0]:at[0] + n].copy(); at[0] += n
+        return v.reshape(shape) if shape else v
+    r['cnt'] = take(ints, n_rows)
+    r['hcnt'] = take(ints, n_rows) if has_hit else None
+    r['hlo'] = take(ints, n_rows) if has_hlo else None
+    r['ord'] = take(ints, n_rows) if has_ord else None
+    r['ordu'] = take(ints, n_rows) if has_ordu else None
+    for k, n in (('id_rows', n_rows), ('id_other', n_other), ('orig_rows', n_rows), ('orig_other', n_other),
+                 ('loc_rows', n_rows), ('loc_other', n_other)):
+        r[k] = take(ints, n)
+    r['nbr_word'] = take(ints, n_rows * cap, (n_rows, cap))
+    r['hit_word'] = take(ints, n_rows * cap, (n_rows, cap)) if has_hit else None
+    assert at[0] == len(ints)
+    mask = (1 << bits) - 1 if bits else -1
+    for k in ('nbr', 'hit'):
+        w = r[k + '_word']
+        r[k] = None if w is None else (w & mask)
+        r[k + '_slot'] = None if (w is None or not bits) else (w.view('u4') >> bits).astype('i4')
+    at[0] = 0
+    for k, n in (('cur_rows', n_rows), ('cur_other', n_other), ('cache_rows', n_rows), ('cache_other', n_other)):
+        v = take(floats, n * 4, (n, 4))
+        r[k] = v[:, :3].copy()
+        if k.startswith('cache'):
+            r[k.replace('cache', 'cache_id')] = v[:, 3].copy().view('i4')
+    r['src_rows'] = take(floats, n_rows * 3, (n_rows, 3))
+    r['src_other'] = take(floats, n_other * 3, (n_other, 3))
+    assert at[0] == len(floats)
+    return r
+
+
 class Ensemble(object):
     """S systems of one topology resident on one GPU, driven through the `upside_hip_*` extension of the C-ABI
     (include/upside_engine_c.h): what `upside_main` does for its `systems` vector (main.cpp:441-700), with the
@@ -486,6 +529,70 @@ class Ensemble(object):
         out = np.zeros((ns, self.n_system, self.n_cv), 'f4')
         self._check(self.calc.upside_hip_cv_read(self.engine, 0, ns, out.ctypes.data, None, None, int(bool(reset))), 'cv_read')
         return (out, ns, na) if with_counts else out
+
+    # -- diagnostics of the pair lists (read only) ----------------------------------------------
+    def set_temperature(self, temperature):
+        t = np.ascontiguousarray(np.broadcast_to(np.asarray(temperature, 'f4'), (self.n_system,)))
+        self.calc.upside_hip_set_temperature.argtypes = [ct.c_void_p, ct.c_void_p]
+        self._check(self.calc.upside_hip_set_temperature(self.engine, t.ctypes.data), 'set_temperature')
+        self.temperature = t.copy()
+
+    def rebuild_flags(self, node_name):
+        """flags[s] = 1 where system s rebuilt the cached pair list of `node_name` in the last force pass"""
+        fl = np.zeros(self.n_system, 'i4')
+        self.calc.upside_hip_rebuild_flags.argtypes = [ct.c_void_p, ct.c_char_p, ct.c_void_p]
+        self._check(self.calc.upside_hip_rebuild_flags(self.engine, _b(node_name), fl.ctypes.data), 'rebuild_flags')
+        return fl
+
+    def walked_lists(self, node_name, system, side):
+        """what the pair passes of the last force pass walked for (node, system, side): a dict of numpy arrays (the layout of
+        upside_hip_get_walked_lists, include/upside_engine_c.h, taken apart: `nbr` / `hit` hold the partner's element index,
+        `nbr_slot` / `hit_slot` the slot field of a rotamer word, `nbr_word` / `hit_word` the words unchanged).  Raises
+        RuntimeError with the library's reason, e.g. for a side the MD path does not keep (`.status` == 2)."""
+        f = self.calc.upside_hip_get_walked_lists
+        f.argtypes = [ct.c_void_p, ct.c_char_p, ct.c_int, ct.c_int, ct.c_void_p, ct.c_void_p, ct.c_char_p, ct.c_int,
+                      ct.c_int, ct.c_void_p, ct.c_int, ct.c_void_p]
+        info = np.zeros(20, 'i4'); cut = np.zeros(2, 'f4'); names = ct.create_string_buffer(512)
+
+        def call(n_int, ints, n_float, floats):
+            rc = f(self.engine, _b(node_name), int(system), int(side), info.ctypes.data, cut.ctypes.data, names, 512,
+                   n_int, ints, n_float, floats)
+            if rc:
+                err = RuntimeError('walked_lists(%s, system %d, side %d): %s' % (
+                    node_name, system, side, self.calc.upside_hip_last_error().decode()))
+                err.status = rc
+                raise err
+        call(0, None, 0, None)
+        ints = np.zeros(int(info[14]), 'i4'); floats = np.zeros(int(info[15]), 'f4')
+        call(len(ints), ints.ctypes.data, len(floats), floats.ctypes.data)
+        return unpack_walked_lists(node_name, system, side, info, cut, names.value.decode(), ints, floats)
+
+    def backbone_list(self, node_name, system, must_have_list=True):
+        """the cached residue-pair list of a backbone_pairs node for one system: dict(list_on, cap, skin, dist_cutoff, potential (the
+        node's, of this system, in the last force pass that asked for energies), cnt, id, list [n_residue, cap], ref [n_residue, 3]:
+        the reference centres the next force pass reads, centre: the current ones).  A node that keeps no list: RuntimeError
+        (`.status` == 2), or with must_have_list=False the dict without the arrays and list_on False."""
+        f = self.calc.upside_hip_get_backbone_list
+        f.argtypes = [ct.c_void_p, ct.c_char_p, ct.c_int, ct.c_void_p, ct.c_void_p, ct.c_int, ct.c_void_p, ct.c_int, ct.c_void_p]
+        info = np.zeros(2, 'i4'); cut = np.zeros(3, 'f4')
+
+        def call(n_int, ints, n_float, floats):
+            rc = f(self.engine, _b(node_name), int(system), info.ctypes.data, cut.ctypes.data, n_int, ints, n_float, floats)
+            if rc and not (rc == 2 and not must_have_list):
+                err = RuntimeError('backbone_list(%s, system %d): %s' % (node_name, system, self.calc.upside_hip_last_error().decode()))
+                err.status = rc
+                raise err
+            return rc
+        rc = call(0, None, 0, None)
+        n, cap = int(info[0]), int(info[1])
+        r = dict(node=node_name, system=int(system), side=0, list_on=rc == 0, n_residue=n, cap=cap)
+        if rc == 0:
+            ints = np.zeros(n * (2 + cap), 'i4'); floats = np.zeros(n * 7, 'f4')
+            call(len(ints), ints.ctypes.data, len(floats), floats.ctypes.data)
+            r.update(cnt=ints[:n].copy(), id=ints[n:2 * n].copy(), list=ints[2 * n:].reshape(n, cap).copy(),
+                     ref=floats[:n * 4].reshape(n, 4)[:, :3].copy(), centre=floats[n * 4:].reshape(n, 3).copy())
+        r.update(skin=np.float32(cut[0]), dist_cutoff=np.float32(cut[1]), potential=np.float32(cut[2]))
+        return r
 
     def restraint_values(self, node_name):
         """(n_system, n_cv) CV values the cv_restraint node `node_name` saw in the last force pass (energies(), MD steps): the bits
