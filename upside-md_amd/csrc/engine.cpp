@@ -30,6 +30,8 @@ void upk_check(int code, const char* what) {
                              "indices for every graph but the rotamer's, <= 65534 elements per side)"; break;
             case 9011: why = ": the hit-list refine exists for the side-chain graph (symmetric, 32-bit words) and for two-sided graphs with 16-bit words; "
                              "a symmetric radial graph walks its cached lists and has no hit lists"; break;
+            case 9012: why = ": a graph with 16-bit list words packs bits beside the partner's index (upk_igraph_t::nbr_j_bits): the refine reads such a "
+                             "word as the index itself"; break;
             default: break;
         }
         throw string("kernel launcher ") + what + " rejected its arguments (code " + to_string(code) + ")" + why;

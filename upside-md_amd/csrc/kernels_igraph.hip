@@ -332,114 +332,104 @@ extern "C" int upk_pairlist_build_sides(const upk_launch_t* L, const upk_igraph_
 
 // ------------------------------------------------------------------------------------------------
 // K2b: this step's in-range pairs (the refine of interaction_graph.h:201-257, once per step and graph side).  A workgroup
-// stages the other side's positions (16 bytes per element) in LDS and serves rows_per_wg rows; one wavefront per row tests
-// 64 cached neighbours per trip and appends the survivors' list words to the row's hit list in list order (ballot +
-// popcount prefix).  Latency bound by design -- it runs on the upkeep streams next to the VALU-bound pair passes -- so a
-// wavefront fetches the positions and list lengths of ALL its rows with one load each and keeps the first list words of
-// the next PLR_DEPTH row pairs in flight.
+// stages the other side's positions (16 bytes per element) in LDS and serves rows_per_wg rows, a contiguous run of them per
+// wavefront; the survivors' list words are appended to the row's hit list in list order (ballot + popcount prefix).
 #ifndef PLR_BLOCK
 #define PLR_BLOCK 256
 #endif
-#ifndef PLR_DEPTH
-#define PLR_DEPTH 2
-#endif
-static_assert(PLR_ROWS <= 64 * (PLR_BLOCK / 64), "a wavefront of the refine keeps the positions and list lengths of its rows one per lane: at most 64 rows per wavefront");
-// squared distances of two pairs at once, every operation rounded separately (no contraction): the same bits as dist2_exact,
-// from v_pk_add_f32 / v_pk_mul_f32 (3 + 3 + 2 packed instructions for the two candidates of a lane)
-typedef float plr_v2 __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ plr_v2 dist2_exact2(plr_v2 ax, plr_v2 ay, plr_v2 az, plr_v2 bx, plr_v2 by, plr_v2 bz) {
-#pragma clang fp contract(off)
-    const plr_v2 dx = ax - bx, dy = ay - by, dz = az - bz;
-    const plr_v2 xx = dx * dx, yy = dy * dy, zz = dz * dz;
-    const plr_v2 s = xx + yy;
-    return s + zz;
-}
-// TWO rows per wavefront trip (rows 2a and 2a+1 of the wavefront's run: one candidate of each per lane), so that the distance
-// arithmetic issues packed and the per-trip bookkeeping (loop control, ballots, list-length broadcasts) is shared: the kernel
-// is bound by instruction issue, not by the 4 bytes it reads per cached pair.
-template <bool SYM, typename W>
+// A row served by a GROUP of LPR lanes (16 or 32), so that 64 / LPR consecutive rows of the wavefront's run (a set) share every trip and
+// every piece of loop control; the groups advance together until the longest row of the set is done (tools/refine_groups.py: trips per
+// row by LPR).  A lane loads its own row's position and list length -- no broadcasts -- and takes word k0 + lane % LPR of its row per trip;
+// the survivors are compacted with one ballot, the group's bit field of it and a popcount below the lane, so the hit list keeps the
+// order of the cached row.  The first PLR_AHEAD words of the next set's rows (and the list lengths of the set after it, which say where
+// those words end) are in flight while this set is tested.
+template <bool SYM, typename W, int LPR = SYM ? PLR_LPR_SYM : PLR_LPR_W16>
 __device__ __forceinline__ void d_pairlist_refine(const upk_igraph_t& G, int side, int rows_per_wg, const BX B, float* plr_lds) {
-        float4* oth = (float4*)plr_lds;
+    static_assert(LPR == 16 || LPR == 32, "a group's bit field of the ballot is taken with 32-bit operations");
+    static_assert(PLR_AHEAD % LPR == 0 && PLR_AHEAD >= LPR, "whole trips in flight");
+    constexpr int NG = 64 / LPR, U = PLR_AHEAD / LPR;
+    float4* oth = (float4*)plr_lds;
     const int s = B.by;
-    // (the wavefront index is uniform, which the compiler cannot see: made scalar, row numbers, list lengths and row base addresses
-    //  stay in scalar registers and the loop control runs on the scalar unit)
     const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), n_wave = blockDim.x >> 6;
     const bool rows1 = side == 1;
     const int n_rows = rows1 ? G.n1 : G.n2, n_other = rows1 ? G.n2 : G.n1;
     const int cap = rows1 ? G.cap1 : G.cap2;
     const float4* src = (const float4*)((rows1 ? G.cur_pos2 : G.cur_pos1) + (size_t)s * n_other * 4);
-    const float4* mine = (const float4*)((rows1 ? G.cur_pos1 : G.cur_pos2) + (size_t)s * n_rows * 4);
     for (int j = threadIdx.x; j <= n_other; j += blockDim.x) oth[j] = j < n_other ? src[j] : make_float4(1e18f, 1e18f, 1e18f, 0.f);
     __syncthreads();
     // (lanes past the end of their row carry the word n_other, which names the far-away sentinel behind the staged elements: such a
     //  lane fails the distance test by itself and the trip needs no validity masks)
     const int dead = n_other;
-    const W* nbr_base = (const W*)(rows1 ? G.nbr1 : G.nbr2) + (size_t)s * n_rows * cap;
-    const int* cnt_arr = (rows1 ? G.cnt1 : G.cnt2) + (size_t)s * n_rows;
-    W* hit_base = (W*)(rows1 ? G.hit1 : G.hit2) + (size_t)s * n_rows * cap;
-    int* hcnt = (rows1 ? G.hcnt1 : G.hcnt2) + (size_t)s * n_rows;
-    int* hlo = (SYM && G.hlo1) ? G.hlo1 + (size_t)s * n_rows : nullptr;
     const float cut2 = G.cutoff * G.cutoff;
     const int jmask = G.nbr_j_bits ? (1 << G.nbr_j_bits) - 1 : 0x7fffffff;
-    // this wavefront's rows: a contiguous run of at most 64 (lane r holds row r0 + r's position and list length)
-    const int per_wave = (rows_per_wg + n_wave - 1) / n_wave;     // <= 64 (launcher)
+    const int per_wave = (rows_per_wg + n_wave - 1) / n_wave;
     const int r0 = B.bx * rows_per_wg + wave * per_wave;
     int r1 = r0 + per_wave; { const int wg_end = (B.bx + 1) * rows_per_wg; if (r1 > wg_end) r1 = wg_end; if (r1 > n_rows) r1 = n_rows; }
     if (r0 >= r1) return;
-    const bool have = r0 + lane < r1;
-    const float4 my_x = have ? mine[r0 + lane] : make_float4(0.f, 0.f, 0.f, 0.f);
-    const int my_cnt = have ? cnt_arr[r0 + lane] : 0;
-    int my_n = 0, my_lo = 0;                                      // results of row r0 + lane
-    auto bcast = [&](float v, int l) { return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), l)); };
-    // The first 64 list words of the next PLR_DEPTH row pairs are in flight while this pair is tested: a wavefront's share of the memory
-    // system is what it keeps in flight, and one pair (two 256-byte rows) per wavefront left the refine at 2.4 TB/s of list traffic
-    // with neither the vector unit nor the LDS half busy (round 5: two pairs ahead).
-    auto fetch_pair = [&](int ra, int& a, int& b) {      // words [0, 64) of rows ra, ra + 1 (dead past the rows or their ends)
-        a = dead; b = dead;
-        if (ra < r1) {
-            const int la = ra - r0;
-            const int cA = __builtin_amdgcn_readlane(my_cnt, la & 63), cB = ra + 1 < r1 ? __builtin_amdgcn_readlane(my_cnt, (la + 1) & 63) : 0;
-            if (lane < cA) a = nbr_base[(size_t)ra * cap + lane];
-            if (lane < cB) b = nbr_base[(size_t)(ra + 1) * cap + lane];
-        }
+    // the wavefront's run of rows [r0, r1): scalar bases, and 32-bit offsets from them per lane (a run is at most per_wave rows of cap words)
+    const int n_run = r1 - r0;
+    const size_t run0 = (size_t)s * n_rows + r0;
+    const float4* mine = (const float4*)(rows1 ? G.cur_pos1 : G.cur_pos2) + run0;
+    const int* cnt_arr = (rows1 ? G.cnt1 : G.cnt2) + run0;
+    const char* nbr_run = (const char*)((const W*)(rows1 ? G.nbr1 : G.nbr2) + run0 * cap);
+    char* hit_run = (char*)((W*)(rows1 ? G.hit1 : G.hit2) + run0 * cap);
+    int* hcnt = (rows1 ? G.hcnt1 : G.hcnt2) + run0;
+    int* hlo = (SYM && G.hlo1) ? G.hlo1 + run0 : nullptr;
+    const unsigned row_bytes = (unsigned)cap * (unsigned)sizeof(W);
+    const int grp = lane / LPR, sub = lane % LPR;                 // the lane's group (row b + grp of the set at b) and its place in it
+    const unsigned gshift = grp * LPR, gmask = LPR == 32 ? 0xffffffffu : (1u << LPR) - 1u, below = (1u << sub) - 1u;
+    // (rows past the run: the load goes to the run's last row instead of under a branch, so that no wait is placed behind it)
+    auto ld_cnt = [&](int b) { const int lr = b + grp, c = cnt_arr[lr < n_run ? lr : n_run - 1]; return lr < n_run ? c : 0; };
+    // a set of NG rows: the lane's row of it (list length, position), the set's longest row and the lane's first U words of its row
+    struct RowSet { int cnt; float4 x; int cmax; int q[U]; };
+    // (a list word is loaded only where the row has one: words past the end of a row, loaded and thrown away, were tried and cost the
+    //  symmetric graph's refine a third more time -- its 32-bit lists are most of what the kernel moves)
+    auto fetch = [&](int b, RowSet& S) {           // S.cnt was loaded a set earlier: no load here waits for another
+        const int lr = b + grp;
+        S.x = mine[lr < n_run ? lr : n_run - 1];
+        S.cmax = 0;
+#pragma unroll
+        for (int g = 0; g < NG; ++g) { const int c = __builtin_amdgcn_readlane(S.cnt, g * LPR); S.cmax = c > S.cmax ? c : S.cmax; }
+        const W* mine_words = (const W*)(nbr_run + ((unsigned)lr * row_bytes + (unsigned)sub * (unsigned)sizeof(W)));
+#pragma unroll
+        for (int u = 0; u < U; ++u) S.q[u] = (u * LPR < S.cmax && u * LPR + sub < S.cnt) ? (int)mine_words[u * LPR] : dead;
     };
-    int qA[PLR_DEPTH], qB[PLR_DEPTH];
+    auto refine_set = [&](int b, const RowSet& S) {
+        const int lr = b + grp, row = r0 + lr;
+        const unsigned out = (unsigned)lr * row_bytes;
+        int n = 0, lo = 0;
+        auto test = [&](int w) {
+            const int j = sizeof(W) == 2 ? w : w & jmask;       // (a 16-bit word is the partner's index and nothing else)
+            const float4 y = oth[j];
+            const bool h = dist2_exact(S.x.x, S.x.y, S.x.z, y.x, y.y, y.z) < cut2;
+            const unsigned long long m = __builtin_amdgcn_ballot_w64(h);
+            const unsigned gb = (unsigned)(m >> gshift) & gmask;
+            if (h) *(W*)(hit_run + (out + (unsigned)(n + __popc(gb & below)) * (unsigned)sizeof(W))) = (W)w;
+            n += __popc(gb);
+            if (SYM) lo += __popc((unsigned)((__builtin_amdgcn_ballot_w64(j < row) & m) >> gshift) & gmask);
+        };
 #pragma unroll
-    for (int d = 0; d < PLR_DEPTH; ++d) fetch_pair(r0 + 2 * d, qA[d], qB[d]);
-    for (int ra = r0; ra < r1; ra += 2) {
-        const int la = ra - r0, lb = la + 1;
-        const bool hasB = ra + 1 < r1;
-        const int cntA = __builtin_amdgcn_readlane(my_cnt, la), cntB = hasB ? __builtin_amdgcn_readlane(my_cnt, lb & 63) : 0;
-        int wA = qA[0], wB = qB[0];
-#pragma unroll
-        for (int d = 0; d + 1 < PLR_DEPTH; ++d) { qA[d] = qA[d + 1]; qB[d] = qB[d + 1]; }
-        fetch_pair(ra + 2 * PLR_DEPTH, qA[PLR_DEPTH - 1], qB[PLR_DEPTH - 1]);
-        plr_v2 xx, xy, xz;
-        xx.x = bcast(my_x.x, la); xy.x = bcast(my_x.y, la); xz.x = bcast(my_x.z, la);
-        xx.y = bcast(my_x.x, lb & 63); xy.y = bcast(my_x.y, lb & 63); xz.y = bcast(my_x.z, lb & 63);
-        const W* nbrA = nbr_base + (size_t)ra * cap; const W* nbrB = nbrA + cap;
-        W* outA = hit_base + (size_t)ra * cap; W* outB = outA + cap;
-        int na = 0, nb = 0, loa = 0, lob = 0;
-        const int cmax = cntA > cntB ? cntA : cntB;
-        for (int k0 = 0; k0 < cmax; k0 += 64) {
-            const int k = k0 + lane;
-            if (k0) { wA = k < cntA ? nbrA[k] : dead; wB = k < cntB ? nbrB[k] : dead; }
-            const int jA = wA & jmask, jB = wB & jmask;
-            const float4 yA = oth[jA], yB = oth[jB];
-            plr_v2 yx, yy, yz; yx.x = yA.x; yx.y = yB.x; yy.x = yA.y; yy.y = yB.y; yz.x = yA.z; yz.y = yB.z;
-            const plr_v2 d2 = dist2_exact2(xx, xy, xz, yx, yy, yz);
-            const bool hitA = d2.x < cut2, hitB = d2.y < cut2;
-            const unsigned long long mA = __builtin_amdgcn_ballot_w64(hitA), mB = __builtin_amdgcn_ballot_w64(hitB);
-            const unsigned long long below = (1ull << lane) - 1ull;
-            if (hitA) outA[na + __popcll(mA & below)] = (W)wA;
-            if (hitB) outB[nb + __popcll(mB & below)] = (W)wB;
-            na += __popcll(mA); nb += __popcll(mB);
-            if (SYM) { loa += __popcll(__builtin_amdgcn_ballot_w64(hitA && jA < ra)); lob += __popcll(__builtin_amdgcn_ballot_w64(hitB && jB < ra + 1)); }
-        }
-        if (lane == la) { my_n = na; my_lo = loa; }
-        if (hasB && lane == lb) { my_n = nb; my_lo = lob; }
+        for (int u = 0; u < U; ++u) { if (u * LPR >= S.cmax) break; test(S.q[u]); }
+        for (int k = U * LPR + sub; k - sub < S.cmax; k += LPR)      // (rows longer than PLR_AHEAD words: the rest as it comes)
+            test(k < S.cnt ? (int)*(const W*)(nbr_run + (out + (unsigned)k * (unsigned)sizeof(W))) : dead);
+        if (sub == 0 && lr < n_run) { hcnt[lr] = n; if (SYM && hlo) hlo[lr] = lo; }
+    };
+    // two sets in turn, each fetched while the other is tested (no copies between them)
+    RowSet A, Bs;
+    A.cnt = ld_cnt(0); Bs.cnt = ld_cnt(NG);
+    fetch(0, A);
+    for (int b = 0;;) {
+        int after = ld_cnt(b + 2 * NG);
+        fetch(b + NG, Bs);
+        refine_set(b, A);
+        A.cnt = after; b += NG;
+        if (b >= n_run) break;
+        after = ld_cnt(b + 2 * NG);
+        fetch(b + NG, A);
+        refine_set(b, Bs);
+        Bs.cnt = after; b += NG;
+        if (b >= n_run) break;
     }
-    if (have) { hcnt[r0 + lane] = my_n; if (SYM && hlo) hlo[r0 + lane] = my_lo; }
 }
 template <bool SYM, typename W>
 __global__ void __launch_bounds__(PLR_BLOCK) k_pairlist_refine(upk_igraph_t G, int side, int rows_per_wg)  {
@@ -447,8 +437,8 @@ __global__ void __launch_bounds__(PLR_BLOCK) k_pairlist_refine(upk_igraph_t G, i
     d_pairlist_refine<SYM, W>(G, side, rows_per_wg, BX_REAL, lds_dyn_);
 }
 // Rows of a handful of cached neighbours (backbone hydrogen bonds: three per donor or acceptor): one LANE per row walks its list --
-// the row-pair machinery above costs a fixed ~100 instructions and a dependent chain per pair of rows, 0.19 ms per launch for
-// 840 cached pairs per system.  Same hit lists, in the same order.
+// a wavefront trip of the refine above would carry three words per group (the two-rows-per-trip refine of round 5 took 0.19 ms per
+// launch for 840 cached pairs per system).  Same hit lists, in the same order.
 __device__ __forceinline__ void d_pairlist_refine_short(const upk_igraph_t& G, int side, const BX B, float* lds_unused) {
     const int s = B.by, row = B.bx * blockDim.x + threadIdx.x;
     const bool rows1 = side == 1;
@@ -488,11 +478,12 @@ extern "C" int upk_pairlist_refine(const upk_launch_t* L, const upk_igraph_t* G,
         return launch_status();
     }
     if (!list_words_match(G)) return 9010;
+    if (G->word16 && G->nbr_j_bits) return 9012;                // a 16-bit list word is the partner's index and nothing else
     if ((G->symmetric != 0) == (G->word16 != 0)) return 9011;   // the two list forms there are: the rotamer graph's (symmetric, 32-bit words) and everyone else's
     const size_t lds = (size_t)((n_other > 0 ? n_other : 0) + 1) * 16;
     if (lds > PLAN_LIST_LDS) return 9006;   // (callers fall back to the list-walking kernels long before this)
     const int rows_per_wg = plan_refine_rows(L->n_system, upk_device_cu_count(), n_rows);
-    {   // merged launch: 1024-lane workgroups, four times the wavefronts -- four times the rows, so that a wavefront keeps its run of row pairs
+    {   // merged launch: 1024-lane workgroups, four times the wavefronts -- four times the rows, so that a wavefront keeps its run of rows
         const int rows_b = rows_per_wg * 4;
         if (batch_add(L, G->symmetric ? BK_REFINE_SYM : BK_REFINE, (n_rows + rows_b - 1) / rows_b, L->n_system, lds, G, sizeof(*G), nullptr, 0, side, rows_b)) return 0;
     }

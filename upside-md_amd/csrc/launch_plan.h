@@ -19,6 +19,24 @@
 #ifndef PLR_ROWS
 #define PLR_ROWS 256    // rows per workgroup of the list refine in a batch that fills the device
 #endif
+// Lanes per row of the list refine (LPR), per instance: the symmetric side-chain graph with 32-bit words, and everyone else's 16-bit
+// words.  LPR lanes serve a row and 64 / LPR rows share a wavefront trip.  From tools/refine_groups.py (profiles/refine_groups_ab.txt) on
+// the benchmark protein, trips per row at LPR 16 / 32: side-chain graph 2.10 / 2.10, hydrophobe coverage 1.65 / 1.67, hbond coverage
+// 1.11 / 1.17, environment 1.72 / 1.67 -- the same trips, and 16 shares each of them and the per-set bookkeeping among four rows
+// instead of two.  Measured at 4096 systems on one box, LPR 16 / 32: VALU instructions per launch 131.7 M / 140.5 M (16-bit words) and
+// 180.5 M / 189.1 M (side-chain graph), time per launch 387 / 471 us and 675 / 681 us.  Against the two-rows-per-trip refine this
+// replaces (one wavefront per row pair, 64 words of each per trip), alternating runs on one box: 16-bit words 159.4 M -> 126.5 M VALU
+// instructions and 496 -> 411 us per launch, side-chain graph 223.9 M -> 180.5 M and 691 -> 672 us (its 32-bit lists are most of what
+// the kernel moves: with the old body for that instance alone the benchmark lost a third of the gain).
+#ifndef PLR_LPR_SYM
+#define PLR_LPR_SYM 16
+#endif
+#ifndef PLR_LPR_W16
+#define PLR_LPR_W16 16
+#endif
+#ifndef PLR_AHEAD
+#define PLR_AHEAD 128   // list words per row that the refine keeps in flight for the next set of rows
+#endif
 #define BP_BLOCK 1024
 #ifndef BP_NODE_STRIDE
 #define BP_NODE_STRIDE 6      // (8 = one b128 + one b64 per node row: measured equal, and 6 leaves 7 KB more of the LDS to the inbox)
@@ -239,8 +257,9 @@ inline int plan_upkeep_block(int S, int n_cu, int large) { return S >= 2 * n_cu 
 inline int plan_list_build_rows(int S, int n_cu) { return S >= n_cu ? 128 : 64; }
 inline bool plan_list_build_staged(const PlanSwitches& sw, size_t lds_bytes) { return lds_bytes <= PLAN_LIST_LDS && !sw.PLB_UNSTAGED; }
 // rows per workgroup of the refine: every workgroup stages the other side again: few fat workgroups for a large batch, many small ones for
-// a small one.  A side of a few hundred rows (environment graph: 300): smaller workgroups, or one of its two would walk 256 rows as 32
-// dependent row pairs per wavefront while the other has 44 (0.30 -> 0.24 ms)
+// a small one.  A wavefront takes a contiguous run of a quarter of them, 64 / LPR rows (a set) at a time.  A side of a few hundred rows
+// (environment graph: 300): smaller workgroups, or one of its two would walk 256 rows, 64 per wavefront, while the other has 44
+// (0.30 -> 0.24 ms with the two-rows-per-trip refine of round 5)
 inline int plan_refine_rows(int S, int n_cu, int n_rows) {
     const int rows = S >= n_cu ? PLR_ROWS : (S >= 16 ? 64 : 16);
     return n_rows <= 512 && rows > 128 ? 128 : rows;
